@@ -3,6 +3,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--config stromgren|stromgren_diffuse|lexington]
+                    [--full] [--dump-outputs DIR]
 
 One "step" is one full iteration of the reference's loop
 (src/IonizationSimulation.cpp:359-643) on every rank:
@@ -24,8 +25,14 @@ themselves say 1e6).
 N > 1 is the replicated-grid mode of the reference's MPI path: every rank
 holds the whole grid, the accumulators are sum-reduced with one RCCL
 all-reduce. The timed steps are WEAK scaling (every rank shoots `--packets`
-packets, `value` counts all of them); the same line carries a
+packets, `value` counts all of them); with --full the same line carries a
 `strong_scaling` object: the iteration with `--packets` packets IN TOTAL.
+
+A plain run does what the headline figure needs: set up, converge, warm up,
+time `--steps` steps, print the line. --full adds the rest: the CPU baseline,
+the other single-GPU configs under `also` (N = 1), the strong-scaling leg,
+config 5's shape and the native group driver (N > 1). --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 """
 import argparse
 import json
@@ -475,6 +482,16 @@ def parse_args():
     ap.add_argument("--copies", type=int, default=1,
                     help="engines per block that holds a source (the "
                          "reference's copies of busy subgrids): only 1 here")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU "
+                         "baseline, the `also` legs (N = 1), the strong-"
+                         "scaling leg, config 5's shape and the native group "
+                         "driver (N > 1); without it a run sets up, warms "
+                         "up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a fixed "
+                         "sample of the cells' fields and the step's "
+                         "counters) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.copies != 1:
         # (DomainIterationDriver hands a flight to THE rank that owns the cell
@@ -490,6 +507,42 @@ def parse_args():
     if args.converge_packets is None:
         args.converge_packets = args.packets
     return args
+
+
+# --dump-outputs: the files of all fields together stay below this
+DUMP_BYTES = 48 << 20
+
+
+def dump_outputs(directory, engine, cfg, counters, suffix=""):
+    """What one iteration hands its caller, after the last timed step: the
+    cell state after the update (ionic fractions; the temperature where the
+    step solves for it), the step's accumulators (mean intensities, heating
+    where tracked) and its counters (total weight, the four packet types, DDA
+    steps). A field is a fixed sample of the engine's cells (seed 0: the same
+    cells for the same grid), small enough that all files together stay below
+    DUMP_BYTES; `suffix` names the rank of a block in domain mode."""
+    from cmacionize_amd import engine as E
+    if cfg["lexington"]:
+        fields = {"ionic_fraction_%02d" % i: E.FIELD_IONIC_FRACTION + i
+                  for i in range(E.NION)}
+        fields.update({"mean_intensity_%02d" % i: E.FIELD_MEAN_INTENSITY + i
+                       for i in range(E.NION)})
+        fields.update({"heating_H": E.FIELD_HEATING,
+                       "heating_He": E.FIELD_HEATING + 1,
+                       "temperature": E.FIELD_TEMPERATURE})
+    else:
+        fields = {"ionic_fraction_00": E.FIELD_IONIC_FRACTION,
+                  "mean_intensity_00": E.FIELD_MEAN_INTENSITY}
+    n = engine.n
+    size = min(n, DUMP_BYTES // (8 * len(fields)))
+    cells = np.sort(np.random.default_rng(0).choice(n, size, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    for name, field in fields.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"),
+                engine.download_field(field)[cells].astype(np.float64))
+    tw, tc, nsteps = counters
+    np.save(os.path.join(directory, "counters" + suffix + ".npy"),
+            np.array([tw] + list(tc) + [nsteps], dtype=np.float64))
 
 
 class Ranks:
@@ -536,12 +589,13 @@ class Ranks:
 
 
 def run_leg(args, ranks, config, steps, warmup, cpu_seconds=None,
-            cpu_hint=None):
+            cpu_hint=None, dump_dir=None):
     """One benchmark configuration from the ionised start to the JSON record:
     the reference's run (untimed for `value`), `warmup` + `steps` iterations
     on the converged state, the roofline of the first-generation kernel and
-    the CPU baseline on the same state. Returns the record on rank 0, None on
-    the other ranks; the engine is closed before returning."""
+    the CPU baseline on the same state. `dump_dir`: the outputs of the last
+    timed step are written there (dump_outputs). Returns the record on rank
+    0, None on the other ranks; the engine is closed before returning."""
     import torch
     from cmacionize_amd.simulation import GpuBackend, ReplicaIterationDriver
     from cmacionize_amd import STROMGREN as S
@@ -664,8 +718,12 @@ def run_leg(args, ranks, config, steps, warmup, cpu_seconds=None,
         driver.iteration(loop, global_packets, 42)
         loop += 1
     elapsed, nsteps_total, timing, launches = timed(global_packets, steps)
+    if dump_dir and (domain or rank == 0):
+        dump_outputs(dump_dir, backend.engine, cfg,
+                     (driver.totweight, driver.typecount, driver.nsteps),
+                     ".rank%d" % rank if domain and world > 1 else "")
     strong = None
-    if world > 1 and not domain and not args.no_strong:
+    if world > 1 and not domain and args.full and not args.no_strong:
         # the same iteration with npk packets IN TOTAL (npk / world per rank)
         for _ in range(warmup):
             driver.iteration(loop, npk, 42)
@@ -873,7 +931,8 @@ def run_native(args, config, ncell, domain, steps, warmup, devices):
             backends.append(b)
     group = EngineGroup([b.engine for b in backends])
     pool = ThreadPoolExecutor(max_workers=n)
-    state = dict(rounds=0, flights=0, nsteps=0)
+    state = dict(rounds=0, flights=0, nsteps=0, totweight=0.,
+                 typecount=np.zeros(E.NTYPE))
 
     def start(job):
         r, loop, total = job
@@ -902,7 +961,8 @@ def run_native(args, config, ncell, domain, steps, warmup, devices):
             group.reduce_accumulators()
         tw = sum(c[0] for c in counters)
         state.update(rounds=rounds, flights=flights,
-                     nsteps=sum(c[2] for c in counters))
+                     nsteps=sum(c[2] for c in counters), totweight=tw,
+                     typecount=sum(c[1] for c in counters))
         group.update_cells(loop, tw)
 
     def synchronize():
@@ -929,6 +989,12 @@ def run_native(args, config, ncell, domain, steps, warmup, devices):
     synchronize()
     elapsed = time.perf_counter() - t0
     st = group.exchange_stats(reset=True)
+    if args.dump_outputs:
+        for r, b in enumerate(backends if domain else backends[:1]):
+            dump_outputs(args.dump_outputs, b.engine, cfg,
+                         (state["totweight"], state["typecount"],
+                          state["nsteps"]),
+                         ".rank%d" % r if domain and n > 1 else "")
     xH = np.concatenate([b.engine.download_field(E.FIELD_IONIC_FRACTION)
                          for b in (backends if domain else backends[:1])])
     out = {
@@ -1057,6 +1123,28 @@ def child_line(args, config, ncell, domain, steps, warmup, driver,
 # seconds the extra legs of an N > 1 run may take together
 EXTRAS_BUDGET_S = 420
 
+
+def wait_for_exit(pids, timeout):
+    """Wait until the processes `pids` (the other ranks, on this node) have
+    ended - or are zombies their launcher has not reaped yet, which hold no
+    device any more. Returns those still running after `timeout` seconds."""
+    t_end = time.monotonic() + timeout
+    left = []
+    for pid in pids:
+        while True:
+            try:
+                with open("/proc/%d/stat" % pid) as f:
+                    state = f.read().rsplit(")", 1)[1].split()[0]
+            except (OSError, IndexError):
+                break
+            if state in ("Z", "X"):
+                break
+            if time.monotonic() > t_end:
+                left.append(pid)
+                break
+            time.sleep(0.1)
+    return left
+
 # what an `also` leg carries into the headline line
 ALSO_KEYS = ("metric", "value", "unit", "steps", "warmup", "ms_per_step",
              "transport_only_packets_per_s", "transport_kernels_ms_per_step",
@@ -1085,13 +1173,15 @@ def main():
 
     t_start = time.perf_counter()
     ranks = Ranks(args)
-    also = (ranks.world == 1 and args.config == "stromgren" and
+    # a plain run measures the headline figure only; --full adds the rest
+    also = (args.full and ranks.world == 1 and args.config == "stromgren" and
             not args.no_also and args.decomposition == "replica")
-    cpu = not args.no_cpu_baseline and ranks.world == 1
+    cpu = args.full and not args.no_cpu_baseline and ranks.world == 1
     # the CPU sample: ~12 s when the headline config runs alone, ~6 s per leg
     # when the line carries all three (the driver's default run: <= 90 s)
     out = run_leg(args, ranks, args.config, args.steps, args.warmup,
-                  cpu_seconds=(6. if also else 12.) if cpu else None)
+                  cpu_seconds=(6. if also else 12.) if cpu else None,
+                  dump_dir=args.dump_outputs)
     if also and ranks.rank == 0:
         # BASELINE.json configs[2] and configs[3] - the other benchmarks
         # north_star names - under the same clock, one after the other on the
@@ -1119,20 +1209,30 @@ def main():
                                        if k != "calibration"}
             out["also"][config] = rec
         out["bench_wall_s"] = time.perf_counter() - t_start
-    extras = (ranks.world > 1 and args.config == "stromgren" and
-              not args.no_also and args.decomposition == "replica")
+    extras = (args.full and ranks.world > 1 and args.config == "stromgren"
+              and not args.no_also and args.decomposition == "replica")
+    pids = [None] * ranks.world
+    if ranks.world > 1:
+        if extras:
+            ranks.dist.all_gather_object(pids, os.getpid())
+        ranks.dist.barrier()
+        ranks.dist.destroy_process_group()
+    if ranks.rank != 0:
+        return
     if extras:
-        # N > 1, the driver's command: the line also carries config 5's shape
+        # N > 1 with --full: the line also carries config 5's shape
         # (lexingtonHII40 in one block per GPU, flights exchanged over RCCL)
         # and the product's own multi-GPU path (the group API) on both
         # shapes - each as a job of its own (child_line), so that nothing
         # that happens there can take the headline line with it. They need
-        # the GPUs to themselves: the other ranks wait on the rendezvous
-        # store (a host-side wait: a collective would spin on their devices).
-        from datetime import timedelta
+        # the GPUs to themselves: the other ranks have left the collective
+        # and end; their processes are gone before the first job starts (a
+        # job's N ranks do not run next to the N of this run).
         steps = args.also_steps or min(args.steps, 20)
         ncell5 = args.config5_ncell or (512 if ranks.world == 8 else 256)
-        store = ranks.dist.distributed_c10d._get_default_store()
+        left = wait_for_exit(pids[1:], timeout=120.)
+        if left:
+            out["ranks_not_ended_before_extras"] = left
         # (the three legs together get EXTRAS_BUDGET_S: a leg that hangs must
         # not hold the headline line back beyond what a scaling run may take)
         t_extras = time.perf_counter()
@@ -1145,41 +1245,30 @@ def main():
             return child_line(args, config, ncell, domain, steps, args.warmup,
                               driver, timeout=min(300., left))
 
-        if ranks.rank == 0:
-            # (whatever happens here, the other ranks are released and the
-            # headline line is printed)
-            try:
-                leg = extra("lexington", ncell5, True, "torch")
-                keep = ALSO_KEYS + (
-                    "n_gpus", "ranks_in_collective",
-                    "packets_per_rank_per_step", "scaling",
-                    "exchange_rounds_last_step",
-                    "flights_exchanged_last_step", "idle_ms_per_step_by_rank",
-                    "emitted_packets_per_step_by_rank",
-                    "error")
-                rec = {k: leg[k] for k in keep if k in leg}
-                if "iterations_to_converge" in leg:
-                    rec["iterations_to_converge"] = \
-                        leg["iterations_to_converge"]["value"]
-                out["config5"] = rec
-                out["native"] = {
-                    "replica": extra("stromgren", args.ncell, False,
-                                     "native"),
-                    "config5": extra("lexington", ncell5, True, "native")}
-            except Exception as e:  # noqa: BLE001 - recorded, not raised
-                out.setdefault("config5", {})["error"] = \
-                    "extras failed: %s: %s" % (type(e).__name__, e)
-            finally:
-                out["bench_wall_s"] = time.perf_counter() - t_start
-                store.set("cmi_bench_extras_done", "1")
-        else:
-            store.wait(["cmi_bench_extras_done"],
-                       timedelta(seconds=EXTRAS_BUDGET_S + 600))
-    if ranks.rank == 0:
-        print(json.dumps(out))
-    if ranks.world > 1:
-        ranks.dist.barrier()
-        ranks.dist.destroy_process_group()
+        # (whatever happens here, the headline line is printed)
+        try:
+            leg = extra("lexington", ncell5, True, "torch")
+            keep = ALSO_KEYS + (
+                "n_gpus", "ranks_in_collective",
+                "packets_per_rank_per_step", "scaling",
+                "exchange_rounds_last_step",
+                "flights_exchanged_last_step", "idle_ms_per_step_by_rank",
+                "emitted_packets_per_step_by_rank",
+                "error")
+            rec = {k: leg[k] for k in keep if k in leg}
+            if "iterations_to_converge" in leg:
+                rec["iterations_to_converge"] = \
+                    leg["iterations_to_converge"]["value"]
+            out["config5"] = rec
+            out["native"] = {
+                "replica": extra("stromgren", args.ncell, False, "native"),
+                "config5": extra("lexington", ncell5, True, "native")}
+        except Exception as e:  # noqa: BLE001 - recorded, not raised
+            out.setdefault("config5", {})["error"] = \
+                "extras failed: %s: %s" % (type(e).__name__, e)
+        finally:
+            out["bench_wall_s"] = time.perf_counter() - t_start
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

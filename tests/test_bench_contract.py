@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -38,11 +40,50 @@ def test_driver_command_line_defaults(monkeypatch):
     assert args.packets == 1e8 and args.converge_packets == 1e8
     assert args.driver == "torch" and args.decomposition == "replica"
     assert not args.no_also and not args.no_cpu_baseline
+    # a plain run: the headline figure alone, no outputs written
+    assert not args.full and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs",
+                                      "out"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "out"
     # BASELINE.json's three single-GPU configs
     assert sorted(bench.CONFIGS) == ["lexington", "stromgren",
                                      "stromgren_diffuse"]
     assert bench.CONFIGS["stromgren"]["bytes_per_step"] == 32.
     assert bench.CONFIGS["lexington"]["bytes_per_step"] == 280.
+
+
+class _FakeEngine:
+    """download_field of a fake engine: the field's number in every cell"""
+
+    def __init__(self, n):
+        self.n = n
+
+    def download_field(self, field):
+        return np.full(self.n, float(field))
+
+
+def test_dumped_outputs_are_a_fixed_sample_below_the_limit(tmp_path):
+    import bench
+    from cmacionize_amd import engine as E
+    for config, nfields in (("stromgren", 2), ("lexington", 31)):
+        out = [tmp_path / ("%s_%d" % (config, k)) for k in range(2)]
+        for d in out:
+            bench.dump_outputs(str(d), _FakeEngine(256 ** 3),
+                               bench.CONFIGS[config],
+                               (1e8, np.arange(4.), 12345), suffix="")
+        names = sorted(os.listdir(str(out[0])))
+        assert len(names) == nfields + 1 and "counters.npy" in names
+        assert sum(os.path.getsize(str(out[0] / n)) for n in names) < \
+            64 << 20
+        for name in names:
+            a = np.load(str(out[0] / name))
+            assert a.dtype == np.float64
+            assert np.array_equal(a, np.load(str(out[1] / name)))
+        assert list(np.load(str(out[0] / "counters.npy"))) == \
+            [1e8, 0., 1., 2., 3., 12345.]
+        x = np.load(str(out[0] / "ionic_fraction_00.npy"))
+        assert (x == E.FIELD_IONIC_FRACTION).all() and x.size > 1e5
 
 
 def test_roofline_without_a_profile_says_so():

@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -72,15 +73,15 @@ def test_two_ranks_replica_and_domain_reach_the_one_rank_state():
 
 
 def test_default_line_carries_the_other_single_gpu_configs():
-    """The driver's command (`bench.py --gpus 1`, default config) prints the
-    headline config's line with the other two single-GPU configs of
+    """The full command (`bench.py --gpus 1 --full`, default config) prints
+    the headline config's line with the other two single-GPU configs of
     BASELINE.json under `also`, each with its own value, roofline and CPU
     baseline, timed one after the other on the same device."""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps",
                         "3", "--warmup", "1", "--ncell", "48", "--packets",
-                        "2e5", "--converge-iterations", "6"],
+                        "2e5", "--converge-iterations", "6", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -104,6 +105,51 @@ def test_default_line_carries_the_other_single_gpu_configs():
         line["dda_steps_per_packet"]
     assert "roofline_cell_update" in line["also"]["lexington"]
     assert line["bench_wall_s"] > 0.
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline
+    line alone - no CPU baseline, no `also` legs; --dump-outputs writes what
+    the last timed step computed as float64 .npy files, and two runs with the
+    same arguments give the same outputs up to the order of the atomics."""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--ncell", "32", "--packets", "1e5",
+           "--converge-iterations", "2"]
+    lines = []
+    for k in range(2):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / str(k))],
+                           cwd=ROOT, env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1, r.stdout
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0.
+    assert abs(line["ms_per_step"] * 1e-3 * line["value"] - 1e5) < 1.
+    for key in ("cpu_baseline", "also", "strong_scaling", "config5"):
+        assert key not in line
+    names = sorted(os.listdir(str(tmp_path / "0")))
+    assert names == ["counters.npy", "ionic_fraction_00.npy",
+                     "mean_intensity_00.npy"]
+    got = [{n: np.load(str(tmp_path / str(k) / n)) for n in names}
+           for k in range(2)]
+    for name in names:
+        assert got[0][name].dtype == np.float64
+        assert got[0][name].shape == got[1][name].shape
+    x = got[0]["ionic_fraction_00.npy"]
+    assert x.shape == (32 ** 3,) and (x >= 0.).all() and (x <= 1.).all()
+    assert (got[0]["mean_intensity_00.npy"] > 0.).any()
+    # total weight = packets of the step (weight 1 each), then the 4 types
+    # and the DDA steps
+    counters = got[0]["counters.npy"]
+    assert counters.shape == (6,) and counters[0] == 1e5
+    assert counters[5] > 0.
+    assert got[1]["counters.npy"][0] == 1e5
+    rel = np.abs(x - got[1]["ionic_fraction_00.npy"]) / np.maximum(x, 1e-300)
+    assert np.median(rel) < 1e-6
 
 
 def test_more_ranks_than_gpus_is_refused():
@@ -147,13 +193,13 @@ def test_eight_ranks_on_one_device():
         assert len(lines) == 1, r.stdout
         return json.loads(lines[0])
 
-    # the driver's command as it stands (no --no-also): the line of N > 1
-    # ranks also carries config 5's shape over torch.distributed and the
-    # native group driver (one process, eight engines) on both shapes
+    # the full command (--full, no --no-also): the line of N > 1 ranks also
+    # carries config 5's shape over torch.distributed and the native group
+    # driver (one process, eight engines) on both shapes
     import time
     small.remove("--no-also")
     t0 = time.perf_counter()
-    replica = run(8, ["--config5-ncell", "48"])
+    replica = run(8, ["--full", "--config5-ncell", "48"])
     # the driver allows a scaling run 25 minutes; the extras have a budget of
     # 420 s of their own (bench.py EXTRAS_BUDGET_S)
     assert time.perf_counter() - t0 < 25 * 60

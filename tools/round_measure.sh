@@ -26,12 +26,12 @@ if [ -z "${SKIP_PMC:-}" ]; then
   cp "$OUT/counters.json" "$REPO/profiles/$ROUND/counters.json"
 fi
 for CFG in stromgren stromgren_diffuse lexington; do
-  python3 bench.py --config $CFG --no-also > "$OUT/bench_$CFG.json" 2> "$OUT/bench_$CFG.err"
+  python3 bench.py --config $CFG --full --no-also > "$OUT/bench_$CFG.json" 2> "$OUT/bench_$CFG.err"
   echo "bench $CFG rc=$?"
 done
-# the round driver's own command: the headline line with the other two
-# single-GPU configs under "also"
-( time python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+# the full command: the headline line with the other two single-GPU configs
+# under "also"
+( time python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ) > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 echo "bench default rc=$?"
 cd /tmp
 for CFG in stromgren stromgren_diffuse lexington; do
