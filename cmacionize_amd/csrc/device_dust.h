@@ -1,0 +1,468 @@
+/*
+ * device_dust.h - device functions of the dusty radiative transfer mode
+ * (DustSimulation, src/DustSimulation.cpp:67-186): Henyey-Greenstein
+ * scattering with Stokes parameters, the peel-off towards the observer, the
+ * spiral galaxy source and the CCD projection.
+ *
+ * Random numbers of packet i (stream seed = DustSimulation:random seed,
+ * iteration 0, packet i), in the order DustPhotonShootJob::execute
+ * (src/DustPhotonShootJob.hpp:107-164) draws them:
+ *   1   PhotonSource::get_random_photon's selector (src/PhotonSource.cpp:217;
+ *       always continuous here, the value is not used)
+ *   2.. SpiralGalaxyContinuousPhotonSource::get_random_incoming_direction
+ *       (src/SpiralGalaxyContinuousPhotonSource.hpp:277-340), per attempt of
+ *       the rejection loop: bulge/disc selector, then bulge {u, phi, cos} or
+ *       disc {u1, phi, u2}; attempts repeat until the position is in the box
+ *   +2  the source's isotropic direction (PhotonSource::get_random_direction),
+ *       which the job throws away
+ *   +2  the job's own direction {cos theta, phi}
+ *   +1  the forced first optical depth, -log(1 - u (1 - exp(-tau_max)))
+ *   then per scattering: DustScattering::scatter's HG cosine, its azimuth
+ *   (only if |cos| != 1), and the next optical depth -log(u).
+ * The CPU restatement (tests/support/dust_reference.c) draws in the same
+ * order.
+ */
+#ifndef CMI_DEVICE_DUST_H
+#define CMI_DEVICE_DUST_H
+
+#include "device_transport.h"
+
+/* scatterings after which a packet is stopped and counted (the reference has
+ * no cap: the albedo is a weight, a packet scatters until it leaves) */
+#define CMI_DUST_MAX_SCATTER 100000
+/* attempts of the source's rejection loop after which a packet is dropped
+ * and counted (the loop ends at once for a box centred on the origin; the
+ * host refuses boxes that do not contain it, this bounds the rest) */
+#define CMI_DUST_MAX_ATTEMPTS 1000000u
+
+/* everything the dust kernels read, by value */
+struct DustDev {
+  /* DustScattering (src/DustScattering.hpp): g, g^2, 1 - g^2, 2g, 1 - g,
+   * 1 / 2g, 1 + g^2, p_l, sc = 1, pc = 0, albedo */
+  double hgg, g2, omg2, thgg, omhgg, od2hgg, opg2, pl, sc, pc, albedo;
+  /* CCDImage (src/CCDImage.hpp:123-200): sin theta, cos theta, phi, sin phi,
+   * cos phi of the observer, its direction, resolution, anchor, sides */
+  double view[5];
+  double obs_dir[3];
+  double obs_inv_dir[3];
+  int32_t res[2];
+  double img_anchor[2], img_sides[2];
+  double *image; /* [3][res[0] * res[1]]: I, Q, U */
+  /* SpiralGalaxyContinuousPhotonSource (:98-150): box, bulge radii, disc
+   * scales, corrected B/T, the disc CDF {x[n], y[n]} */
+  double box_anchor[3], box_sides[3];
+  double rC, rB, rJ, r_stars, h_stars, bulge_to_total;
+  double rB_over_rJ_plus_rB, rC_over_rJ_plus_rC;
+  const double *cdf_x, *cdf_y;
+  int32_t cdf_n;
+};
+
+/* counters of a dust launch */
+struct DustCountersDev {
+  unsigned long long nsteps;    /* DDA steps, both marches */
+  unsigned long long nscatter;  /* scattering events */
+  unsigned long long ncapped;   /* packets stopped at CMI_DUST_MAX_SCATTER */
+  unsigned long long natomics;  /* fp64 atomics into the image */
+  unsigned long long npackets;
+  unsigned long long nsource_capped; /* packets the source gave no position
+                                        (CMI_DUST_MAX_ATTEMPTS) */
+  unsigned long long pad[2];
+};
+
+/* Photon with what the dust path reads: position, direction, its angles
+ * (src/Photon.hpp:165-228) and the Stokes vector (:229-250) */
+struct DustPhoton {
+  double pos[3];
+  double dir[3];
+  double inv_dir[3];
+  double par[5]; /* sin theta, cos theta, phi, sin phi, cos phi */
+  double stokes[4];
+};
+
+__device__ __forceinline__ void dust_set_direction(DustPhoton &p,
+                                                   const double d[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p.dir[a] = d[a];
+    p.inv_dir[a] = 1. / d[a];
+  }
+}
+
+/* Utilities::locate, src/Utilities.hpp:726-742 */
+__device__ __forceinline__ int dust_locate(double x, const double *xarr,
+                                           int length) {
+  int jl = 0, ju = length;
+  while (ju - jl > 1) {
+    const int jm = (ju + jl) >> 1;
+    if (x > xarr[jm])
+      jl = jm;
+    else
+      ju = jm;
+  }
+  if (jl == length - 1)
+    --jl;
+  return jl;
+}
+
+/* SpiralGalaxyContinuousPhotonSource::get_random_incoming_direction without
+ * the final direction (src/SpiralGalaxyContinuousPhotonSource.hpp:277-334):
+ * the rejection loop until Box::inside (src/Box.hpp:191-195). false: no
+ * position in the box after CMI_DUST_MAX_ATTEMPTS attempts (the reference
+ * would loop on) */
+__device__ inline bool dust_source_position(const DustDev &d, PacketRng &rng,
+                                            double pos[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    pos[a] = d.box_anchor[a] - d.box_sides[a];
+  auto inside = [&]() {
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      in &= pos[a] >= d.box_anchor[a] &&
+            pos[a] < d.box_anchor[a] + d.box_sides[a];
+    return in;
+  };
+  for (uint32_t attempt = 0; !inside(); ++attempt) {
+    if (attempt == CMI_DUST_MAX_ATTEMPTS)
+      return false;
+    const double x_bulge = rng.next();
+    if (x_bulge <= d.bulge_to_total) {
+      const double u = rng.next();
+      const double A =
+          u * d.rB_over_rJ_plus_rB + (1. - u) * d.rC_over_rJ_plus_rC;
+      const double r = d.rJ / (1. / A - 1.);
+      const double phi = 2. * M_PI * rng.next();
+      const double cost = 2. * rng.next() - 1.;
+      const double sint = sqrt(fmax(1. - cost * cost, 0.));
+      pos[0] = r * sint * cos(phi);
+      pos[1] = r * sint * sin(phi);
+      pos[2] = r * cost;
+    } else {
+      const double u1 = 2. * rng.next() - 1.;
+      const double z = (u1 > 0.) ? -d.h_stars * log(u1) : d.h_stars * log(-u1);
+      const double phi = 2. * M_PI * rng.next();
+      const double u2 = rng.next();
+      const int i = dust_locate(u2, d.cdf_y, d.cdf_n);
+      const double w = d.cdf_x[i] + (u2 - d.cdf_y[i]) /
+                                        (d.cdf_y[i + 1] - d.cdf_y[i]) *
+                                        (d.cdf_x[i + 1] - d.cdf_x[i]);
+      pos[0] = w * cos(phi);
+      pos[1] = w * sin(phi);
+      pos[2] = z;
+    }
+  }
+  return true;
+}
+
+/* the draws of DustPhotonShootJob::execute up to the first march
+ * (src/DustPhotonShootJob.hpp:113-127): selector, position, the discarded
+ * source direction, the job's direction; Stokes (1, 0, 0, 0)
+ * (src/Photon.hpp:89-92); false if the source found no position */
+__device__ __noinline__ bool dust_emit(const DustDev &d, PacketRng &rng,
+                                       DustPhoton &p) {
+  (void)rng.next();
+  if (!dust_source_position(d, rng, p.pos))
+    return false;
+  (void)rng.next();
+  (void)rng.next();
+  const double cost = 2. * rng.next() - 1.;
+  const double sint = sqrt(fmax(1. - cost * cost, 0.));
+  const double phi = 2. * M_PI * rng.next();
+  const double cosp = cos(phi);
+  const double sinp = sin(phi);
+  const double dir[3] = {sint * cosp, sint * sinp, cost};
+  dust_set_direction(p, dir);
+  p.par[0] = sint;
+  p.par[1] = cost;
+  p.par[2] = phi;
+  p.par[3] = sinp;
+  p.par[4] = cosp;
+  p.stokes[0] = 1.;
+  p.stokes[1] = 0.;
+  p.stokes[2] = 0.;
+  p.stokes[3] = 0.;
+  return true;
+}
+
+/* the march's packet for a photon: dust opacity records are {n kappa x_H, 0},
+ * so sigma_H = 1 and sigma_He_corr = 0 give tau = ds n kappa x_H
+ * (src/DensityGrid.hpp:118-140 at sigma_He = 0, x_He = 0) */
+__device__ __forceinline__ void dust_march_packet(const GridDev &g,
+                                                  const double pos[3],
+                                                  const double dir[3],
+                                                  const double inv_dir[3],
+                                                  Packet<false> &q) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    q.pos[a] = pos[a];
+    q.dir[a] = dir[a];
+    q.inv_dir[a] = inv_dir[a];
+  }
+  q.sigma_H = 1.;
+  q.sigma_He_corr = 0.;
+  locate_cell(g, q);
+}
+
+/* CartesianDensityGrid::integrate_optical_depth,
+ * src/CartesianDensityGrid.cpp:328-363; `cells` (if not null) receives the
+ * first max_cells cells */
+__device__ __noinline__ double
+dust_integrate(const GridDev &g, const double2 *__restrict__ opacity,
+               const double pos[3], const double dir[3],
+               const double inv_dir[3], unsigned long long &nsteps,
+               double *cells = nullptr, int max_cells = 0) {
+  Packet<false> q;
+  dust_march_packet(g, pos, dir, inv_dir, q);
+  q.tau = HUGE_VAL; /* never reached: the march ends at the box edge */
+  double optical_depth = 0.;
+  int n = 0;
+  while (is_inside(g, q)) {
+    int64_t cell;
+    double2 kappa;
+    const double ds = dda_step<false>(g, opacity, q, cell, kappa);
+    optical_depth += ds * fmax(kappa.x, 0.);
+    if (cells && n < max_cells)
+      cells[n] = (double)cell;
+    ++n;
+  }
+  nsteps += n;
+  return optical_depth;
+}
+
+/* CartesianDensityGrid::interact, src/CartesianDensityGrid.cpp:375-452,
+ * without the integrals: moves the photon; false = DensityGrid::end() (the
+ * photon left the box, or no step was taken) */
+__device__ __noinline__ bool dust_interact(const GridDev &g,
+                                     const double2 *__restrict__ opacity,
+                                     DustPhoton &p, double optical_depth,
+                                     unsigned long long &nsteps) {
+  Packet<false> q;
+  dust_march_packet(g, p.pos, p.dir, p.inv_dir, q);
+  q.tau = optical_depth;
+  int n = 0;
+  while (is_inside(g, q) && q.tau > 0.) {
+    int64_t cell;
+    double2 kappa;
+    (void)dda_step<false>(g, opacity, q, cell, kappa);
+    ++n;
+  }
+  nsteps += n;
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    p.pos[a] = q.pos[a];
+  return n > 0 && is_inside(g, q);
+}
+
+/* White (1979), eqs. 3-6: the elements P1..P4 of the dust's scattering matrix
+ * for the cosine mu of the scattering angle. The skew of eq. 6 is taken in
+ * radians for a scattering and in degrees for a peel-off, as the reference
+ * does in the two places (src/DustScattering.cpp:138-147, :374-380); the two
+ * round differently. */
+struct DustPhase {
+  double P1, P2, P3, P4;
+};
+
+__device__ __forceinline__ DustPhase dust_phase(const DustDev &d, double mu,
+                                                bool degrees) {
+  DustPhase m;
+  const double mu2 = mu * mu;
+  m.P1 = d.omg2 * pow(d.opg2 - d.thgg * mu, -1.5);
+  const double q = 1. / (1. + mu2);
+  m.P2 = -d.pl * m.P1 * (1. - mu2) * q;
+  m.P3 = 2. * m.P1 * mu * q;
+  double c;
+  if (degrees) {
+    const double t = acos(mu) * 180. * M_1_PI;
+    const double f = 3.13 * t * exp(-7. * t / 180.);
+    c = cos((t + d.sc * f) * M_PI / 180.);
+  } else {
+    const double t = acos(mu);
+    c = cos(t + d.sc * 3.13 * t * exp(-7. * t * M_1_PI));
+  }
+  const double c2 = c * c;
+  m.P4 = -d.pc * m.P1 * (1. - c2) / (1. + c2);
+  return m;
+}
+
+/* Code & Whitney (1995), eq. 2: the Stokes vector rotated into the
+ * scattering plane, scattered, rotated out of it. (c1, s1) and (c2, s2) are
+ * cos and sin of twice the two rotation angles; for an azimuth above pi the
+ * reference measures the angle the other way round, which flips the sign of
+ * every term odd in s1 or s2 (src/DustScattering.cpp:177-282, :391-491).
+ * `s` is normalised to I = 1 on the way in and scaled back on the way out. */
+__device__ __forceinline__ void dust_apply_phase(const DustPhase &m, double c1,
+                                                 double s1, double c2,
+                                                 double s2, bool mirror,
+                                                 double s[4]) {
+  const double I0 = s[0], r = 1. / I0;
+  const double v[4] = {1., s[1] * r, s[2] * r, s[3] * r};
+  const double ss = s2 * s1, cc = c2 * c1, sc = s2 * c1, cs = c2 * s1;
+  const double row0[3] = {m.P1, m.P2 * c1, mirror ? m.P2 * s1 : -m.P2 * s1};
+  const double row1[4] = {m.P2 * c2, m.P1 * cc - m.P3 * ss,
+                          mirror ? m.P1 * cs + m.P3 * sc
+                                 : -m.P1 * cs - m.P3 * sc,
+                          mirror ? -m.P4 * s2 : m.P4 * s2};
+  const double row2[4] = {mirror ? -m.P2 * s2 : m.P2 * s2,
+                          mirror ? -m.P1 * sc - m.P3 * cs
+                                 : m.P1 * sc + m.P3 * cs,
+                          -m.P1 * ss + m.P3 * cc, -m.P4 * c2};
+  const double row3[3] = {mirror ? -m.P4 * s1 : m.P4 * s1, m.P4 * c1, m.P3};
+  const double inv = 1. / m.P1;
+  const double o0 = (row0[0] * v[0] + row0[1] * v[1] + row0[2] * v[2]) * inv;
+  const double o1 = (row1[0] * v[0] + row1[1] * v[1] + row1[2] * v[2] +
+                     row1[3] * v[3]) *
+                    inv;
+  const double o2 = (row2[0] * v[0] + row2[1] * v[1] + row2[2] * v[2] +
+                     row2[3] * v[3]) *
+                    inv;
+  const double o3 = (row3[0] * v[1] + row3[1] * v[2] + row3[2] * v[3]) * inv;
+  s[0] = o0 * I0;
+  s[1] = o1 * I0;
+  s[2] = o2 * I0;
+  s[3] = o3 * I0;
+}
+
+/* cos and sin of twice an angle given its cos and sin */
+__device__ __forceinline__ void dust_double_angle(double c, double s,
+                                                  double &c2, double &s2) {
+  c2 = 2. * c * c - 1.;
+  s2 = 2. * s * c;
+}
+
+/* DustScattering::scatter, src/DustScattering.cpp:41-323: a scattering
+ * angle from the HG phase function (Witt 1977, eq. 19), an azimuth of the
+ * scattering plane, the new direction (Yusef-Zadeh, Morris & White 1984,
+ * eq. 16) and the Stokes vector through dust_apply_phase */
+__device__ __noinline__ void dust_scatter(const DustDev &d, PacketRng &rng,
+                                          DustPhoton &p) {
+  const double t = d.omg2 / (d.omhgg + d.thgg * rng.next());
+  const double mu = fmin(1., fmax(-1., d.od2hgg * (d.opg2 - t * t)));
+  if (fabs(mu) == 1.) {
+    /* straight on: nothing changes; straight back: the direction and U
+     * change sign, phi turns by pi */
+    if (mu == -1.) {
+      p.stokes[2] = -p.stokes[2];
+      const double back[3] = {-p.dir[0], -p.dir[1], -p.dir[2]};
+      dust_set_direction(p, back);
+      p.par[1] = -p.par[1];
+      p.par[2] += M_PI;
+      p.par[3] = -p.par[3];
+      p.par[4] = -p.par[4];
+    }
+    return;
+  }
+  const DustPhase m = dust_phase(d, mu, false);
+  const double smu = sqrt(fmax(0., 1. - mu * mu));
+  const double psi = 2. * M_PI * rng.next();
+  const bool mirror = psi > M_PI;
+  const double a1 = mirror ? 2. * M_PI - psi : psi;
+  const double c1 = cos(a1), s1 = sin(a1);
+  const double st0 = p.par[0], ct0 = p.par[1];
+  const double ct = ct0 * mu + st0 * smu * c1;
+  double st, s2, c2;
+  if (fabs(ct) < 1.) {
+    st = fabs(sqrt(1. - ct * ct));
+    s2 = s1 * st0 / st;
+    c2 = (ct0 - ct * mu) / (st * smu);
+  } else {
+    st = 0.;
+    s2 = 0.;
+    c2 = ct >= 1. ? -1. : 1.;
+  }
+  const double dphi = acos(fmin(1., fmax(-1., -c2 * c1 + s2 * s1 * mu)));
+  double ph = mirror ? p.par[2] + dphi : p.par[2] - dphi;
+  if (ph > 2. * M_PI)
+    ph -= 2. * M_PI;
+  if (ph < 0.)
+    ph += 2. * M_PI;
+  double cc1, ss1, cc2, ss2;
+  dust_double_angle(c1, s1, cc1, ss1);
+  dust_double_angle(c2, s2, cc2, ss2);
+  dust_apply_phase(m, cc1, ss1, cc2, ss2, mirror, p.stokes);
+  const double cph = cos(ph), sph = sin(ph);
+  const double dir[3] = {st * cph, st * sph, ct};
+  dust_set_direction(p, dir);
+  p.par[0] = st;
+  p.par[1] = ct;
+  p.par[2] = ph;
+  p.par[3] = sph;
+  p.par[4] = cph;
+}
+
+/* DustScattering::scatter_towards, src/DustScattering.cpp:325-518: the
+ * photon's Stokes vector after a scattering towards the observer (direction
+ * d.obs_dir, angles d.view); the photon takes the observer's direction.
+ * Returns the HG phase function per steradian. */
+__device__ __noinline__ double dust_scatter_towards(const DustDev &d,
+                                                    DustPhoton &p) {
+  const double mu = d.obs_dir[0] * p.dir[0] + d.obs_dir[1] * p.dir[1] +
+                    d.obs_dir[2] * p.dir[2];
+  if (fabs(mu) == 1.) {
+    if (mu == -1.)
+      p.stokes[2] = -p.stokes[2];
+  } else {
+    const DustPhase m = dust_phase(d, mu, true);
+    const double smu = sqrt(-(mu * mu - 1.));
+    const double st0 = p.par[0], ct0 = p.par[1];
+    const double so = d.view[0], co = d.view[1];
+    double r1;
+    if (st0 == 0.) {
+      r1 = M_PI;
+    } else {
+      const double y = sin(p.par[2] - d.view[2] - M_PI) * so / smu;
+      const double x = (co - ct0 * mu) / (st0 * smu);
+      r1 = atan2(y, x) + M_PI;
+    }
+    const bool mirror = r1 > M_PI;
+    const double a1 = mirror ? 2. * M_PI - r1 : r1;
+    const double c1 = cos(a1), s1 = sin(a1);
+    double s2, c2;
+    if (fabs(co) < 1.) {
+      s2 = s1 * st0 / so;
+      const double den = so * smu;
+      c2 = ct0 / den - co * mu / den;
+    } else {
+      s2 = 0.;
+      c2 = co >= 1. ? -1. : 1.;
+    }
+    double cc1, ss1, cc2, ss2;
+    dust_double_angle(c1, s1, cc1, ss1);
+    dust_double_angle(c2, s2, cc2, ss2);
+    dust_apply_phase(m, cc1, ss1, cc2, ss2, mirror, p.stokes);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p.dir[a] = d.obs_dir[a];
+    p.inv_dir[a] = d.obs_inv_dir[a];
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k)
+    p.par[k] = d.view[k];
+  return 0.25 * d.omg2 * pow(d.opg2 - d.thgg * mu, -1.5) * M_1_PI;
+}
+
+/* CCDImage::add_photon, src/CCDImage.hpp:242-270: the pixel (ix * ny + iy)
+ * a position projects to, or -1 outside the image */
+__device__ __forceinline__ int64_t dust_pixel(const DustDev &d,
+                                              const double pos[3]) {
+  const double cospo = d.view[4], sinpo = d.view[3], costo = d.view[1],
+               sinto = d.view[0];
+  double xphoton = pos[1] * cospo - pos[0] * sinpo;
+  double yphoton =
+      pos[2] * sinto - pos[1] * costo * sinpo - pos[0] * costo * cospo;
+  if (xphoton >= d.img_anchor[0] && yphoton >= d.img_anchor[1]) {
+    xphoton -= d.img_anchor[0];
+    yphoton -= d.img_anchor[1];
+    if (xphoton < d.img_sides[0] && yphoton < d.img_sides[1]) {
+      const uint32_t ix = (uint32_t)(d.res[0] * xphoton / d.img_sides[0]);
+      const uint32_t iy = (uint32_t)(d.res[1] * yphoton / d.img_sides[1]);
+      /* res x / sides can round up to res just below the far edge; the
+       * reference would index past its vectors there */
+      if (ix < (uint32_t)d.res[0] && iy < (uint32_t)d.res[1])
+        return (int64_t)ix * d.res[1] + iy;
+    }
+  }
+  return -1;
+}
+
+#endif

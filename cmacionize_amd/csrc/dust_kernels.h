@@ -1,0 +1,234 @@
+/*
+ * dust_kernels.h - kernels of the dusty radiative transfer mode: one thread
+ * per packet of DustPhotonShootJob::execute
+ * (src/DustPhotonShootJob.hpp:107-164). Both marches (interact up to an
+ * optical depth, integrate_optical_depth to the box edge) are dda_step over
+ * the per-cell records {n kappa x_H, 0} built by dust_opacity_kernel; the
+ * peel-off I, Q, U go into the image with fp64 atomics.
+ */
+#ifndef CMI_DUST_KERNELS_H
+#define CMI_DUST_KERNELS_H
+
+#include "device_dust.h"
+
+/* {n kappa x_H, 0} per cell (the march reads .x; .y is multiplied by
+ * sigma_He_corr = 0) */
+__global__ void __launch_bounds__(256)
+    dust_opacity_kernel(const double *__restrict__ number_density,
+                        const double *__restrict__ xH, double kappa,
+                        int64_t ncell, double2 *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ncell)
+    out[i] = make_double2(number_density[i] * kappa * xH[i], 0.);
+}
+
+/* what one packet contributes to the image: either atomics into d.image
+ * (TRACE = false) or the event rows {x, y, z, I, Q, U, V, weight} of a trace
+ * (the direct light first, then one row per scattering) */
+struct DustEvents {
+  double *rows;
+  int max_events;
+  int n;
+};
+
+template <bool TRACE>
+__device__ __forceinline__ void dust_add(const DustDev &d, const double pos[3],
+                                         double wi, double wq, double wu,
+                                         const double stokes[4], double weight,
+                                         DustEvents &ev,
+                                         unsigned long long &natomics) {
+  if (TRACE) {
+    if (ev.n < ev.max_events) {
+      double *r = ev.rows + 8 * ev.n;
+      r[0] = pos[0];
+      r[1] = pos[1];
+      r[2] = pos[2];
+      r[3] = stokes[0];
+      r[4] = stokes[1];
+      r[5] = stokes[2];
+      r[6] = stokes[3];
+      r[7] = weight;
+    }
+    ++ev.n;
+    return;
+  }
+  const int64_t pixel = dust_pixel(d, pos);
+  if (pixel < 0)
+    return;
+  const int64_t npixel = (int64_t)d.res[0] * d.res[1];
+  /* x + 0 == x: zero terms (Q and U of the direct light, a packet on a ray
+   * without dust) cost no atomic */
+  if (wi != 0.) {
+    atomicAdd(d.image + pixel, wi);
+    ++natomics;
+  }
+  if (wq != 0.) {
+    atomicAdd(d.image + npixel + pixel, wq);
+    ++natomics;
+  }
+  if (wu != 0.) {
+    atomicAdd(d.image + 2 * npixel + pixel, wu);
+    ++natomics;
+  }
+}
+
+/* DustPhotonShootJob::execute for one packet */
+template <bool TRACE>
+__device__ inline void dust_packet(const GridDev &g, const DustDev &d,
+                                   const double2 *__restrict__ opacity,
+                                   uint32_t seed, uint64_t id,
+                                   DustCountersDev &c, DustEvents &ev) {
+  PacketRng rng;
+  rng.init(seed, 0u, id);
+  DustPhoton p;
+  c.npackets += 1;
+  if (!dust_emit(d, rng, p)) {
+    c.nsource_capped += 1;
+    return;
+  }
+
+  /* direct light towards the observer, :127-130 */
+  const double tau_old =
+      dust_integrate(g, opacity, p.pos, d.obs_dir, d.obs_inv_dir, c.nsteps);
+  const double w_direct = 0.25 * exp(-tau_old) / M_PI;
+  const double unpolarised[4] = {1., 0., 0., 0.};
+  dust_add<TRACE>(d, p.pos, w_direct, 0., 0., unpolarised, w_direct, ev,
+                  c.natomics);
+
+  /* forced first interaction, :132-138 */
+  double albedo = 1.;
+  const double tau_max =
+      dust_integrate(g, opacity, p.pos, p.dir, p.inv_dir, c.nsteps);
+  const double weight = 1. - exp(-tau_max);
+  double tau = -log(1. - rng.next() * weight);
+  bool inside = dust_interact(g, opacity, p, tau, c.nsteps);
+  uint32_t nscatter = 0;
+  while (inside) {
+    /* peel-off, :141-155 */
+    DustPhoton peel = p;
+    const double hgfac = dust_scatter_towards(d, peel);
+    const double tau_new = dust_integrate(g, opacity, peel.pos, peel.dir,
+                                          peel.inv_dir, c.nsteps);
+    albedo *= d.albedo;
+    const double weight_new = weight * hgfac * albedo * exp(-tau_new);
+    dust_add<TRACE>(d, peel.pos, weight_new * peel.stokes[0],
+                    weight_new * peel.stokes[1], weight_new * peel.stokes[2],
+                    peel.stokes, weight_new, ev, c.natomics);
+    /* scatter and fly on, :157-159 */
+    dust_scatter(d, rng, p);
+    ++nscatter;
+    if (nscatter >= CMI_DUST_MAX_SCATTER) {
+      c.ncapped += 1;
+      break;
+    }
+    tau = -log(rng.next());
+    inside = dust_interact(g, opacity, p, tau, c.nsteps);
+  }
+  c.nscatter += nscatter;
+}
+
+/* sum of a 64-bit counter over the wave, added by its first active lane */
+__device__ __forceinline__ void dust_count(unsigned long long *dst,
+                                           unsigned long long v) {
+  for (int off = 32; off > 0; off >>= 1)
+    v += __shfl_down(v, off, 64);
+  if (threadIdx.x % 64 == 0 && v)
+    atomicAdd(dst, v);
+}
+
+/* packets [first, first + n) */
+__global__ void __launch_bounds__(256)
+    dust_shoot_kernel(GridDev g, DustDev d,
+                      const double2 *__restrict__ opacity, uint32_t seed,
+                      uint64_t first, uint64_t n, DustCountersDev *counters) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  DustCountersDev c = {};
+  DustEvents ev = {nullptr, 0, 0};
+  if (k < n)
+    dust_packet<false>(g, d, opacity, seed, first + k, c, ev);
+  /* the whole wave reaches the reduction (no early return above) */
+  dust_count(&counters->nsteps, c.nsteps);
+  dust_count(&counters->nscatter, c.nscatter);
+  dust_count(&counters->ncapped, c.ncapped);
+  dust_count(&counters->natomics, c.natomics);
+  dust_count(&counters->npackets, c.npackets);
+  dust_count(&counters->nsource_capped, c.nsource_capped);
+}
+
+enum {
+  DUST_PROBE_EMIT = 0,
+  DUST_PROBE_SCATTER = 1,
+  DUST_PROBE_SCATTER_TOWARDS = 2,
+  DUST_PROBE_OPTICAL_DEPTH = 3,
+  DUST_PROBE_TRACE = 4
+};
+
+/* the parity probes of cmi_gpu_dust_probe (include/cmi_gpu.h gives the row
+ * layouts); row k uses the stream of packet first + k */
+__global__ void __launch_bounds__(64)
+    dust_probe_kernel(GridDev g, DustDev d,
+                      const double2 *__restrict__ opacity, int32_t kind,
+                      uint32_t seed, uint64_t first, int64_t n, int32_t width,
+                      const double *__restrict__ in, double *__restrict__ out,
+                      int32_t max_events) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n)
+    return;
+  PacketRng rng;
+  rng.init(seed, 0u, first + k);
+  double *o = out + k * width;
+  if (kind == DUST_PROBE_EMIT) {
+    DustPhoton p;
+    const bool ok = dust_emit(d, rng, p);
+    for (int a = 0; a < 3; ++a) {
+      o[a] = ok ? p.pos[a] : __builtin_nan("");
+      o[3 + a] = ok ? p.dir[a] : __builtin_nan("");
+    }
+  } else if (kind == DUST_PROBE_SCATTER ||
+             kind == DUST_PROBE_SCATTER_TOWARDS) {
+    /* in: {dir[3], sin theta, cos theta, phi, sin phi, cos phi, I, Q, U, V} */
+    const double *r = in + k * 12;
+    DustPhoton p;
+    dust_set_direction(p, r);
+    for (int j = 0; j < 5; ++j)
+      p.par[j] = r[3 + j];
+    for (int j = 0; j < 4; ++j)
+      p.stokes[j] = r[8 + j];
+    for (int a = 0; a < 3; ++a)
+      p.pos[a] = 0.;
+    if (kind == DUST_PROBE_SCATTER) {
+      dust_scatter(d, rng, p);
+      for (int a = 0; a < 3; ++a)
+        o[a] = p.dir[a];
+      for (int j = 0; j < 5; ++j)
+        o[3 + j] = p.par[j];
+      for (int j = 0; j < 4; ++j)
+        o[8 + j] = p.stokes[j];
+    } else {
+      o[0] = dust_scatter_towards(d, p);
+      for (int j = 0; j < 4; ++j)
+        o[1 + j] = p.stokes[j];
+    }
+  } else if (kind == DUST_PROBE_OPTICAL_DEPTH) {
+    /* in: {pos[3], dir[3]}; out: {tau, nsteps, cells[max_events]} */
+    const double *r = in + k * 6;
+    double inv[3];
+    for (int a = 0; a < 3; ++a)
+      inv[a] = 1. / r[3 + a];
+    unsigned long long nsteps = 0;
+    o[0] = dust_integrate(g, opacity, r, r + 3, inv, nsteps, o + 2,
+                          max_events);
+    o[1] = (double)nsteps;
+  } else if (kind == DUST_PROBE_TRACE) {
+    /* out: {nevents, nscatter, nsteps, ncapped, rows[max_events][8]} */
+    DustCountersDev c = {};
+    DustEvents ev = {o + 4, max_events, 0};
+    dust_packet<true>(g, d, opacity, seed, first + k, c, ev);
+    o[0] = ev.n;
+    o[1] = (double)c.nscatter;
+    o[2] = (double)c.nsteps;
+    o[3] = (double)(c.ncapped + c.nsource_capped);
+  }
+}
+
+#endif

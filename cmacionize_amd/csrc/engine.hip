@@ -8,6 +8,7 @@
 #include "atomic_data.h"
 #include "linecooling_data.h"
 #include "kernels.h"
+#include "dust_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -215,6 +216,17 @@ struct cmi_gpu_engine {
      * generation (padded march / pre-computed emission rows) */
     bool block_first_kernels = true;
   } tune;
+
+  /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
+   * image [3][nx][ny], the source's disc CDF, the records {n kappa x_H, 0}
+   * and the counters */
+  DustDev dust = {};
+  double dust_kappa = 0.;
+  bool have_dust_scattering = false, have_ccd = false, have_dust_source = false;
+  double *dust_image = nullptr;
+  double *dust_cdf = nullptr;
+  double2 *dust_opacity = nullptr;
+  DustCountersDev *dust_counters = nullptr;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1091,6 +1103,10 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->tile_block);
   (void)hipFree(e->tile_counts);
   (void)hipFree(e->launch_steps);
+  (void)hipFree(e->dust_image);
+  (void)hipFree(e->dust_cdf);
+  (void)hipFree(e->dust_opacity);
+  (void)hipFree(e->dust_counters);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
   delete e;
@@ -3666,6 +3682,331 @@ int cmi_gpu_get_kernel_timing(cmi_gpu_engine *e, double *kernel_ms,
     *kernel_ms = k;
   if (kernel_launches)
     *kernel_launches = e->kernel_events.size();
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------ dusty radiative transfer -- */
+
+/* dust_shoot_kernel launches: the first takes CMI_DUST_FIRST_LAUNCH
+ * packets; every later one is sized from the DDA steps per packet measured so
+ * far so that it takes about CMI_DUST_STEPS_PER_LAUNCH steps (~20 ms at the
+ * measured 2.5e10 steps/s), between 64 and 2^20 packets. A dense medium, whose
+ * packets scatter many times, thus gets short launches too. */
+#define CMI_DUST_FIRST_LAUNCH (1ull << 14)
+#define CMI_DUST_MIN_LAUNCH 64ull
+#define CMI_DUST_MAX_LAUNCH (1ull << 20)
+#define CMI_DUST_STEPS_PER_LAUNCH (1ull << 29)
+/* rows per dust_probe_kernel launch */
+#define CMI_DUST_PROBE_LAUNCH (1ll << 14)
+
+int cmi_gpu_set_dust_scattering(cmi_gpu_engine *e, double g, double p_l,
+                                double albedo, double kappa) {
+  if (!e || !(g != 0.) || !(kappa >= 0.))
+    return fail(CMI_GPU_EINVAL, "set_dust_scattering: bad argument (g must "
+                                "be non-zero, kappa >= 0)");
+  /* DustScattering ctor, src/DustScattering.hpp:171-185 */
+  DustDev &d = e->dust;
+  d.hgg = g;
+  d.g2 = g * g;
+  d.omg2 = 1. - d.g2;
+  d.thgg = 2. * g;
+  d.omhgg = 1. - g;
+  d.od2hgg = 0.5 / g;
+  d.opg2 = 1. + d.g2;
+  d.pl = p_l;
+  d.sc = 1.;
+  d.pc = 0.;
+  d.albedo = albedo;
+  e->dust_kappa = kappa;
+  e->have_dust_scattering = true;
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_ccd_image(cmi_gpu_engine *e, double theta, double phi,
+                          int32_t nx, int32_t ny, const double *anchor,
+                          const double *sides) {
+  if (!e || nx <= 0 || ny <= 0 || !anchor || !sides || !(sides[0] > 0.) ||
+      !(sides[1] > 0.) || (int64_t)nx * ny > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "set_ccd_image: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  /* CCDImage ctor, src/CCDImage.hpp:123-160 */
+  DustDev &d = e->dust;
+  d.view[0] = std::sin(theta);
+  d.view[1] = std::cos(theta);
+  d.view[2] = phi;
+  d.view[3] = std::sin(phi);
+  d.view[4] = std::cos(phi);
+  d.obs_dir[0] = d.view[0] * d.view[4];
+  d.obs_dir[1] = d.view[0] * d.view[3];
+  d.obs_dir[2] = d.view[1];
+  for (int a = 0; a < 3; ++a)
+    d.obs_inv_dir[a] = 1. / d.obs_dir[a];
+  d.res[0] = nx;
+  d.res[1] = ny;
+  for (int a = 0; a < 2; ++a) {
+    d.img_anchor[a] = anchor[a];
+    d.img_sides[a] = sides[a];
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  /* no launch may see the old image once it is freed, whatever follows */
+  e->have_ccd = false;
+  (void)hipFree(e->dust_image);
+  e->dust_image = nullptr;
+  d.image = nullptr;
+  const size_t bytes = 3 * (size_t)nx * ny * sizeof(double);
+  HIP_TRY(hipMalloc(&e->dust_image, bytes));
+  d.image = e->dust_image;
+  e->have_ccd = true;
+  return cmi_gpu_reset_image(e);
+}
+
+int cmi_gpu_set_continuous_source_spiral_galaxy(cmi_gpu_engine *e,
+                                                double r_stars, double h_stars,
+                                                double bulge_over_total) {
+  if (!e || !(r_stars > 0.) || !(h_stars > 0.))
+    return fail(CMI_GPU_EINVAL,
+                "set_continuous_source_spiral_galaxy: bad argument");
+  /* the sampler assumes a box centred on the origin
+   * (src/SpiralGalaxyContinuousPhotonSource.hpp:112-113): its rejection loop
+   * would practically never end for a box away from the galaxy */
+  for (int a = 0; a < 3; ++a)
+    if (!(0. >= e->grid.anchor[a] &&
+          0. < e->grid.anchor[a] + e->grid.box_sides[a]))
+      return fail(CMI_GPU_EINVAL,
+                  "set_continuous_source_spiral_galaxy: the box must contain "
+                  "the origin (the galaxy's centre)");
+  HIP_TRY(hipSetDevice(e->device));
+  /* SpiralGalaxyContinuousPhotonSource ctor,
+   * src/SpiralGalaxyContinuousPhotonSource.hpp:98-150 */
+  DustDev &d = e->dust;
+  const double kpc = 3.086e19;
+  d.rC = 0.2 * kpc;
+  d.rB = 2. * kpc;
+  d.rJ = 0.4 * kpc;
+  d.r_stars = r_stars;
+  d.h_stars = h_stars;
+  d.rB_over_rJ_plus_rB = d.rB / (d.rB + d.rJ);
+  d.rC_over_rJ_plus_rC = d.rC / (d.rC + d.rJ);
+  d.bulge_to_total =
+      bulge_over_total * (1. - d.rC_over_rJ_plus_rC / d.rB_over_rJ_plus_rB);
+  for (int a = 0; a < 3; ++a) {
+    d.box_anchor[a] = e->grid.anchor[a];
+    d.box_sides[a] = e->grid.box_sides[a];
+  }
+  const double *A = d.box_anchor;
+  const double rmax = 1.2 * std::sqrt(A[0] * A[0] + A[1] * A[1] + A[2] * A[2]);
+  const int nbin = 1000;
+  std::vector<double> cdf(2 * (nbin + 1));
+  for (int i = 0; i < nbin; ++i) {
+    const double w = i * rmax / nbin;
+    const double x = w / r_stars;
+    cdf[i] = w;
+    cdf[nbin + 1 + i] = 1. - (1. + x) * std::exp(-x);
+  }
+  cdf[nbin] = rmax;
+  cdf[2 * nbin + 1] = 1.;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (!e->dust_cdf)
+    HIP_TRY(hipMalloc(&e->dust_cdf, cdf.size() * sizeof(double)));
+  HIP_TRY(hipMemcpy(e->dust_cdf, cdf.data(), cdf.size() * sizeof(double),
+                    hipMemcpyHostToDevice));
+  d.cdf_x = e->dust_cdf;
+  d.cdf_y = e->dust_cdf + nbin + 1;
+  d.cdf_n = nbin + 1;
+  e->have_dust_source = true;
+  return CMI_GPU_OK;
+}
+
+/* everything a dust launch needs; builds the records {n kappa x_H, 0} */
+static int dust_prepare(cmi_gpu_engine *e) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  const GridDev &g = e->grid;
+  if (g.decomposed)
+    return fail(CMI_GPU_ESTATE, "dust: not available on a block of a "
+                                "decomposed grid");
+  if (g.periodic[0] || g.periodic[1] || g.periodic[2])
+    return fail(CMI_GPU_EINVAL,
+                "dust: periodic boxes are not supported (the reference's "
+                "integrate_optical_depth never reaches the edge of a periodic "
+                "box, src/CartesianDensityGrid.cpp:187-227,341)");
+  if (!e->have_cells || !e->have_dust_scattering || !e->have_ccd ||
+      !e->have_dust_source)
+    return fail(CMI_GPU_ESTATE, "dust: upload_cells, set_dust_scattering, "
+                                "set_ccd_image and "
+                                "set_continuous_source_spiral_galaxy first");
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->dust_opacity)
+    HIP_TRY(hipMalloc(&e->dust_opacity, (size_t)e->ncell * sizeof(double2)));
+  if (!e->dust_counters) {
+    HIP_TRY(hipMalloc(&e->dust_counters, sizeof(DustCountersDev)));
+    HIP_TRY(hipMemsetAsync(e->dust_counters, 0, sizeof(DustCountersDev),
+                           e->stream));
+  }
+  const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
+  dust_opacity_kernel<<<blocks, 256, 0, e->stream>>>(
+      e->cells.number_density, e->cells.x[0], e->dust_kappa, e->ncell,
+      e->dust_opacity);
+  HIP_TRY(hipGetLastError());
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
+                       uint64_t n) {
+  int rc = dust_prepare(e);
+  if (rc)
+    return rc;
+  uint64_t size = CMI_DUST_FIRST_LAUNCH;
+  for (uint64_t done = 0; done < n;) {
+    const uint64_t chunk = std::min<uint64_t>(n - done, size);
+    /* only a launch that another follows is measured: both copies are
+     * waited for below, before these variables end */
+    const bool measure = done + chunk < n;
+    unsigned long long steps_before = 0, steps_after = 0;
+    if (measure)
+      HIP_TRY(hipMemcpyAsync(&steps_before, &e->dust_counters->nsteps,
+                             sizeof steps_before, hipMemcpyDeviceToHost,
+                             e->stream));
+    EventPair ev;
+    rc = timer_begin(e, ev);
+    if (rc)
+      return rc;
+    dust_shoot_kernel<<<(unsigned)((chunk + 255) / 256), 256, 0, e->stream>>>(
+        e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
+        e->dust_counters);
+    HIP_TRY(hipGetLastError());
+    rc = timer_end(e, e->shoot_events, ev, chunk);
+    if (rc)
+      return rc;
+    done += chunk;
+    if (measure) {
+      /* the next launch's size from this one's steps per packet */
+      HIP_TRY(hipMemcpyAsync(&steps_after, &e->dust_counters->nsteps,
+                             sizeof steps_after, hipMemcpyDeviceToHost,
+                             e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      const double per_packet =
+          std::max(1., (double)(steps_after - steps_before) / (double)chunk);
+      size = (uint64_t)std::min<double>(
+          (double)CMI_DUST_MAX_LAUNCH,
+          std::max<double>((double)CMI_DUST_MIN_LAUNCH,
+                           (double)CMI_DUST_STEPS_PER_LAUNCH / per_packet));
+    }
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_get_dust_counters(cmi_gpu_engine *e, uint64_t *counters) {
+  if (!e || !counters)
+    return fail(CMI_GPU_EINVAL, "get_dust_counters: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  DustCountersDev c = {};
+  if (e->dust_counters)
+    HIP_TRY(hipMemcpy(&c, e->dust_counters, sizeof c, hipMemcpyDeviceToHost));
+  counters[0] = c.nsteps;
+  counters[1] = c.nscatter;
+  counters[2] = c.ncapped;
+  counters[3] = c.natomics;
+  counters[4] = c.npackets;
+  counters[5] = c.nsource_capped;
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
+                           double *U) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (!e->have_ccd)
+    return fail(CMI_GPU_ESTATE, "download_image: no image (set_ccd_image)");
+  uint64_t c[6];
+  int rc = cmi_gpu_get_dust_counters(e, c);
+  if (rc)
+    return rc;
+  if (c[5])
+    return fail(CMI_GPU_ESTATE,
+                "download_image: the source found no position in the box for "
+                "%llu packet(s) in %u attempts; the image is incomplete",
+                (unsigned long long)c[5], CMI_DUST_MAX_ATTEMPTS);
+  if (c[2])
+    return fail(CMI_GPU_ESTATE,
+                "download_image: %llu packet(s) reached the cap of %d "
+                "scatterings; the image is incomplete",
+                (unsigned long long)c[2], CMI_DUST_MAX_SCATTER);
+  const size_t npixel = (size_t)e->dust.res[0] * e->dust.res[1];
+  double *dst[3] = {I, Q, U};
+  for (int k = 0; k < 3; ++k)
+    if (dst[k])
+      HIP_TRY(hipMemcpy(dst[k], e->dust_image + k * npixel,
+                        npixel * sizeof(double), hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_reset_image(cmi_gpu_engine *e) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (e->dust_image)
+    HIP_TRY(hipMemsetAsync(e->dust_image, 0,
+                           3 * (size_t)e->dust.res[0] * e->dust.res[1] *
+                               sizeof(double),
+                           e->stream));
+  if (e->dust_counters)
+    HIP_TRY(hipMemsetAsync(e->dust_counters, 0, sizeof(DustCountersDev),
+                           e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
+                       uint64_t first_packet, int64_t n, const double *in,
+                       double *out, int32_t max_events) {
+  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_TRACE ||
+      max_events < 0 || n > (1 << 24))
+    return fail(CMI_GPU_EINVAL, "dust_probe: bad argument");
+  static const int in_width[5] = {0, 12, 12, 6, 0};
+  const int width = kind == DUST_PROBE_EMIT              ? 6
+                    : kind == DUST_PROBE_SCATTER         ? 12
+                    : kind == DUST_PROBE_SCATTER_TOWARDS ? 5
+                    : kind == DUST_PROBE_OPTICAL_DEPTH   ? 2 + max_events
+                                                         : 4 + 8 * max_events;
+  if (in_width[kind] && !in)
+    return fail(CMI_GPU_EINVAL, "dust_probe: input rows missing");
+  int rc = dust_prepare(e);
+  if (rc)
+    return rc;
+  if (n == 0)
+    return CMI_GPU_OK;
+  double *din = nullptr, *dout = nullptr;
+  const size_t in_bytes = (size_t)n * in_width[kind] * sizeof(double);
+  const size_t out_bytes = (size_t)n * width * sizeof(double);
+  HIP_TRY(hipMalloc(&dout, out_bytes));
+  hipError_t err = hipSuccess;
+  if (in_bytes) {
+    err = hipMalloc(&din, in_bytes);
+    if (err == hipSuccess)
+      err = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice);
+  }
+  if (err == hipSuccess)
+    err = hipMemsetAsync(dout, 0, out_bytes, e->stream);
+  /* short launches: a row of a trace can be a whole packet */
+  for (int64_t k = 0; err == hipSuccess && k < n; k += CMI_DUST_PROBE_LAUNCH) {
+    const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
+    dust_probe_kernel<<<(unsigned)((m + 63) / 64), 64, 0, e->stream>>>(
+        e->grid, e->dust, e->dust_opacity, kind, seed, first_packet + k, m,
+        width, din ? din + k * in_width[kind] : nullptr, dout + k * width,
+        max_events);
+    err = hipGetLastError();
+    if (err == hipSuccess)
+      err = hipStreamSynchronize(e->stream);
+  }
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  HIP_TRY(err);
   return CMI_GPU_OK;
 }
 

@@ -30,6 +30,9 @@ CONTINUOUS_NONE, CONTINUOUS_ISOTROPIC, CONTINUOUS_PLANAR = 0, 1, 2
 # cmi_gpu_set_*_table (the generic lowering of a plugin into a table)
 ROLE_SOURCE, ROLE_CONTINUOUS = 0, 1
 TABLE_LINEAR, TABLE_LOGLOG = 0, 1
+# cmi_gpu_dust_probe kinds
+DUST_PROBE_EMIT, DUST_PROBE_SCATTER, DUST_PROBE_SCATTER_TOWARDS = 0, 1, 2
+DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
 
 _dp = C.POINTER(C.c_double)
 
@@ -95,6 +98,10 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_get_tracker_counts", "cmi_gpu_set_trackers",
     "cmi_gpu_get_tracker_absorption", "cmi_gpu_set_tracker_frequency_bins",
     "cmi_gpu_get_tracker_flux", "cmi_gpu_projected_areas",
+    "cmi_gpu_set_dust_scattering", "cmi_gpu_set_ccd_image",
+    "cmi_gpu_set_continuous_source_spiral_galaxy", "cmi_gpu_dust_shoot",
+    "cmi_gpu_download_image", "cmi_gpu_reset_image",
+    "cmi_gpu_get_dust_counters", "cmi_gpu_dust_probe",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -235,6 +242,18 @@ def load_library():
         vp, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]
     L.cmi_gpu_group_exchange_stats.argtypes = [
         vp, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_int32]
+    L.cmi_gpu_set_dust_scattering.argtypes = [vp, C.c_double, C.c_double,
+                                              C.c_double, C.c_double]
+    L.cmi_gpu_set_ccd_image.argtypes = [vp, C.c_double, C.c_double, C.c_int32,
+                                        C.c_int32, _dp, _dp]
+    L.cmi_gpu_set_continuous_source_spiral_galaxy.argtypes = [
+        vp, C.c_double, C.c_double, C.c_double]
+    L.cmi_gpu_dust_shoot.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64]
+    L.cmi_gpu_download_image.argtypes = [vp, _dp, _dp, _dp]
+    L.cmi_gpu_reset_image.argtypes = [vp]
+    L.cmi_gpu_get_dust_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cmi_gpu_dust_probe.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint64,
+                                     C.c_int64, _dp, _dp, C.c_int32]
     _lib = L
     return L
 
@@ -755,6 +774,62 @@ class GpuEngine:
         out = np.zeros((rows.shape[0], width_out))
         self._check(self._lib.cmi_gpu_physics_probe(
             self._h, kind, rows.shape[0], _p(rows), _p(out)))
+        return out
+
+    # dusty radiative transfer ------------------------------------------------
+    def set_dust_scattering(self, g, p_l, albedo, kappa):
+        self._check(self._lib.cmi_gpu_set_dust_scattering(
+            self._h, g, p_l, albedo, kappa))
+
+    def set_ccd_image(self, theta, phi, nx, ny, anchor, sides):
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        self._check(self._lib.cmi_gpu_set_ccd_image(
+            self._h, theta, phi, int(nx), int(ny), _p(a), _p(s)))
+        self.image_shape = (int(nx), int(ny))
+
+    def set_continuous_source_spiral_galaxy(self, r_stars, h_stars,
+                                            bulge_over_total):
+        self._check(self._lib.cmi_gpu_set_continuous_source_spiral_galaxy(
+            self._h, r_stars, h_stars, bulge_over_total))
+
+    def dust_shoot(self, seed, first_packet, n):
+        self._check(self._lib.cmi_gpu_dust_shoot(self._h, seed, first_packet,
+                                                 n))
+
+    def download_image(self):
+        """I, Q, U as an array of shape (3, nx, ny), unnormalised"""
+        out = np.zeros((3,) + self.image_shape)
+        self._check(self._lib.cmi_gpu_download_image(
+            self._h, _p(out[0]), _p(out[1]), _p(out[2])))
+        return out
+
+    def reset_image(self):
+        self._check(self._lib.cmi_gpu_reset_image(self._h))
+
+    def get_dust_counters(self):
+        c = (C.c_uint64 * 6)()
+        self._check(self._lib.cmi_gpu_get_dust_counters(self._h, c))
+        return dict(zip(("nsteps", "nscatter", "ncapped", "natomics",
+                         "npackets", "nsource_capped"), (int(v) for v in c)))
+
+    def dust_probe(self, kind, seed, first_packet, n, rows=None,
+                   max_events=0):
+        """Device dust functions, one row per packet (include/cmi_gpu.h,
+        cmi_gpu_dust_probe); returns the output rows."""
+        width = {DUST_PROBE_EMIT: 6, DUST_PROBE_SCATTER: 12,
+                 DUST_PROBE_SCATTER_TOWARDS: 5,
+                 DUST_PROBE_OPTICAL_DEPTH: 2 + max_events,
+                 DUST_PROBE_TRACE: 4 + 8 * max_events}[kind]
+        in_width = {DUST_PROBE_SCATTER: 12, DUST_PROBE_SCATTER_TOWARDS: 12,
+                    DUST_PROBE_OPTICAL_DEPTH: 6}.get(kind, 0)
+        inp = None
+        if in_width:
+            inp = _f64(rows).reshape(n, in_width)
+        out = np.zeros((n, width))
+        self._check(self._lib.cmi_gpu_dust_probe(
+            self._h, kind, seed, first_packet, n,
+            _p(inp) if inp is not None else None, _p(out), max_events))
         return out
 
     def get_timing(self, reset=True):

@@ -114,6 +114,45 @@ public:
   virtual DensityValues operator()(const Cell &cell) = 0;
 };
 
+/* src/SpiralGalaxyDensityFunction.hpp:73-130: the dusty disc of the
+ * DustSimulation mode (which constructs it directly, whatever
+ * DensityFunction:type says). n_0 is turned into a mass density
+ * (x 1.674e-27 kg); zero beyond 15 kpc; x_H = 1, x_He = 0. */
+class SpiralGalaxyDensityFunction : public DensityFunction {
+  const double _r_ISM, _h_ISM, _n_0, _kpc;
+
+public:
+  SpiralGalaxyDensityFunction(double rdust, double hdust, double n_0)
+      : _r_ISM(rdust), _h_ISM(hdust), _n_0(1.674e-27 * n_0), _kpc(3.086e19) {}
+  explicit SpiralGalaxyDensityFunction(ParameterFile &params)
+      : SpiralGalaxyDensityFunction(
+            params.get_physical_value(QUANTITY_LENGTH,
+                                      "DensityFunction:scale length ISM",
+                                      "6. kpc"),
+            params.get_physical_value(QUANTITY_LENGTH,
+                                      "DensityFunction:scale height ISM",
+                                      "0.22 kpc"),
+            params.get_physical_value(QUANTITY_NUMBER_DENSITY,
+                                      "DensityFunction:central density",
+                                      "1. cm^-3")) {}
+  double central_density() const { return _n_0; }
+  double scale_length() const { return _r_ISM; }
+  double scale_height() const { return _h_ISM; }
+  DensityValues operator()(const Cell &cell) override {
+    const CoordinateVector x = cell.get_cell_midpoint();
+    const double w = std::sqrt(x.x() * x.x() + x.y() * x.y());
+    double n = 0.;
+    if (w < 15. * _kpc && std::abs(x.z()) < 15. * _kpc)
+      n = _n_0 * std::exp(-w / _r_ISM) * std::exp(-std::abs(x.z()) / _h_ISM);
+    DensityValues values;
+    values.set_number_density(n);
+    values.set_ionic_fraction(ION_H_n, 1.);
+    values.set_ionic_fraction(ION_He_n, 0.);
+    values.set_temperature(0.);
+    return values;
+  }
+};
+
 /* src/HomogeneousDensityFunction.hpp:41-107 */
 class HomogeneousDensityFunction : public DensityFunction {
   const double _density, _temperature, _neutral_fraction_H;

@@ -9,9 +9,10 @@
  * (EmissivityCalculationSimulation.hpp), and --task-based: the run takes its
  * control parameters from the TaskBasedIonizationSimulation: block of the
  * file (src/CMacIonize.cpp:335-345, src/TaskBasedIonizationSimulation.cpp:
- * 190-260) instead of IonizationSimulation:. Flags that select other code paths
- * of the reference (--rhd, --dusty-radiative-transfer, --task-based-rhd) are
- * rejected.
+ * 190-260) instead of IonizationSimulation:, and the dusty radiative transfer
+ * mode --dusty-radiative-transfer (src/CMacIonize.cpp: DustSimulation,
+ * GpuDustSimulation.hpp). Flags that select other code paths of the reference
+ * (--rhd, --task-based-rhd) are rejected.
  * New: --device N (HIP device ordinal), --describe (print the lowered plugin
  * descriptors as JSON; with --dry-run no GPU is needed), --blocks BX,BY,BZ
  * (domain decomposition: one engine per block of the grid, the counterpart of
@@ -22,6 +23,7 @@
  * per device, 2^level at most).
  */
 #include "EmissivityCalculationSimulation.hpp"
+#include "GpuDustSimulation.hpp"
 #include "GpuIonizationSimulation.hpp"
 
 #include <cstring>
@@ -139,7 +141,7 @@ int main(int argc, char **argv) {
     return values;
   };
   bool dry_snapshot = false;
-  bool emission = false;
+  bool emission = false, dusty = false;
   std::string input_file;
   bool every_iteration = false, statistics = false, dry_run = false,
        verbose = false, do_describe = false, task_based = false;
@@ -171,6 +173,8 @@ int main(int argc, char **argv) {
       copies = std::atoi(need("--copies").c_str());
     else if (a == "--emission" || a == "-m")
       emission = true;
+    else if (a == "--dusty-radiative-transfer")
+      dusty = true;
     else if (a == "--file" || a == "-f")
       input_file = need("--file");
     else if (a == "--every-iteration-output" || a == "-e")
@@ -198,13 +202,26 @@ int main(int argc, char **argv) {
                    "[--task-based] [--every-iteration-output] [--output-statistics] "
                    "[--dry-run] [--dry-run-snapshot] [--describe] [--verbose]\n"
                    "       cmi-gpu --emission --params FILE --file "
-                   "SNAPSHOT.hdf5 [--device N]\n";
+                   "SNAPSHOT.hdf5 [--device N]\n"
+                   "       cmi-gpu --dusty-radiative-transfer --params FILE "
+                   "[--device N] [--dry-run] [--describe]\n";
       return 1;
     }
   }
   if (params.empty()) {
     std::cerr << "Required option --params missing\n";
     return 1;
+  }
+  if (dusty) {
+    /* src/CMacIonize.cpp: DustSimulation::do_simulation */
+    try {
+      GpuDustSimulation simulation(params);
+      return simulation.run(device, true, dry_run,
+                            verbose || !do_describe, do_describe);
+    } catch (std::exception &e) {
+      std::cerr << "Error: " << e.what() << std::endl;
+      return 1;
+    }
   }
   if (emission) {
     /* src/CMacIonize.cpp: the emission mode */

@@ -808,6 +808,95 @@ int cmi_gpu_get_launch_times(cmi_gpu_engine *engine, uint64_t capacity,
 int cmi_gpu_get_launch_steps(cmi_gpu_engine *engine, uint64_t capacity,
                              uint64_t *steps, uint64_t *count);
 
+/* ------------------------------------------ dusty radiative transfer -- */
+/* The reference's other mode on the Cartesian grid, `--dusty-radiative-
+ * transfer` (DustSimulation::do_simulation, src/DustSimulation.cpp:67-186):
+ * packets from a spiral galaxy source scatter off dust (Henyey-Greenstein
+ * phase function with Stokes parameters) until they leave the box; after
+ * every scattering a peel-off towards the observer adds I, Q, U to a CCD
+ * image. The grid is the engine's (cmi_gpu_create, not periodic, not a block
+ * of a decomposed grid); the densities come through cmi_gpu_upload_cells,
+ * whose number density is the dust's mass density (kg m^-3) and whose x_H is
+ * 1 (src/SpiralGalaxyDensityFunction.hpp:116-130). The march reads
+ * n kappa x_H per cell. Packet i draws from the stream (seed, iteration 0,
+ * packet i) in the order csrc/device_dust.h lists. */
+
+/* replaces: the DustScattering ctor (src/DustScattering.hpp:171-185, bands
+ * V / K :94-160): HG asymmetry g, peak linear polarisation p_l, albedo and
+ * the dust attenuation coefficient kappa (m^2 kg^-1); sc = 1, pc = 0 */
+int cmi_gpu_set_dust_scattering(cmi_gpu_engine *engine, double g, double p_l,
+                                double albedo, double kappa);
+
+/* replaces: the CCDImage ctor (src/CCDImage.hpp:123-160): view angles theta,
+ * phi (radians), resolution nx x ny, image anchor[2] and sides[2] (m). The
+ * image is I, Q, U of nx x ny pixels, pixel (ix, iy) at ix * ny + iy
+ * (src/CCDImage.hpp:242-270). A new call replaces and clears the image. */
+int cmi_gpu_set_ccd_image(cmi_gpu_engine *engine, double theta, double phi,
+                          int32_t nx, int32_t ny, const double *anchor,
+                          const double *sides);
+
+/* replaces: the SpiralGalaxyContinuousPhotonSource ctor
+ * (src/SpiralGalaxyContinuousPhotonSource.hpp:98-150): disc scale length and
+ * height (m) and the bulge-to-total ratio (corrected for the cut-off bulge
+ * centre as the reference does); the 1001-point disc CDF out to 1.2 x
+ * |box anchor| is built here. The box is the engine's and must contain the
+ * origin: the reference's sampler assumes a box centred on it (:112-113) and
+ * its rejection loop would practically never end otherwise (CMI_GPU_EINVAL).
+ * A packet whose source finds no position in the box in 1e6 attempts is
+ * dropped and counted; cmi_gpu_download_image then fails. */
+int cmi_gpu_set_continuous_source_spiral_galaxy(cmi_gpu_engine *engine,
+                                                double r_stars, double h_stars,
+                                                double bulge_over_total);
+
+/* replaces: DustPhotonShootJob::execute for packets [first_packet,
+ * first_packet + n) (src/DustPhotonShootJob.hpp:107-164), adding to the
+ * image, accumulating. The first launch takes 2^14 packets; each later one
+ * is sized from the DDA steps per packet measured so far to about 2^29 steps
+ * (between 64 and 2^20 packets), so the call waits for every launch but the
+ * last, which it leaves enqueued. A launch of a medium so dense that 64
+ * packets take more than 2^29 steps still runs longer: its bound is 64
+ * packets x 1e5 scatterings. A packet is stopped after 100000 scatterings and
+ * counted (the reference has no cap); cmi_gpu_download_image then fails.
+ * Periodic boxes are refused. */
+int cmi_gpu_dust_shoot(cmi_gpu_engine *engine, uint32_t seed,
+                       uint64_t first_packet, uint64_t n);
+
+/* replaces: the image buffers of CCDImage (src/CCDImage.hpp:60-70) as
+ * CCDImage::save reads them (:299-362), unnormalised. I, Q, U: host
+ * [nx * ny] each, any of them may be NULL. Synchronous; fails if a packet
+ * reached the scattering cap, or found no source position, since the last
+ * reset. */
+int cmi_gpu_download_image(cmi_gpu_engine *engine, double *I, double *Q,
+                           double *U);
+/* replaces: CCDImage::reset (src/CCDImage.hpp:226-232); also clears the
+ * dust counters. Synchronous. */
+int cmi_gpu_reset_image(cmi_gpu_engine *engine);
+
+/* counters since the last reset: counters[6] = {DDA steps of both marches,
+ * scatterings, packets stopped at the scattering cap, fp64 atomics into the
+ * image, packets, packets the source found no position for}. Synchronous. */
+int cmi_gpu_get_dust_counters(cmi_gpu_engine *engine, uint64_t *counters);
+
+/* Parity probes of the device functions (synchronous, in launches of 2^14
+ * rows); row k uses the random stream of packet first_packet + k with the
+ * given seed. Rows, fp64:
+ *  0 EMIT (src/DustPhotonShootJob.hpp:113-125): out {pos[3], dir[3]}, NaN if
+ *    the source found no position
+ *  1 SCATTER (src/DustScattering.cpp:41-323): in {dir[3], sin theta,
+ *    cos theta, phi, sin phi, cos phi, I, Q, U, V}; out the same after
+ *  2 SCATTER_TOWARDS (src/DustScattering.cpp:325-518): in as 1; out
+ *    {hgfac, I, Q, U, V}
+ *  3 OPTICAL_DEPTH (src/CartesianDensityGrid.cpp:328-363): in {pos[3],
+ *    dir[3]}; out {tau, steps, first max_events cells}
+ *  4 TRACE (src/DustPhotonShootJob.hpp:107-164): out {events, scatterings,
+ *    steps, capped (either cap), rows[max_events] of {pos[3], I, Q, U, V,
+ *    weight}}: the
+ *    direct light (Stokes 1, 0, 0, 0, weight 0.25 exp(-tau) / pi), then
+ *    each peel-off */
+int cmi_gpu_dust_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
+                       uint64_t first_packet, int64_t n, const double *in,
+                       double *out, int32_t max_events);
+
 #ifdef __cplusplus
 }
 #endif
