@@ -12,6 +12,7 @@
 #include "sort.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -40,6 +41,13 @@ int fail(int code, const char *fmt, ...) {
     if (err__ != hipSuccess)                                                   \
       return fail(CMI_GPU_EDEVICE, "%s failed: %s (%s:%d)", #expr,             \
                   hipGetErrorString(err__), __FILE__, __LINE__);               \
+  } while (0)
+/* ... and for the functions of this file that return a CMI_GPU_* code */
+#define CMI_TRY(expr)                                                          \
+  do {                                                                         \
+    const int rc__ = (expr);                                                   \
+    if (rc__)                                                                  \
+      return rc__;                                                             \
   } while (0)
 
 struct EventPair {
@@ -177,7 +185,6 @@ struct cmi_gpu_engine {
     uint64_t tile_min_flights = 100000;
     int tile_min_per_item = -1; /* flights per unit of work; -1 = auto */
     int tile_refill_threshold = 48;
-    int tile_max_rounds = 1000;
     bool tile_counting_sort = true; /* false: rocPRIM radix sort of the slots */
     /* multi-ion runs: the cross sections of re-emitted flights in a kernel of
      * their own (flight_weights_kernel) instead of inside the interaction
@@ -208,13 +215,6 @@ struct cmi_gpu_engine {
     /* the first generation parks an absorbed packet at the place of its
      * position in the launch's order (no queue counter) */
     bool park_in_place = true;
-    /* a block of a decomposed grid picks its own packets out of a launch's
-     * ids before keys, sort and transport (block_select_kernel); 0: every
-     * packet goes through them and the transport kernel drops the others */
-    bool block_select = true;
-    /* ... and flies them with the kernels built for a whole grid's first
-     * generation (padded march / pre-computed emission rows) */
-    bool block_first_kernels = true;
   } tune;
 
   /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
@@ -239,6 +239,22 @@ struct cmi_gpu_engine {
 };
 
 namespace {
+
+/* A device buffer that only grows: make sure `ptr` holds `want` units, `bytes`
+ * in all. The contents are not kept; launches still in flight may read the old
+ * buffer, so the stream runs dry before it goes. */
+template <class T, class N>
+int grow(cmi_gpu_engine *e, T *&ptr, N &capacity, N want, size_t bytes) {
+  if (capacity >= want)
+    return CMI_GPU_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  (void)hipFree(ptr);
+  ptr = nullptr;
+  capacity = 0;
+  HIP_TRY(hipMalloc(&ptr, bytes));
+  capacity = want;
+  return CMI_GPU_OK;
+}
 
 #define CMI_MAX_TIMED_LAUNCHES 65536
 /* start / stop of a timed region on the engine's stream; no-ops unless timing
@@ -329,11 +345,7 @@ static int ensure_mailbox(cmi_gpu_engine *e) {
 }
 
 static int download_counters(cmi_gpu_engine *e, CountersDev &sum) {
-  {
-    int rc = ensure_mailbox(e);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(ensure_mailbox(e));
   static_assert(sizeof(CountersDev) <= 16 * sizeof(unsigned int),
                 "the counters fit the mailbox");
   counters_sum_kernel<<<1, 256, 0, e->stream>>>(
@@ -1296,10 +1308,8 @@ int cmi_gpu_set_spectrum_table(cmi_gpu_engine *e, int32_t role, int32_t n,
       return fail(CMI_GPU_EINVAL,
                   "cmi_gpu_set_spectrum_table: frequency %d is not positive",
                   i);
-  int rc = store_user_table(e, role, e->model.spectrum_table[role], n, 1,
-                            cumulative, frequency, interpolation);
-  if (rc)
-    return rc;
+  CMI_TRY(store_user_table(e, role, e->model.spectrum_table[role], n, 1,
+                           cumulative, frequency, interpolation));
   if (role == CMI_GPU_ROLE_SOURCE) {
     e->model.spectrum_type = CMI_GPU_SPECTRUM_TABLE;
     e->have_spectrum = true;
@@ -1327,10 +1337,8 @@ int cmi_gpu_set_cross_sections_table(cmi_gpu_engine *e, int32_t n,
                   "cmi_gpu_set_cross_sections_table: cross section %zu of ion "
                   "%zu is negative or not finite",
                   i % (size_t)n, i / (size_t)n);
-  int rc = store_user_table(e, 2, e->model.xsec_table, n, CMI_NION, frequency,
-                            sigma, interpolation);
-  if (rc)
-    return rc;
+  CMI_TRY(store_user_table(e, 2, e->model.xsec_table, n, CMI_NION, frequency,
+                           sigma, interpolation));
   e->model.xsec_verner = 2;
   e->have_xsec = true;
   e->spectra_dirty = true;
@@ -1355,10 +1363,8 @@ int cmi_gpu_set_recombination_rates_table(cmi_gpu_engine *e, int32_t n,
                   "cmi_gpu_set_recombination_rates_table: rate %zu of ion %zu "
                   "is negative or not finite",
                   i % (size_t)n, i / (size_t)n);
-  int rc = store_user_table(e, 3, e->model.recomb_table, n, CMI_NION,
-                            temperature, alpha, interpolation);
-  if (rc)
-    return rc;
+  CMI_TRY(store_user_table(e, 3, e->model.recomb_table, n, CMI_NION,
+                           temperature, alpha, interpolation));
   e->model.recomb_verner = 2;
   e->have_recomb = true;
   return CMI_GPU_OK;
@@ -1461,9 +1467,7 @@ int cmi_gpu_upload_cells(cmi_gpu_engine *e, const double *number_density,
   } else {
     HIP_TRY(hipMemsetAsync(e->cells.x[0], 0, CMI_NION * bytes, e->stream));
   }
-  int rc = rebuild_opacity(e);
-  if (rc)
-    return rc;
+  CMI_TRY(rebuild_opacity(e));
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->have_cells = true;
   return CMI_GPU_OK;
@@ -1502,9 +1506,7 @@ int cmi_gpu_upload_field(cmi_gpu_engine *e, int32_t field,
   if (field == CMI_GPU_FIELD_NUMBER_DENSITY ||
       field == CMI_GPU_FIELD_IONIC_FRACTION + ION_H_n ||
       field == CMI_GPU_FIELD_IONIC_FRACTION + ION_He_n) {
-    int rc = rebuild_opacity(e);
-    if (rc)
-      return rc;
+    CMI_TRY(rebuild_opacity(e));
   }
   HIP_TRY(hipStreamSynchronize(e->stream));
   return CMI_GPU_OK;
@@ -1632,10 +1634,6 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.tile_compact_ratio = (int)(value < -1 ? -1 : value);
   else if (k == "park_in_place")
     e->tune.park_in_place = value != 0;
-  else if (k == "block_select")
-    e->tune.block_select = value != 0;
-  else if (k == "block_first_kernels")
-    e->tune.block_first_kernels = value != 0;
   else if (k == "accumulators_dirty")
     e->acc_block_dirty = e->acc_block_dirty || value != 0;
   else if (k == "temperature_finish_slots")
@@ -1652,79 +1650,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.defer_weights = value != 0;
   else if (k == "tile_counting_sort")
     e->tune.tile_counting_sort = value != 0;
-  else if (k == "tile_max_rounds")
-    e->tune.tile_max_rounds = (int)(value < 0 ? 0 : value);
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
-  return CMI_GPU_OK;
-}
-
-/* make sure the sort buffers hold n packets */
-static int reserve_sort_buffers(cmi_gpu_engine *e, uint64_t n) {
-  if (e->sort_capacity >= n)
-    return CMI_GPU_OK;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(e->sort_keys[0]);
-  (void)hipFree(e->sort_temp);
-  e->sort_keys[0] = nullptr;
-  e->sort_temp = nullptr;
-  e->sort_capacity = 0;
-  uint32_t *block = nullptr;
-  HIP_TRY(hipMalloc(&block, sizeof(uint32_t) * 4 * n));
-  e->sort_keys[0] = block;
-  e->sort_keys[1] = block + n;
-  e->sort_ids[0] = block + 2 * n;
-  e->sort_ids[1] = block + 3 * n;
-  size_t bytes = 0;
-  HIP_TRY(cmi_sort_pairs_temp_bytes(n, 32, &bytes));
-  e->sort_temp_bytes = bytes;
-  HIP_TRY(hipMalloc(&e->sort_temp, bytes ? bytes : 16));
-  e->sort_capacity = n;
-  return CMI_GPU_OK;
-}
-
-/* make sure the two re-emission queues hold n packets each */
-static int reserve_queues(cmi_gpu_engine *e, uint64_t n) {
-  if (e->queue_capacity >= n)
-    return CMI_GPU_OK;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(e->queue_block);
-  e->queue_block = nullptr;
-  e->queue_capacity = 0;
-  /* ended flights: pos[3], nu + cell, id, meta = 5.5 doubles per packet;
-   * ready flights: pos[3], dir[3], tau, nu + id, meta = 9 doubles per packet;
-   * every packet of a launch can be in either */
-  const size_t ended_doubles = 6, ready_doubles = 9;
-  HIP_TRY(hipMalloc(&e->queue_block,
-                    sizeof(double) * (ended_doubles + ready_doubles) * n));
-  if (!e->queue_counts) {
-    HIP_TRY(hipMalloc(&e->queue_counts, 2 * sizeof(unsigned int)));
-  }
-  QueueDev &q = e->ended_queue;
-  double *base = e->queue_block;
-  for (int a = 0; a < 3; ++a) {
-    q.pos[a] = base + (size_t)a * n;
-    q.dir[a] = nullptr;
-  }
-  q.tau = nullptr;
-  q.nu = base + (size_t)3 * n;
-  q.cell = (int32_t *)(base + (size_t)4 * n);
-  q.id = (uint32_t *)q.cell + n;
-  q.meta = q.id + n;
-  q.count = e->queue_counts;
-  QueueDev &r = e->ready_queue;
-  base = e->queue_block + ended_doubles * n;
-  for (int a = 0; a < 3; ++a) {
-    r.pos[a] = base + (size_t)a * n;
-    r.dir[a] = base + (size_t)(3 + a) * n;
-  }
-  r.tau = base + (size_t)6 * n;
-  r.nu = base + (size_t)7 * n;
-  r.cell = nullptr;
-  r.id = (uint32_t *)(base + (size_t)8 * n);
-  r.meta = r.id + n;
-  r.count = e->queue_counts + 1;
-  e->queue_capacity = n;
   return CMI_GPU_OK;
 }
 
@@ -1735,122 +1662,11 @@ __global__ void iota_kernel(uint32_t *out, uint64_t n) {
     out[i] = (uint32_t)i;
 }
 
-/* tiles of the engine's grid for the current transport flavour */
-static TileGridDev tile_grid(const cmi_gpu_engine *e) {
-  TileGridDev t;
-  const bool heat = e->config.track_heating != 0;
-  if (e->full_ions) {
-    t.log2[0] = TileShape<true, true>::LX;
-    t.log2[1] = TileShape<true, true>::LY;
-    t.log2[2] = TileShape<true, true>::LZ;
-  } else if (heat) {
-    t.log2[0] = TileShape<false, true>::LX;
-    t.log2[1] = TileShape<false, true>::LY;
-    t.log2[2] = TileShape<false, true>::LZ;
-  } else {
-    t.log2[0] = TileShape<false, false>::LX;
-    t.log2[1] = TileShape<false, false>::LY;
-    t.log2[2] = TileShape<false, false>::LZ;
-  }
-  int64_t total = 1;
-  for (int a = 0; a < 3; ++a) {
-    const int side = 1 << t.log2[a];
-    t.ntile[a] = (e->grid.ncell[a] + side - 1) / side;
-    total *= t.ntile[a];
-  }
-  t.ntiles = (int32_t)total;
-  return t;
-}
-
-/* make sure the flight rows of the tile rounds hold n flights each */
-static int reserve_tile_buffers(cmi_gpu_engine *e, uint64_t n) {
-  const bool weights = e->full_ions;
-  if (e->tile_capacity >= n && (e->tile_has_weights || !weights))
-    return CMI_GPU_OK;
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  (void)hipFree(e->tile_block);
-  e->tile_block = nullptr;
-  e->tile_capacity = 0;
-  const TileGridDev t = tile_grid(e);
-  const size_t row_bytes = sizeof(double) * CMI_FLIGHT_DOUBLES * n;
-  const size_t weight_bytes = weights ? sizeof(double) * CMI_NACC * n : 0;
-  const size_t key_bytes = (sizeof(uint32_t) * n + 255) & ~(size_t)255;
-  const size_t nitems =
-      (size_t)t.ntiles + n / CMI_TILE_ITEM_FLIGHTS_FULL + 4;
-  const size_t item_bytes = sizeof(TileItemDev) * nitems;
-  const size_t begin_bytes =
-      (sizeof(uint32_t) * ((size_t)t.ntiles + 2) + 255) & ~(size_t)255;
-  const size_t count_bytes =
-      (sizeof(unsigned int) * nitems + 255) & ~(size_t)255;
-  const bool counting = t.ntiles <= CMI_TILE_SORT_MAX_TILES;
-  const size_t hist_bytes =
-      counting ? sizeof(uint32_t) * (size_t)t.ntiles * CMI_TILE_SORT_BLOCKS : 0;
-  const size_t total = 2 * (row_bytes + weight_bytes + key_bytes) +
-                       6 * key_bytes + 2 * begin_bytes + 2 * count_bytes +
-                       item_bytes + hist_bytes;
-  HIP_TRY(hipMalloc(&e->tile_block, total));
-  if (!e->tile_counts)
-    HIP_TRY(hipMalloc(&e->tile_counts, 8 * sizeof(unsigned int)));
-  char *at = e->tile_block;
-  for (int k = 0; k < 2; ++k) {
-    FlightRowsDev &r = e->tile_rows[k];
-    r.rows = (double *)at;
-    at += row_bytes;
-    r.weights = weights ? (double *)at : nullptr;
-    at += weight_bytes;
-    r.keys = (uint32_t *)at;
-    at += key_bytes;
-    r.count = e->tile_counts + k;
-    r.capacity = (unsigned int)n;
-  }
-  e->tile_iota = (uint32_t *)at;
-  at += key_bytes;
-  e->tile_ended_slot = (uint32_t *)at;
-  at += key_bytes;
-  e->tile_ended_pos = (uint32_t *)at;
-  at += key_bytes;
-  for (int k = 0; k < 2; ++k) {
-    e->tile_slot_of[k] = (uint32_t *)at;
-    at += key_bytes;
-  }
-  e->tile_new_slots = (uint32_t *)at;
-  at += key_bytes;
-  e->tile_begin = (uint32_t *)at;
-  at += begin_bytes;
-  e->tile_total = counting ? (uint32_t *)at : nullptr;
-  at += begin_bytes;
-  e->tile_absorbed_count = (unsigned int *)at;
-  at += count_bytes;
-  e->tile_absorbed_before = (unsigned int *)at;
-  at += count_bytes;
-  e->tile_items = (TileItemDev *)at;
-  at += item_bytes;
-  e->tile_blockhist = counting ? (uint32_t *)at : nullptr;
-  iota_kernel<<<grid_blocks(e, (int64_t)n, 8), CMI_BLOCK, 0, e->stream>>>(
-      e->tile_iota, n);
-  HIP_TRY(hipGetLastError());
-  e->tile_capacity = n;
-  e->tile_has_weights = weights;
-  return CMI_GPU_OK;
-}
-
-/* Transport of n_packets flights and of everything they re-emit: new packets
- * (flights == NULL) or flights handed over by other blocks of a decomposed
- * grid (device rows of CMI_FLIGHT_DOUBLES doubles). */
-/* A block of a decomposed grid flies the packets that start in it (after at
- * most one step of length zero, see shoot_kernel): no source within one cell
- * of the block - and, for the block at the grid's origin, none outside the
- * whole grid - means nothing to emit, and the pass over the packet ids can be
- * skipped altogether. */
 /* n <= 16 counters at `src` (device memory) as they are once the stream has
  * run dry */
 static int read_counters(cmi_gpu_engine *e, const unsigned int *src, int n,
                          unsigned int *out) {
-  {
-    int rc = ensure_mailbox(e);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(ensure_mailbox(e));
   mailbox_kernel<<<1, 16, 0, e->stream>>>(src, e->mailbox_dev, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1859,921 +1675,7 @@ static int read_counters(cmi_gpu_engine *e, const unsigned int *src, int n,
   return CMI_GPU_OK;
 }
 
-static bool block_emits_nothing(const cmi_gpu_engine *e) {
-  if (e->model.continuous_type != 0)
-    return false; /* its packets enter through every face of the box */
-  const GridDev &g = e->grid;
-  const bool at_origin = (g.offset[0] | g.offset[1] | g.offset[2]) == 0;
-  for (int32_t s = 0; s < e->model.nsource; ++s) {
-    bool near = true, in_grid = true;
-    for (int a = 0; a < 3; ++a) {
-      const double x = e->source_position_host[3 * (size_t)s + a];
-      const double lo = g.anchor[a] + g.cellside[a] * (g.offset[a] - 1);
-      const double hi =
-          g.anchor[a] + g.cellside[a] * (g.offset[a] + g.ncell[a] + 1);
-      near &= (x >= lo && x <= hi);
-      /* (a cell of margin: the kernel decides by cell index) */
-      in_grid &= (x >= g.anchor[a] + g.cellside[a] &&
-                  x <= g.anchor[a] + g.box_sides[a] - g.cellside[a]);
-    }
-    if (near || (!in_grid && at_origin))
-      return false;
-  }
-  return e->model.nsource > 0;
-}
-
-static uint64_t reemit_inline_below(const cmi_gpu_engine *e) {
-  if (e->tune.reemit_inline_below >= 0)
-    return (uint64_t)e->tune.reemit_inline_below;
-  return e->grid.decomposed ? 262144u : 4096u;
-}
-
-static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
-                      uint64_t first_packet, uint64_t n_packets,
-                      const double *flights) {
-  if (!e)
-    return fail(CMI_GPU_EINVAL, "null engine");
-  if (!e->have_sources || (e->model.nsource > 0 && !e->have_spectrum) ||
-      (e->model.continuous_type != 0 && !e->have_continuous_spectrum) ||
-      !e->have_xsec || !e->have_cells)
-    return fail(CMI_GPU_ESTATE,
-                "cmi_gpu_shoot: sources, their spectra, cross sections and "
-                "cell data must be set first");
-  if (n_packets == 0)
-    return CMI_GPU_OK;
-  /* (packet ids of a call are 32-bit, and 0xffffffff marks a place of the
-   * ended queue that holds no flight: CMI_QUEUE_HOLE) */
-  if (n_packets >= 0xffffffffull)
-    return fail(CMI_GPU_EINVAL,
-                "cmi_gpu_shoot: at most 2^32 - 2 packets per call");
-  if (e->grid.decomposed &&
-      (e->tune.exact_dda || !e->export_rows ||
-       e->ncell >= CMI_FAST_MARCHER_MAX_CELLS))
-    return fail(CMI_GPU_ESTATE,
-                "cmi_gpu_shoot: a block of a decomposed grid needs an export "
-                "buffer (cmi_gpu_set_export_buffer) and the incremental "
-                "marcher (fewer than 2^28 cells per block)");
-  if (!flights && e->grid.decomposed && block_emits_nothing(e))
-    return CMI_GPU_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  {
-    int rc = ensure_spectra(e);
-    if (rc)
-      return rc;
-  }
-
-  const bool heat = e->config.track_heating != 0;
-  const bool reemit = e->model.reemit_type != CMI_GPU_REEMIT_NONE;
-  /* cross-lane aggregation keys and the fast marcher use 32-bit cell
-   * indices, and the marcher a 32-bit BYTE offset into the 16-B transport
-   * records (fast_load_record): 2^28 cells. Larger engines (768^3 and up;
-   * 2^28 cells are 73 GB of state) march with the exact marcher. */
-  const bool small_grid = e->ncell < CMI_FAST_MARCHER_MAX_CELLS;
-  const int agg = small_grid ? e->tune.aggregate : CMI_AGG_NONE;
-  const int agg_reemit = small_grid ? e->tune.aggregate_reemit : CMI_AGG_NONE;
-  const bool tracking = e->trackers_enabled && e->trackers.n != 0;
-  /* (trackers count in the exact marcher on an undivided grid - the counts
-   * equal the oracle's one by one - and in the incremental one on the blocks
-   * of a decomposed grid, whose hand-overs carry its state) */
-  const bool exact = e->tune.exact_dda || !small_grid ||
-                     (tracking && !e->grid.decomposed);
-  /* with re-emission in passes the transport launches use the variant WITHOUT
-   * the re-emission code (absorbed packets go to the interaction kernel); the
-   * variant with it follows re-emissions in place */
-  /* (a handful of handed-over flights - the late hand-over rounds of a
-   * decomposed grid - are followed in place, re-emissions and all, by ONE
-   * launch: a pass, the interaction kernel and the in-place kernel after it
-   * each cost the latency of the longest flight, ~1 ms, whatever their
-   * number) */
-  const bool passes = reemit && e->tune.reemit_passes &&
-                      !(flights && n_packets < reemit_inline_below(e));
-  void (*kernel)(const ShootArgs) = nullptr;
-  void (*kernel_inline)(const ShootArgs) = nullptr;
-#define PICK(F, H, X)                                                          \
-  if (e->full_ions == F && heat == H && exact == X) {                          \
-    kernel = shoot_kernel<F, H, false, X>;                                     \
-    kernel_inline = shoot_kernel<F, H, true, X>;                               \
-  }
-  PICK(false, false, false)
-  PICK(false, true, false)
-  PICK(true, false, false)
-  PICK(true, true, false)
-  PICK(false, false, true)
-  PICK(false, true, true)
-  PICK(true, false, true)
-  PICK(true, true, true)
-#undef PICK
-  if (tracking && !exact) {
-    /* (a block of a decomposed grid: the hook in the incremental marcher) */
-#define PICK_TRACK(F, H)                                                       \
-  if (e->full_ions == F && heat == H) {                                        \
-    kernel = shoot_kernel<F, H, false, false, false, false, false, true>;     \
-    kernel_inline = shoot_kernel<F, H, true, false, false, false, false, true>; \
-  }
-    PICK_TRACK(false, false)
-    PICK_TRACK(false, true)
-    PICK_TRACK(true, false)
-    PICK_TRACK(true, true)
-#undef PICK_TRACK
-  }
-  if (reemit && !passes)
-    kernel = kernel_inline;
-  /* the first generation of new packets on a non-periodic grid with the
-   * block combining table (every benchmark config): the specialised build of
-   * the same kernel */
-  void (*kernel_first)(const ShootArgs) = kernel;
-  if (!flights && !exact && !tracking && agg == CMI_AGG_BLOCK &&
-      kernel != kernel_inline &&
-      !(e->grid.periodic[0] | e->grid.periodic[1] | e->grid.periodic[2])) {
-    if (e->full_ions)
-      kernel_first = heat ? shoot_kernel<true, true, false, false, true>
-                          : shoot_kernel<true, false, false, false, true>;
-    else
-      kernel_first = heat ? shoot_kernel<false, true, false, false, true>
-                          : shoot_kernel<false, false, false, false, true>;
-  }
-  /* ... and, hydrogen only on a whole grid, marching through padded records */
-  /* (the kernel addresses padded records by 32-bit byte offsets:
-   * (nx + 2)(ny + 2)(nz + 2) < 2^29, which a flat grid of fewer than 2^28
-   * cells - 1 x 13400 x 13400 - can exceed) */
-  const int64_t padded_cells =
-      ((int64_t)e->grid.ncell[0] + 2 * CMI_PAD_LAYERS) *
-      ((int64_t)e->grid.ncell[1] + 2 * CMI_PAD_LAYERS) *
-      ((int64_t)e->grid.ncell[2] + 2 * CMI_PAD_LAYERS);
-  /* (a block of a decomposed grid: its ghost layer says "left the block", the
-   * end of the flight then decides between "left the box" and a hand-over) */
-  const bool block_ok = !e->grid.decomposed || e->tune.block_first_kernels;
-  const bool pad = kernel_first != kernel && !e->full_ions &&
-                   e->tune.pad_march && block_ok &&
-                   padded_cells < ((int64_t)1 << 29);
-  const bool pad_big = pad && e->ncell > CMI_TABLE_BIG_CELLS;
-  if (pad_big)
-    kernel_first = heat ? shoot_kernel<false, true, false, false, true, false,
-                                       true, false, true>
-                        : shoot_kernel<false, false, false, false, true, false,
-                                       true, false, true>;
-  else if (pad)
-    kernel_first =
-        heat ? shoot_kernel<false, true, false, false, true, false, true>
-             : shoot_kernel<false, false, false, false, true, false, true>;
-  /* ... and, for multi-ion runs whose packets are sorted anyway, with the
-   * emission physics done by the key kernel (the rows live in the second
-   * weights buffer of the tile rounds, idle during the first generation) */
-  void (*kernel_first_pre)(const ShootArgs) = nullptr;
-  if (kernel_first != kernel && e->full_ions && e->tune.pre_emission &&
-      e->tune.sort_packets && passes && e->tune.tile_rounds && block_ok)
-    kernel_first_pre =
-        heat ? shoot_kernel<true, true, false, false, true, true>
-             : shoot_kernel<true, false, false, false, true, true>;
-
-  /* (the hydrogen-only kernels built for the table run in larger blocks) */
-  const int first_threads =
-      (kernel_first != kernel && !e->full_ions)
-          ? (pad_big ? shoot_block_threads<false, true, true>()
-                     : shoot_block_threads<false, true>())
-          : CMI_BLOCK;
-  auto occupancy = [&](void (*k)(const ShootArgs), int &blocks_per_cu,
-                       int threads = CMI_BLOCK) -> int {
-    blocks_per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k,
-                                                         threads, 0));
-    if (blocks_per_cu < 1)
-      blocks_per_cu = 1;
-    if (blocks_per_cu > e->tune.max_blocks_per_cu)
-      blocks_per_cu = e->tune.max_blocks_per_cu;
-    return CMI_GPU_OK;
-  };
-  int blocks_per_cu = 0, blocks_per_cu_inline = 0;
-  {
-    int rc = occupancy(kernel, blocks_per_cu);
-    if (rc)
-      return rc;
-    rc = occupancy(kernel_inline, blocks_per_cu_inline);
-    if (rc)
-      return rc;
-  }
-
-  /* (the specialised first-generation kernels may fit more blocks per CU) */
-  int blocks_per_cu_first = blocks_per_cu;
-  if (kernel_first != kernel) {
-    int rc = occupancy(kernel_first_pre ? kernel_first_pre : kernel_first,
-                       blocks_per_cu_first, first_threads);
-    if (rc)
-      return rc;
-  }
-  const bool sorted = e->tune.sort_packets && !flights;
-  const uint64_t max_launch = e->tune.max_packets_per_launch;
-  /* later generations in tile rounds: needs the incremental marcher */
-  const bool tiles = passes && e->tune.tile_rounds && !exact && !tracking;
-  /* a block of a decomposed grid picks its own packets out of each launch's
-   * ids first (block_select_kernel): buffers for what it picks, not for all
-   * ids (1 / 8 of them in config 5 - sort buffers, queues and flight slots
-   * are 40 GB per 1e8 packets) */
-  const bool select_mode =
-      sorted && e->grid.decomposed && e->tune.block_select;
-  auto reserve_for = [&](uint64_t cap) -> int {
-    if (sorted || tiles) {
-      int rc = reserve_sort_buffers(e, cap);
-      if (rc)
-        return rc;
-    }
-    if (passes) {
-      int rc = reserve_queues(e, cap);
-      if (rc)
-        return rc;
-    }
-    if (tiles) {
-      int rc = reserve_tile_buffers(e, cap);
-      if (rc)
-        return rc;
-    }
-    return CMI_GPU_OK;
-  };
-  if (!select_mode) {
-    int rc = reserve_for(n_packets < max_launch ? n_packets : max_launch);
-    if (rc)
-      return rc;
-  }
-  void (*tkernel)(const TileArgs) = nullptr;
-  int tile_threads = 0, tile_blocks_per_cu = 0;
-  if (tiles) {
-    if (e->full_ions)
-      tkernel = heat ? tile_kernel<true, true> : tile_kernel<true, false>;
-    else
-      tkernel = heat ? tile_kernel<false, true> : tile_kernel<false, false>;
-    tile_threads = e->full_ions
-                       ? TileShape<true, true>::THREADS
-                       : (heat ? TileShape<false, true>::THREADS
-                               : TileShape<false, false>::THREADS);
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &tile_blocks_per_cu, tkernel, tile_threads, 0));
-    if (tile_blocks_per_cu < 1)
-      tile_blocks_per_cu = 1;
-  }
-  QueueDev no_queue;
-  memset(&no_queue, 0, sizeof no_queue);
-  /* sort key: 22 direction bits, the tau class and the source index. The
-   * tau classes only help when a packet's range follows from its optical
-   * depth alone (one cross section for all packets). */
-  uint32_t tau_bits = 0;
-  {
-    const uint64_t per_source =
-        (n_packets < max_launch ? n_packets : max_launch) /
-        (uint64_t)(e->model.nsource > 0 ? e->model.nsource : 1);
-    if (e->tune.sort_tau_bits >= 0)
-      tau_bits = (uint32_t)e->tune.sort_tau_bits;
-    else
-      /* measured on 256^3: the classes pay off once a direction bin of
-       * 64 x 2^bits packets is still narrower than a few cells */
-      /* (multi-ion runs since round 5's cell-by-cell sums: 0 / 1 / 2 / 3 /
-       * 4 class bits 71.8 / 70.0 / 66.3 / 68.0 / 68.0 ms per 1e8 packets) */
-      tau_bits = per_source >= (1ull << 24)
-                     ? (e->full_ions ? 2u : 3u)
-                     : (per_source >= (1ull << 22) ? 2u : 0u);
-  }
-  double sigma_ref = 1.;
-  if (e->full_ions) {
-    double sigma_He;
-    const ModelDev host_model = host_model_of(e);
-    cmi_cross_sections_H_He(host_model, 1.0001 * e->model.nu_H, sigma_ref,
-                            sigma_He);
-  }
-  uint32_t source_bits = 0;
-  /* (the continuous source counts as one more) */
-  for (int s = e->model.nsource - (e->model.continuous_type != 0 ? 0 : 1);
-       s > 0; s >>= 1)
-    ++source_bits;
-  if (source_bits > 10u - tau_bits)
-    source_bits = 10u - tau_bits;
-  uint32_t dir_bits = 22u;
-  if (e->tune.sort_dir_bits >= 0) {
-    dir_bits = (uint32_t)e->tune.sort_dir_bits;
-  } else {
-    /* measured on 256^3, 1e8 packets: 21 bits order the packets as well as
-     * 22 (20 nearly, 18 not), and 21 + 3 tau bits are three passes, not four */
-    const uint32_t over = (22u + tau_bits + source_bits) % 8u;
-    if (over == 1u || over == 2u)
-      dir_bits = 22u - over;
-  }
-  const int key_bits = (int)(dir_bits + tau_bits + source_bits);
-
-  if (pad) {
-    /* the padded records of this call's cell state (0.1 ms at 256^3) */
-    const GridDev &g = e->grid;
-    const int64_t padded = (int64_t)(g.ncell[0] + 2 * CMI_PAD_LAYERS) *
-                           (g.ncell[1] + 2 * CMI_PAD_LAYERS) *
-                           (g.ncell[2] + 2 * CMI_PAD_LAYERS);
-    if (!e->pad_H)
-      HIP_TRY(hipMalloc(&e->pad_H, sizeof(double) * (size_t)padded));
-    pad_record_kernel<<<grid_blocks(e, padded, 8), CMI_BLOCK, 0, e->stream>>>(
-        e->cells.opacity, e->pad_H, g.ncell[0], g.ncell[1], g.ncell[2]);
-    HIP_TRY(hipGetLastError());
-  }
-
-  for (uint64_t done = 0; done < n_packets; done += max_launch) {
-    /* the launch's packet ids ... */
-    const uint64_t nids = n_packets - done < max_launch ? n_packets - done
-                                                        : max_launch;
-    /* ... and what it flies: all of them, or - a block of a decomposed grid -
-     * those that start in the block */
-    uint64_t n = nids;
-    const uint32_t *select = nullptr;
-    if (select_mode) {
-      if (!e->select_count)
-        HIP_TRY(hipMalloc(&e->select_count, sizeof(unsigned int)));
-      if (e->select_capacity < nids) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        (void)hipFree(e->select_ids);
-        e->select_ids = nullptr;
-        e->select_capacity = 0;
-        HIP_TRY(hipMalloc(&e->select_ids, sizeof(uint32_t) * nids));
-        e->select_capacity = nids;
-      }
-      HIP_TRY(hipMemsetAsync(e->select_count, 0, sizeof(unsigned int),
-                             e->stream));
-      SelectArgs sa;
-      sa.grid = e->grid;
-      sa.model = e->model;
-      sa.first_packet = first_packet + done;
-      sa.batch_offset = done;
-      sa.n_packets = nids;
-      sa.seed = seed;
-      sa.iteration = iteration;
-      sa.select = e->select_ids;
-      sa.count = e->select_count;
-      block_select_kernel<false>
-          <<<grid_blocks(e, (int64_t)nids, 8), CMI_BLOCK, 0, e->stream>>>(sa);
-      HIP_TRY(hipGetLastError());
-      unsigned int mine = 0;
-      int rrc = read_counters(e, e->select_count, 1, &mine);
-      if (rrc)
-        return rrc;
-      if (mine == 0)
-        continue;
-      n = mine;
-      select = e->select_ids;
-      /* (some headroom: the count differs by a per cent from one iteration
-       * to the next, and growing means freeing and allocating again) */
-      int rc = reserve_for(n + n / 16 + 1024);
-      if (rc)
-        return rc;
-    }
-    ShootArgs a;
-    a.grid = e->grid;
-    a.model = e->model;
-    a.cells = e->cells;
-    a.counters = e->counters;
-    a.first_packet = first_packet;
-    a.batch_offset = done;
-    a.n_packets = n;
-    a.order = nullptr;
-    a.pre_rows = nullptr;
-    a.xin = flights ? flights + (size_t)CMI_FLIGHT_DOUBLES * done : nullptr;
-    a.xin_local = 0;
-    a.xout.rows = e->export_rows;
-    a.xout.count = e->export_count;
-    a.xout.capacity = (unsigned int)e->export_capacity;
-    a.pad_H = pad ? e->pad_H : nullptr;
-    a.xcd_remap = (sorted && e->tune.xcd_remap) ? 1 : 0;
-    a.pad_ny = e->grid.ncell[1] + 2 * CMI_PAD_LAYERS;
-    a.pad_nz = e->grid.ncell[2] + 2 * CMI_PAD_LAYERS;
-    a.pad_inv_yz = 1. / ((double)a.pad_ny * (double)a.pad_nz);
-    a.pad_inv_z = 1. / (double)a.pad_nz;
-    a.chunk = e->tune.chunk;
-    a.seed = seed;
-    a.iteration = iteration;
-    /* handed-over flights are no ray bundles worth keeping together */
-    a.refill_threshold = flights ? e->tune.refill_threshold_reemit
-                                 : e->tune.refill_threshold;
-    a.exp_no_atomics = e->tune.exp_no_atomics;
-    a.trackers = e->trackers;
-    if (!tracking)
-      a.trackers.n = 0;
-    a.aggregate = flights ? agg_reemit : agg;
-    a.qin = no_queue;
-    a.qout = no_queue;
-    a.park_in_place = 0;
-    if (passes) {
-      HIP_TRY(hipMemsetAsync(e->queue_counts, 0, 2 * sizeof(unsigned int),
-                             e->stream));
-      a.qout = e->ended_queue;
-      if (!flights && e->tune.park_in_place) {
-        /* new packets: parked at their place in the launch's order */
-        a.park_in_place = 1;
-        HIP_TRY(hipMemsetAsync(e->ended_queue.id, 0xff,
-                               sizeof(uint32_t) * (size_t)n, e->stream));
-      }
-    }
-
-    EventPair ev;
-    {
-      int trc = timer_begin(e, ev);
-      if (trc)
-        return trc;
-    }
-    if (sorted) {
-      KeyArgs k;
-      k.model = e->model;
-      k.first_packet = first_packet + done;
-      k.n_packets = n;
-      k.seed = seed;
-      k.iteration = iteration;
-      k.tau_bits = tau_bits;
-      k.full_ions = e->full_ions ? 1 : 0;
-      k.sigma_ref = sigma_ref;
-      k.source_mask = (1u << source_bits) - 1u;
-      /* coarse direction bins of ~64 x 2^tau_bits packets per source */
-      k.dir_hi_bits = 0;
-      k.dir_bits = dir_bits;
-      if (tau_bits != 0) {
-        const uint64_t per_bin = 64ull << tau_bits;
-        /* (a block's own packets fill its part of the sphere as densely as
-         * the launch's ids fill the whole) */
-        const uint64_t per_source =
-            nids / (uint64_t)(e->model.nsource > 0 ? e->model.nsource : 1);
-        while (k.dir_hi_bits < dir_bits &&
-               (per_source >> (k.dir_hi_bits + 1u)) >= per_bin)
-          ++k.dir_hi_bits;
-      }
-      k.keys = e->sort_keys[0];
-      k.ids = e->sort_ids[0];
-      k.pre_rows = kernel_first_pre ? e->tile_rows[1].weights : nullptr;
-      if (kernel_first_pre && select) {
-        /* the rows are addressed by packet id within the launch (that is what
-         * the transport kernel knows): a block that flies a selection of the
-         * ids needs room for all of them - the flight slots it borrows the
-         * room from otherwise are sized for its selection */
-        if (e->select_rows_capacity < nids) {
-          HIP_TRY(hipStreamSynchronize(e->stream));
-          (void)hipFree(e->select_rows);
-          e->select_rows = nullptr;
-          e->select_rows_capacity = 0;
-          HIP_TRY(hipMalloc(&e->select_rows,
-                            sizeof(double) * CMI_NACC * (size_t)nids));
-          e->select_rows_capacity = nids;
-        }
-        k.pre_rows = e->select_rows;
-      }
-      k.select = select;
-      a.pre_rows = k.pre_rows;
-      if (k.pre_rows)
-        emission_key_kernel<<<grid_blocks(e, (int64_t)n, 8), CMI_BLOCK, 0,
-                              e->stream>>>(k);
-      else
-        direction_key_kernel<<<grid_blocks(e, (int64_t)n, 8), CMI_BLOCK, 0,
-                               e->stream>>>(k);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(cmi_sort_pairs(e->sort_temp, e->sort_temp_bytes, e->sort_keys[0],
-                             e->sort_keys[1], e->sort_ids[0], e->sort_ids[1],
-                             n, key_bits, e->stream));
-      a.order = e->sort_ids[1];
-    }
-    /* enough chunks for every wave of a full grid, else fewer blocks */
-    const uint64_t nchunks = (n + a.chunk - 1) / a.chunk;
-    int64_t blocks = (int64_t)e->num_cu * blocks_per_cu_first;
-    const int64_t need = (int64_t)((nchunks + (first_threads / 64) - 1) /
-                                   (first_threads / 64));
-    if (blocks > need)
-      blocks = need;
-    if (blocks < 1)
-      blocks = 1;
-    EventPair kev;
-    {
-      int trc = timer_begin(e, kev);
-      if (trc)
-        return trc;
-    }
-    if (sorted && kernel_first_pre)
-      kernel_first_pre<<<(unsigned)blocks, CMI_BLOCK, 0, e->stream>>>(a);
-    else
-      kernel_first<<<(unsigned)blocks, first_threads, 0, e->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    {
-      int trc = timer_end(e, e->kernel_events, kev, n);
-      if (trc)
-        return trc;
-    }
-    /* later generations, in tile rounds (tile_kernels.h): the interaction
-     * kernel turns the ended flights into flight rows keyed by the tile they
-     * start in; every round sorts the rows by tile, flies each flight through
-     * ONE tile with the tile's accumulators in LDS, and collects the flights
-     * that go on (into another tile, or re-emitted) for the next round */
-    const double *handover = nullptr; /* flights the tile rounds leave over */
-    unsigned int handover_count = 0;
-    if (tiles) {
-      const TileGridDev tg = tile_grid(e);
-      int tile_bits = 1; /* keys: tiles and the "free slot" key ntiles */
-      while ((1ll << tile_bits) < (int64_t)tg.ntiles + 1)
-        ++tile_bits;
-      InteractArgs ia;
-      ia.model = e->model;
-      ia.cells = e->cells;
-      ia.counters = e->counters;
-      ia.first_packet = a.first_packet;
-      ia.seed = seed;
-      ia.iteration = iteration;
-      ia.qin = e->ended_queue;
-      ia.n_in = a.park_in_place ? (uint32_t)n : 0u;
-      ia.qout = no_queue;
-      ia.grid = e->grid;
-      ia.tiles = tg;
-      ia.items = e->tile_items;
-      ia.nitems = e->tile_counts + 2;
-      ia.absorbed_before = e->tile_absorbed_before;
-      ia.ended_slot = e->tile_ended_slot;
-      const uint32_t item_flights = e->full_ions ? CMI_TILE_ITEM_FLIGHTS_FULL
-                                                 : CMI_TILE_ITEM_FLIGHTS_H;
-      const bool defer = e->full_ions && e->tune.defer_weights;
-      unsigned int *const d_new = e->tile_counts + 4;
-      ia.new_slots = e->tile_new_slots;
-      ia.new_count = d_new;
-      unsigned int *const d_nrows = e->tile_counts;
-      unsigned int *const d_nlive = e->tile_counts + 1;
-      unsigned int *const d_nitems = e->tile_counts + 2;
-      unsigned int *const d_next = e->tile_counts + 3;
-      HIP_TRY(hipMemsetAsync(e->tile_counts, 0, 8 * sizeof(unsigned int),
-                             e->stream));
-      /* the absorbed packets of the first generation -> flights in slots */
-      int cur = 0; /* which set of rows holds the flights */
-      FlightRowsDev rows = e->tile_rows[cur];
-      ia.rows = rows;
-      ia.rows.count = d_nrows;
-      ia.ended_pos = nullptr;
-      ia.key_out = nullptr;
-      {
-        const int iblocks = e->num_cu * 8;
-        if (e->full_ions && defer)
-          interaction_kernel<true, true, true>
-              <<<iblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-        else if (e->full_ions)
-          interaction_kernel<true, true>
-              <<<iblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-        else
-          interaction_kernel<false, true>
-              <<<iblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-        HIP_TRY(hipGetLastError());
-      }
-      unsigned int nslots = 0;
-      {
-        int rrc = read_counters(e, d_nrows, 1, &nslots);
-        if (rrc)
-          return rrc;
-      }
-      if (nslots > rows.capacity)
-        return fail(CMI_GPU_ENOMEM,
-                    "tile rounds: %u flights, room for %u - flights were "
-                    "lost, the iteration is invalid",
-                    nslots, rows.capacity);
-      if (defer && nslots != 0) {
-        FlightWeightsArgs wa;
-        wa.model = e->model;
-        wa.rows = rows;
-        wa.slots = nullptr;
-        wa.count = nullptr;
-        wa.n = nslots;
-        flight_weights_kernel<<<grid_blocks(e, (int64_t)nslots, 8), CMI_BLOCK,
-                                0, e->stream>>>(wa);
-        HIP_TRY(hipGetLastError());
-      }
-      /* The flights of a round by position (TileArgs): keys[i] and the slot
-       * of position i < npos. Round 0: the slots as the interaction kernel
-       * filled them, position = slot; every round writes the arrays of the
-       * next one in its tile order, flights only - the rows never move, and
-       * what has ended is gone from the arrays one round later. */
-      uint32_t *keys = rows.keys;
-      uint32_t *keys_next = e->tile_rows[1].keys;
-      const uint32_t *slot_of = nullptr;
-      int next_slot_of = 0;
-      unsigned int npos = nslots;
-      /* slots the flights are spread over (since the last compaction) */
-      unsigned int extent = nslots;
-      const unsigned int compact_ratio =
-          e->tune.tile_compact_ratio >= 0
-              ? (unsigned int)e->tune.tile_compact_ratio
-              : (e->full_ions ? 2u : 0u);
-      for (int round = 0; npos != 0; ++round) {
-        /* the positions in tile order (ended flights last), cut into units
-         * of work */
-        TilePlanArgs pa;
-        pa.tiles = tg;
-        pa.sorted_keys = e->sort_keys[1];
-        pa.nslots = npos;
-        pa.tile_begin = e->tile_begin;
-        pa.item_flights = item_flights;
-        pa.items = e->tile_items;
-        pa.nitems = d_nitems;
-        pa.next_item = d_next;
-        pa.nlive = d_nlive;
-        if (e->tile_blockhist && e->tune.tile_counting_sort) {
-          TileSortArgs sa;
-          sa.keys = keys;
-          sa.nslots = npos;
-          sa.ntiles = (uint32_t)tg.ntiles;
-          /* (about a counter per slot and workgroup at least) */
-          {
-            uint64_t nb = ((uint64_t)npos / sa.ntiles + 7) / 8 * 8;
-            if (nb < 8)
-              nb = 8;
-            if (nb > CMI_TILE_SORT_BLOCKS)
-              nb = CMI_TILE_SORT_BLOCKS;
-            sa.nblocks = (uint32_t)nb;
-          }
-          sa.blockhist = e->tile_blockhist;
-          sa.total = e->tile_total;
-          sa.tile_begin = e->tile_begin;
-          sa.order = e->sort_ids[1];
-          tile_count_kernel<<<sa.nblocks, CMI_TILE_SORT_THREADS, 0,
-                              e->stream>>>(sa);
-          tile_column_kernel<<<(sa.ntiles + CMI_BLOCK - 1) / CMI_BLOCK,
-                               CMI_BLOCK, 0, e->stream>>>(sa);
-          tile_offsets_kernel<<<1, CMI_TILE_SORT_THREADS, 0, e->stream>>>(sa);
-          tile_scatter_kernel<<<sa.nblocks, CMI_TILE_SORT_THREADS, 0,
-                                e->stream>>>(sa);
-          HIP_TRY(hipGetLastError());
-        } else {
-          HIP_TRY(cmi_sort_pairs(e->sort_temp, e->sort_temp_bytes, keys,
-                                 e->sort_keys[1], e->tile_iota,
-                                 e->sort_ids[1], npos, tile_bits, e->stream));
-          tile_begin_kernel<<<grid_blocks(e, (int64_t)npos + 1, 8),
-                              CMI_BLOCK, 0, e->stream>>>(pa);
-          HIP_TRY(hipGetLastError());
-        }
-        tile_plan_kernel<<<1, CMI_TILE_PLAN_THREADS, 0, e->stream>>>(pa);
-        HIP_TRY(hipGetLastError());
-        unsigned int plan[2] = {0, 0}; /* flights, units of work */
-        {
-          int rrc = read_counters(e, d_nlive, 2, plan);
-          if (rrc)
-            return rrc;
-        }
-        const unsigned int nlive = plan[0];
-        if (nlive == 0)
-          break;
-        /* a unit of work costs a fixed ~10-20 us (tile records in, tile
-         * accumulators out); measured on MI355X the round beats single
-         * atomics while a unit has a few hundred flights to share that */
-        const uint64_t per_item =
-            e->tune.tile_min_per_item >= 0
-                ? (uint64_t)e->tune.tile_min_per_item
-                : 200u;
-        const bool finish = nlive < e->tune.tile_min_flights ||
-                            (uint64_t)nlive < per_item * plan[1] ||
-                            round >= e->tune.tile_max_rounds;
-        const uint32_t *order = e->sort_ids[1];
-        if (finish || (compact_ratio != 0 &&
-                       (uint64_t)compact_ratio * nlive < (uint64_t)extent)) {
-          /* the live rows into the other set of rows, in tile order: position
-           * j of this round is then place j and slot j */
-          TileCompactArgs ca;
-          ca.from = rows;
-          ca.to = e->tile_rows[1 - cur];
-          /* (the two key arrays change hands every round, whatever set of
-           * rows is in use: the copies' keys go to the one that is free) */
-          ca.to.keys = keys_next;
-          ca.order = e->sort_ids[1];
-          ca.slot_in = slot_of;
-          ca.keys_in = keys;
-          ca.nlive = d_nlive;
-          ca.with_weights = e->full_ions ? 1 : 0;
-          tile_compact_kernel<<<grid_blocks(e, 8ll * nlive, 8), CMI_BLOCK, 0,
-                                e->stream>>>(ca);
-          HIP_TRY(hipGetLastError());
-          cur = 1 - cur;
-          rows = e->tile_rows[cur];
-          {
-            uint32_t *t = keys;
-            keys = keys_next;
-            keys_next = t;
-          }
-          slot_of = nullptr;
-          order = e->tile_iota;
-          extent = nlive;
-        }
-        if (finish) {
-          /* too few flights per tile for the LDS accumulators to pay: the
-           * rest goes on as passes of the transport kernel (below), the first
-           * of which resumes the flights from their (fresh, dense) rows */
-          handover = rows.rows;
-          handover_count = nlive;
-          break;
-        }
-        TileArgs ta;
-        ta.grid = e->grid;
-        ta.model = e->model;
-        ta.cells = e->cells;
-        ta.counters = e->counters;
-        ta.tiles = tg;
-        ta.refill_threshold = e->tune.tile_refill_threshold;
-        ta.rows = rows;
-        ta.order = order;
-        ta.slot_in = slot_of;
-        ta.keys_out = keys_next;
-        ta.slot_out = e->tile_slot_of[next_slot_of];
-        ta.items = e->tile_items;
-        ta.nitems = d_nitems;
-        ta.next_item = d_next;
-        ta.ended = e->ended_queue;
-        ta.ended_slot = e->tile_ended_slot;
-        ta.ended_pos = e->tile_ended_pos;
-        ta.absorbed_count = e->tile_absorbed_count;
-        ta.xout = a.xout;
-        /* no more workgroups than units of work can exist */
-        int64_t tb = (int64_t)e->num_cu * tile_blocks_per_cu;
-        const int64_t most =
-            (int64_t)tg.ntiles + (int64_t)nlive / item_flights + 1;
-        if (tb > most)
-          tb = most;
-        EventPair tev;
-        {
-          int trc = timer_begin(e, tev);
-          if (trc)
-            return trc;
-        }
-        tkernel<<<(unsigned)tb, tile_threads, 0, e->stream>>>(ta);
-        HIP_TRY(hipGetLastError());
-        {
-          int trc = timer_end(e, e->kernel_events, tev, nlive);
-          if (trc)
-            return trc;
-        }
-        ++e->tile_rounds_run;
-        /* the packets absorbed in this round: re-emitted into their slots,
-         * their new keys at their positions of the next round */
-        ia.rows = rows;
-        ia.ended_pos = e->tile_ended_pos;
-        ia.key_out = keys_next;
-        absorbed_scan_kernel<<<1, CMI_TILE_PLAN_THREADS, 0, e->stream>>>(
-            d_nitems, e->tile_absorbed_count, e->tile_absorbed_before);
-        HIP_TRY(hipGetLastError());
-        /* (about a quarter of a round's flights are absorbed) */
-        const int sblocks = grid_blocks(e, (int64_t)nlive / 2 + 1, 8);
-        if (defer) {
-          HIP_TRY(hipMemsetAsync(d_new, 0, sizeof(unsigned int), e->stream));
-          interaction_slots_kernel<true, true>
-              <<<sblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-          HIP_TRY(hipGetLastError());
-          FlightWeightsArgs wa;
-          wa.model = e->model;
-          wa.rows = rows;
-          wa.slots = e->tile_new_slots;
-          wa.count = d_new;
-          wa.n = 0;
-          /* (about a tenth of a round's flights are re-emitted) */
-          flight_weights_kernel<<<grid_blocks(e, (int64_t)nlive / 4 + 1, 8),
-                                  CMI_BLOCK, 0, e->stream>>>(wa);
-        } else if (e->full_ions)
-          interaction_slots_kernel<true>
-              <<<sblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-        else
-          interaction_slots_kernel<false>
-              <<<sblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-        HIP_TRY(hipGetLastError());
-        /* the next round: this round's places are its positions */
-        {
-          uint32_t *t = keys;
-          keys = keys_next;
-          keys_next = t;
-        }
-        slot_of = e->tile_slot_of[next_slot_of];
-        next_slot_of = 1 - next_slot_of;
-        npos = nlive;
-      }
-    }
-    /* ... or as passes of the transport kernel: the interaction kernel turns
-     * the ended flights of one launch into the ready flights of the next.
-     * Those start all over the grid in random directions, so these launches
-     * refill eagerly instead of keeping ray bundles together. */
-    if (handover_count != 0) {
-      /* pass 0 of the tail: the flights resume from their slots, absorbed
-       * ones are parked for the interaction kernel as in every pass */
-      const bool last = handover_count < reemit_inline_below(e);
-      ShootArgs b = a;
-      b.park_in_place = 0;
-      b.order = nullptr;
-      b.xin = handover;
-      b.xin_local = 1;
-      b.n_packets = handover_count;
-      b.refill_threshold = e->tune.refill_threshold_reemit;
-      b.aggregate = agg_reemit;
-      b.qin = no_queue;
-      b.qout = last ? no_queue : e->ended_queue;
-      if (!last)
-        HIP_TRY(hipMemsetAsync(e->ended_queue.count, 0, sizeof(unsigned int),
-                               e->stream));
-      const uint64_t nch = ((uint64_t)handover_count + b.chunk - 1) / b.chunk;
-      int64_t nb =
-          (int64_t)e->num_cu * (last ? blocks_per_cu_inline : blocks_per_cu);
-      const int64_t nneed =
-          (int64_t)((nch + (CMI_BLOCK / 64) - 1) / (CMI_BLOCK / 64));
-      if (nb > nneed)
-        nb = nneed;
-      if (nb < 1)
-        nb = 1;
-      EventPair gev;
-      {
-        int trc = timer_begin(e, gev);
-        if (trc)
-          return trc;
-      }
-      (last ? kernel_inline : kernel)<<<(unsigned)nb, CMI_BLOCK, 0,
-                                        e->stream>>>(b);
-      HIP_TRY(hipGetLastError());
-      {
-        int trc = timer_end(e, e->kernel_events, gev, handover_count);
-        if (trc)
-          return trc;
-      }
-      if (last)
-        handover_count = 0;
-    }
-    for (int gen = 0; passes && (!tiles || handover_count != 0); ++gen) {
-      InteractArgs ia;
-      ia.model = e->model;
-      ia.cells = e->cells;
-      ia.counters = e->counters;
-      ia.first_packet = a.first_packet;
-      ia.seed = seed;
-      ia.iteration = iteration;
-      ia.qin = e->ended_queue;
-      /* (the first pass reads what the first generation parked) */
-      ia.n_in = (gen == 0 && !tiles && a.park_in_place) ? (uint32_t)n : 0u;
-      ia.qout = e->ready_queue;
-      HIP_TRY(hipMemsetAsync(e->ready_queue.count, 0, sizeof(unsigned int),
-                             e->stream));
-      const int iblocks = e->num_cu * 8;
-      memset(&ia.rows, 0, sizeof ia.rows);
-      ia.grid = e->grid;
-      memset(&ia.tiles, 0, sizeof ia.tiles);
-      ia.items = nullptr;
-      ia.nitems = nullptr;
-      ia.absorbed_before = nullptr;
-      ia.ended_slot = nullptr;
-      ia.ended_pos = nullptr;
-      ia.key_out = nullptr;
-      if (e->full_ions)
-        interaction_kernel<true, false>
-            <<<iblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-      else
-        interaction_kernel<false, false>
-            <<<iblocks, CMI_BLOCK, 0, e->stream>>>(ia);
-      HIP_TRY(hipGetLastError());
-      unsigned int count = 0;
-      {
-        int rrc = read_counters(e, e->ready_queue.count, 1, &count);
-        if (rrc)
-          return rrc;
-      }
-      if (count == 0)
-        break;
-      const bool last = count < reemit_inline_below(e) ||
-                        gen + 2 >= e->tune.reemit_max_passes;
-      ShootArgs b = a;
-      b.park_in_place = 0;
-      b.order = nullptr;
-      b.xin = nullptr;
-      b.n_packets = count;
-      b.refill_threshold = e->tune.refill_threshold_reemit;
-      b.aggregate = agg_reemit;
-      b.qin = e->ready_queue;
-      b.qout = last ? no_queue : e->ended_queue;
-      if (!last)
-        HIP_TRY(hipMemsetAsync(e->ended_queue.count, 0, sizeof(unsigned int),
-                               e->stream));
-      const uint64_t nch = ((uint64_t)count + b.chunk - 1) / b.chunk;
-      int64_t nb =
-          (int64_t)e->num_cu * (last ? blocks_per_cu_inline : blocks_per_cu);
-      const int64_t nneed =
-          (int64_t)((nch + (CMI_BLOCK / 64) - 1) / (CMI_BLOCK / 64));
-      if (nb > nneed)
-        nb = nneed;
-      if (nb < 1)
-        nb = 1;
-      EventPair gev;
-      {
-        int trc = timer_begin(e, gev);
-        if (trc)
-          return trc;
-      }
-      /* the last pass follows whatever is still re-emitted in place */
-      (last ? kernel_inline : kernel)<<<(unsigned)nb, CMI_BLOCK, 0,
-                                        e->stream>>>(b);
-      HIP_TRY(hipGetLastError());
-      {
-        int trc = timer_end(e, e->kernel_events, gev, count);
-        if (trc)
-          return trc;
-      }
-      if (last)
-        break;
-    }
-    {
-      int trc = timer_end(e, e->shoot_events, ev, 0);
-      if (trc)
-        return trc;
-    }
-  }
-  return CMI_GPU_OK;
-}
+#include "transport_driver.h"
 
 int cmi_gpu_shoot(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
                   uint64_t first_packet, uint64_t n_packets) {
@@ -2842,9 +1744,7 @@ int cmi_gpu_download_exports(cmi_gpu_engine *e, double *host_rows,
   if (!e || !count || (!host_rows && capacity))
     return fail(CMI_GPU_EINVAL, "download_exports: bad argument");
   uint64_t n = 0;
-  int rc = cmi_gpu_get_export_count(e, &n);
-  if (rc)
-    return rc;
+  CMI_TRY(cmi_gpu_get_export_count(e, &n));
   *count = n;
   if (n > capacity)
     return fail(CMI_GPU_ENOMEM,
@@ -2867,15 +1767,8 @@ int cmi_gpu_shoot_flights_host(cmi_gpu_engine *e, uint32_t seed,
   if (n_flights == 0)
     return CMI_GPU_OK;
   HIP_TRY(hipSetDevice(e->device));
-  if (e->import_capacity < n_flights) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(e->import_rows);
-    e->import_rows = nullptr;
-    e->import_capacity = 0;
-    HIP_TRY(hipMalloc(&e->import_rows,
-                      sizeof(double) * CMI_FLIGHT_DOUBLES * n_flights));
-    e->import_capacity = n_flights;
-  }
+  CMI_TRY(grow(e, e->import_rows, e->import_capacity, n_flights,
+               sizeof(double) * CMI_FLIGHT_DOUBLES * n_flights));
   /* launches of an earlier call may still read the staging buffer */
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpyAsync(e->import_rows, host_rows,
@@ -2901,11 +1794,7 @@ int cmi_gpu_get_counters(cmi_gpu_engine *e, double *totweight,
     return fail(CMI_GPU_EINVAL, "null engine");
   HIP_TRY(hipSetDevice(e->device));
   CountersDev host;
-  {
-    int rc = download_counters(e, host);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(download_counters(e, host));
   if (totweight)
     *totweight = host.totweight;
   if (typecount)
@@ -2921,11 +1810,7 @@ int cmi_gpu_get_atomic_count(cmi_gpu_engine *e, uint64_t *natomics) {
     return fail(CMI_GPU_EINVAL, "get_atomic_count: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   CountersDev host;
-  {
-    int rc = download_counters(e, host);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(download_counters(e, host));
   *natomics = host.natomics;
   return CMI_GPU_OK;
 }
@@ -2935,11 +1820,7 @@ int cmi_gpu_get_wave_steps(cmi_gpu_engine *e, uint64_t *nwavesteps) {
     return fail(CMI_GPU_EINVAL, "get_wave_steps: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   CountersDev host;
-  {
-    int rc = download_counters(e, host);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(download_counters(e, host));
   *nwavesteps = host.nwavesteps;
   return CMI_GPU_OK;
 }
@@ -2956,14 +1837,8 @@ static int temperature_pipeline(cmi_gpu_engine *e, const UpdateArgs &a) {
     return sizeof(double) * (state_doubles + eval_doubles) * cap +
            sizeof(uint32_t) * 4 * (size_t)cap;
   };
-  if (e->temp_pipe_capacity < want) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(e->temp_pipe_block);
-    e->temp_pipe_block = nullptr;
-    e->temp_pipe_capacity = 0;
-    HIP_TRY(hipMalloc(&e->temp_pipe_block, bytes_for(want)));
-    e->temp_pipe_capacity = want;
-  }
+  CMI_TRY(grow(e, e->temp_pipe_block, e->temp_pipe_capacity, want,
+               bytes_for(want)));
   if (!e->temp_pipe_counts)
     HIP_TRY(hipMalloc(&e->temp_pipe_counts, 4 * sizeof(unsigned int)));
   const uint32_t cap = e->temp_pipe_capacity;
@@ -2993,11 +1868,7 @@ static int temperature_pipeline(cmi_gpu_engine *e, const UpdateArgs &a) {
                         e->stream>>>(p);
     HIP_TRY(hipGetLastError());
     unsigned int nactive = 0;
-    {
-      int rrc = read_counters(e, p.counts, 1, &nactive);
-      if (rrc)
-        return rrc;
-    }
+    CMI_TRY(read_counters(e, p.counts, 1, &nactive));
     /* (a solve ends after t_max_iterations steps at the latest) */
     while (nactive != 0) {
       p.nactive = nactive;
@@ -3017,9 +1888,7 @@ static int temperature_pipeline(cmi_gpu_engine *e, const UpdateArgs &a) {
       temp_secant_kernel<<<grid_blocks(e, (int64_t)nactive, 8), CMI_BLOCK, 0,
                            e->stream>>>(p);
       HIP_TRY(hipGetLastError());
-      int rrc = read_counters(e, next_count, 1, &nactive);
-      if (rrc)
-        return rrc;
+      CMI_TRY(read_counters(e, next_count, 1, &nactive));
       p.current = 1 - p.current;
     }
   }
@@ -3069,16 +1938,10 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
   a.count = ncell;
 
   EventPair ev;
-  {
-    int trc = timer_begin(e, ev);
-    if (trc)
-      return trc;
-  }
+  CMI_TRY(timer_begin(e, ev));
   const int blocks = grid_blocks(e, ncell, 8);
   if (solve_temperature && e->tune.temperature_pipeline) {
-    int prc = temperature_pipeline(e, a);
-    if (prc)
-      return prc;
+    CMI_TRY(temperature_pipeline(e, a));
   } else if (solve_temperature)
     temperature_kernel<<<blocks, CMI_BLOCK, 0, e->stream>>>(a);
   else if (e->full_ions)
@@ -3088,11 +1951,7 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
   else
     ionization_kernel<false, false><<<blocks, CMI_BLOCK, 0, e->stream>>>(a);
   HIP_TRY(hipGetLastError());
-  {
-    int trc = timer_end(e, e->update_events, ev, 0);
-    if (trc)
-      return trc;
-  }
+  CMI_TRY(timer_end(e, e->update_events, ev, 0));
   return CMI_GPU_OK;
 }
 
@@ -3375,11 +2234,7 @@ int cmi_gpu_emit_packets(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
   if (n == 0)
     return CMI_GPU_OK;
   HIP_TRY(hipSetDevice(e->device));
-  {
-    int rc = ensure_spectra(e);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(ensure_spectra(e));
   double *d = nullptr;
   const size_t per = 3 + 3 + 1 + CMI_NION + 1;
   HIP_TRY(hipMalloc(&d, sizeof(double) * per * n));
@@ -3853,9 +2708,7 @@ static int dust_prepare(cmi_gpu_engine *e) {
 
 int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
                        uint64_t n) {
-  int rc = dust_prepare(e);
-  if (rc)
-    return rc;
+  CMI_TRY(dust_prepare(e));
   uint64_t size = CMI_DUST_FIRST_LAUNCH;
   for (uint64_t done = 0; done < n;) {
     const uint64_t chunk = std::min<uint64_t>(n - done, size);
@@ -3868,16 +2721,12 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
                              sizeof steps_before, hipMemcpyDeviceToHost,
                              e->stream));
     EventPair ev;
-    rc = timer_begin(e, ev);
-    if (rc)
-      return rc;
+    CMI_TRY(timer_begin(e, ev));
     dust_shoot_kernel<<<(unsigned)((chunk + 255) / 256), 256, 0, e->stream>>>(
         e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
         e->dust_counters);
     HIP_TRY(hipGetLastError());
-    rc = timer_end(e, e->shoot_events, ev, chunk);
-    if (rc)
-      return rc;
+    CMI_TRY(timer_end(e, e->shoot_events, ev, chunk));
     done += chunk;
     if (measure) {
       /* the next launch's size from this one's steps per packet */
@@ -3920,9 +2769,7 @@ int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
   if (!e->have_ccd)
     return fail(CMI_GPU_ESTATE, "download_image: no image (set_ccd_image)");
   uint64_t c[6];
-  int rc = cmi_gpu_get_dust_counters(e, c);
-  if (rc)
-    return rc;
+  CMI_TRY(cmi_gpu_get_dust_counters(e, c));
   if (c[5])
     return fail(CMI_GPU_ESTATE,
                 "download_image: the source found no position in the box for "
@@ -3972,9 +2819,7 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
                                                          : 4 + 8 * max_events;
   if (in_width[kind] && !in)
     return fail(CMI_GPU_EINVAL, "dust_probe: input rows missing");
-  int rc = dust_prepare(e);
-  if (rc)
-    return rc;
+  CMI_TRY(dust_prepare(e));
   if (n == 0)
     return CMI_GPU_OK;
   double *din = nullptr, *dout = nullptr;

@@ -1,6 +1,7 @@
 /*
- * group.h - several engines driven by ONE host process (included at the end
- * of engine.hip): the native multi-GPU layer of the C ABI.
+ * group.h - several engines driven by ONE host process: the native multi-GPU
+ * layer of the C ABI (host code of engine.hip's translation unit, included at
+ * its end as transport_driver.h is further up).
  *
  *  replica mode   every engine holds the whole grid and flies its share of
  *                 the packets; cmi_gpu_group_reduce_accumulators sums the
@@ -558,11 +559,7 @@ static int reduce_class(cmi_gpu_group *g, GroupClass &c) {
     HIP_TRY(hipStreamSynchronize(e0->stream));
     return CMI_GPU_OK;
   }
-  {
-    const int rc = class_comm(g, c);
-    if (rc)
-      return rc;
-  }
+  CMI_TRY(class_comm(g, c));
   /* one grouped all-reduce per piece: every engine's call is enqueued on its
    * own stream, behind its transport kernels */
   for (int p = 0; p < pieces; ++p) {
@@ -597,9 +594,7 @@ int cmi_gpu_group_reduce_accumulators(cmi_gpu_group *g) {
   for (GroupClass &c : g->classes) {
     if (c.member.size() == 1 && !force)
       continue;
-    const int rc = reduce_class(g, c);
-    if (rc)
-      return rc;
+    CMI_TRY(reduce_class(g, c));
   }
   return CMI_GPU_OK;
 }
@@ -624,10 +619,8 @@ static int update_class(cmi_gpu_group *g, GroupClass &c, uint32_t loop,
       /* (a fresh host thread has device 0 current, and update_cells_range
        * returns before its own hipSetDevice for an empty slab) */
       HIP_TRY(hipSetDevice(e->device));
-      const int urc = cmi_gpu_update_cells_range(e, loop, totweight, first[r],
-                                                 first[r + 1] - first[r]);
-      if (urc)
-        return urc;
+      CMI_TRY(cmi_gpu_update_cells_range(e, loop, totweight, first[r],
+                                         first[r + 1] - first[r]));
       HIP_TRY(hipEventRecord(g->solved[c.member[r]], e->stream));
       return CMI_GPU_OK;
     });
@@ -638,9 +631,7 @@ static int update_class(cmi_gpu_group *g, GroupClass &c, uint32_t loop,
     /* MPICommunicator::gather of the temperature and the ionic fractions
      * (src/IonizationSimulation.cpp:540-618) as grouped in-place
      * ncclAllGathers: slab r of a field sits at its place in every engine */
-    const int rc0 = class_comm(g, c);
-    if (rc0)
-      return rc0;
+    CMI_TRY(class_comm(g, c));
     const int64_t count = ncell / n;
     int rc = g_rccl.GroupStart();
     hipError_t herr = hipSuccess;

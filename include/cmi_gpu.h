@@ -557,7 +557,7 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *                           with the tile's transport records and accumulators
  *                           in LDS (written back with full-line atomics)
  *                           instead of one memory-side atomic per DDA step
- *   "tile_min_flights" (100000), "tile_min_per_item" (-1 = auto: 200), "tile_max_rounds" (1000)
+ *   "tile_min_flights" (100000), "tile_min_per_item" (-1 = auto: 200)
  *                           the rounds end - and passes of the transport
  *                           kernel take over - once fewer flights than this,
  *                           or fewer than this per unit of work (<= 8192
@@ -570,17 +570,6 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *                           launch's order instead of claiming a place from
  *                           the queue's counter (one returning atomic per
  *                           bundle on one word)
- *   "block_select" (1)      a block of a decomposed grid picks the packets
- *                           that start in it out of a launch's ids before
- *                           keys, sort and transport (the reference gives a
- *                           subgrid's source task its own share of the
- *                           packets, src/DistributedPhotonSource.hpp:140-200);
- *                           0: every block runs all ids through them and the
- *                           transport kernel drops the others
- *   "block_first_kernels" (1)  ... and flies them with the kernels built for
- *                           a whole grid's first generation (padded march,
- *                           emission rows from the key kernel); 0: the pass
- *                           kernels, as before round 6
  *   "tile_compact_ratio" (-1)  the rows of the live flights are copied into
  *                           fresh rows, in tile order, once the flights are
  *                           spread over this many slots per flight; 0: never;
