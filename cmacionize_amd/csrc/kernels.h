@@ -61,6 +61,13 @@ constexpr int shoot_block_threads() {
 #ifndef CMI_PAD_HASH_LOW_BITS
 #define CMI_PAD_HASH_LOW_BITS 0
 #endif
+/* distance of the PAD table's tags in 4-byte words. 2: a slot's tag and its
+ * value sit at the same offset of their arrays - one address register and one
+ * shift per look-up instead of two - for 8 KB more LDS per 2048 slots and tags
+ * in every other bank. */
+#ifndef CMI_PAD_TAG_STRIDE
+#define CMI_PAD_TAG_STRIDE 1
+#endif
 /* experiment: look at a slot's tag with a plain LDS read before trying the
  * compare-and-swap (a hit then costs no LDS atomic; measured: 39.0 instead of
  * 34.5 ms - the second round trip of every first visit costs more than the
@@ -236,6 +243,14 @@ struct ShootArgs {
 #define CMI_PAD_LAYERS 1
 #define CMI_PAD_VACUUM (-0.)
 #define CMI_PAD_GHOST (-2.)
+/* The PAD march keeps a packet's cell - Packet::cell and cstep[], the run key,
+ * the table's tags, last_cell until the flight's end - as the BYTE OFFSET of
+ * the cell's record, 8 x the padded long index (< 2^32: an unsigned 32-bit
+ * value): it is the offset operand of the record's load as it stands, no
+ * shift per step. The padded long index of such an offset: */
+__device__ __forceinline__ int32_t cmi_pad_index(int32_t offset) {
+  return (int32_t)((uint32_t)offset >> 3);
+}
 /* long index in the grid of the padded long index c of a cell inside it
  * (c < 2^29; (c + 0.5) / d is never within 0.5 / d of an integer, far more
  * than the rounding of the product) */
@@ -261,7 +276,7 @@ __device__ __forceinline__ int32_t cmi_unpad_cell(const ShootArgs &a,
 template <bool FULL>
 __device__ __forceinline__ int64_t
 exit_cell_global_padded(const ShootArgs &a, const GridDev &g, Packet<FULL> &p) {
-  const int32_t c = p.cell;
+  const int32_t c = cmi_pad_index(p.cell);
   const int32_t ix = (int32_t)(((double)c + 0.5) * a.pad_inv_yz);
   const int32_t r = c - ix * (a.pad_ny * a.pad_nz);
   const int32_t iy = (int32_t)(((double)r + 0.5) * a.pad_inv_z);
@@ -424,70 +439,128 @@ __device__ __forceinline__ void quad_run_sums(int32_t key, double (&v)[N],
  * under the mask in VCC) and a plain add: three vector instructions per value
  * and round. (A group's first 2^r - 1 lanes have their stop bit set by round
  * r whatever the neighbouring group's bits shifted in say.) The LAST lane of
- * every run holds its total; `tails` is the mask of those lanes. */
-#define CMI_DPP_ROW_SHL(n) (0x100 + (n))
-/* stops ? 0 : (v of the lane D below, 0 where the row has none): one
- * v_cndmask_b32_dpp per half under the mask in VCC. (Inline assembly: the
- * compiler turns the select into moves under the execution mask. Two wait
- * states between the vector instruction that wrote v and a DPP read of it:
- * the s_mov and the s_nop.) */
-#define CMI_TAKE_UNLESS(D)                                                     \
-  template <> __device__ __forceinline__ double take_unless<D>(               \
-      unsigned long long stops, double v, int zero) {                          \
-    int lo, hi;                                                                \
-    asm("s_mov_b64 vcc, %4\n\ts_nop 0\n\t"                                    \
-        "v_cndmask_b32_dpp %0, %2, %5, vcc row_shr:" #D                        \
-        " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                         \
-        "v_cndmask_b32_dpp %1, %3, %5, vcc row_shr:" #D                        \
-        " row_mask:0xf bank_mask:0xf bound_ctrl:1"                             \
-        : "=&v"(lo), "=&v"(hi)                                                 \
-        : "v"(__double2loint(v)), "v"(__double2hiint(v)), "s"(stops),          \
-          "v"(zero)                                                            \
-        : "vcc");                                                              \
-    return __hiloint2double(hi, lo);                                           \
-  }
-template <int D>
-__device__ __forceinline__ double take_unless(unsigned long long stops,
-                                              double v, int zero);
-CMI_TAKE_UNLESS(1)
-CMI_TAKE_UNLESS(2)
-CMI_TAKE_UNLESS(4)
-CMI_TAKE_UNLESS(8)
-#undef CMI_TAKE_UNLESS
-/* (`zero`: a vector register that holds 0, kept by the caller across its
- * loop) */
-template <int N, int ROUNDS>
-__device__ __forceinline__ void run_sums_masked(int32_t key, double (&v)[N],
-                                                unsigned long long &tails,
-                                                int zero) {
+ * every run holds its total; `tails` is the mask of those lanes.
+ *
+ * The loops this runs in are bound by instruction issue, vector and scalar
+ * alike, so the masks cost as little as they can:
+ *  - the stops live in VCC from the OR that forms them to the last select
+ *    (operands tied to the register: no copy into VCC per round);
+ *  - a DPP read needs two wait states after the vector instruction that wrote
+ *    its source - they are the two scalar instructions that widen the stops
+ *    for the round (three in the first round), not a no-op;
+ *  - lane i ends a run exactly where lane i + 1 starts one, so the tails are
+ *    the first round's stops shifted down by one, not a second DPP move and
+ *    compare (row and group ends: `last`);
+ *  - the group masks come in scalar register pairs the caller loads once
+ *    (RunMasks), not as two 32-bit literals each. */
+struct RunMasks {
+  unsigned long long first, last; /* first / last lanes of the groups */
+};
+template <int ROUNDS> __device__ __forceinline__ RunMasks run_masks() {
   static_assert(ROUNDS >= 1 && ROUNDS <= 4, "groups of 2 to 16 lanes");
-  /* first / last lanes of the groups of 2^ROUNDS lanes */
   constexpr unsigned long long first =
       ROUNDS == 1 ? 0x5555555555555555ull
                   : ROUNDS == 2 ? 0x1111111111111111ull
                                 : ROUNDS == 3 ? 0x0101010101010101ull
                                               : 0x0001000100010001ull;
-  constexpr unsigned long long last = first << ((1 << ROUNDS) - 1);
-  /* (lanes at the ends of a row of 16 read 0: they start / end a group) */
-  const int32_t prev = dpp_zero<CMI_DPP_ROW_SHR(1), 0xf>(key);
-  const int32_t next = dpp_zero<CMI_DPP_ROW_SHL(1), 0xf>(key);
-  unsigned long long stops = mask_ne(key, prev) | first;
-  tails = mask_ne(key, next) | last;
-#define CMI_MASKED_ROUND(D)                                                    \
-  {                                                                            \
-    _Pragma("unroll") for (int k = 0; k < N; ++k) v[k] +=                      \
-        take_unless<D>(stops, v[k], zero);                                     \
-    stops |= stops << (D);                                                     \
-  }
-  CMI_MASKED_ROUND(1)
-  if (ROUNDS > 1)
-    CMI_MASKED_ROUND(2)
-  if (ROUNDS > 2)
-    CMI_MASKED_ROUND(4)
-  if (ROUNDS > 3)
-    CMI_MASKED_ROUND(8)
-#undef CMI_MASKED_ROUND
+  RunMasks m = {first, first << ((1 << ROUNDS) - 1)};
+  /* (materialised here, outside the caller's loop) */
+  asm volatile("" : "+s"(m.first), "+s"(m.last));
+  return m;
 }
+/* stops ? 0 : (v of the lane D below, 0 where the row has none): one
+ * v_cndmask_b32_dpp per half under the mask in VCC. (Inline assembly: the
+ * compiler turns the select into moves under the execution mask.) */
+#define CMI_TAKE_DPP(OUT, IN, D)                                               \
+  "v_cndmask_b32_dpp " OUT ", " IN ", %[zero], vcc row_shr:" #D                \
+  " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+/* the scalar part of a round, ahead of its selects: the first forms the
+ * stops and the tails, a later one of distance D = 2 W widens the stops */
+#define CMI_RUN_FIRST                                                          \
+  "s_or_b64 vcc, %[ne], %[first]\n\t"                                          \
+  "s_lshr_b64 %[tails], vcc, 1\n\t"                                            \
+  "s_or_b64 %[tails], %[tails], %[last]\n\t"
+#define CMI_RUN_WIDEN(W)                                                       \
+  "s_lshl_b64 %[wide], vcc, " #W "\n\t"                                        \
+  "s_or_b64 vcc, vcc, %[wide]\n\t"
+#define CMI_RUN_OUT1 [lo0] "=&v"(lo0), [hi0] "=&v"(hi0), "=s"(stops)
+#define CMI_RUN_OUT2 CMI_RUN_OUT1, [lo1] "=&v"(lo1), [hi1] "=&v"(hi1)
+#define CMI_RUN_IN1                                                            \
+  [a0] "v"(__double2loint(v[0])), [b0] "v"(__double2hiint(v[0])),              \
+      [zero] "v"(zero)
+#define CMI_RUN_IN2                                                            \
+  CMI_RUN_IN1, [a1] "v"(__double2loint(v[N - 1])),                             \
+      [b1] "v"(__double2hiint(v[N - 1]))
+#define CMI_RUN_SEL1(D)                                                        \
+  CMI_TAKE_DPP("%[lo0]", "%[a0]", D) CMI_TAKE_DPP("%[hi0]", "%[b0]", D)
+#define CMI_RUN_SEL2(D)                                                        \
+  CMI_RUN_SEL1(D)                                                              \
+  CMI_TAKE_DPP("%[lo1]", "%[a1]", D) CMI_TAKE_DPP("%[hi1]", "%[b1]", D)
+#define CMI_RUN_ADD                                                            \
+  v[0] += __hiloint2double(hi0, lo0);                                          \
+  if (N > 1)                                                                   \
+    v[N - 1] += __hiloint2double(hi1, lo1);
+#define CMI_RUN_ROUND(D, W)                                                    \
+  {                                                                            \
+    unsigned long long wide;                                                   \
+    if (N == 1)                                                                \
+      asm(CMI_RUN_WIDEN(W) CMI_RUN_SEL1(D)                                     \
+          : CMI_RUN_OUT1, [wide] "=&s"(wide)                                   \
+          : CMI_RUN_IN1, "2"(stops)                                            \
+          : "scc");                                                            \
+    else                                                                       \
+      asm(CMI_RUN_WIDEN(W) CMI_RUN_SEL2(D)                                     \
+          : CMI_RUN_OUT2, [wide] "=&s"(wide)                                   \
+          : CMI_RUN_IN2, "2"(stops)                                            \
+          : "scc");                                                            \
+    CMI_RUN_ADD                                                                \
+  }
+/* (`zero`: a vector register that holds 0, kept by the caller across its
+ * loop; `m`: run_masks<ROUNDS>(), likewise) */
+template <int N, int ROUNDS>
+__device__ __forceinline__ void run_sums_masked(int32_t key, double (&v)[N],
+                                                unsigned long long &tails,
+                                                int zero, const RunMasks &m) {
+  static_assert(N == 1 || N == 2, "one or two values");
+  /* (lanes at the start of a row of 16 read 0: they start a group anyway) */
+  const int32_t prev = dpp_zero<CMI_DPP_ROW_SHR(1), 0xf>(key);
+  const unsigned long long ne = mask_ne(key, prev);
+  /* (a variable bound to VCC: the selects can take their mask nowhere else,
+   * and an operand tied to it passes the stops from round to round without
+   * a copy) */
+  register unsigned long long stops asm("vcc");
+  unsigned long long ends;
+  int lo0, hi0, lo1 = 0, hi1 = 0;
+  if (N == 1)
+    asm(CMI_RUN_FIRST CMI_RUN_SEL1(1)
+        : CMI_RUN_OUT1, [tails] "=&s"(ends)
+        : CMI_RUN_IN1, [ne] "s"(ne), [first] "s"(m.first), [last] "s"(m.last)
+        : "scc");
+  else
+    asm(CMI_RUN_FIRST CMI_RUN_SEL2(1)
+        : CMI_RUN_OUT2, [tails] "=&s"(ends)
+        : CMI_RUN_IN2, [ne] "s"(ne), [first] "s"(m.first), [last] "s"(m.last)
+        : "scc");
+  tails = ends;
+  CMI_RUN_ADD
+  if (ROUNDS > 1)
+    CMI_RUN_ROUND(2, 1)
+  if (ROUNDS > 2)
+    CMI_RUN_ROUND(4, 2)
+  if (ROUNDS > 3)
+    CMI_RUN_ROUND(8, 4)
+}
+#undef CMI_RUN_FIRST
+#undef CMI_RUN_WIDEN
+#undef CMI_RUN_OUT1
+#undef CMI_RUN_OUT2
+#undef CMI_RUN_IN1
+#undef CMI_RUN_IN2
+#undef CMI_RUN_SEL1
+#undef CMI_RUN_SEL2
+#undef CMI_RUN_ADD
+#undef CMI_RUN_ROUND
+#undef CMI_TAKE_DPP
 
 /* FULL mode (all 14 ions + 2 heating terms per step): update_integrals as a
  * cooperative, transposed accumulation. A lane's 16 accumulation weights
@@ -1139,7 +1212,8 @@ __global__ void
   constexpr int lds_slots =
       GROUPED ? 1 : (FULL ? CMI_FTABLE_SLOTS : TSLOTS);
   constexpr int lds_values = FULL ? CMI_NACC : (HEAT ? 2 : 1);
-  __shared__ int32_t lds_tag[lds_slots];
+  constexpr int TS = PAD ? CMI_PAD_TAG_STRIDE : 1;
+  __shared__ int32_t lds_tag[TS * lds_slots];
   /* FULL: one more row, the sink of table_row() for lanes without a slot */
   __shared__ double lds_val[lds_values * (lds_slots + (FULL ? 1 : 0))];
   __shared__ int32_t block_has_work[BLOCK / 64];
@@ -1167,7 +1241,7 @@ __global__ void
       !GROUPED && (TABLE || a.aggregate == CMI_AGG_BLOCK);
   if (use_table) {
     for (int k = threadIdx.x; k < lds_slots; k += BLOCK)
-      lds_tag[k] = -1;
+      lds_tag[TS * k] = -1;
     for (int k = threadIdx.x; k < lds_values * lds_slots; k += BLOCK)
       lds_val[k] = 0.;
     __syncthreads();
@@ -1199,9 +1273,11 @@ __global__ void
       }
     } else {
       for (int k = threadIdx.x; k < lds_slots; k += BLOCK) {
-        const int32_t t = lds_tag[k];
-        if (t >= 0) {
-          const int32_t c = PAD ? cmi_unpad_cell(a, a.grid, t) : t;
+        const int32_t t = lds_tag[TS * k];
+        /* (PAD: a record's byte offset, which may have bit 31 set) */
+        if (PAD ? t != -1 : t >= 0) {
+          const int32_t c =
+              PAD ? cmi_unpad_cell(a, a.grid, cmi_pad_index(t)) : t;
           atomic_add_f64(acc_at(a.cells, ION_H_n, c), lds_val[k]);
           lds_val[k] = 0.;
           if (HEAT) {
@@ -1209,7 +1285,7 @@ __global__ void
                            lds_val[lds_slots + k]);
             lds_val[lds_slots + k] = 0.;
           }
-          lds_tag[k] = -1;
+          lds_tag[TS * k] = -1;
           natomics += HEAT ? 2 : 1;
         }
       }
@@ -1238,16 +1314,20 @@ __global__ void
        * + 4 x modulo 8 with an even padded extent: the cells of a 2 x 2 x 2
        * neighbourhood, where the lanes of a bundle sit at any one step, fall
        * into different LDS banks -, the rest is hashed */
+      const uint32_t index = (uint32_t)cmi_pad_index(cell);
       asm("v_mul_u32_u24 %0, 0x9e3779, %1"
           : "=v"(product)
-          : "v"(cell >> CMI_PAD_HASH_LOW_BITS));
+          : "v"(index >> CMI_PAD_HASH_LOW_BITS));
       slot = (((product >> (24 - TBITS + CMI_PAD_HASH_LOW_BITS))
                << CMI_PAD_HASH_LOW_BITS) |
-              ((uint32_t)cell & ((1u << CMI_PAD_HASH_LOW_BITS) - 1u))) &
+              (index & ((1u << CMI_PAD_HASH_LOW_BITS) - 1u))) &
              (TSLOTS - 1);
 #else
+      /* (`cell` is 8 x the padded index: the product's bits sit three places
+       * up, and the multiply's 24 bits hold the index's low 21 - cells 2^21
+       * apart in the padded index share a slot, no neighbours do) */
       asm("v_mul_u32_u24 %0, 0x9e3779, %1" : "=v"(product) : "v"(cell));
-      slot = (product >> (24 - TBITS)) & (TSLOTS - 1);
+      slot = (product >> (24 - TBITS + 3)) & (TSLOTS - 1);
 #endif
     } else {
       slot = ((uint32_t)cell * 0x9E3779B1u) >> (32 - TBITS);
@@ -1260,19 +1340,19 @@ __global__ void
       unsigned long long found;
       if (CMI_TABLE_READ_FIRST) {
         if (lanes_of(looking))
-          was = *(volatile int32_t *)&lds_tag[slot];
+          was = *(volatile int32_t *)&lds_tag[TS * slot];
         found = looking & mask_eq(was, cell);
         const unsigned long long vacant = looking & mask_eq(was, -1);
         if (vacant != 0ull) {
           int32_t got;
           asm volatile("" : "=v"(got));
           if (lanes_of(vacant))
-            got = atomicCAS(&lds_tag[slot], -1, cell);
+            got = atomicCAS(&lds_tag[TS * slot], -1, cell);
           found |= vacant & (mask_eq(got, -1) | mask_eq(got, cell));
         }
       } else {
         if (lanes_of(looking))
-          was = atomicCAS(&lds_tag[slot], -1, cell);
+          was = atomicCAS(&lds_tag[TS * slot], -1, cell);
         found = looking & (mask_eq(was, -1) | mask_eq(was, cell));
       }
       if (lanes_of(found)) {
@@ -1287,7 +1367,8 @@ __global__ void
         return;
     }
     if (lanes_of(looking)) {
-      const int32_t c = PAD ? cmi_unpad_cell(a, a.grid, cell) : cell;
+      const int32_t c =
+          PAD ? cmi_unpad_cell(a, a.grid, cmi_pad_index(cell)) : cell;
       atomic_add_f64(acc_at(a.cells, ION_H_n, c), v0);
       if (HEAT)
         atomic_add_f64(acc_at(a.cells, CMI_NION, c), v1);
@@ -1424,16 +1505,19 @@ __global__ void
             /* the padded long index and its strides (start_flight has set
              * index[], the signs and rem[0] < 0 for a start outside the box) */
             const int32_t sy = a.pad_nz, sx = a.pad_ny * a.pad_nz;
-            p.cstep[0] = (p.dir[0] > 0.) ? sx : -sx;
-            p.cstep[1] = (p.dir[1] > 0.) ? sy : -sy;
-            p.cstep[2] = (p.dir[2] > 0.) ? 1 : -1;
+            /* (as byte offsets of the records: cmi_pad_index) */
+            p.cstep[0] = 8 * ((p.dir[0] > 0.) ? sx : -sx);
+            p.cstep[1] = 8 * ((p.dir[1] > 0.) ? sy : -sy);
+            p.cstep[2] = (p.dir[2] > 0.) ? 8 : -8;
             const bool outside = fast_outside(p);
-            p.cell = outside ? 0
-                             : ((p.index[0] + CMI_PAD_LAYERS) * a.pad_ny +
-                                (p.index[1] + CMI_PAD_LAYERS)) *
-                                       a.pad_nz +
-                                   (p.index[2] + CMI_PAD_LAYERS);
-            pad_next = outside ? CMI_PAD_GHOST : a.pad_H[p.cell];
+            const int32_t padded =
+                outside ? 0
+                        : ((p.index[0] + CMI_PAD_LAYERS) * a.pad_ny +
+                           (p.index[1] + CMI_PAD_LAYERS)) *
+                                  a.pad_nz +
+                              (p.index[2] + CMI_PAD_LAYERS);
+            p.cell = (int32_t)((uint32_t)padded << 3);
+            pad_next = outside ? CMI_PAD_GHOST : a.pad_H[padded];
           }
           if (mine) {
             if (PRE)
@@ -1498,26 +1582,41 @@ __global__ void
        * vacuum is the record -0.: sigma x -0. leaves the optical depth alone
        * without a max(), its sign bit says "do not accumulate". */
       const unsigned long long active_lanes = wave_ballot(active);
-      const int32_t not_lane = ~lane;
-      /* (in vector registers: the scalar copy did not survive the register
-       * pressure - it was spilled to lanes of a VGPR and read back, two
-       * v_readlane and a wait, in every iteration) */
-      const char *pad_base = reinterpret_cast<const char *>(a.pad_H);
-      asm volatile("" : "+v"(pad_base));
+      /* the run key of a lane that does not accumulate: something no other
+       * lane has. Not a multiple of 8, as the cells' keys - byte offsets -
+       * are, and not the table's "empty" -1 either way. (Kept in a register
+       * of its own: the compiler rebuilds it in every iteration otherwise;
+       * `lane` itself is not needed inside the loop.) */
+      int32_t not_lane = ~(lane << 3);
+      asm volatile("" : "+v"(not_lane));
+      /* the base of the records in a scalar register pair: the load is
+       * global_load_dwordx2 v, v_offset, s[base], no 64-bit add per lane */
+      const __attribute__((address_space(1))) char *pad_base =
+          (const __attribute__((address_space(1))) char *)a.pad_H;
+      asm volatile("" : "+s"(pad_base));
       /* a refill is due once this many lanes are idle (never, if the wave
-       * has no positions left) */
+       * has no positions left): the loop goes on while more than
+       * 64 - idle_limit lanes step - one population count serves the test
+       * and the step counter, and "no lane steps" is the same test */
       const int idle_limit = __builtin_amdgcn_readfirstlane(
           avail_after != 0 ? a.refill_threshold : 65);
+      const int fly_min = idle_limit < 64 ? 64 - idle_limit : 0;
       int zero = 0;
       asm volatile("" : "+v"(zero)); /* one register for the whole loop */
+      const RunMasks pad_run_masks = run_masks<CMI_PAD_SCAN_ROUNDS>();
       unsigned int bundle_steps = 0; /* wave-uniform: a scalar register */
-      for (;;) {
-        const unsigned long long flying =
-            active_lanes & mask_gt(p.tau, 0.) & mask_gt(pad_next, -1.5);
-        if (flying == 0ull || (int)__popcll(~flying) >= idle_limit)
-          break;
+      /* the lanes' steps of this bundle (at most 64 per iteration: 32 bits
+       * hold 6.7e7 iterations, a bundle has thousands) */
+      unsigned int bundle_lane_steps = 0;
+      /* the lanes whose packet has optical depth left, and of those the ones
+       * inside the grid: they step. The loop is tested at its bottom - one
+       * compare and one branch back, no exit flag. */
+      unsigned long long in_flight = active_lanes & mask_gt(p.tau, 0.);
+      unsigned long long flying = in_flight & mask_gt(pad_next, -1.5);
+      int nflying = (int)__popcll(flying);
+      if (nflying > fly_min) do {
         ++bundle_steps;
-        nsteps_wave += (unsigned long long)__popcll(flying);
+        bundle_lane_steps += (unsigned int)nflying;
         const bool stepping = lanes_of(flying);
         /* number density > 0: the record's sign bit is clear */
         const unsigned long long accumulating =
@@ -1525,34 +1624,46 @@ __global__ void
         /* the run key - the cell about to be crossed, or something no other
          * lane has - before the march moves on (this IS the copy of the old
          * cell index the accumulation needs) */
-        const int32_t key = lanes_of(accumulating) ? p.cell : not_lane;
+        int32_t key = lanes_of(accumulating) ? p.cell : not_lane;
+        /* (here, not after the march: that would take a copy of the cell) */
+        asm volatile("" : "+v"(key));
         /* (lanes that do not step take part in the run sums with a key of
          * their own and are never a tail that adds: their path length may be
          * anything, run_sums_masked selects, it does not multiply) */
         double ds;
         asm volatile("" : "=v"(ds));
         if (stepping) {
-          const double k = pad_next;
           const double tmin =
               min_f64(p.tmax[0], min_f64(p.tmax[1], p.tmax[2]));
           const double t_old = p.t;
           ds = tmin - t_old;
-          const double sk = sigma * k;
+          const double sk = sigma * pad_next;
           p.tau -= ds * sk;
-#pragma unroll
-          for (int ax = 0; ax < 3; ++ax) {
-            /* every tied axis advances, under the execution mask: one add
-             * each for the wall parameter and the cell (vector instructions
-             * are what the loop is short of; the mask costs two scalar ones,
-             * no branch round two instructions) */
+          /* every tied axis advances, under the execution mask: one add each
+           * for the wall parameter and the cell (vector instructions are what
+           * the loop is short of). The three masks are chained: one save and
+           * one restore of the execution mask for all of them. */
+          {
             unsigned long long saved;
-            asm volatile("s_and_saveexec_b64 %2, %3\n\t"
-                         "v_add_f64 %0, %0, %4\n\t"
-                         "v_add_u32 %1, %1, %5\n\t"
-                         "s_mov_b64 exec, %2"
-                         : "+v"(p.tmax[ax]), "+v"(p.cell), "=&s"(saved)
-                         : "s"(mask_eq(p.tmax[ax], tmin)), "v"(p.tdelta[ax]),
-                           "v"(p.cstep[ax])
+            asm volatile("s_and_saveexec_b64 %[saved], %[m0]\n\t"
+                         "v_add_f64 %[t0], %[t0], %[d0]\n\t"
+                         "v_add_u32 %[cell], %[cell], %[c0]\n\t"
+                         "s_and_b64 exec, %[saved], %[m1]\n\t"
+                         "v_add_f64 %[t1], %[t1], %[d1]\n\t"
+                         "v_add_u32 %[cell], %[cell], %[c1]\n\t"
+                         "s_and_b64 exec, %[saved], %[m2]\n\t"
+                         "v_add_f64 %[t2], %[t2], %[d2]\n\t"
+                         "v_add_u32 %[cell], %[cell], %[c2]\n\t"
+                         "s_mov_b64 exec, %[saved]"
+                         : [t0] "+v"(p.tmax[0]), [t1] "+v"(p.tmax[1]),
+                           [t2] "+v"(p.tmax[2]), [cell] "+v"(p.cell),
+                           [saved] "=&s"(saved)
+                         : [m0] "s"(mask_eq(p.tmax[0], tmin)),
+                           [m1] "s"(mask_eq(p.tmax[1], tmin)),
+                           [m2] "s"(mask_eq(p.tmax[2], tmin)),
+                           [d0] "v"(p.tdelta[0]), [d1] "v"(p.tdelta[1]),
+                           [d2] "v"(p.tdelta[2]), [c0] "v"(p.cstep[0]),
+                           [c1] "v"(p.cstep[1]), [c2] "v"(p.cstep[2])
                          : "scc");
           }
           p.t = tmin;
@@ -1571,16 +1682,20 @@ __global__ void
               p.t = t_old + ds;
             }
           }
-        }
-        /* (a GLOBAL load: through the laundered pointer the compiler knows
-         * no address space and issues flat_load, which also counts as an LDS
-         * operation - the wait for the table's compare-and-swap below would
-         * then wait for this record as well, every iteration) */
-        if (stepping && p.tau >= 0.)
+          /* the record of the next cell, for every lane that stepped. (A
+           * lane whose flight has just ended inside the cell loads one too -
+           * its neighbour's, a valid padded index -: nothing reads it, and
+           * the compare, the mask and the branch that kept it from loading
+           * cost every iteration.) */
           pad_next = *reinterpret_cast<
               const __attribute__((address_space(1))) double *>(
-              (const __attribute__((address_space(1))) char *)pad_base +
-              ((uint32_t)p.cell << 3));
+              pad_base + (uint32_t)p.cell);
+        }
+        /* whose packet has optical depth left: the head test of the next
+         * iteration. (Outside the branch of the stepping lanes: a mask formed
+         * inside it is a per-lane value to the compiler, and all the loop's
+         * scalar bookkeeping with it.) */
+        in_flight = flying & mask_gt(p.tau, 0.);
         if (CMI_EXP(a) == 12) {
           /* experiment: the march alone (results are wrong) */
           asm volatile("" ::"v"(ds), "s"(accumulating));
@@ -1592,25 +1707,30 @@ __global__ void
          * groups of 8 43.0, groups of 16 44.6) */
         unsigned long long tails;
         if (HEAT)
-          run_sums_masked<2, CMI_PAD_SCAN_ROUNDS>(key, v, tails, zero);
+          run_sums_masked<2, CMI_PAD_SCAN_ROUNDS>(key, v, tails, zero,
+                                                  pad_run_masks);
         else
           run_sums_masked<1, CMI_PAD_SCAN_ROUNDS>(
-              key, reinterpret_cast<double(&)[1]>(v), tails, zero);
+              key, reinterpret_cast<double(&)[1]>(v), tails, zero,
+              pad_run_masks);
         if (CMI_EXP(a) == 11) {
           /* experiment: no table (results are wrong) */
           asm volatile("" ::"v"(v[0]), "s"(tails));
           continue;
         }
         table_add_masked(tails & accumulating, key, v[0], v[1]);
-      }
+      } while ((flying = in_flight & mask_gt(pad_next, -1.5),
+                nflying = (int)__popcll(flying), nflying > fly_min));
       nwavesteps += bundle_steps;
+      nsteps_wave += bundle_lane_steps;
       /* the rest of the kernel reads the flight's end the usual way */
       if (active && !(p.tau > 0. && pad_next > -1.5)) {
         p.rem[0] = (p.tau >= 0. && !(pad_next > -1.5)) ? -1 : 0;
         p.rem[1] = 0;
         p.rem[2] = 0;
-        if (last_cell >= 0)
-          last_cell = cmi_unpad_cell(a, a.grid, last_cell);
+        /* (a byte offset, which may have bit 31 set, or still -1) */
+        if (last_cell != -1)
+          last_cell = cmi_unpad_cell(a, a.grid, cmi_pad_index(last_cell));
       }
     }
     double2 kappa_next = make_double2(0., 0.);
@@ -1621,6 +1741,7 @@ __global__ void
     const unsigned long long active_lanes = wave_ballot(active);
     const int idle_limit = __builtin_amdgcn_readfirstlane(
         avail_after != 0 ? a.refill_threshold : 65);
+    const RunMasks table_run_masks = run_masks<CMI_TABLE_SCAN_ROUNDS>();
     for (; !PAD;) {
       unsigned long long flying;
       if (EXACT)
@@ -1734,10 +1855,12 @@ __global__ void
           int zero = 0;
           asm volatile("" : "+v"(zero));
           if (HEAT)
-            run_sums_masked<2, CMI_TABLE_SCAN_ROUNDS>(key, v, tails, zero);
+            run_sums_masked<2, CMI_TABLE_SCAN_ROUNDS>(key, v, tails, zero,
+                                                      table_run_masks);
           else
             run_sums_masked<1, CMI_TABLE_SCAN_ROUNDS>(
-                key, reinterpret_cast<double(&)[1]>(v), tails, zero);
+                key, reinterpret_cast<double(&)[1]>(v), tails, zero,
+                table_run_masks);
           table_add_masked(tails & wave_ballot(accumulate), last_cell, v[0],
                            v[1]);
           continue;
