@@ -9,6 +9,7 @@
 #include "linecooling_data.h"
 #include "kernels.h"
 #include "dust_kernels.h"
+#include "line_image_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -2851,6 +2853,303 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     err = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
   (void)hipFree(din);
   (void)hipFree(dout);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+/* --------------------------------------------------- line images -- */
+extern "C++" {
+namespace {
+/* device buffers of one render call, freed however it ends */
+struct LineImageBuffers {
+  double *records = nullptr, *samples = nullptr, *image = nullptr,
+         *fields = nullptr, *extinction = nullptr;
+  ~LineImageBuffers() {
+    (void)hipFree(records);
+    (void)hipFree(samples);
+    (void)hipFree(image);
+    (void)hipFree(fields);
+    (void)hipFree(extinction);
+  }
+};
+
+int line_image_view(const cmi_gpu_engine *e, const char *what, double theta,
+                    double phi, LineViewDev &v) {
+  const GridDev &g = e->grid;
+  if (g.decomposed)
+    return fail(CMI_GPU_ESTATE, "%s: not available on a block of a decomposed "
+                "grid (an image of one block is not an image)", what);
+  if (g.periodic[0] || g.periodic[1] || g.periodic[2])
+    return fail(CMI_GPU_EINVAL, "%s: periodic boxes are not supported (a line "
+                "of sight through a periodic box has no end)", what);
+  if (!std::isfinite(theta) || !std::isfinite(phi))
+    return fail(CMI_GPU_EINVAL, "%s: view angles must be finite", what);
+  const double st = std::sin(theta), ct = std::cos(theta);
+  const double sp = std::sin(phi), cp = std::cos(phi);
+  v.n[0] = st * cp;
+  v.n[1] = st * sp;
+  v.n[2] = ct;
+  v.ex[0] = -sp;
+  v.ex[1] = cp;
+  v.ex[2] = 0.;
+  v.ey[0] = -ct * cp;
+  v.ey[1] = -ct * sp;
+  v.ey[2] = st;
+  for (int a = 0; a < 3; ++a)
+    v.inv_n[a] = 1. / v.n[a];
+  v.nx = v.ny = v.s = 1;
+  v.pad = 0;
+  v.img_anchor[0] = v.img_anchor[1] = 0.;
+  v.img_sides[0] = v.img_sides[1] = 1.;
+  return CMI_GPU_OK;
+}
+
+int line_image_geometry(const cmi_gpu_engine *e, const char *what,
+                        double theta, double phi, int32_t nx, int32_t ny,
+                        const double *anchor, const double *sides,
+                        int32_t supersample, LineViewDev &v) {
+  if (!anchor || !sides)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nx <= 0 || ny <= 0 || (int64_t)nx * ny > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "%s: the image must have between 1 and 2^28 "
+                "pixels (%d x %d asked for)", what, (int)nx, (int)ny);
+  if (supersample < 1 || supersample > CMI_LINE_IMAGE_MAX_SUPERSAMPLE)
+    return fail(CMI_GPU_EINVAL, "%s: supersampling must be 1..%d (%d asked "
+                "for)", what, CMI_LINE_IMAGE_MAX_SUPERSAMPLE, (int)supersample);
+  /* the sample grid is indexed with 32-bit integers */
+  if ((int64_t)nx * supersample > (1ll << 30) ||
+      (int64_t)ny * supersample > (1ll << 30))
+    return fail(CMI_GPU_EINVAL, "%s: %d x %d pixels at supersampling %d: more "
+                "than 2^30 samples along an axis", what, (int)nx, (int)ny,
+                (int)supersample);
+  if (!(sides[0] > 0.) || !(sides[1] > 0.) || !std::isfinite(sides[0]) ||
+      !std::isfinite(sides[1]) || !std::isfinite(anchor[0]) ||
+      !std::isfinite(anchor[1]))
+    return fail(CMI_GPU_EINVAL, "%s: the image sides must be positive", what);
+  CMI_TRY(line_image_view(e, what, theta, phi, v));
+  v.nx = nx;
+  v.ny = ny;
+  v.s = supersample;
+  for (int a = 0; a < 2; ++a) {
+    v.img_anchor[a] = anchor[a];
+    v.img_sides[a] = sides[a];
+  }
+  return CMI_GPU_OK;
+}
+
+/* f(std::integral_constant<int, ND>) for the record of nd doubles: 2, 4, 6
+ * or 8 (line_image_record_doubles) */
+template <class F> void line_image_for_record(int nd, F &&f) {
+  switch (nd) {
+  case 2: f(std::integral_constant<int, 2>()); break;
+  case 4: f(std::integral_constant<int, 4>()); break;
+  case 6: f(std::integral_constant<int, 6>()); break;
+  default: f(std::integral_constant<int, 8>()); break;
+  }
+}
+
+template <int ND>
+void line_image_launch_march(cmi_gpu_engine *e, const LineMarchArgs &a) {
+  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
+  const int64_t NY = (int64_t)a.view.ny * a.view.s;
+  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
+  const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
+  line_image_march_kernel<ND>
+      <<<(unsigned)(tiles_x * tiles_y), 256, 0, e->stream>>>(a);
+}
+
+/* images [nl][nx * ny] of the records [ncell][nd] into b.image (device) */
+int line_image_march(cmi_gpu_engine *e, const LineViewDev &v, int nd, int nl,
+                     LineImageBuffers &b) {
+  const int64_t npixel = (int64_t)v.nx * v.ny;
+  const int64_t NY = (int64_t)v.ny * v.s;
+  /* pixel rows per launch */
+  const int64_t rows = std::max<int64_t>(
+      1, std::min<int64_t>(v.nx, CMI_LINE_IMAGE_LAUNCH_SAMPLES / (NY * v.s)));
+  const int64_t chunk_samples = rows * v.s * NY;
+  if (v.s > 1 && !b.samples)
+    HIP_TRY(hipMalloc(&b.samples, sizeof(double) * (size_t)chunk_samples *
+                                      CMI_LINE_IMAGE_BATCH));
+  for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
+    const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
+    LineMarchArgs a;
+    a.grid = e->grid;
+    a.view = v;
+    a.records = b.records;
+    a.sx0 = (int32_t)(ix0 * v.s);
+    a.sx1 = (int32_t)(ix1 * v.s);
+    a.nlines = nl;
+    if (v.s > 1) {
+      a.out = b.samples;
+      a.line_stride = chunk_samples;
+    } else {
+      a.out = b.image + ix0 * v.ny;
+      a.line_stride = npixel;
+    }
+    line_image_for_record(nd, [&](auto width) {
+      line_image_launch_march<decltype(width)::value>(e, a);
+    });
+    HIP_TRY(hipGetLastError());
+    if (v.s > 1) {
+      const int64_t work = (ix1 - ix0) * v.ny * nl;
+      line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
+                                 e->stream>>>(
+          b.samples, chunk_samples, nl, (int32_t)ix0, (int32_t)ix1, v.ny, v.s,
+          npixel, b.image);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return CMI_GPU_OK;
+}
+
+/* doubles of the record of a batch of nl lines: {k, s[nl]} padded to 16 B */
+inline int line_image_record_doubles(int nl) { return (nl + 2) & ~1; }
+} // namespace
+} // extern "C++"
+
+int cmi_gpu_render_line_images(cmi_gpu_engine *e, int32_t nlines,
+                               const int32_t *lines, double theta, double phi,
+                               int32_t nx, int32_t ny, const double *anchor,
+                               const double *sides, int32_t supersample,
+                               double dust_cross_section, double *images) {
+  static const char *what = "render_line_images";
+  if (!e || !lines || !images)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
+    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
+                (int)nlines, CMI_NEMISSIONLINE);
+  for (int32_t l = 0; l < nlines; ++l)
+    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
+      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
+                  (int)lines[l]);
+  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
+    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
+                what);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t npixel = (int64_t)nx * ny;
+  LineImageBuffers b;
+  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records, sizeof(double) * (size_t)e->ncell *
+                                    line_image_record_doubles(nb)));
+  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel * nb));
+  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
+    const int nd = line_image_record_doubles(nl);
+    LineRecordArgs r;
+    r.model = e->model;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.nlines = nl;
+    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l)
+      r.lines[l] = l < nl ? lines[first + l] : 0;
+    r.dust_cross_section = dust_cross_section;
+    r.records = b.records;
+    const int blocks = grid_blocks(e, e->ncell, 8);
+    line_image_for_record(nd, [&](auto width) {
+      line_record_kernel<decltype(width)::value>
+          <<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
+    });
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(line_image_march(e, v, nd, nl, b));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(images + (size_t)first * npixel, b.image,
+                      sizeof(double) * (size_t)npixel * nl,
+                      hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_field_images(cmi_gpu_engine *e, int32_t nfields,
+                                const double *fields, double theta, double phi,
+                                int32_t nx, int32_t ny, const double *anchor,
+                                const double *sides, int32_t supersample,
+                                const double *extinction, double *images) {
+  static const char *what = "render_field_images";
+  if (!e || !fields || !images)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nfields < 1 || nfields > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
+                what, (int)nfields);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  HIP_TRY(hipSetDevice(e->device));
+  const int64_t npixel = (int64_t)nx * ny;
+  const size_t ncell = (size_t)e->ncell;
+  LineImageBuffers b;
+  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records,
+                    sizeof(double) * ncell * line_image_record_doubles(nb)));
+  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel * nb));
+  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
+  if (extinction) {
+    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
+    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice));
+  }
+  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
+    const int nd = line_image_record_doubles(nl);
+    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
+    line_image_for_record(nd, [&](auto width) {
+      field_record_kernel<decltype(width)::value><<<blocks, 256, 0, e->stream>>>(
+          b.fields, b.extinction, e->ncell, nl, b.records);
+    });
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(line_image_march(e, v, nd, nl, b));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(images + (size_t)first * npixel, b.image,
+                      sizeof(double) * (size_t)npixel * nl,
+                      hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_line_image_probe(cmi_gpu_engine *e, double theta, double phi,
+                             int64_t n, const double *xy, int32_t max_cells,
+                             double *out) {
+  static const char *what = "line_image_probe";
+  if (!e || n < 0 || n > (1 << 24) || max_cells < 0 || (n && (!xy || !out)))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  LineViewDev v;
+  CMI_TRY(line_image_view(e, what, theta, phi, v));
+  for (int64_t k = 0; k < 2 * n; ++k)
+    if (!std::isfinite(xy[k]))
+      return fail(CMI_GPU_EINVAL, "%s: image coordinate %lld of ray %lld is "
+                  "not finite", what, (long long)(k % 2), (long long)(k / 2));
+  if (n == 0)
+    return CMI_GPU_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  double *dxy = nullptr, *drows = nullptr;
+  const size_t width = 3 + 2 * (size_t)max_cells;
+  hipError_t err = hipMalloc(&dxy, sizeof(double) * 2 * (size_t)n);
+  if (err == hipSuccess)
+    err = hipMalloc(&drows, sizeof(double) * width * (size_t)n);
+  if (err == hipSuccess)
+    err = hipMemcpy(dxy, xy, sizeof(double) * 2 * (size_t)n,
+                    hipMemcpyHostToDevice);
+  if (err == hipSuccess)
+    err = hipMemsetAsync(drows, 0, sizeof(double) * width * (size_t)n,
+                         e->stream);
+  if (err == hipSuccess) {
+    line_image_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
+        e->grid, v, dxy, n, max_cells, drows);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, drows, sizeof(double) * width * (size_t)n,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(dxy);
+  (void)hipFree(drows);
   HIP_TRY(err);
   return CMI_GPU_OK;
 }

@@ -102,6 +102,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_set_continuous_source_spiral_galaxy", "cmi_gpu_dust_shoot",
     "cmi_gpu_download_image", "cmi_gpu_reset_image",
     "cmi_gpu_get_dust_counters", "cmi_gpu_dust_probe",
+    "cmi_gpu_render_line_images", "cmi_gpu_render_field_images",
+    "cmi_gpu_line_image_probe",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -254,6 +256,14 @@ def load_library():
     L.cmi_gpu_get_dust_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cmi_gpu_dust_probe.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint64,
                                      C.c_int64, _dp, _dp, C.c_int32]
+    L.cmi_gpu_render_line_images.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), C.c_double, C.c_double,
+        C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double, _dp]
+    L.cmi_gpu_render_field_images.argtypes = [
+        vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
+        _dp, C.c_int32, _dp, _dp]
+    L.cmi_gpu_line_image_probe.argtypes = [vp, C.c_double, C.c_double,
+                                           C.c_int64, _dp, C.c_int32, _dp]
     _lib = L
     return L
 
@@ -830,6 +840,49 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_dust_probe(
             self._h, kind, seed, first_packet, n,
             _p(inp) if inp is not None else None, _p(out), max_events))
+        return out
+
+    # emission-line images ----------------------------------------------------
+    def render_line_images(self, lines, theta, phi, nx, ny, anchor, sides,
+                           supersample=1, dust_cross_section=0.):
+        """Line-of-sight maps of emission lines (names from EMISSION_LINES;
+        None: all) for the view (theta, phi): {name: (nx, ny) array} in
+        W m^-2 sr^-1, dust of `dust_cross_section` m^2 per hydrogen nucleus
+        along the way (include/cmi_gpu.h, cmi_gpu_render_line_images)."""
+        names = list(EMISSION_LINES if lines is None else lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(names), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_line_images(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
+            dust_cross_section, _p(out)))
+        return dict(zip(names, out))
+
+    def render_field_images(self, fields, theta, phi, nx, ny, anchor, sides,
+                            supersample=1, extinction=None):
+        """The same maps of any per-cell quantities: fields[nfields][ncell]
+        and the optional extinction[ncell] (m^-1); (nfields, nx, ny)."""
+        f = _f64(fields).reshape(-1, self.n)
+        k = None if extinction is None else _f64(extinction).reshape(self.n)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(f), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_field_images(
+            self._h, len(f), _p(f), theta, phi, int(nx), int(ny), _p(a),
+            _p(s), int(supersample), _p(k) if k is not None else None,
+            _p(out)))
+        return out
+
+    def line_image_probe(self, theta, phi, xy, max_cells):
+        """The rays through the image coordinates xy[n][2]: rows {t_in, t_out,
+        steps, cells[max_cells], ds[max_cells]}."""
+        xy = _f64(xy).reshape(-1, 2)
+        out = np.zeros((len(xy), 3 + 2 * max_cells))
+        self._check(self._lib.cmi_gpu_line_image_probe(
+            self._h, theta, phi, len(xy), _p(xy), max_cells, _p(out)))
         return out
 
     def get_timing(self, reset=True):

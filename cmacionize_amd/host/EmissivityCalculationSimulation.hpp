@@ -9,12 +9,32 @@
  * The reference appends the datasets through libhdf5; here the file is read
  * with Hdf5Reader and written anew with Hdf5Writer (same groups, attributes
  * and datasets, plus the lines), then moved over the original.
+ *
+ * Beyond the reference: if - and only if - the parameter file has an
+ * "EmissionImages:" block, every flagged line is also rendered as a
+ * line-of-sight map (cmi_gpu_render_line_images) and written to
+ * <output folder>/<filename prefix>_<LineName>.dat or .pgm:
+ *   EmissionImages:view theta / view phi         0. degrees / 0. degrees
+ *   EmissionImages:image width / image height    200 / 200
+ *   EmissionImages:anchor x / anchor y / sides x / sides y
+ *                    the bounding rectangle of the box's projected corners
+ *   EmissionImages:supersampling                 1
+ *   EmissionImages:dust cross section per hydrogen   0. m^2
+ *   EmissionImages:type                          BinaryArray (or PGM)
+ *   EmissionImages:filename prefix               line_image
+ *   EmissionImages:output folder                 .
+ * For the images the cells go on the snapshot's real grid: the box from
+ * /Parameters (SimulationBox:anchor, sides), each cell where its row of
+ * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
+ * task-based snapshots are stored subgrid after subgrid). Without the block
+ * nothing of this is read and the mode's files are what they were.
  */
 #ifndef CMI_EMISSIVITYCALCULATIONSIMULATION_HPP
 #define CMI_EMISSIVITYCALCULATIONSIMULATION_HPP
 
 #include "GpuIonizationSimulation.hpp"
 #include "Hdf5Reader.hpp"
+#include "ImageWriter.hpp"
 
 #include <cstdio>
 #include <iostream>
@@ -27,6 +47,59 @@ class EmissivityCalculationSimulation {
       throw std::runtime_error(std::string(what) + ": " +
                                cmi_gpu_last_error());
   }
+
+  /* the EmissionImages: block (read only if the file has one) */
+  struct ImageSettings {
+    double theta = 0., phi = 0.;
+    long long nx = 200, ny = 200, supersample = 1;
+    bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
+    double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
+    double dust_cross_section = 0.;
+    std::string type, prefix, folder;
+
+    void read(ParameterFile &params) {
+      theta = params.get_physical_value(QUANTITY_ANGLE,
+                                        "EmissionImages:view theta", "0. degrees");
+      phi = params.get_physical_value(QUANTITY_ANGLE,
+                                      "EmissionImages:view phi", "0. degrees");
+      nx = params.get_integer("EmissionImages:image width", 200);
+      ny = params.get_integer("EmissionImages:image height", 200);
+      static const char *axis[2] = {"x", "y"};
+      for (int a = 0; a < 2; ++a) {
+        const std::string ka = std::string("EmissionImages:anchor ") + axis[a];
+        const std::string ks = std::string("EmissionImages:sides ") + axis[a];
+        if ((have_anchor[a] = params.has_value(ka)))
+          anchor[a] = params.get_physical_value(QUANTITY_LENGTH, ka, "0. m");
+        if ((have_sides[a] = params.has_value(ks)))
+          sides[a] = params.get_physical_value(QUANTITY_LENGTH, ks, "1. m");
+      }
+      supersample = params.get_integer("EmissionImages:supersampling", 1);
+      dust_cross_section = params.get_physical_value(
+          QUANTITY_SURFACE_AREA,
+          "EmissionImages:dust cross section per hydrogen", "0. m^2");
+      type = params.get_string("EmissionImages:type", "BinaryArray");
+      prefix = params.get_string("EmissionImages:filename prefix",
+                                 "line_image");
+      folder = params.get_string("EmissionImages:output folder", ".");
+      if (!is_image_type(type))
+        throw ParameterError("Unknown EmissionImages:type \"" + type +
+                             "\" (BinaryArray or PGM)");
+      if (nx <= 0 || ny <= 0 || nx * ny > (1ll << 28))
+        throw ParameterError("EmissionImages: image width and height must be "
+                             "positive, 2^28 pixels at most (" +
+                             std::to_string(nx) + " x " + std::to_string(ny) +
+                             " asked for)");
+      if (supersample < 1 || supersample > 8)
+        throw ParameterError("EmissionImages:supersampling must be 1..8");
+      if (!(dust_cross_section >= 0.))
+        throw ParameterError("EmissionImages:dust cross section per hydrogen "
+                             "must not be negative");
+      for (int a = 0; a < 2; ++a)
+        if (have_sides[a] && !(sides[a] > 0.))
+          throw ParameterError("EmissionImages: the image sides must be "
+                               "positive");
+    }
+  };
 
 public:
   /* EmissivityCalculationSimulation::do_simulation, :58-299 */
@@ -45,6 +118,10 @@ public:
                   GpuIonizationSimulation::emission_line_name(i),
               false))
         lines.push_back(i);
+    const bool do_images = params.has_block("EmissionImages");
+    ImageSettings img;
+    if (do_images)
+      img.read(params);
     if (write_output) {
       std::ofstream pfile(parameterfile_name + ".used-values");
       params.print_contents(pfile);
@@ -61,9 +138,10 @@ public:
                                       Hdf5Reader::as_string(kv.second));
     /* :123-147 */
     double unit_number_density_in_SI = 1., unit_temperature_in_SI = 1.;
+    double unit_length_in_SI = 1.;
     if (file.exists("/Units")) {
       const Hdf5Reader::Object units = file.open("/Units");
-      const double unit_length_in_SI =
+      unit_length_in_SI =
           0.01 * Hdf5Reader::as_doubles(
                      units.attributes.at("Unit length in cgs (U_L)"))
                      .at(0);
@@ -124,15 +202,70 @@ public:
       temperature[i] *= unit_temperature_in_SI;
     }
 
+    /* images: the real grid. cell_of_row[i] = the cell row i of the file
+     * describes (its midpoint, with the box anchor as the origin) */
+    std::array<double, 3> box_anchor = {0., 0., 0.}, box_sides = {1., 1., 1.};
+    std::vector<size_t> cell_of_row;
+    if (do_images && !lines.empty()) {
+      box_anchor = simulation_parameters.get_physical_vector(
+          QUANTITY_LENGTH, "SimulationBox:anchor", "");
+      box_sides = simulation_parameters.get_physical_vector(
+          QUANTITY_LENGTH, "SimulationBox:sides", "");
+      const std::vector<double> midpoints =
+          file.read_doubles("/PartType0/Coordinates");
+      if (midpoints.size() != 3 * size)
+        throw ParameterError("snapshot with " + std::to_string(size) +
+                             " cells and " +
+                             std::to_string(midpoints.size() / 3) +
+                             " coordinates");
+      cell_of_row.resize(size);
+      std::vector<char> seen(size, 0);
+      for (size_t i = 0; i < size; ++i) {
+        size_t index = 0;
+        for (int a = 0; a < 3; ++a) {
+          const double p = midpoints[3 * i + a] * unit_length_in_SI;
+          const long long k = (long long)std::floor(ncell[a] * p / box_sides[a]);
+          if (k < 0 || k >= ncell[a])
+            throw ParameterError("EmissionImages: row " + std::to_string(i) +
+                                 " of /PartType0/Coordinates lies outside "
+                                 "the snapshot's box");
+          index = index * (size_t)ncell[a] + (size_t)k;
+        }
+        if (seen[index])
+          throw ParameterError(
+              "EmissionImages: the snapshot's coordinates put two rows into "
+              "cell " + std::to_string(index) + ": they are not one per cell "
+              "of the grid");
+        seen[index] = 1;
+        cell_of_row[i] = index;
+      }
+    }
+
     status("Starting emissivity calculation...");
     std::vector<double> values(lines.size() * size);
     if (!lines.empty()) {
-      /* the cells in the file's order on a device grid of the same shape
-       * (every cell on its own: the shape only has to hold them) */
+      /* without images: the cells in the file's order on a device grid of
+       * the same shape (every cell on its own: the shape only has to hold
+       * them); with them, every cell in its place in the real box */
+      const bool placed = !cell_of_row.empty();
+      if (placed) {
+        std::vector<double> n2(size), t2(size),
+            f2((size_t)NUMBER_OF_IONNAMES * size);
+        for (size_t i = 0; i < size; ++i) {
+          const size_t c = cell_of_row[i];
+          n2[c] = number_density[i];
+          t2[c] = temperature[i];
+          for (int ion = 0; ion < NUMBER_OF_IONNAMES; ++ion)
+            f2[(size_t)ion * size + c] = fractions[(size_t)ion * size + i];
+        }
+        number_density.swap(n2);
+        temperature.swap(t2);
+        fractions.swap(f2);
+      }
       cmi_gpu_config config = {};
       for (int a = 0; a < 3; ++a) {
-        config.anchor[a] = 0.;
-        config.sides[a] = 1.;
+        config.anchor[a] = placed ? box_anchor[a] : 0.;
+        config.sides[a] = placed ? box_sides[a] : 1.;
         config.ncell[a] = (int32_t)ncell[a];
       }
       config.device = device;
@@ -146,10 +279,60 @@ public:
         rc = cmi_gpu_compute_emissivities(engine, (int32_t)lines.size(),
                                           lines.data(), 0, (int64_t)size,
                                           values.data());
+      if (rc == CMI_GPU_OK && placed) {
+        /* the datasets keep the file's order */
+        std::vector<double> v2(values.size());
+        for (size_t k = 0; k < lines.size(); ++k)
+          for (size_t i = 0; i < size; ++i)
+            v2[k * size + i] = values[k * size + cell_of_row[i]];
+        values.swap(v2);
+      }
+      std::string written;
+      if (rc == CMI_GPU_OK && placed) {
+        status("Rendering emission line images...");
+        /* default image: the rectangle around the box's projected corners */
+        const double st = std::sin(img.theta), ct = std::cos(img.theta),
+                     sp = std::sin(img.phi), cp = std::cos(img.phi);
+        const double ex[3] = {-sp, cp, 0.};
+        const double ey[3] = {-ct * cp, -ct * sp, st};
+        double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
+        for (int corner = 0; corner < 8; ++corner) {
+          double p[2] = {0., 0.};
+          for (int a = 0; a < 3; ++a) {
+            const double x =
+                box_anchor[a] + ((corner >> a) & 1) * box_sides[a];
+            p[0] += x * ex[a];
+            p[1] += x * ey[a];
+          }
+          for (int k = 0; k < 2; ++k) {
+            lo[k] = std::min(lo[k], p[k]);
+            hi[k] = std::max(hi[k], p[k]);
+          }
+        }
+        double anchor[2], sides[2];
+        for (int k = 0; k < 2; ++k) {
+          anchor[k] = img.have_anchor[k] ? img.anchor[k] : lo[k];
+          sides[k] = img.have_sides[k] ? img.sides[k] : hi[k] - anchor[k];
+        }
+        const size_t npixel = (size_t)img.nx * (size_t)img.ny;
+        std::vector<double> images(lines.size() * npixel);
+        rc = cmi_gpu_render_line_images(
+            engine, (int32_t)lines.size(), lines.data(), img.theta, img.phi,
+            (int32_t)img.nx, (int32_t)img.ny, anchor, sides,
+            (int32_t)img.supersample, img.dust_cross_section, images.data());
+        if (rc == CMI_GPU_OK && write_output)
+          for (size_t k = 0; k < lines.size(); ++k)
+            written += " " + write_image(
+                img.folder + "/" + img.prefix + "_" +
+                    GpuIonizationSimulation::emission_line_name(lines[k]),
+                img.type, images.data() + k * npixel, img.nx, img.ny, 1.);
+      }
       const std::string message = rc ? cmi_gpu_last_error() : "";
       cmi_gpu_destroy(engine);
       if (rc)
         throw std::runtime_error("emissivity calculation: " + message);
+      if (!written.empty())
+        status("Wrote" + written + ".");
     }
     status("Finished emissivity calculation.");
 

@@ -33,6 +33,7 @@
 #define CMI_GPUDUSTSIMULATION_HPP
 
 #include "../../include/cmi_gpu.h"
+#include "ImageWriter.hpp"
 #include "ParameterFile.hpp"
 #include "Plugins.hpp"
 
@@ -290,46 +291,10 @@ private:
                                cmi_gpu_last_error());
   }
 
-  static bool ends_with(const std::string &s, const std::string &tail) {
-    return s.size() >= tail.size() &&
-           s.compare(s.size() - tail.size(), tail.size(), tail) == 0;
-  }
-
-  /* CCDImage::save, src/CCDImage.hpp:299-362: PGM (P2, 255 levels, rows of
-   * constant iy, unnormalised) or the raw doubles of I x normalization */
+  /* CCDImage::save, src/CCDImage.hpp:299-362 (ImageWriter.hpp) */
   void save(const std::vector<double> &image, double normalization) const {
-    std::string filename = _output_folder + "/" + _image_filename;
-    if (_image_type == "PGM") {
-      if (!ends_with(filename, ".pgm"))
-        filename += ".pgm";
-      double min_value = image[0], max_value = image[0];
-      for (size_t i = 1; i < image.size(); ++i) {
-        min_value = std::min(min_value, image[i]);
-        max_value = std::max(max_value, image[i]);
-      }
-      max_value -= min_value;
-      std::ofstream file(filename);
-      file << "P2\n" << _nx << " " << _ny << "\n" << 255 << "\n";
-      for (long long iy = 0; iy < _ny; ++iy) {
-        for (long long ix = 0; ix < _nx; ++ix) {
-          unsigned long value = 0;
-          if (max_value > 0.)
-            value = (unsigned long)std::round(
-                255 * (image[ix * _ny + iy] - min_value) / max_value);
-          file << (ix ? " " : "") << value;
-        }
-        file << "\n";
-      }
-    } else {
-      if (!ends_with(filename, ".dat"))
-        filename += ".dat";
-      std::vector<double> copy(image);
-      for (double &v : copy)
-        v *= normalization;
-      std::ofstream file(filename, std::ios::binary);
-      file.write(reinterpret_cast<const char *>(copy.data()),
-                 copy.size() * sizeof(double));
-    }
+    (void)write_image(_output_folder + "/" + _image_filename, _image_type,
+                      image.data(), _nx, _ny, normalization);
   }
 };
 

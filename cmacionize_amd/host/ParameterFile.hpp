@@ -200,6 +200,13 @@ public:
   bool has_value(const std::string &key) const {
     return _dictionary.count(key) > 0;
   }
+  /* does the file have any key of the block "<name>:"? */
+  bool has_block(const std::string &name) const {
+    const std::string prefix = name + ":";
+    const auto it = _dictionary.lower_bound(prefix);
+    return it != _dictionary.end() &&
+           it->first.compare(0, prefix.size(), prefix) == 0;
+  }
   void add_value(const std::string &key, const std::string &value) {
     _dictionary[key] = value;
     _used[key] = value;

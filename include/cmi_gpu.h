@@ -886,6 +886,68 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events);
 
+/* ------------------------------------------------ emission-line images -- */
+/* Ray-traced line-of-sight maps of the grid: what an observer in the
+ * direction (theta, phi) sees of the cells' emissivities, with dust
+ * extinction along the ray. The reference has no such mode (its users sum
+ * cells along an axis in Python; SurfaceDensityCalculator does it for
+ * densities along z). The geometry is that of the CCD image above
+ * (src/CCDImage.hpp:242-270), inverted:
+ *   n   = (sin theta cos phi, sin theta sin phi, cos theta)   to the observer
+ *   e_x = (-sin phi, cos phi, 0),  e_y = (-cos theta cos phi,
+ *         -cos theta sin phi, sin theta)
+ * a world point p projects to (p . e_x, p . e_y); pixel (ix, iy) is stored
+ * at ix * ny + iy. With supersampling s, sample (a, b) of a pixel has image
+ * coordinates anchor + sides * ((ix + (a + 0.5) / s) / nx, (iy + (b + 0.5) /
+ * s) / ny); its ray x e_x + y e_y + t n runs through the box from the far
+ * side to the observer's (a slab test; a ray that misses contributes 0) and
+ * is marched cell by cell with the exact marcher's arithmetic. Per cell with
+ * extinction coefficient k (m^-1), emissivity j (J m^-3 s^-1) and path ds:
+ *   k == 0:  I += (j / 4 pi) ds
+ *   else:    dtau = k ds,  I = I exp(-dtau) + (j / 4 pi / k) (-expm1(-dtau))
+ * A pixel is the mean of its s^2 samples (summed a outer, b inner): surface
+ * brightness in W m^-2 sr^-1, not normalised. No atomics: the same call on
+ * the same state gives the same bits. Periodic boxes are refused
+ * (CMI_GPU_EINVAL), blocks of a decomposed grid too (CMI_GPU_ESTATE): an
+ * image of one block is not an image. CMI_GPU_EINVAL for nx, ny <= 0,
+ * nx ny > 2^28, supersample outside 1..8 (or more than 2^30 samples along
+ * an axis), non-positive sides. All three
+ * calls are synchronous. */
+
+/* images[k * nx * ny + pixel] (host) of the emission lines lines[k], numbered
+ * as in cmi_gpu_compute_emissivities and with its preconditions: it needs
+ * the abundances and the state of all 14 ions to mean anything but, like that
+ * call, checks only that cell data was set (CMI_GPU_ESTATE). k = n_H
+ * dust_cross_section, a cross section per hydrogen nucleus in m^2 (0: no
+ * dust; negative: EINVAL). The emissivities are computed on the device, 7
+ * lines per march. */
+int cmi_gpu_render_line_images(cmi_gpu_engine *engine, int32_t nlines,
+                               const int32_t *lines, double theta, double phi,
+                               int32_t nx, int32_t ny, const double *anchor,
+                               const double *sides, int32_t supersample,
+                               double dust_cross_section, double *images);
+
+/* the same for any per-cell quantities: fields[nfields][ncell] and the
+ * optional extinction[ncell] (m^-1, may be NULL) are host arrays in the
+ * engine's cell order, images[k * nx * ny + pixel]. The fields take the place
+ * of j, 1 / 4 pi included: 4 pi times the image of a density is its column
+ * density along the view (SurfaceDensityCalculator for any view). Needs only
+ * cmi_gpu_create. */
+int cmi_gpu_render_field_images(cmi_gpu_engine *engine, int32_t nfields,
+                                const double *fields, double theta, double phi,
+                                int32_t nx, int32_t ny, const double *anchor,
+                                const double *sides, int32_t supersample,
+                                const double *extinction, double *images);
+
+/* Parity probe of the ray geometry: the rays through the image coordinates
+ * xy[n][2]. out[n][3 + 2 max_cells], fp64: {t_in, t_out, steps, the first
+ * max_cells cells, their path lengths}; steps = 0 and t_in = t_out = NaN for
+ * a ray that misses the box. n <= 2^24; a coordinate that is not finite is
+ * CMI_GPU_EINVAL. */
+int cmi_gpu_line_image_probe(cmi_gpu_engine *engine, double theta, double phi,
+                             int64_t n, const double *xy, int32_t max_cells,
+                             double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,10 +8,16 @@ allowed to spill, the march loop is not.
 
     python tools/check_hot_loops.py [cmacionize_amd/csrc/engine.s]
 exit code 1 if a variant the benchmark configs launch has scratch accesses in
-its march loop.
+its march loop. The march loop of the emission-line images
+(line_image_march_kernel, tools/line_image_loop.py) is reported after them;
+scratch accesses or atomics in it fail too.
 """
+import os
 import re
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import line_image_loop  # noqa: E402
 
 path = sys.argv[1] if len(sys.argv) > 1 else "cmacionize_amd/csrc/engine.s"
 text = open(path).read().split("\n")
@@ -57,4 +63,5 @@ for s in starts:
     if scratch and tuple(flags[:5]) in (("0", "0", "0", "0", "1"),
                                         ("1", "1", "0", "0", "1")):
         bad = 1
+bad |= line_image_loop.report(text)
 sys.exit(bad)

@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """x_H of the converged stromgren run on the GPU engine, saved for
-tools/cpu_baseline_scan.py:  python tools/converged_state.py ncell out.npy"""
+tools/cpu_baseline_scan.py:  python tools/converged_state.py ncell out.npy
+
+With a third argument `lexington [iterations [packets]]`: the full state
+(number density, temperature, the 14 ionic fractions) of lexingtonHII40 after
+that many iterations, as out.npz, for tools/line_image_rate.py."""
 import os
 import sys
 
@@ -13,11 +17,39 @@ from cmacionize_amd import STROMGREN as S  # noqa: E402
 from cmacionize_amd import engine as E  # noqa: E402
 from cmacionize_amd.simulation import GpuBackend, ReplicaIterationDriver  # noqa: E402
 
-ncell = int(sys.argv[1])
-backend = GpuBackend((ncell,) * 3, S["anchor"], S["sides"], S["periodic"],
-                     device=0, track_heating=False)
-bench.setup_engine(backend, ncell, bench.CONFIGS["stromgren"])
-driver = ReplicaIterationDriver(backend, 0, 1, None)
-for loop in range(20):
-    driver.iteration(loop, 20000000, 42)
-np.save(sys.argv[2], backend.engine.download_field(E.FIELD_IONIC_FRACTION))
+
+def lexington_state(ncell, iterations=20, packets=20000000, device=0):
+    """the backend of lexingtonHII40 at ncell^3 after `iterations` iterations
+    (its .engine holds the state; the backend owns device blocks the engine
+    points to, so the caller keeps the backend for as long as the engine)"""
+    backend = GpuBackend((ncell,) * 3, S["anchor"], S["sides"], S["periodic"],
+                         device=device, track_heating=True)
+    bench.setup_engine(backend, ncell, bench.CONFIGS["lexington"])
+    driver = ReplicaIterationDriver(backend, 0, 1, None)
+    for loop in range(iterations):
+        driver.iteration(loop, packets, 42)
+    return backend
+
+
+def download_state(eng):
+    return dict(
+        number_density=eng.download_field(E.FIELD_NUMBER_DENSITY),
+        temperature=eng.download_field(E.FIELD_TEMPERATURE),
+        x=np.array([eng.download_field(E.FIELD_IONIC_FRACTION + i)
+                    for i in range(E.NION)]))
+
+
+if __name__ == "__main__":
+    ncell = int(sys.argv[1])
+    if len(sys.argv) > 3 and sys.argv[3] == "lexington":
+        extra = [int(float(v)) for v in sys.argv[4:6]]
+        backend = lexington_state(ncell, *extra)
+        np.savez(sys.argv[2], **download_state(backend.engine))
+        sys.exit(0)
+    backend = GpuBackend((ncell,) * 3, S["anchor"], S["sides"], S["periodic"],
+                         device=0, track_heating=False)
+    bench.setup_engine(backend, ncell, bench.CONFIGS["stromgren"])
+    driver = ReplicaIterationDriver(backend, 0, 1, None)
+    for loop in range(20):
+        driver.iteration(loop, 20000000, 42)
+    np.save(sys.argv[2], backend.engine.download_field(E.FIELD_IONIC_FRACTION))
