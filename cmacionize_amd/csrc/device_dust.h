@@ -21,6 +21,33 @@
  *   (only if |cos| != 1), and the next optical depth -log(u).
  * The CPU restatement (tests/support/dust_reference.c) draws in the same
  * order.
+ *
+ * The cell-luminosity source (DUST_SOURCE_CELLS, dust_emit_cells; the
+ * scattered-light line images of DESIGN.md 4.8, no counterpart in the
+ * reference) draws, for packet i of the same stream:
+ *   1   the cell selector
+ *   3   x, y, z inside the cell: lower wall + u cell side per axis
+ *   2   the direction {cos theta, phi}, as the job's own above
+ *   +1  the forced first optical depth, and from there on exactly the list
+ *       above
+ * (tests/support/scattered_line_reference.c draws in the same order.)
+ *
+ * Its tables, over blocks of CMI_CELL_SOURCE_BLOCK consecutive cells: C[c],
+ * the running sum of the weights w >= 0 within c's block (from 0 in every
+ * block, cell by cell), and B[b], the running sum of the block totals. One
+ * uniform u gives t = u B[last]; b is the first block with B[b] > t (if
+ * rounding put t at B[last], the first block with B[b] == B[last]); r = t -
+ * B[b - 1] (B[-1] = 0); the cell is the first k of block b with C[k] > r,
+ * or, if rounding leaves none, the first k with C[k] == C[last of b].
+ * A cell with w == 0 is never chosen: adding 0 leaves a running sum as it
+ * is, so C[k] == C[k - 1] for such a cell (C[k] == 0 for a block's first)
+ * and B[b] == B[b - 1] for a block of them. The chosen block has B[b] >
+ * B[b - 1] - either B[b] > t >= B[b - 1], or B[b] == B[last] > 0 is the
+ * first to reach that value - so it emits and C[last of b] > 0. In it r >= 0
+ * (B is monotone: t >= B[b - 1]), and the chosen k has either C[k] > r >=
+ * C[k - 1] (k is the first above r), or C[k] > r >= 0 at k = first of b, or
+ * is the first to reach C[last of b] > 0: in every case C[k] differs from
+ * the sum before it, which w_k == 0 cannot do.
  */
 #ifndef CMI_DEVICE_DUST_H
 #define CMI_DEVICE_DUST_H
@@ -34,6 +61,25 @@
  * and counted (the loop ends at once for a box centred on the origin; the
  * host refuses boxes that do not contain it, this bounds the rest) */
 #define CMI_DUST_MAX_ATTEMPTS 1000000u
+
+/* cells per block of the cell source's tables: the top level stays resident
+ * in L2 (65 536 entries, 512 KB, at 256^3 cells) and the search within a
+ * block touches 2 KB */
+#define CMI_CELL_SOURCE_BLOCK 256
+
+/* where a packet starts: template parameter of dust_packet and its kernels */
+enum { DUST_SOURCE_GALAXY = 0, DUST_SOURCE_CELLS = 1 };
+
+/* what a source reads beyond DustDev, a kernel argument of its own: nothing
+ * for the spiral galaxy (its parameters are DustDev's), the tables for the
+ * cells */
+template <int SOURCE> struct DustSource {};
+template <> struct DustSource<DUST_SOURCE_CELLS> {
+  const double *block_sums; /* B[nblock] */
+  const double *cell_sums;  /* C[ncell] */
+  int64_t ncell, nblock;
+};
+typedef DustSource<DUST_SOURCE_CELLS> CellSourceDev;
 
 /* everything the dust kernels read, by value */
 struct DustDev {
@@ -182,6 +228,88 @@ __device__ __noinline__ bool dust_emit(const DustDev &d, PacketRng &rng,
   p.stokes[2] = 0.;
   p.stokes[3] = 0.;
   return true;
+}
+
+/* first index in [lo, hi) with a[i] > x, or hi (a is non-decreasing) */
+__device__ __forceinline__ int64_t cell_source_first_above(const double *a,
+                                                           int64_t lo,
+                                                           int64_t hi,
+                                                           double x) {
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] > x)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo;
+}
+
+/* first index in [lo, hi) with a[i] == a[hi - 1] */
+__device__ __forceinline__ int64_t cell_source_first_last(const double *a,
+                                                          int64_t lo,
+                                                          int64_t hi) {
+  const double last = a[hi - 1];
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] == last)
+      hi = mid;
+    else
+      lo = mid + 1;
+  }
+  return lo;
+}
+
+/* the selection rule of the header comment for one uniform */
+__device__ __forceinline__ int64_t cell_source_select(const CellSourceDev &s,
+                                                      double u) {
+  const double t = u * s.block_sums[s.nblock - 1];
+  int64_t b = cell_source_first_above(s.block_sums, 0, s.nblock, t);
+  if (b == s.nblock)
+    b = cell_source_first_last(s.block_sums, 0, s.nblock);
+  const double r = t - (b > 0 ? s.block_sums[b - 1] : 0.);
+  const int64_t lo = b * CMI_CELL_SOURCE_BLOCK;
+  const int64_t hi = (lo + CMI_CELL_SOURCE_BLOCK < s.ncell)
+                         ? lo + CMI_CELL_SOURCE_BLOCK
+                         : s.ncell;
+  int64_t k = cell_source_first_above(s.cell_sums, lo, hi, r);
+  if (k == hi)
+    k = cell_source_first_last(s.cell_sums, lo, hi);
+  return k;
+}
+
+/* the draws of a packet of the cell source up to the first march: the cell,
+ * a position inside it, the direction as dust_emit's own; Stokes (1, 0, 0,
+ * 0). The grid is whole (the host refuses blocks of a decomposed one). */
+__device__ __noinline__ int64_t dust_emit_cells(const GridDev &g,
+                                                const CellSourceDev &s,
+                                                PacketRng &rng,
+                                                DustPhoton &p) {
+  const int64_t cell = cell_source_select(s, rng.next());
+  const int64_t nyz = (int64_t)g.ncell[1] * g.ncell[2];
+  const int64_t index[3] = {cell / nyz, (cell / g.ncell[2]) % g.ncell[1],
+                            cell % g.ncell[2]};
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    p.pos[a] = (g.anchor[a] + g.cellside[a] * (double)index[a]) +
+               rng.next() * g.cellside[a];
+  const double cost = 2. * rng.next() - 1.;
+  const double sint = sqrt(fmax(1. - cost * cost, 0.));
+  const double phi = 2. * M_PI * rng.next();
+  const double cosp = cos(phi);
+  const double sinp = sin(phi);
+  const double dir[3] = {sint * cosp, sint * sinp, cost};
+  dust_set_direction(p, dir);
+  p.par[0] = sint;
+  p.par[1] = cost;
+  p.par[2] = phi;
+  p.par[3] = sinp;
+  p.par[4] = cosp;
+  p.stokes[0] = 1.;
+  p.stokes[1] = 0.;
+  p.stokes[2] = 0.;
+  p.stokes[3] = 0.;
+  return cell;
 }
 
 /* the march's packet for a photon: dust opacity records are {n kappa x_H, 0},

@@ -22,6 +22,17 @@ __global__ void __launch_bounds__(256)
     out[i] = make_double2(number_density[i] * kappa * xH[i], 0.);
 }
 
+/* {n sigma, 0} per cell: dust that follows the gas, sigma per hydrogen
+ * nucleus (cmi_gpu_set_dust_scattering_per_hydrogen); x_H is not read */
+__global__ void __launch_bounds__(256)
+    dust_opacity_per_hydrogen_kernel(const double *__restrict__ number_density,
+                                     double sigma, int64_t ncell,
+                                     double2 *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < ncell)
+    out[i] = make_double2(number_density[i] * sigma, 0.);
+}
+
 /* what one packet contributes to the image: either atomics into d.image
  * (TRACE = false) or the event rows {x, y, z, I, Q, U, V, weight} of a trace
  * (the direct light first, then one row per scattering) */
@@ -72,9 +83,12 @@ __device__ __forceinline__ void dust_add(const DustDev &d, const double pos[3],
   }
 }
 
-/* DustPhotonShootJob::execute for one packet */
-template <bool TRACE>
+/* DustPhotonShootJob::execute for one packet; SOURCE selects where it
+ * starts (at compile time: the galaxy's instantiation has no trace of the
+ * other source), everything after the emission is the same */
+template <bool TRACE, int SOURCE>
 __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
+                                   const DustSource<SOURCE> &src,
                                    const double2 *__restrict__ opacity,
                                    uint32_t seed, uint64_t id,
                                    DustCountersDev &c, DustEvents &ev) {
@@ -82,9 +96,13 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   rng.init(seed, 0u, id);
   DustPhoton p;
   c.npackets += 1;
-  if (!dust_emit(d, rng, p)) {
-    c.nsource_capped += 1;
-    return;
+  if constexpr (SOURCE == DUST_SOURCE_CELLS) {
+    (void)dust_emit_cells(g, src, rng, p);
+  } else {
+    if (!dust_emit(d, rng, p)) {
+      c.nsource_capped += 1;
+      return;
+    }
   }
 
   /* direct light towards the observer, :127-130 */
@@ -137,15 +155,17 @@ __device__ __forceinline__ void dust_count(unsigned long long *dst,
 }
 
 /* packets [first, first + n) */
+template <int SOURCE>
 __global__ void __launch_bounds__(256)
     dust_shoot_kernel(GridDev g, DustDev d,
                       const double2 *__restrict__ opacity, uint32_t seed,
-                      uint64_t first, uint64_t n, DustCountersDev *counters) {
+                      uint64_t first, uint64_t n, DustCountersDev *counters,
+                      DustSource<SOURCE> src) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   DustCountersDev c = {};
   DustEvents ev = {nullptr, 0, 0};
   if (k < n)
-    dust_packet<false>(g, d, opacity, seed, first + k, c, ev);
+    dust_packet<false, SOURCE>(g, d, src, opacity, seed, first + k, c, ev);
   /* the whole wave reaches the reduction (no early return above) */
   dust_count(&counters->nsteps, c.nsteps);
   dust_count(&counters->nscatter, c.nscatter);
@@ -160,13 +180,16 @@ enum {
   DUST_PROBE_SCATTER = 1,
   DUST_PROBE_SCATTER_TOWARDS = 2,
   DUST_PROBE_OPTICAL_DEPTH = 3,
-  DUST_PROBE_TRACE = 4
+  DUST_PROBE_TRACE = 4,
+  DUST_PROBE_CELL_SOURCE = 5
 };
 
 /* the parity probes of cmi_gpu_dust_probe (include/cmi_gpu.h gives the row
- * layouts); row k uses the stream of packet first + k */
+ * layouts); row k uses the stream of packet first + k. EMIT and TRACE follow
+ * SOURCE; CELL_SOURCE exists in the cell source's instantiation only. */
+template <int SOURCE>
 __global__ void __launch_bounds__(64)
-    dust_probe_kernel(GridDev g, DustDev d,
+    dust_probe_kernel(GridDev g, DustDev d, DustSource<SOURCE> src,
                       const double2 *__restrict__ opacity, int32_t kind,
                       uint32_t seed, uint64_t first, int64_t n, int32_t width,
                       const double *__restrict__ in, double *__restrict__ out,
@@ -179,7 +202,11 @@ __global__ void __launch_bounds__(64)
   double *o = out + k * width;
   if (kind == DUST_PROBE_EMIT) {
     DustPhoton p;
-    const bool ok = dust_emit(d, rng, p);
+    bool ok = true;
+    if constexpr (SOURCE == DUST_SOURCE_CELLS)
+      (void)dust_emit_cells(g, src, rng, p);
+    else
+      ok = dust_emit(d, rng, p);
     for (int a = 0; a < 3; ++a) {
       o[a] = ok ? p.pos[a] : __builtin_nan("");
       o[3 + a] = ok ? p.dir[a] : __builtin_nan("");
@@ -223,11 +250,21 @@ __global__ void __launch_bounds__(64)
     /* out: {nevents, nscatter, nsteps, ncapped, rows[max_events][8]} */
     DustCountersDev c = {};
     DustEvents ev = {o + 4, max_events, 0};
-    dust_packet<true>(g, d, opacity, seed, first + k, c, ev);
+    dust_packet<true, SOURCE>(g, d, src, opacity, seed, first + k, c, ev);
     o[0] = ev.n;
     o[1] = (double)c.nscatter;
     o[2] = (double)c.nsteps;
     o[3] = (double)(c.ncapped + c.nsource_capped);
+  } else if (kind == DUST_PROBE_CELL_SOURCE) {
+    /* out: {cell, pos[3], dir[3]} */
+    if constexpr (SOURCE == DUST_SOURCE_CELLS) {
+      DustPhoton p;
+      o[0] = (double)dust_emit_cells(g, src, rng, p);
+      for (int a = 0; a < 3; ++a) {
+        o[1 + a] = p.pos[a];
+        o[4 + a] = p.dir[a];
+      }
+    }
   }
 }
 

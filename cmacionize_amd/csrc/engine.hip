@@ -229,6 +229,17 @@ struct cmi_gpu_engine {
   double *dust_cdf = nullptr;
   double2 *dust_opacity = nullptr;
   DustCountersDev *dust_counters = nullptr;
+  /* dust that follows the gas: records {n sigma, 0}, dust_kappa holds sigma */
+  bool dust_per_hydrogen = false;
+  /* the cell-luminosity source (DUST_SOURCE_CELLS): its tables, whether they
+   * came from the cells (a line source is stale once the cells changed:
+   * cells_epoch counts the changes) and the host's copy of the block sums */
+  int dust_source = DUST_SOURCE_GALAXY;
+  CellSourceDev cell_source = {};
+  double *cell_source_cells = nullptr, *cell_source_blocks = nullptr;
+  std::vector<double> cell_source_blocks_host;
+  bool have_cell_source = false, cell_source_from_cells = false;
+  uint64_t cells_epoch = 0, cell_source_epoch = 0;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1121,6 +1132,8 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->dust_cdf);
   (void)hipFree(e->dust_opacity);
   (void)hipFree(e->dust_counters);
+  (void)hipFree(e->cell_source_cells);
+  (void)hipFree(e->cell_source_blocks);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
   delete e;
@@ -1458,6 +1471,7 @@ int cmi_gpu_upload_cells(cmi_gpu_engine *e, const double *number_density,
   if (!e || !number_density || !temperature)
     return fail(CMI_GPU_EINVAL, "upload_cells: bad argument");
   HIP_TRY(hipSetDevice(e->device));
+  ++e->cells_epoch;
   const size_t bytes = (size_t)e->ncell * sizeof(double);
   HIP_TRY(hipMemcpyAsync(e->cells.number_density, number_density, bytes,
                          hipMemcpyHostToDevice, e->stream));
@@ -1483,6 +1497,8 @@ int cmi_gpu_upload_field(cmi_gpu_engine *e, int32_t field,
   if (!dst)
     return fail(CMI_GPU_EINVAL, "upload_field: unknown field %d", field);
   HIP_TRY(hipSetDevice(e->device));
+  if (field < CMI_GPU_FIELD_MEAN_INTENSITY)
+    ++e->cells_epoch; /* a field of the cells' state */
   const int64_t stride = field_stride(e, field);
   if (stride == 1) {
     HIP_TRY(hipMemcpyAsync(dst, values, (size_t)e->ncell * sizeof(double),
@@ -1912,6 +1928,7 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
     return fail(CMI_GPU_EINVAL, "update_cells_range: cells [%lld, %lld) are "
                 "not inside the engine's %lld cells", (long long)first_cell,
                 (long long)(first_cell + ncell), (long long)e->ncell);
+  ++e->cells_epoch;
   if (ncell == 0)
     return CMI_GPU_OK;
   if (!e->have_sources || !e->have_recomb || !e->have_cells)
@@ -2575,7 +2592,21 @@ int cmi_gpu_set_dust_scattering(cmi_gpu_engine *e, double g, double p_l,
   d.pc = 0.;
   d.albedo = albedo;
   e->dust_kappa = kappa;
+  e->dust_per_hydrogen = false;
   e->have_dust_scattering = true;
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *e, double g,
+                                             double p_l, double albedo,
+                                             double sigma) {
+  if (!e || !(sigma >= 0.) || !std::isfinite(sigma))
+    return fail(CMI_GPU_EINVAL, "set_dust_scattering_per_hydrogen: bad "
+                                "argument (sigma must be >= 0)");
+  /* the same phase function constants; kappa 0 passes its check */
+  CMI_TRY(cmi_gpu_set_dust_scattering(e, g, p_l, albedo, 0.));
+  e->dust_kappa = sigma;
+  e->dust_per_hydrogen = true;
   return CMI_GPU_OK;
 }
 
@@ -2671,13 +2702,12 @@ int cmi_gpu_set_continuous_source_spiral_galaxy(cmi_gpu_engine *e,
   d.cdf_y = e->dust_cdf + nbin + 1;
   d.cdf_n = nbin + 1;
   e->have_dust_source = true;
+  e->dust_source = DUST_SOURCE_GALAXY;
   return CMI_GPU_OK;
 }
 
-/* everything a dust launch needs; builds the records {n kappa x_H, 0} */
-static int dust_prepare(cmi_gpu_engine *e) {
-  if (!e)
-    return fail(CMI_GPU_EINVAL, "null engine");
+/* what the dust mode asks of the grid, for either source */
+static int dust_check_grid(const cmi_gpu_engine *e) {
   const GridDev &g = e->grid;
   if (g.decomposed)
     return fail(CMI_GPU_ESTATE, "dust: not available on a block of a "
@@ -2687,11 +2717,158 @@ static int dust_prepare(cmi_gpu_engine *e) {
                 "dust: periodic boxes are not supported (the reference's "
                 "integrate_optical_depth never reaches the edge of a periodic "
                 "box, src/CartesianDensityGrid.cpp:187-227,341)");
+  return CMI_GPU_OK;
+}
+
+/* the cell source's tables from the weights in e->cell_source_cells (device_
+ * dust.h has the contract): refuses bad weights and a source that does not
+ * emit, selects the source */
+static int cell_source_build(cmi_gpu_engine *e, const char *what,
+                             bool from_cells) {
+  const int64_t ncell = e->ncell;
+  const int64_t nblock =
+      (ncell + CMI_CELL_SOURCE_BLOCK - 1) / CMI_CELL_SOURCE_BLOCK;
+  if (!e->cell_source_blocks)
+    HIP_TRY(hipMalloc(&e->cell_source_blocks, (size_t)nblock * sizeof(double)));
+  unsigned int *ninvalid = nullptr;
+  HIP_TRY(hipMalloc(&ninvalid, sizeof(unsigned int)));
+  unsigned int bad = 0;
+  std::vector<double> &B = e->cell_source_blocks_host;
+  B.assign((size_t)nblock, 0.);
+  hipError_t err = hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream);
+  if (err == hipSuccess) {
+    cell_source_check_kernel<<<grid_blocks(e, ncell, 8), 256, 0, e->stream>>>(
+        e->cell_source_cells, ncell, ninvalid);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                         e->stream);
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  (void)hipFree(ninvalid);
+  HIP_TRY(err);
+  if (bad)
+    return fail(CMI_GPU_EINVAL, "%s: %u weight(s) are negative or not finite",
+                what, bad);
+  cell_source_block_kernel<<<(unsigned)((nblock + 63) / 64), 64, 0,
+                             e->stream>>>(e->cell_source_cells, ncell, nblock,
+                                          e->cell_source_blocks);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(B.data(), e->cell_source_blocks,
+                         (size_t)nblock * sizeof(double),
+                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  /* B: the running sum of the block totals, block by block */
+  double total = 0.;
+  for (int64_t b = 0; b < nblock; ++b) {
+    total += B[(size_t)b];
+    B[(size_t)b] = total;
+  }
+  if (!(total > 0.))
+    return fail(CMI_GPU_ESTATE, "%s: nothing emits (the weights sum to 0)",
+                what);
+  if (!std::isfinite(total))
+    return fail(CMI_GPU_EINVAL, "%s: the weights' sum is not finite", what);
+  HIP_TRY(hipMemcpy(e->cell_source_blocks, B.data(),
+                    (size_t)nblock * sizeof(double), hipMemcpyHostToDevice));
+  e->cell_source.block_sums = e->cell_source_blocks;
+  e->cell_source.cell_sums = e->cell_source_cells;
+  e->cell_source.ncell = ncell;
+  e->cell_source.nblock = nblock;
+  e->cell_source_from_cells = from_cells;
+  e->cell_source_epoch = e->cells_epoch;
+  e->have_cell_source = true;
+  e->dust_source = DUST_SOURCE_CELLS;
+  return CMI_GPU_OK;
+}
+
+/* the checks both setters share; the weights' buffer */
+static int cell_source_begin(cmi_gpu_engine *e) {
+  CMI_TRY(dust_check_grid(e));
+  HIP_TRY(hipSetDevice(e->device));
+  /* no launch reads the tables while they are rebuilt; a failed build
+   * leaves no source */
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->have_cell_source = false;
+  if (!e->cell_source_cells)
+    HIP_TRY(hipMalloc(&e->cell_source_cells,
+                      (size_t)e->ncell * sizeof(double)));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_cell_source_line(cmi_gpu_engine *e, int32_t line) {
+  static const char *what = "set_cell_source_line";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (line < 0 || line >= CMI_NEMISSIONLINE)
+    return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what, (int)line);
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  CMI_TRY(cell_source_begin(e));
+  CellSourceLineArgs a;
+  a.model = e->model;
+  a.cells = e->cells;
+  a.ncell = e->ncell;
+  a.line = line;
+  a.weights = e->cell_source_cells;
+  cell_source_line_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
+                            e->stream>>>(a);
+  HIP_TRY(hipGetLastError());
+  return cell_source_build(e, what, true);
+}
+
+int cmi_gpu_set_cell_source_field(cmi_gpu_engine *e, const double *field) {
+  static const char *what = "set_cell_source_field";
+  if (!e || !field)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(cell_source_begin(e));
+  HIP_TRY(hipMemcpy(e->cell_source_cells, field,
+                    (size_t)e->ncell * sizeof(double), hipMemcpyHostToDevice));
+  return cell_source_build(e, what, false);
+}
+
+int cmi_gpu_get_cell_source(cmi_gpu_engine *e, double *total_luminosity,
+                            double *block_sums, double *cell_sums) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "get_cell_source: null engine");
+  if (!e->have_cell_source)
+    return fail(CMI_GPU_ESTATE, "get_cell_source: no cell source is set");
+  const std::vector<double> &B = e->cell_source_blocks_host;
+  if (total_luminosity)
+    *total_luminosity = e->grid.cellside[0] * e->grid.cellside[1] *
+                        e->grid.cellside[2] * B.back();
+  if (block_sums)
+    std::copy(B.begin(), B.end(), block_sums);
+  if (cell_sums) {
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(cell_sums, e->cell_source_cells,
+                      (size_t)e->ncell * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+/* everything a dust launch needs; builds the records {n kappa x_H, 0} or
+ * {n sigma, 0} */
+static int dust_prepare(cmi_gpu_engine *e) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  CMI_TRY(dust_check_grid(e));
+  const bool have_source = e->dust_source == DUST_SOURCE_CELLS
+                               ? e->have_cell_source
+                               : e->have_dust_source;
   if (!e->have_cells || !e->have_dust_scattering || !e->have_ccd ||
-      !e->have_dust_source)
+      !have_source)
     return fail(CMI_GPU_ESTATE, "dust: upload_cells, set_dust_scattering, "
                                 "set_ccd_image and "
-                                "set_continuous_source_spiral_galaxy first");
+                                "set_continuous_source_spiral_galaxy (or a "
+                                "cell source) first");
+  if (e->dust_source == DUST_SOURCE_CELLS && e->cell_source_from_cells &&
+      e->cell_source_epoch != e->cells_epoch)
+    return fail(CMI_GPU_ESTATE, "dust: the cells changed after the line "
+                                "source was set; set_cell_source_line again");
   HIP_TRY(hipSetDevice(e->device));
   if (!e->dust_opacity)
     HIP_TRY(hipMalloc(&e->dust_opacity, (size_t)e->ncell * sizeof(double2)));
@@ -2701,9 +2878,13 @@ static int dust_prepare(cmi_gpu_engine *e) {
                            e->stream));
   }
   const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
-  dust_opacity_kernel<<<blocks, 256, 0, e->stream>>>(
-      e->cells.number_density, e->cells.x[0], e->dust_kappa, e->ncell,
-      e->dust_opacity);
+  if (e->dust_per_hydrogen)
+    dust_opacity_per_hydrogen_kernel<<<blocks, 256, 0, e->stream>>>(
+        e->cells.number_density, e->dust_kappa, e->ncell, e->dust_opacity);
+  else
+    dust_opacity_kernel<<<blocks, 256, 0, e->stream>>>(
+        e->cells.number_density, e->cells.x[0], e->dust_kappa, e->ncell,
+        e->dust_opacity);
   HIP_TRY(hipGetLastError());
   return CMI_GPU_OK;
 }
@@ -2724,9 +2905,15 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
                              e->stream));
     EventPair ev;
     CMI_TRY(timer_begin(e, ev));
-    dust_shoot_kernel<<<(unsigned)((chunk + 255) / 256), 256, 0, e->stream>>>(
-        e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
-        e->dust_counters);
+    const unsigned blocks = (unsigned)((chunk + 255) / 256);
+    if (e->dust_source == DUST_SOURCE_CELLS)
+      dust_shoot_kernel<DUST_SOURCE_CELLS><<<blocks, 256, 0, e->stream>>>(
+          e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
+          e->dust_counters, e->cell_source);
+    else
+      dust_shoot_kernel<DUST_SOURCE_GALAXY><<<blocks, 256, 0, e->stream>>>(
+          e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
+          e->dust_counters, DustSource<DUST_SOURCE_GALAXY>());
     HIP_TRY(hipGetLastError());
     CMI_TRY(timer_end(e, e->shoot_events, ev, chunk));
     done += chunk;
@@ -2810,18 +2997,21 @@ int cmi_gpu_reset_image(cmi_gpu_engine *e) {
 int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events) {
-  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_TRACE ||
+  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_CELL_SOURCE ||
       max_events < 0 || n > (1 << 24))
     return fail(CMI_GPU_EINVAL, "dust_probe: bad argument");
-  static const int in_width[5] = {0, 12, 12, 6, 0};
+  static const int in_width[6] = {0, 12, 12, 6, 0, 0};
   const int width = kind == DUST_PROBE_EMIT              ? 6
                     : kind == DUST_PROBE_SCATTER         ? 12
                     : kind == DUST_PROBE_SCATTER_TOWARDS ? 5
                     : kind == DUST_PROBE_OPTICAL_DEPTH   ? 2 + max_events
+                    : kind == DUST_PROBE_CELL_SOURCE     ? 7
                                                          : 4 + 8 * max_events;
   if (in_width[kind] && !in)
     return fail(CMI_GPU_EINVAL, "dust_probe: input rows missing");
   CMI_TRY(dust_prepare(e));
+  if (kind == DUST_PROBE_CELL_SOURCE && e->dust_source != DUST_SOURCE_CELLS)
+    return fail(CMI_GPU_ESTATE, "dust_probe: no cell source is selected");
   if (n == 0)
     return CMI_GPU_OK;
   double *din = nullptr, *dout = nullptr;
@@ -2839,10 +3029,17 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
   /* short launches: a row of a trace can be a whole packet */
   for (int64_t k = 0; err == hipSuccess && k < n; k += CMI_DUST_PROBE_LAUNCH) {
     const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
-    dust_probe_kernel<<<(unsigned)((m + 63) / 64), 64, 0, e->stream>>>(
-        e->grid, e->dust, e->dust_opacity, kind, seed, first_packet + k, m,
-        width, din ? din + k * in_width[kind] : nullptr, dout + k * width,
-        max_events);
+    const unsigned blocks = (unsigned)((m + 63) / 64);
+    const double *rows = din ? din + k * in_width[kind] : nullptr;
+    if (e->dust_source == DUST_SOURCE_CELLS)
+      dust_probe_kernel<DUST_SOURCE_CELLS><<<blocks, 64, 0, e->stream>>>(
+          e->grid, e->dust, e->cell_source, e->dust_opacity, kind, seed,
+          first_packet + k, m, width, rows, dout + k * width, max_events);
+    else
+      dust_probe_kernel<DUST_SOURCE_GALAXY><<<blocks, 64, 0, e->stream>>>(
+          e->grid, e->dust, DustSource<DUST_SOURCE_GALAXY>(), e->dust_opacity,
+          kind, seed, first_packet + k, m, width, rows, dout + k * width,
+          max_events);
     err = hipGetLastError();
     if (err == hipSuccess)
       err = hipStreamSynchronize(e->stream);

@@ -47,6 +47,7 @@
 #ifndef CMI_LINE_IMAGE_KERNELS_H
 #define CMI_LINE_IMAGE_KERNELS_H
 
+#include "device_dust.h"
 #include "device_emissivity.h"
 #include "device_transport.h"
 
@@ -193,6 +194,72 @@ __global__ void __launch_bounds__(CMI_BLOCK)
     line_image_store_record<ND>(a.records + c * ND, ntot * a.dust_cross_section,
                                 j, a.nlines);
   }
+}
+
+/* ---- the cell-luminosity source of the scattered-light images (device_dust.h
+ * has the tables' contract and the selection rule) ---- */
+
+struct CellSourceLineArgs {
+  ModelDev model;
+  CellsDev cells;
+  int64_t ncell;
+  int32_t line;
+  double *weights; /* [ncell] */
+};
+
+/* the weights of a line source from the cells as they are: the emissivity of
+ * one line (W m^-3), cell_emissivities as emissivity_kernel calls it */
+__global__ void __launch_bounds__(CMI_BLOCK)
+    cell_source_line_kernel(const CellSourceLineArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < a.ncell;
+       c += stride) {
+    double x[CMI_NION], values[CMI_NEMISSIONLINE];
+#pragma unroll
+    for (int i = 0; i < CMI_NION; ++i)
+      x[i] = a.cells.x[i][c];
+    cell_emissivities(a.model, a.cells.number_density[c],
+                      a.cells.temperature[c], x, values);
+    a.weights[c] = values[a.line];
+  }
+}
+
+/* the number of weights that are negative or not finite, added to *ninvalid
+ * (summed over the wave first, one atomic per wave that found any) */
+__global__ void __launch_bounds__(256)
+    cell_source_check_kernel(const double *__restrict__ weights, int64_t ncell,
+                             unsigned int *ninvalid) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  unsigned int bad = 0;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < ncell;
+       c += stride) {
+    const double w = weights[c];
+    bad += (!(w >= 0.) || w == HUGE_VAL) ? 1u : 0u;
+  }
+  for (int off = 32; off > 0; off >>= 1)
+    bad += __shfl_down(bad, off, 64);
+  if (threadIdx.x % 64 == 0 && bad)
+    atomicAdd(ninvalid, bad);
+}
+
+/* C in place of the weights, one thread per block of CMI_CELL_SOURCE_BLOCK
+ * cells in cell order - the summation order is the contract -, and the
+ * block's total; the running sum B of the totals is the host's pass */
+__global__ void __launch_bounds__(64)
+    cell_source_block_kernel(double *sums, int64_t ncell, int64_t nblock,
+                             double *__restrict__ totals) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nblock)
+    return;
+  const int64_t lo = b * CMI_CELL_SOURCE_BLOCK;
+  const int64_t hi =
+      (lo + CMI_CELL_SOURCE_BLOCK < ncell) ? lo + CMI_CELL_SOURCE_BLOCK : ncell;
+  double sum = 0.;
+  for (int64_t c = lo; c < hi; ++c) {
+    sum += sums[c];
+    sums[c] = sum;
+  }
+  totals[b] = sum;
 }
 
 /* records of a batch of caller-supplied fields ([nfields][ncell] on the

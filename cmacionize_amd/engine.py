@@ -33,6 +33,7 @@ TABLE_LINEAR, TABLE_LOGLOG = 0, 1
 # cmi_gpu_dust_probe kinds
 DUST_PROBE_EMIT, DUST_PROBE_SCATTER, DUST_PROBE_SCATTER_TOWARDS = 0, 1, 2
 DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
+DUST_PROBE_CELL_SOURCE = 5
 
 _dp = C.POINTER(C.c_double)
 
@@ -104,6 +105,9 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_get_dust_counters", "cmi_gpu_dust_probe",
     "cmi_gpu_render_line_images", "cmi_gpu_render_field_images",
     "cmi_gpu_line_image_probe",
+    "cmi_gpu_set_dust_scattering_per_hydrogen",
+    "cmi_gpu_set_cell_source_line", "cmi_gpu_set_cell_source_field",
+    "cmi_gpu_get_cell_source",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -262,6 +266,11 @@ def load_library():
     L.cmi_gpu_render_field_images.argtypes = [
         vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
         _dp, C.c_int32, _dp, _dp]
+    L.cmi_gpu_set_dust_scattering_per_hydrogen.argtypes = [
+        vp, C.c_double, C.c_double, C.c_double, C.c_double]
+    L.cmi_gpu_set_cell_source_line.argtypes = [vp, C.c_int32]
+    L.cmi_gpu_set_cell_source_field.argtypes = [vp, _dp]
+    L.cmi_gpu_get_cell_source.argtypes = [vp, _dp, _dp, _dp]
     L.cmi_gpu_line_image_probe.argtypes = [vp, C.c_double, C.c_double,
                                            C.c_int64, _dp, C.c_int32, _dp]
     _lib = L
@@ -791,6 +800,39 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_set_dust_scattering(
             self._h, g, p_l, albedo, kappa))
 
+    def set_dust_scattering_per_hydrogen(self, g, p_l, albedo, sigma):
+        """Dust that follows the gas: opacity n sigma, sigma in m^2 per
+        hydrogen nucleus (x_H is not read)."""
+        self._check(self._lib.cmi_gpu_set_dust_scattering_per_hydrogen(
+            self._h, g, p_l, albedo, sigma))
+
+    def set_cell_source_line(self, line):
+        """Packets of dust_shoot / dust_probe start in the cells, in
+        proportion to the emissivity of `line` (a name from EMISSION_LINES)
+        of the cells as they are."""
+        self._check(self._lib.cmi_gpu_set_cell_source_line(
+            self._h, EMISSION_LINES.index(line)))
+
+    def set_cell_source_field(self, field):
+        """The same for a per-cell luminosity density field[ncell] (W m^-3)
+        of the caller's."""
+        f = _f64(field).reshape(self.n)
+        self._check(self._lib.cmi_gpu_set_cell_source_field(self._h, _p(f)))
+
+    def get_cell_source(self, tables=True):
+        """The cell source's total luminosity (W) and, with `tables`, its
+        block sums [ceil(ncell / 256)] and cell sums [ncell]."""
+        total = C.c_double()
+        if not tables:
+            self._check(self._lib.cmi_gpu_get_cell_source(
+                self._h, C.byref(total), None, None))
+            return total.value
+        blocks = np.zeros((self.n + 255) // 256)
+        cells = np.zeros(self.n)
+        self._check(self._lib.cmi_gpu_get_cell_source(
+            self._h, C.byref(total), _p(blocks), _p(cells)))
+        return total.value, blocks, cells
+
     def set_ccd_image(self, theta, phi, nx, ny, anchor, sides):
         a = _f64(anchor).reshape(2)
         s = _f64(sides).reshape(2)
@@ -830,7 +872,8 @@ class GpuEngine:
         width = {DUST_PROBE_EMIT: 6, DUST_PROBE_SCATTER: 12,
                  DUST_PROBE_SCATTER_TOWARDS: 5,
                  DUST_PROBE_OPTICAL_DEPTH: 2 + max_events,
-                 DUST_PROBE_TRACE: 4 + 8 * max_events}[kind]
+                 DUST_PROBE_TRACE: 4 + 8 * max_events,
+                 DUST_PROBE_CELL_SOURCE: 7}[kind]
         in_width = {DUST_PROBE_SCATTER: 12, DUST_PROBE_SCATTER_TOWARDS: 12,
                     DUST_PROBE_OPTICAL_DEPTH: 6}.get(kind, 0)
         inp = None
@@ -860,6 +903,33 @@ class GpuEngine:
             theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
             dust_cross_section, _p(out)))
         return dict(zip(names, out))
+
+    def render_scattered_line_images(self, lines, theta, phi, nx, ny, anchor,
+                                     sides, npackets, seed, sigma, albedo, g,
+                                     p_l):
+        """Monte Carlo images of emission lines in direct and dust-scattered
+        light: (nlines, 3, nx, ny), I, Q and U in W m^-2 sr^-1. Each line is
+        one run of `npackets` packets from the cells' emissivities through
+        dust of `sigma` m^2 per hydrogen nucleus (albedo, HG asymmetry g,
+        peak linear polarisation p_l); the unnormalised image is scaled by
+        L_total / (npackets A_pixel), which makes it comparable with
+        render_line_images. Replaces the engine's CCD image, dust and dust
+        source."""
+        names = list(EMISSION_LINES if lines is None else lines)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        pixel_area = s[0] * s[1] / (int(nx) * int(ny))
+        self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
+        self.set_ccd_image(theta, phi, nx, ny, a, s)
+        out = np.zeros((len(names), 3, int(nx), int(ny)))
+        for k, name in enumerate(names):
+            self.set_cell_source_line(name)
+            self.reset_image()
+            self.dust_shoot(seed, 0, int(npackets))
+            total = self.get_cell_source(tables=False)
+            out[k] = self.download_image() * \
+                (total / (int(npackets) * pixel_area))
+        return out
 
     def render_field_images(self, fields, theta, phi, nx, ny, anchor, sides,
                             supersample=1, extinction=None):

@@ -23,6 +23,17 @@
  *   EmissionImages:type                          BinaryArray (or PGM)
  *   EmissionImages:filename prefix               line_image
  *   EmissionImages:output folder                 .
+ * With "EmissionImages:scattering: true" every flagged line is also shot as
+ * a Monte Carlo run (cmi_gpu_set_cell_source_line, cmi_gpu_dust_shoot): its
+ * packets start in the cells in proportion to the line's emissivity, scatter
+ * off dust of the same cross section per hydrogen and are peeled off towards
+ * the observer. I, Q and U are written next to the ray-traced image as
+ * <prefix>_<LineName>_scattered_I / _Q / _U, scaled by L_total / (packets x
+ * pixel area) to W m^-2 sr^-1 like it. Read only then:
+ *   EmissionImages:number of packets             1000000
+ *   EmissionImages:random seed                   42
+ *   EmissionImages:dust albedo / dust asymmetry / dust peak linear
+ *                    polarisation: required if the cross section is > 0
  * For the images the cells go on the snapshot's real grid: the box from
  * /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -56,6 +67,10 @@ class EmissivityCalculationSimulation {
     double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
     double dust_cross_section = 0.;
     std::string type, prefix, folder;
+    /* scattered light (the keys below are read only if scattering is set) */
+    bool scattering = false;
+    long long npackets = 1000000, seed = 42;
+    double albedo = 0., asymmetry = 0.5, polarisation = 0.;
 
     void read(ParameterFile &params) {
       theta = params.get_physical_value(QUANTITY_ANGLE,
@@ -98,6 +113,36 @@ class EmissivityCalculationSimulation {
         if (have_sides[a] && !(sides[a] > 0.))
           throw ParameterError("EmissionImages: the image sides must be "
                                "positive");
+      /* (a key that is read shows in the used-values: with the switch
+       * absent or off none of these is, the switch included) */
+      if (!params.peek_bool("EmissionImages:scattering"))
+        return;
+      scattering = params.get_bool("EmissionImages:scattering", false);
+      npackets = params.get_integer("EmissionImages:number of packets",
+                                    1000000);
+      seed = params.get_integer("EmissionImages:random seed", 42);
+      if (npackets <= 0)
+        throw ParameterError("EmissionImages:number of packets must be "
+                             "positive");
+      if (seed < 0 || seed > 0xffffffffll)
+        throw ParameterError("EmissionImages:random seed must fit 32 bits");
+      static const char *keys[3] = {
+          "EmissionImages:dust albedo", "EmissionImages:dust asymmetry",
+          "EmissionImages:dust peak linear polarisation"};
+      double *values[3] = {&albedo, &asymmetry, &polarisation};
+      for (int k = 0; k < 3; ++k) {
+        if (params.has_value(keys[k]))
+          *values[k] = params.get_double(keys[k], *values[k]);
+        else if (dust_cross_section > 0.)
+          throw ParameterError(std::string(keys[k]) +
+                               " is required for scattering off dust with a "
+                               "cross section above 0");
+      }
+      if (!(albedo >= 0. && albedo <= 1.))
+        throw ParameterError("EmissionImages:dust albedo must be in [0, 1]");
+      if (!(asymmetry != 0. && std::fabs(asymmetry) < 1.))
+        throw ParameterError("EmissionImages:dust asymmetry must be non-zero "
+                             "and inside (-1, 1)");
     }
   };
 
@@ -326,6 +371,44 @@ public:
                 img.folder + "/" + img.prefix + "_" +
                     GpuIonizationSimulation::emission_line_name(lines[k]),
                 img.type, images.data() + k * npixel, img.nx, img.ny, 1.);
+        if (rc == CMI_GPU_OK && img.scattering) {
+          status("Shooting the lines' packets through the dust...");
+          rc = cmi_gpu_set_dust_scattering_per_hydrogen(
+              engine, img.asymmetry, img.polarisation, img.albedo,
+              img.dust_cross_section);
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_ccd_image(engine, img.theta, img.phi,
+                                       (int32_t)img.nx, (int32_t)img.ny,
+                                       anchor, sides);
+          const double pixel_area =
+              sides[0] * sides[1] / ((double)img.nx * (double)img.ny);
+          std::vector<double> iqu(3 * npixel);
+          for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
+            double total = 0.;
+            rc = cmi_gpu_set_cell_source_line(engine, lines[k]);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_reset_image(engine);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_dust_shoot(engine, (uint32_t)img.seed, 0,
+                                      (uint64_t)img.npackets);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_download_image(engine, iqu.data(),
+                                          iqu.data() + npixel,
+                                          iqu.data() + 2 * npixel);
+            static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
+                                            "_scattered_U"};
+            if (rc == CMI_GPU_OK && write_output)
+              for (int j = 0; j < 3; ++j)
+                written += " " + write_image(
+                    img.folder + "/" + img.prefix + "_" +
+                        GpuIonizationSimulation::emission_line_name(lines[k]) +
+                        stokes[j],
+                    img.type, iqu.data() + j * npixel, img.nx, img.ny,
+                    total / ((double)img.npackets * pixel_area));
+          }
+        }
       }
       const std::string message = rc ? cmi_gpu_last_error() : "";
       cmi_gpu_destroy(engine);

@@ -207,6 +207,13 @@ public:
     return it != _dictionary.end() &&
            it->first.compare(0, prefix.size(), prefix) == 0;
   }
+  /* a switch of the file as it stands there, false if absent, without
+   * counting as read: a switch that is off then leaves no trace in the
+   * used-values (print_contents) */
+  bool peek_bool(const std::string &key) const {
+    const auto it = _dictionary.find(key);
+    return it != _dictionary.end() && to_bool(it->second);
+  }
   void add_value(const std::string &key, const std::string &value) {
     _dictionary[key] = value;
     _used[key] = value;

@@ -816,6 +816,15 @@ int cmi_gpu_get_launch_steps(cmi_gpu_engine *engine, uint64_t capacity,
 int cmi_gpu_set_dust_scattering(cmi_gpu_engine *engine, double g, double p_l,
                                 double albedo, double kappa);
 
+/* The same phase function constants for dust that follows the gas: the march
+ * reads n sigma per cell, sigma in m^2 per hydrogen nucleus, and x_H is not
+ * read - the k = n_H sigma_dust of cmi_gpu_render_line_images. sigma = 0 is
+ * allowed (direct light only); a negative sigma is CMI_GPU_EINVAL. The later
+ * of the two setters holds. */
+int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *engine, double g,
+                                             double p_l, double albedo,
+                                             double sigma);
+
 /* replaces: the CCDImage ctor (src/CCDImage.hpp:123-160): view angles theta,
  * phi (radians), resolution nx x ny, image anchor[2] and sides[2] (m). The
  * image is I, Q, U of nx x ny pixels, pixel (ix, iy) at ix * ny + iy
@@ -836,6 +845,41 @@ int cmi_gpu_set_ccd_image(cmi_gpu_engine *engine, double theta, double phi,
 int cmi_gpu_set_continuous_source_spiral_galaxy(cmi_gpu_engine *engine,
                                                 double r_stars, double h_stars,
                                                 double bulge_over_total);
+
+/* The cell-luminosity source (no counterpart in the reference): packets of
+ * cmi_gpu_dust_shoot and cmi_gpu_dust_probe start inside the cells, cell c
+ * with a probability proportional to a weight w_c >= 0 (W m^-3), at a
+ * uniform position in it, in an isotropic direction, with Stokes (1, 0, 0,
+ * 0); their life from the direct light on is the galaxy source's packets'.
+ * The weights are the emissivity of emission line `line` (numbered as in
+ * cmi_gpu_compute_emissivities) of the cells as they are, computed on the
+ * device, or the caller's field[ncell] in the engine's cell order.
+ * The sampling tables, over blocks of 256 consecutive cells (the last may be
+ * partial): cell_sums[c], the running sum of w within c's block, cell by cell
+ * from 0 in every block; block_sums[b], the running sum of the block totals,
+ * block by block. One uniform u gives t = u block_sums[last]: the block is
+ * the first with block_sums[b] > t, the cell the first of it with
+ * cell_sums[k] > t - block_sums[b - 1] (csrc/device_dust.h has what happens
+ * when rounding leaves none, and why a cell with w = 0 is never chosen).
+ * A weight that is negative or not finite is CMI_GPU_EINVAL; weights that
+ * sum to 0 are CMI_GPU_ESTATE ("nothing emits"); a line source needs the
+ * abundances and the cell data as cmi_gpu_compute_emissivities does;
+ * periodic boxes and blocks of a decomposed grid are refused. A call that
+ * fails leaves no cell source. A later
+ * cmi_gpu_set_continuous_source_spiral_galaxy selects the galaxy again.
+ * A line source's tables are stale once the cells change (cmi_gpu_upload_
+ * cells, an upload of a state field, a cell update): the next shoot or probe
+ * fails with CMI_GPU_ESTATE until the source is set again. A field source
+ * does not depend on the cells. Synchronous. */
+int cmi_gpu_set_cell_source_line(cmi_gpu_engine *engine, int32_t line);
+int cmi_gpu_set_cell_source_field(cmi_gpu_engine *engine, const double *field);
+
+/* The cell source as built: its total luminosity V_cell block_sums[last]
+ * (W) - an unnormalised image x total / (packets x pixel area) is in W m^-2
+ * sr^-1 - and the tables: block_sums host [ceil(ncell / 256)], cell_sums
+ * host [ncell]. Any of the three may be NULL. */
+int cmi_gpu_get_cell_source(cmi_gpu_engine *engine, double *total_luminosity,
+                            double *block_sums, double *cell_sums);
 
 /* replaces: DustPhotonShootJob::execute for packets [first_packet,
  * first_packet + n) (src/DustPhotonShootJob.hpp:107-164), adding to the
@@ -881,7 +925,11 @@ int cmi_gpu_get_dust_counters(cmi_gpu_engine *engine, uint64_t *counters);
  *    steps, capped (either cap), rows[max_events] of {pos[3], I, Q, U, V,
  *    weight}}: the
  *    direct light (Stokes 1, 0, 0, 0, weight 0.25 exp(-tau) / pi), then
- *    each peel-off */
+ *    each peel-off
+ *  5 CELL_SOURCE (the cell source must be selected): out {cell, pos[3],
+ *    dir[3]}
+ * EMIT and TRACE follow the selected source (a cell source always finds a
+ * position). */
 int cmi_gpu_dust_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events);
