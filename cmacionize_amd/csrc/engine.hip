@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "dust_kernels.h"
 #include "line_image_kernels.h"
+#include "sky_image_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -3348,6 +3350,329 @@ int cmi_gpu_line_image_probe(cmi_gpu_engine *e, double theta, double phi,
   (void)hipFree(dxy);
   (void)hipFree(drows);
   HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------------------- sky maps -- */
+extern "C++" {
+namespace {
+/* device buffers of one sky call, freed however it ends */
+struct SkyBuffers {
+  double *records = nullptr, *directions = nullptr, *out = nullptr,
+         *fields = nullptr, *extinction = nullptr;
+  ~SkyBuffers() {
+    (void)hipFree(records);
+    (void)hipFree(directions);
+    (void)hipFree(out);
+    (void)hipFree(fields);
+    (void)hipFree(extinction);
+  }
+};
+
+/* what every sky call asks of the engine and of its rays before a launch */
+int sky_check(const cmi_gpu_engine *e, const char *what, const double *origin,
+              int64_t nrays, int64_t max_rays, const double *directions) {
+  const GridDev &g = e->grid;
+  if (g.decomposed)
+    return fail(CMI_GPU_ESTATE, "%s: not available on a block of a decomposed "
+                "grid (the sky of one block is not a sky)", what);
+  if (g.periodic[0] || g.periodic[1] || g.periodic[2])
+    return fail(CMI_GPU_EINVAL, "%s: periodic boxes are not supported (a line "
+                "of sight through a periodic box has no end)", what);
+  if (nrays <= 0 || nrays > max_rays)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and %lld rays (%lld asked for)",
+                what, (long long)max_rays, (long long)nrays);
+  if (!origin || !directions)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(origin[a]))
+      return fail(CMI_GPU_EINVAL, "%s: component %d of the origin is not "
+                  "finite", what, a);
+  for (int64_t r = 0; r < nrays; ++r) {
+    const double *d = directions + 3 * r;
+    if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]))
+      return fail(CMI_GPU_EINVAL, "%s: the direction of ray %lld is not "
+                  "finite", what, (long long)r);
+    const double norm2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    if (!(std::fabs(norm2 - 1.) <= 1.e-9))
+      return fail(CMI_GPU_EINVAL, "%s: the direction of ray %lld is not a "
+                  "unit vector (|d|^2 = %.17g)", what, (long long)r, norm2);
+  }
+  return CMI_GPU_OK;
+}
+
+/* out[l * nrays + r] (host), l < nl, of the records [ncell][nd] in b.records:
+ * launches of at most CMI_SKY_LAUNCH_RAYS rays, directions up, results down */
+int sky_march(cmi_gpu_engine *e, const double *origin, int64_t nrays,
+              const double *directions, int nd, int nl, SkyBuffers &b,
+              double *out) {
+  const int64_t chunk = std::min<int64_t>(nrays, CMI_SKY_LAUNCH_RAYS);
+  if (!b.directions)
+    HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
+  if (!b.out)
+    HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk *
+                                  CMI_LINE_IMAGE_BATCH));
+  for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
+    const int64_t n = std::min<int64_t>(chunk, nrays - r0);
+    HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
+                      sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    SkyMarchArgs a;
+    a.grid = e->grid;
+    for (int k = 0; k < 3; ++k)
+      a.origin[k] = origin[k];
+    a.directions = b.directions;
+    a.records = b.records;
+    a.nrays = n;
+    a.nlines = nl;
+    a.pad = 0;
+    a.line_stride = chunk;
+    a.out = b.out;
+    line_image_for_record(nd, [&](auto width) {
+      sky_march_kernel<decltype(width)::value>
+          <<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(a);
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int l = 0; l < nl; ++l)
+      HIP_TRY(hipMemcpy(out + (size_t)l * nrays + r0, b.out + (size_t)l * chunk,
+                        sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+/* rows of a 3 x 3 frame orthonormal to 1e-9? */
+bool sky_frame_is_orthonormal(const double *frame) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      double dot = 0.;
+      for (int a = 0; a < 3; ++a)
+        dot += frame[3 * i + a] * frame[3 * j + a];
+      if (!(std::fabs(dot - (i == j ? 1. : 0.)) <= 1.e-9))
+        return false;
+    }
+  return true;
+}
+
+int sky_map_check(const char *what, const double *frame, double lon_min,
+                  double lon_max, double lat_min, double lat_max,
+                  int32_t nlon, int32_t nlat) {
+  if (!frame)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nlon <= 0 || nlat <= 0 || (int64_t)nlon * nlat > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "%s: the map must have between 1 and 2^28 "
+                "pixels (%d x %d asked for)", what, (int)nlon, (int)nlat);
+  if (!std::isfinite(lon_min) || !std::isfinite(lon_max) ||
+      !(lon_min < lon_max))
+    return fail(CMI_GPU_EINVAL, "%s: the longitude range must be finite and "
+                "increasing", what);
+  if (!(lat_min < lat_max) || !(lat_min >= -0.5 * M_PI) ||
+      !(lat_max <= 0.5 * M_PI))
+    return fail(CMI_GPU_EINVAL, "%s: the latitude range must be increasing "
+                "and within [-pi / 2, pi / 2]", what);
+  if (!sky_frame_is_orthonormal(frame))
+    return fail(CMI_GPU_EINVAL, "%s: the frame is not orthonormal to 1e-9",
+                what);
+  return CMI_GPU_OK;
+}
+
+/* direction of the centre of pixel (i, j) */
+void sky_map_direction(const double *frame, double lon_min, double lon_max,
+                       double lat_min, double lat_max, int32_t nlon,
+                       int32_t nlat, int32_t i, int32_t j, double *d) {
+  const double l = lon_min + (lon_max - lon_min) * (i + 0.5) / nlon;
+  const double b = lat_min + (lat_max - lat_min) * (j + 0.5) / nlat;
+  const double cb = std::cos(b), sb = std::sin(b);
+  const double c1 = cb * std::cos(l), c2 = cb * std::sin(l);
+  for (int a = 0; a < 3; ++a)
+    d[a] = c1 * frame[a] + c2 * frame[3 + a] + sb * frame[6 + a];
+}
+} // namespace
+} // extern "C++"
+
+int cmi_gpu_render_line_sky(cmi_gpu_engine *e, int32_t nlines,
+                            const int32_t *lines, const double *origin,
+                            int64_t nrays, const double *directions,
+                            double dust_cross_section, double *out) {
+  static const char *what = "render_line_sky";
+  if (!e || !lines || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
+    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
+                (int)nlines, CMI_NEMISSIONLINE);
+  for (int32_t l = 0; l < nlines; ++l)
+    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
+      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
+                  (int)lines[l]);
+  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
+    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
+                what);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  HIP_TRY(hipSetDevice(e->device));
+  SkyBuffers b;
+  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records, sizeof(double) * (size_t)e->ncell *
+                                    line_image_record_doubles(nb)));
+  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
+    const int nd = line_image_record_doubles(nl);
+    LineRecordArgs r;
+    r.model = e->model;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.nlines = nl;
+    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l)
+      r.lines[l] = l < nl ? lines[first + l] : 0;
+    r.dust_cross_section = dust_cross_section;
+    r.records = b.records;
+    const int blocks = grid_blocks(e, e->ncell, 8);
+    line_image_for_record(nd, [&](auto width) {
+      line_record_kernel<decltype(width)::value>
+          <<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
+    });
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(sky_march(e, origin, nrays, directions, nd, nl, b,
+                      out + (size_t)first * nrays));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_field_sky(cmi_gpu_engine *e, int32_t nfields,
+                             const double *fields, const double *origin,
+                             int64_t nrays, const double *directions,
+                             const double *extinction, double *out) {
+  static const char *what = "render_field_sky";
+  if (!e || !fields || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nfields < 1 || nfields > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
+                what, (int)nfields);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t ncell = (size_t)e->ncell;
+  SkyBuffers b;
+  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records,
+                    sizeof(double) * ncell * line_image_record_doubles(nb)));
+  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
+  if (extinction) {
+    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
+    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice));
+  }
+  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
+    const int nd = line_image_record_doubles(nl);
+    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
+    line_image_for_record(nd, [&](auto width) {
+      field_record_kernel<decltype(width)::value><<<blocks, 256, 0, e->stream>>>(
+          b.fields, b.extinction, e->ncell, nl, b.records);
+    });
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(sky_march(e, origin, nrays, directions, nd, nl, b,
+                      out + (size_t)first * nrays));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_sky_probe(cmi_gpu_engine *e, const double *origin, int64_t n,
+                      const double *directions, int32_t max_cells,
+                      double *out) {
+  static const char *what = "sky_probe";
+  if (!e || !out || max_cells < 0)
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  CMI_TRY(sky_check(e, what, origin, n, 1ll << 24, directions));
+  HIP_TRY(hipSetDevice(e->device));
+  double *ddir = nullptr, *drows = nullptr;
+  const size_t width = 3 + 2 * (size_t)max_cells;
+  hipError_t err = hipMalloc(&ddir, sizeof(double) * 3 * (size_t)n);
+  if (err == hipSuccess)
+    err = hipMalloc(&drows, sizeof(double) * width * (size_t)n);
+  if (err == hipSuccess)
+    err = hipMemcpy(ddir, directions, sizeof(double) * 3 * (size_t)n,
+                    hipMemcpyHostToDevice);
+  if (err == hipSuccess)
+    err = hipMemsetAsync(drows, 0, sizeof(double) * width * (size_t)n,
+                         e->stream);
+  if (err == hipSuccess) {
+    sky_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
+        e->grid, origin[0], origin[1], origin[2], ddir, n, max_cells, drows);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, drows, sizeof(double) * width * (size_t)n,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(ddir);
+  (void)hipFree(drows);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_sky_map_directions(const double *frame, double lon_min,
+                               double lon_max, double lat_min, double lat_max,
+                               int32_t nlon, int32_t nlat, double *directions,
+                               double *solid_angles) {
+  static const char *what = "sky_map_directions";
+  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                        nlat));
+  const double dl = (lon_max - lon_min) / nlon;
+  for (int32_t i = 0; i < nlon; ++i)
+    for (int32_t j = 0; j < nlat; ++j) {
+      const size_t p = (size_t)i * nlat + j;
+      if (directions)
+        sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                          nlat, i, j, directions + 3 * p);
+      if (solid_angles) {
+        const double b_lo = lat_min + (lat_max - lat_min) * j / nlat;
+        const double b_hi = lat_min + (lat_max - lat_min) * (j + 1) / nlat;
+        solid_angles[p] = dl * (std::sin(b_hi) - std::sin(b_lo));
+      }
+    }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_line_sky_map(cmi_gpu_engine *e, int32_t nlines,
+                                const int32_t *lines, const double *origin,
+                                const double *frame, double lon_min,
+                                double lon_max, double lat_min, double lat_max,
+                                int32_t nlon, int32_t nlat,
+                                double dust_cross_section, double *maps) {
+  static const char *what = "render_line_sky_map";
+  if (!e || !lines || !maps || nlines < 1)
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                        nlat));
+  /* the rays in 8 x 8 tiles of the map, so that a wave's 64 rays are
+   * neighbours on the sky; pixel[k] is the pixel of ray k */
+  const size_t npixel = (size_t)nlon * nlat;
+  std::vector<int64_t> pixel;
+  std::vector<double> directions, rays;
+  try {
+    pixel.reserve(npixel);
+    directions.resize(3 * npixel);
+    rays.resize((size_t)nlines * npixel);
+  } catch (const std::bad_alloc &) {
+    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
+  }
+  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
+    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
+      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
+        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
+          sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                            nlat, i, j, directions.data() + 3 * pixel.size());
+          pixel.push_back((int64_t)i * nlat + j);
+        }
+  CMI_TRY(cmi_gpu_render_line_sky(e, nlines, lines, origin, (int64_t)npixel,
+                                  directions.data(), dust_cross_section,
+                                  rays.data()));
+  for (int32_t l = 0; l < nlines; ++l)
+    for (size_t k = 0; k < npixel; ++k)
+      maps[(size_t)l * npixel + (size_t)pixel[k]] = rays[(size_t)l * npixel + k];
   return CMI_GPU_OK;
 }
 

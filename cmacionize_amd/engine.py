@@ -108,6 +108,9 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_set_dust_scattering_per_hydrogen",
     "cmi_gpu_set_cell_source_line", "cmi_gpu_set_cell_source_field",
     "cmi_gpu_get_cell_source",
+    "cmi_gpu_render_line_sky", "cmi_gpu_render_field_sky",
+    "cmi_gpu_sky_probe", "cmi_gpu_render_line_sky_map",
+    "cmi_gpu_sky_map_directions",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -273,6 +276,18 @@ def load_library():
     L.cmi_gpu_get_cell_source.argtypes = [vp, _dp, _dp, _dp]
     L.cmi_gpu_line_image_probe.argtypes = [vp, C.c_double, C.c_double,
                                            C.c_int64, _dp, C.c_int32, _dp]
+    L.cmi_gpu_render_line_sky.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), _dp, C.c_int64, _dp, C.c_double,
+        _dp]
+    L.cmi_gpu_render_field_sky.argtypes = [
+        vp, C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _dp]
+    L.cmi_gpu_sky_probe.argtypes = [vp, _dp, C.c_int64, _dp, C.c_int32, _dp]
+    L.cmi_gpu_render_line_sky_map.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.c_double, C.c_double,
+        C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp]
+    L.cmi_gpu_sky_map_directions.argtypes = [
+        _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+        C.c_int32, _dp, _dp]
     _lib = L
     return L
 
@@ -286,6 +301,34 @@ def projected_areas(directions):
     if rc != 0:
         raise RuntimeError("cmi_gpu_projected_areas failed (%d)" % rc)
     return out
+
+
+FULL_SKY_LONGITUDE = (-np.pi, np.pi)
+FULL_SKY_LATITUDE = (-0.5 * np.pi, 0.5 * np.pi)
+IDENTITY_FRAME = ((1., 0., 0.), (0., 1., 0.), (0., 0., 1.))
+
+
+def sky_map_directions(nlon, nlat, lon_range=FULL_SKY_LONGITUDE,
+                       lat_range=FULL_SKY_LATITUDE, frame=IDENTITY_FRAME):
+    """The rays of an equirectangular map (include/cmi_gpu.h, "sky maps"), by
+    the function cmi_gpu_render_line_sky_map calls, run on the host: the
+    directions (nlon * nlat, 3) of the pixel centres in pixel order - pixel
+    (i, j) at i * nlat + j - and the exact solid angles dl (sin b_hi -
+    sin b_lo) of the pixels, so that a flux is sum(I * omega). Radians; the
+    rows of `frame` are e_1 (l = 0, b = 0), e_2 (l = 90 deg) and e_3 (the
+    pole). Users of other pixelisations (HEALPix's pix2vec) pass their own
+    unit vectors to GpuEngine.render_line_sky."""
+    f = _f64(frame).reshape(9)
+    n = max(int(nlon), 0) * max(int(nlat), 0)
+    d = np.zeros((n, 3))
+    omega = np.zeros(n)
+    L = load_library()
+    rc = L.cmi_gpu_sky_map_directions(
+        _p(f), lon_range[0], lon_range[1], lat_range[0], lat_range[1],
+        int(nlon), int(nlat), _p(d), _p(omega))
+    if rc != 0:
+        raise EngineError(L.cmi_gpu_last_error().decode())
+    return d, omega
 
 
 def _p(a):
@@ -954,6 +997,66 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_line_image_probe(
             self._h, theta, phi, len(xy), _p(xy), max_cells, _p(out)))
         return out
+
+    # sky maps ---------------------------------------------------------------
+    def render_line_sky(self, lines, origin, directions,
+                        dust_cross_section=0.):
+        """Surface brightness of emission lines (names from EMISSION_LINES;
+        None: all) seen from `origin` (m) along the unit vectors
+        directions[nrays][3]: {name: (nrays,) array} in W m^-2 sr^-1, dust of
+        `dust_cross_section` m^2 per hydrogen nucleus along the way
+        (include/cmi_gpu.h, cmi_gpu_render_line_sky)."""
+        names = list(EMISSION_LINES if lines is None else lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(names), len(d)))
+        self._check(self._lib.cmi_gpu_render_line_sky(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            _p(o), len(d), _p(d), dust_cross_section, _p(out)))
+        return dict(zip(names, out))
+
+    def render_field_sky(self, fields, origin, directions, extinction=None):
+        """The same of any per-cell quantities: fields[nfields][ncell] and
+        the optional extinction[ncell] (m^-1); (nfields, nrays)."""
+        f = _f64(fields).reshape(-1, self.n)
+        k = None if extinction is None else _f64(extinction).reshape(self.n)
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(f), len(d)))
+        self._check(self._lib.cmi_gpu_render_field_sky(
+            self._h, len(f), _p(f), _p(o), len(d), _p(d),
+            _p(k) if k is not None else None, _p(out)))
+        return out
+
+    def sky_probe(self, origin, directions, max_cells):
+        """The rays from `origin` along directions[n][3]: rows {t_start,
+        t_out, steps, cells[max_cells], ds[max_cells]}."""
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(d), 3 + 2 * max_cells))
+        self._check(self._lib.cmi_gpu_sky_probe(
+            self._h, _p(o), len(d), _p(d), max_cells, _p(out)))
+        return out
+
+    def render_line_sky_map(self, lines, origin, nlon, nlat,
+                            lon_range=FULL_SKY_LONGITUDE,
+                            lat_range=FULL_SKY_LATITUDE,
+                            frame=IDENTITY_FRAME, dust_cross_section=0.):
+        """Equirectangular maps of emission lines around `origin`: {name:
+        (nlon, nlat) array}, the pixels of sky_map_directions."""
+        names = list(EMISSION_LINES if lines is None else lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        o = _f64(origin).reshape(3)
+        f = _f64(frame).reshape(9)
+        out = np.zeros((len(names), max(int(nlon), 0), max(int(nlat), 0)))
+        self._check(self._lib.cmi_gpu_render_line_sky_map(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
+            lat_range[1], int(nlon), int(nlat), dust_cross_section, _p(out)))
+        return dict(zip(names, out))
 
     def get_timing(self, reset=True):
         s = C.c_double()

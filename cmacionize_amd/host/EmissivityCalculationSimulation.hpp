@@ -34,11 +34,29 @@
  *   EmissionImages:random seed                   42
  *   EmissionImages:dust albedo / dust asymmetry / dust peak linear
  *                    polarisation: required if the cross section is > 0
- * For the images the cells go on the snapshot's real grid: the box from
- * /Parameters (SimulationBox:anchor, sides), each cell where its row of
+ * If the file has an "EmissionSkyMaps:" block, every flagged line is
+ * rendered as an equirectangular map of the sky around an observer inside
+ * or near the box (cmi_gpu_render_line_sky_map; pixel (i, j) of longitude i
+ * and latitude j at i * nlat + j) and written to <output folder>/<filename
+ * prefix>_<LineName>.dat or .pgm:
+ *   EmissionSkyMaps:observer position            required, a vector of lengths
+ *   EmissionSkyMaps:number of longitude pixels / number of latitude pixels
+ *                                                360 / 180
+ *   EmissionSkyMaps:longitude range              [-180. degrees, 180. degrees]
+ *   EmissionSkyMaps:latitude range               [-90. degrees, 90. degrees]
+ *   EmissionSkyMaps:frame pole                   [0, 0, 1]
+ *   EmissionSkyMaps:frame zero longitude         [1, 0, 0]
+ *                    orthonormalised by Gram-Schmidt (the pole is kept, the
+ *                    zero of longitude is made perpendicular to it, the
+ *                    third axis is pole x zero longitude); refused if parallel
+ *   EmissionSkyMaps:dust cross section per hydrogen   0. m^2
+ *   EmissionSkyMaps:type / filename prefix / output folder
+ *                                                BinaryArray / sky_map / .
+ * For the images and maps the cells go on the snapshot's real grid: the box
+ * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
- * task-based snapshots are stored subgrid after subgrid). Without the block
- * nothing of this is read and the mode's files are what they were.
+ * task-based snapshots are stored subgrid after subgrid). Without a block
+ * nothing of it is read and the mode's files are what they were.
  */
 #ifndef CMI_EMISSIVITYCALCULATIONSIMULATION_HPP
 #define CMI_EMISSIVITYCALCULATIONSIMULATION_HPP
@@ -146,6 +164,101 @@ class EmissivityCalculationSimulation {
     }
   };
 
+  /* the EmissionSkyMaps: block (read only if the file has one) */
+  struct SkyMapSettings {
+    std::array<double, 3> observer = {0., 0., 0.};
+    long long nlon = 360, nlat = 180;
+    std::array<double, 2> lon = {0., 0.}, lat = {0., 0.};
+    double frame[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
+    double dust_cross_section = 0.;
+    std::string type, prefix, folder;
+
+    void read(ParameterFile &params) {
+      if (!params.has_value("EmissionSkyMaps:observer position"))
+        throw ParameterError("EmissionSkyMaps:observer position is required");
+      observer = params.get_physical_vector(
+          QUANTITY_LENGTH, "EmissionSkyMaps:observer position", "");
+      nlon = params.get_integer("EmissionSkyMaps:number of longitude pixels",
+                                360);
+      nlat = params.get_integer("EmissionSkyMaps:number of latitude pixels",
+                                180);
+      lon = params.get_physical_pair(QUANTITY_ANGLE,
+                                     "EmissionSkyMaps:longitude range",
+                                     "[-180. degrees, 180. degrees]");
+      lat = params.get_physical_pair(QUANTITY_ANGLE,
+                                     "EmissionSkyMaps:latitude range",
+                                     "[-90. degrees, 90. degrees]");
+      const std::array<double, 3> pole = params.get_double_vector(
+          "EmissionSkyMaps:frame pole", {0., 0., 1.});
+      const std::array<double, 3> zero = params.get_double_vector(
+          "EmissionSkyMaps:frame zero longitude", {1., 0., 0.});
+      dust_cross_section = params.get_physical_value(
+          QUANTITY_SURFACE_AREA,
+          "EmissionSkyMaps:dust cross section per hydrogen", "0. m^2");
+      type = params.get_string("EmissionSkyMaps:type", "BinaryArray");
+      prefix = params.get_string("EmissionSkyMaps:filename prefix", "sky_map");
+      folder = params.get_string("EmissionSkyMaps:output folder", ".");
+      if (!is_image_type(type))
+        throw ParameterError("Unknown EmissionSkyMaps:type \"" + type +
+                             "\" (BinaryArray or PGM)");
+      for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(observer[a]))
+          throw ParameterError("EmissionSkyMaps:observer position must be "
+                               "finite");
+      if (nlon <= 0 || nlat <= 0 || nlon * nlat > (1ll << 28))
+        throw ParameterError(
+            "EmissionSkyMaps: the numbers of longitude pixels and latitude "
+            "pixels must be positive, 2^28 pixels at most (" +
+            std::to_string(nlon) + " x " + std::to_string(nlat) +
+            " asked for)");
+      if (!std::isfinite(lon[0]) || !std::isfinite(lon[1]) ||
+          !(lon[0] < lon[1]))
+        throw ParameterError("EmissionSkyMaps:longitude range must be "
+                             "increasing");
+      /* (90 degrees converted to radians may overshoot pi / 2 by an ulp) */
+      const double half_pi = 0.5 * M_PI;
+      for (int k = 0; k < 2; ++k)
+        if (std::fabs(std::fabs(lat[k]) - half_pi) < 1.e-12)
+          lat[k] = lat[k] < 0. ? -half_pi : half_pi;
+      if (!(lat[0] < lat[1]) || !(lat[0] >= -half_pi) || !(lat[1] <= half_pi))
+        throw ParameterError("EmissionSkyMaps:latitude range must be "
+                             "increasing and within [-90, 90] degrees");
+      if (!(dust_cross_section >= 0.))
+        throw ParameterError("EmissionSkyMaps:dust cross section per hydrogen "
+                             "must not be negative");
+      /* Gram-Schmidt: e_3 = the pole, e_1 = the zero of longitude made
+       * perpendicular to it, e_2 = e_3 x e_1 */
+      double e3[3], e1[3];
+      double norm = std::sqrt(pole[0] * pole[0] + pole[1] * pole[1] +
+                              pole[2] * pole[2]);
+      const double zero_norm = std::sqrt(zero[0] * zero[0] + zero[1] * zero[1] +
+                                         zero[2] * zero[2]);
+      if (!(norm > 0.) || !std::isfinite(norm) || !(zero_norm > 0.) ||
+          !std::isfinite(zero_norm))
+        throw ParameterError("EmissionSkyMaps:frame pole and frame zero "
+                             "longitude must be finite vectors, not zero");
+      for (int a = 0; a < 3; ++a)
+        e3[a] = pole[a] / norm;
+      const double along = zero[0] * e3[0] + zero[1] * e3[1] + zero[2] * e3[2];
+      for (int a = 0; a < 3; ++a)
+        e1[a] = zero[a] - along * e3[a];
+      norm = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+      if (!(norm > 1.e-8 * zero_norm))
+        throw ParameterError("EmissionSkyMaps:frame pole and frame zero "
+                             "longitude are parallel");
+      for (int a = 0; a < 3; ++a)
+        e1[a] /= norm;
+      const double e2[3] = {e3[1] * e1[2] - e3[2] * e1[1],
+                            e3[2] * e1[0] - e3[0] * e1[2],
+                            e3[0] * e1[1] - e3[1] * e1[0]};
+      for (int a = 0; a < 3; ++a) {
+        frame[a] = e1[a];
+        frame[3 + a] = e2[a];
+        frame[6 + a] = e3[a];
+      }
+    }
+  };
+
 public:
   /* EmissivityCalculationSimulation::do_simulation, :58-299 */
   static int do_simulation(const std::string &parameterfile_name,
@@ -167,6 +280,10 @@ public:
     ImageSettings img;
     if (do_images)
       img.read(params);
+    const bool do_sky = params.has_block("EmissionSkyMaps");
+    SkyMapSettings sky;
+    if (do_sky)
+      sky.read(params);
     if (write_output) {
       std::ofstream pfile(parameterfile_name + ".used-values");
       params.print_contents(pfile);
@@ -251,7 +368,7 @@ public:
      * describes (its midpoint, with the box anchor as the origin) */
     std::array<double, 3> box_anchor = {0., 0., 0.}, box_sides = {1., 1., 1.};
     std::vector<size_t> cell_of_row;
-    if (do_images && !lines.empty()) {
+    if ((do_images || do_sky) && !lines.empty()) {
       box_anchor = simulation_parameters.get_physical_vector(
           QUANTITY_LENGTH, "SimulationBox:anchor", "");
       box_sides = simulation_parameters.get_physical_vector(
@@ -333,7 +450,7 @@ public:
         values.swap(v2);
       }
       std::string written;
-      if (rc == CMI_GPU_OK && placed) {
+      if (rc == CMI_GPU_OK && placed && do_images) {
         status("Rendering emission line images...");
         /* default image: the rectangle around the box's projected corners */
         const double st = std::sin(img.theta), ct = std::cos(img.theta),
@@ -409,6 +526,22 @@ public:
                     total / ((double)img.npackets * pixel_area));
           }
         }
+      }
+      if (rc == CMI_GPU_OK && placed && do_sky) {
+        status("Rendering emission line sky maps...");
+        const size_t npixel = (size_t)sky.nlon * (size_t)sky.nlat;
+        std::vector<double> maps(lines.size() * npixel);
+        rc = cmi_gpu_render_line_sky_map(
+            engine, (int32_t)lines.size(), lines.data(), sky.observer.data(),
+            sky.frame, sky.lon[0], sky.lon[1], sky.lat[0], sky.lat[1],
+            (int32_t)sky.nlon, (int32_t)sky.nlat, sky.dust_cross_section,
+            maps.data());
+        if (rc == CMI_GPU_OK && write_output)
+          for (size_t k = 0; k < lines.size(); ++k)
+            written += " " + write_image(
+                sky.folder + "/" + sky.prefix + "_" +
+                    GpuIonizationSimulation::emission_line_name(lines[k]),
+                sky.type, maps.data() + k * npixel, sky.nlon, sky.nlat, 1.);
       }
       const std::string message = rc ? cmi_gpu_last_error() : "";
       cmi_gpu_destroy(engine);

@@ -1,7 +1,8 @@
 /*
  * ImageWriter.hpp - an image of nx x ny doubles, pixel (ix, iy) at
  * ix * ny + iy, as a file: CCDImage::save, src/CCDImage.hpp:299-362. Shared
- * by the dusty mode's CCD image and the emission-line images.
+ * by the dusty mode's CCD image, the emission-line images and the sky maps
+ * (nx = longitude pixels, ny = latitude pixels).
  */
 #ifndef CMI_IMAGEWRITER_HPP
 #define CMI_IMAGEWRITER_HPP

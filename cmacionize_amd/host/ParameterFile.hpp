@@ -306,6 +306,45 @@ public:
     return v;
   }
 
+  /* "[a unit, b unit]": a range (not in the reference's parameter files) */
+  std::array<double, 2> get_physical_pair(Quantity q, const std::string &key,
+                                          const std::string &fallback) {
+    const std::string s = raw(key, fallback);
+    const size_t open = s.find('['), comma = s.find(','), close = s.find(']');
+    if (open == std::string::npos || comma == std::string::npos ||
+        close == std::string::npos || !(open < comma && comma < close) ||
+        s.find(',', comma + 1) != std::string::npos)
+      throw ParameterError("Parameter \"" + key + "\" is not a pair "
+                           "\"[a, b]\": \"" + s + "\"");
+    const std::string parts[2] = {s.substr(open + 1, comma - open - 1),
+                                  s.substr(comma + 1, close - comma - 1)};
+    std::array<double, 2> v;
+    std::string used = "[";
+    for (int i = 0; i < 2; ++i) {
+      const auto vu = split_value(parts[i]);
+      v[i] = to_SI(q, vu.first, vu.second);
+      used += number_to_string(v[i]) + " " + SI_unit_name(q);
+      if (i < 1)
+        used += ", ";
+    }
+    _used[key] = used + "]";
+    return v;
+  }
+  /* "[a, b, c]" of plain numbers */
+  std::array<double, 3> get_double_vector(const std::string &key,
+                                          const std::array<double, 3> &fallback) {
+    const std::string s = raw(key, "");
+    std::array<double, 3> v = fallback;
+    if (!s.empty()) {
+      const auto parts = split3(s);
+      for (int i = 0; i < 3; ++i)
+        v[i] = std::stod(parts[i]);
+    }
+    _used[key] = "[" + number_to_string(v[0]) + ", " + number_to_string(v[1]) +
+                 ", " + number_to_string(v[2]) + "]";
+    return v;
+  }
+
   /* YAMLDictionary::print_contents(stream, used_values = true), :270-380:
    * "key: used value # (value in the file)" grouped and indented by block */
   void print_contents(std::ostream &stream) const {

@@ -996,6 +996,99 @@ int cmi_gpu_line_image_probe(cmi_gpu_engine *engine, double theta, double phi,
                              int64_t n, const double *xy, int32_t max_cells,
                              double *out);
 
+/* ------------------------------------------------------------ sky maps -- */
+/* Line images for an observer inside or near the grid: the other camera. The
+ * calls above see the box from infinitely far away, one direction for all
+ * rays; here a call has one origin o (metres, any finite point, inside or
+ * outside the box) and nrays directions d_r, and ray r is o + t d_r, t >= 0:
+ * an all-sky map from a point of the model, or pencil beams towards catalogue
+ * positions. The reference has no such mode.
+ *
+ * The directions are used exactly as given and are not normalised on the
+ * device. The host refuses the call (CMI_GPU_EINVAL, nothing is launched) if
+ * an origin or direction component is not finite or if |d|^2 differs from 1
+ * by more than 1e-9. Components that are exactly zero are allowed (they take
+ * the DBL_MAX branch of the step).
+ *   Slab test: that of the images above with the ray's own 1 / d per axis:
+ *     t0 = (lo - o) (1 / d), t1 = (hi - o) (1 / d), t_in = max over axes of
+ *     min(t0, t1), t_out = min of max(t0, t1); an axis with d == 0 only asks
+ *     lo <= o < hi.
+ *   Hit: t_start = max(t_in, 0); the ray hits if t_start < t_out and t_out is
+ *     finite. A ray that misses gives 0.
+ *   Start: with the origin in the box (t_in <= 0) at o itself, otherwise at
+ *     o + t_in d; in the cell floor((p - anchor) inv_cellside) gives, clamped
+ *     into the grid. An origin exactly on a cell wall with a direction
+ *     pointing back across that wall makes a first step of length 0: allowed,
+ *     not special-cased (an origin on a box face pointing outwards misses).
+ *   Step: the exact marcher's (dda_step<false> at tau = HUGE_VAL), as in the
+ *     images above: walls from the index, every axis that ties the minimum
+ *     advances. The march ends when the index leaves the grid.
+ *   Integration, from the observer outwards, with transmission T = 1 and
+ *     I_l = 0 at the start; a cell {k, s_l} (s = j / 4 pi, or j / 4 pi / k
+ *     where k != 0) with path ds does
+ *       k == 0:  I_l += T * (s_l * ds)
+ *       else:    dtau = k * ds;  I_l += T * (s_l * (-expm1(-dtau)));
+ *                T = T * exp(-dtau)
+ *     in exactly this order of multiplications.
+ * Results are surface brightnesses in W m^-2 sr^-1, the unit of the images
+ * above. One lane per ray in the caller's order (wave w takes rays 64 w ..
+ * 64 w + 63), at most 2^22 rays per launch, 7 sources per march. No atomics:
+ * the same call on the same state gives the same bits. Periodic boxes are
+ * refused (CMI_GPU_EINVAL), blocks of a decomposed grid too (CMI_GPU_ESTATE).
+ * All calls are synchronous; a call that fails leaves the engine usable. */
+
+/* out[k * nrays + r] (host) of the emission lines lines[k] along ray r;
+ * lines, dust_cross_section and preconditions as in
+ * cmi_gpu_render_line_images. 1 <= nrays <= 2^28. */
+int cmi_gpu_render_line_sky(cmi_gpu_engine *engine, int32_t nlines,
+                            const int32_t *lines, const double origin[3],
+                            int64_t nrays,
+                            const double *directions /* [nrays][3] */,
+                            double dust_cross_section,
+                            double *out /* [nlines][nrays] */);
+
+/* the same for any per-cell quantities, fields and extinction as in
+ * cmi_gpu_render_field_images */
+int cmi_gpu_render_field_sky(cmi_gpu_engine *engine, int32_t nfields,
+                             const double *fields, const double origin[3],
+                             int64_t nrays, const double *directions,
+                             const double *extinction,
+                             double *out /* [nfields][nrays] */);
+
+/* Parity probe of the ray geometry: out[n][3 + 2 max_cells], fp64: {t_start,
+ * t_out, steps, the first max_cells cells, their path lengths}; steps = 0 and
+ * t_start = t_out = NaN for a ray that misses. 1 <= n <= 2^24. */
+int cmi_gpu_sky_probe(cmi_gpu_engine *engine, const double origin[3],
+                      int64_t n, const double *directions, int32_t max_cells,
+                      double *out);
+
+/* An equirectangular map, host code over cmi_gpu_render_line_sky: pixel
+ * (i, j), i < nlon, j < nlat, is stored at i * nlat + j; its centre is
+ *   l = lon_min + (lon_max - lon_min) (i + 0.5) / nlon,  b likewise,
+ * its direction d = cos b cos l e_1 + cos b sin l e_2 + sin b e_3 with e_1,
+ * e_2, e_3 the rows of frame[9], which must be orthonormal to 1e-9 (every
+ * |e_i . e_j - delta_ij| <= 1e-9; CMI_GPU_EINVAL otherwise; the directions
+ * then pass the ray-list call's own check like any caller's). Radians;
+ * lon_min < lon_max, -pi / 2 <= lat_min < lat_max <= pi / 2, nlon nlat <=
+ * 2^28. The rays are marched in 8 x 8 tiles of the map and the results put
+ * back in pixel order on the host; the values do not depend on that order.
+ * maps[k * nlon * nlat + pixel]. */
+int cmi_gpu_render_line_sky_map(cmi_gpu_engine *engine, int32_t nlines,
+                                const int32_t *lines, const double origin[3],
+                                const double frame[9], double lon_min,
+                                double lon_max, double lat_min, double lat_max,
+                                int32_t nlon, int32_t nlat,
+                                double dust_cross_section, double *maps);
+
+/* The map's directions[nlon * nlat][3] in pixel order, by the function the
+ * map call uses (host only, no engine), and the exact solid angles of the
+ * pixels, dl (sin b_hi - sin b_lo), so that a flux is sum(I omega). Either
+ * output may be NULL. */
+int cmi_gpu_sky_map_directions(const double frame[9], double lon_min,
+                               double lon_max, double lat_min, double lat_max,
+                               int32_t nlon, int32_t nlat, double *directions,
+                               double *solid_angles);
+
 #ifdef __cplusplus
 }
 #endif
