@@ -48,6 +48,35 @@
  * C[k - 1] (k is the first above r), or C[k] > r >= 0 at k = first of b, or
  * is the first to reach C[last of b] > 0: in every case C[k] differs from
  * the sum before it, which w_k == 0 cannot do.
+ *
+ * The point camera (DUST_CAMERA_POINT, an observer inside or near the grid,
+ * DESIGN.md 4.10, no counterpart in the reference) draws no random number:
+ * both lists above stay true with it, and a packet's emission, optical depths
+ * and scatterings are bit for bit the parallel camera's for the same seed and
+ * id. Per event (the direct light at the emission point, then each peel-off
+ * at a scattering point p), with the observer at o, in exactly these
+ * operations (tests/support/scattered_sky_reference.c restates them):
+ *   v = o - p per axis; r2 = (v_x v_x + v_y v_y) + v_z v_z; r = sqrt(r2);
+ *   k = v / r per axis (a division, not a multiplication by 1 / r);
+ *   1 / k per axis for the march. r2 < r_min^2: the event adds nothing and is
+ *   counted (nexcluded).
+ *   Scattering angles of the observer's direction (dust_scatter_towards_
+ *   point): cos theta = k_z, sin theta = sqrt(fmax(1 - k_z k_z, 0)), phi =
+ *   atan2(k_y, k_x) (0 where sin theta == 0), sin phi, cos phi.
+ *   tau = dust_integrate_to(p, k, r): dust_integrate's march with the length
+ *   s summed step by step; the step with s + ds >= r adds (r - s) kappa and
+ *   ends it. An observer outside the box: the march leaves the grid first.
+ *   Q, U are rotated from the meridian through the grid's z axis to the one
+ *   through the frame's pole e_3 (dust_sky_rotate) unless e_3 is exactly
+ *   (0, 0, 1).
+ *   Pixel (dust_sky_pixel): n = -k; l = atan2(n . e_2, n . e_1), b =
+ *   asin(fmin(1, fmax(-1, n . e_3))); x = l - lon_min; x -= 2 pi floor(x /
+ *   (2 pi)); x += 2 pi if x < 0; x -= 2 pi if x >= 2 pi; y = b - lat_min;
+ *   inside if x < lon_width and 0 <= y <= lat_width; i = (int)(nlon x /
+ *   lon_width), j = (int)(nlat y / lat_width), each clamped to its last
+ *   index (rounding just below the far edge, and b == lat_max itself);
+ *   pixel i nlat + j. Events outside the window are counted (noutside).
+ *   Addend: W / r2 times I, Q, U, with W the parallel camera's weight.
  */
 #ifndef CMI_DEVICE_DUST_H
 #define CMI_DEVICE_DUST_H
@@ -81,6 +110,26 @@ template <> struct DustSource<DUST_SOURCE_CELLS> {
 };
 typedef DustSource<DUST_SOURCE_CELLS> CellSourceDev;
 
+/* where the peel-off goes: template parameter of dust_packet and its kernels.
+ * PARALLEL: the CCD image of an observer infinitely far away (DustDev's);
+ * POINT: the sky map around an observer at a point */
+enum { DUST_CAMERA_PARALLEL = 0, DUST_CAMERA_POINT = 1 };
+
+/* what a camera reads beyond DustDev, a kernel argument of its own: nothing
+ * for the parallel camera */
+template <int CAMERA> struct DustCamera {};
+template <> struct DustCamera<DUST_CAMERA_POINT> {
+  double o[3];               /* the observer */
+  double e1[3], e2[3], e3[3]; /* the frame: l = 0, l = 90 deg, the pole */
+  double lon_min, lat_min, lon_width, lat_width;
+  int32_t nlon, nlat;
+  double r_min2;        /* exclusion radius squared */
+  int32_t pole_is_z;    /* e3 is exactly (0, 0, 1): Q, U are not rotated */
+  int32_t direct_light; /* 0: the direct event and its march are skipped */
+  double *image;        /* [3][nlon * nlat]: I, Q, U */
+};
+typedef DustCamera<DUST_CAMERA_POINT> SkyCameraDev;
+
 /* everything the dust kernels read, by value */
 struct DustDev {
   /* DustScattering (src/DustScattering.hpp): g, g^2, 1 - g^2, 2g, 1 - g,
@@ -112,7 +161,9 @@ struct DustCountersDev {
   unsigned long long npackets;
   unsigned long long nsource_capped; /* packets the source gave no position
                                         (CMI_DUST_MAX_ATTEMPTS) */
-  unsigned long long pad[2];
+  /* the point camera's: events inside the exclusion radius, events outside
+   * the map's window (the parallel camera leaves both 0) */
+  unsigned long long nexcluded, noutside;
 };
 
 /* Photon with what the dust path reads: position, direction, its angles
@@ -567,6 +618,176 @@ __device__ __noinline__ double dust_scatter_towards(const DustDev &d,
   for (int k = 0; k < 5; ++k)
     p.par[k] = d.view[k];
   return 0.25 * d.omg2 * pow(d.opg2 - d.thgg * mu, -1.5) * M_1_PI;
+}
+
+/* dust_integrate's march from pos along dir, cut at the length r (the point
+ * camera's observer): the travelled length s is summed step by step, the step
+ * in which s + ds >= r adds (r - s) kappa and ends the march. If the grid
+ * ends first (an observer outside the box) this is dust_integrate. */
+__device__ __noinline__ double
+dust_integrate_to(const GridDev &g, const double2 *__restrict__ opacity,
+                  const double pos[3], const double dir[3],
+                  const double inv_dir[3], double r,
+                  unsigned long long &nsteps) {
+  Packet<false> q;
+  dust_march_packet(g, pos, dir, inv_dir, q);
+  q.tau = HUGE_VAL;
+  double optical_depth = 0., s = 0.;
+  int n = 0;
+  while (is_inside(g, q)) {
+    int64_t cell;
+    double2 kappa;
+    const double ds = dda_step<false>(g, opacity, q, cell, kappa);
+    ++n;
+    const double k = fmax(kappa.x, 0.);
+    if (s + ds >= r) {
+      optical_depth += (r - s) * k;
+      break;
+    }
+    optical_depth += ds * k;
+    s += ds;
+  }
+  nsteps += n;
+  return optical_depth;
+}
+
+/* dust_scatter_towards for an observer in the direction k (a unit vector)
+ * from the photon: the same operations with the observer's angles computed
+ * from k (the header comment lists them); the photon takes k, 1 / k and
+ * those angles. Returns the HG phase function per steradian.
+ * This body is a copy of dust_scatter_towards' (which is left alone so that
+ * its code stays the parallel camera's to the instruction): a change to
+ * either must be made to both, and to scatter_towards and
+ * scatter_towards_point of the CPU restatements. */
+__device__ __noinline__ double
+dust_scatter_towards_point(const DustDev &d, DustPhoton &p,
+                           const double k[3]) {
+  const double co = k[2];
+  const double so = sqrt(fmax(1. - co * co, 0.));
+  const double pho = so == 0. ? 0. : atan2(k[1], k[0]);
+  const double view[5] = {so, co, pho, sin(pho), cos(pho)};
+  const double mu = k[0] * p.dir[0] + k[1] * p.dir[1] + k[2] * p.dir[2];
+  if (fabs(mu) == 1.) {
+    if (mu == -1.)
+      p.stokes[2] = -p.stokes[2];
+  } else {
+    const DustPhase m = dust_phase(d, mu, true);
+    const double smu = sqrt(-(mu * mu - 1.));
+    const double st0 = p.par[0], ct0 = p.par[1];
+    double r1;
+    if (st0 == 0.) {
+      r1 = M_PI;
+    } else {
+      const double y = sin(p.par[2] - pho - M_PI) * so / smu;
+      const double x = (co - ct0 * mu) / (st0 * smu);
+      r1 = atan2(y, x) + M_PI;
+    }
+    const bool mirror = r1 > M_PI;
+    const double a1 = mirror ? 2. * M_PI - r1 : r1;
+    const double c1 = cos(a1), s1 = sin(a1);
+    double s2, c2;
+    if (fabs(co) < 1.) {
+      s2 = s1 * st0 / so;
+      const double den = so * smu;
+      c2 = ct0 / den - co * mu / den;
+    } else {
+      s2 = 0.;
+      c2 = co >= 1. ? -1. : 1.;
+    }
+    double cc1, ss1, cc2, ss2;
+    dust_double_angle(c1, s1, cc1, ss1);
+    dust_double_angle(c2, s2, cc2, ss2);
+    dust_apply_phase(m, cc1, ss1, cc2, ss2, mirror, p.stokes);
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    p.dir[a] = k[a];
+    p.inv_dir[a] = 1. / k[a];
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    p.par[j] = view[j];
+  return 0.25 * d.omg2 * pow(d.opg2 - d.thgg * mu, -1.5) * M_1_PI;
+}
+
+/* the point camera's direction and distance from pos to the observer (the
+ * header comment has the operations); false inside the exclusion radius */
+__device__ __forceinline__ bool dust_sky_direction(const SkyCameraDev &cam,
+                                                   const double pos[3],
+                                                   double k[3], double &r,
+                                                   double &r2) {
+  const double v[3] = {cam.o[0] - pos[0], cam.o[1] - pos[1],
+                       cam.o[2] - pos[2]};
+  r2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2];
+  r = sqrt(r2);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    k[a] = v[a] / r;
+  return !(r2 < cam.r_min2);
+}
+
+/* Q, U of a photon flying along k, referred by dust_scatter_towards* to the
+ * meridian through k and the grid's z axis, referred to the meridian through
+ * k and the frame's pole e3 instead: a rotation by twice the angle chi from
+ * the projection N_z = z - (z . k) k to N_e = e3 - (e3 . k) k in the plane
+ * perpendicular to k, cos chi = N_z . N_e / (|N_z| |N_e|), sin chi = (N_z x
+ * N_e) . k / (|N_z| |N_e|); chi = 0 where a projection vanishes. The sign
+ * (Q' = Q cos 2 chi - U sin 2 chi, U' = Q sin 2 chi + U cos 2 chi) follows
+ * the handedness of the reference's U (pinned by the
+ * polarisation-pattern test). */
+__device__ __forceinline__ void dust_sky_rotate(const SkyCameraDev &cam,
+                                                const double k[3],
+                                                double stokes[4]) {
+  const double zk = k[2];
+  const double ek = cam.e3[0] * k[0] + cam.e3[1] * k[1] + cam.e3[2] * k[2];
+  const double nz[3] = {-zk * k[0], -zk * k[1], 1. - zk * k[2]};
+  const double ne[3] = {cam.e3[0] - ek * k[0], cam.e3[1] - ek * k[1],
+                        cam.e3[2] - ek * k[2]};
+  const double lz = sqrt(nz[0] * nz[0] + nz[1] * nz[1] + nz[2] * nz[2]);
+  const double le = sqrt(ne[0] * ne[0] + ne[1] * ne[1] + ne[2] * ne[2]);
+  if (lz == 0. || le == 0.)
+    return;
+  const double norm = lz * le;
+  const double cx[3] = {nz[1] * ne[2] - nz[2] * ne[1],
+                        nz[2] * ne[0] - nz[0] * ne[2],
+                        nz[0] * ne[1] - nz[1] * ne[0]};
+  const double cchi = (nz[0] * ne[0] + nz[1] * ne[1] + nz[2] * ne[2]) / norm;
+  const double schi = (cx[0] * k[0] + cx[1] * k[1] + cx[2] * k[2]) / norm;
+  double c2, s2;
+  dust_double_angle(cchi, schi, c2, s2);
+  const double q = stokes[1], u = stokes[2];
+  stokes[1] = q * c2 - u * s2;
+  stokes[2] = q * s2 + u * c2;
+}
+
+/* the pixel (i * nlat + j, DESIGN.md 4.9's order) of the sky direction -k,
+ * or -1 outside the map's window (the header comment has the operations) */
+__device__ __forceinline__ int64_t dust_sky_pixel(const SkyCameraDev &cam,
+                                                  const double k[3]) {
+  const double n[3] = {-k[0], -k[1], -k[2]};
+  const double n1 = n[0] * cam.e1[0] + n[1] * cam.e1[1] + n[2] * cam.e1[2];
+  const double n2 = n[0] * cam.e2[0] + n[1] * cam.e2[1] + n[2] * cam.e2[2];
+  const double n3 = n[0] * cam.e3[0] + n[1] * cam.e3[1] + n[2] * cam.e3[2];
+  const double l = atan2(n2, n1);
+  const double b = asin(fmin(1., fmax(-1., n3)));
+  double x = l - cam.lon_min;
+  x -= 2. * M_PI * floor(x / (2. * M_PI));
+  if (x < 0.)
+    x += 2. * M_PI;
+  if (x >= 2. * M_PI)
+    x -= 2. * M_PI;
+  const double y = b - cam.lat_min;
+  if (!(x < cam.lon_width) || !(y >= 0.) || !(y <= cam.lat_width))
+    return -1;
+  int32_t i = (int32_t)(cam.nlon * x / cam.lon_width);
+  int32_t j = (int32_t)(cam.nlat * y / cam.lat_width);
+  /* n x / width can round up to n just below the far edge, and b == lat_max
+   * itself belongs to the last row */
+  if (i >= cam.nlon)
+    i = cam.nlon - 1;
+  if (j >= cam.nlat)
+    j = cam.nlat - 1;
+  return (int64_t)i * cam.nlat + j;
 }
 
 /* CCDImage::add_photon, src/CCDImage.hpp:242-270: the pixel (ix * ny + iy)

@@ -83,12 +83,98 @@ __device__ __forceinline__ void dust_add(const DustDev &d, const double pos[3],
   }
 }
 
+/* the point camera's dust_add: I, Q, U into pixel `pixel` of cam.image (-1:
+ * outside the window, counted), or the trace's row */
+template <bool TRACE>
+__device__ __forceinline__ void
+dust_sky_add(const SkyCameraDev &cam, const double pos[3], int64_t pixel,
+             double wi, double wq, double wu, const double stokes[4],
+             double weight, DustEvents &ev, DustCountersDev &c) {
+  if (TRACE) {
+    if (ev.n < ev.max_events) {
+      double *r = ev.rows + 8 * ev.n;
+      r[0] = pos[0];
+      r[1] = pos[1];
+      r[2] = pos[2];
+      r[3] = stokes[0];
+      r[4] = stokes[1];
+      r[5] = stokes[2];
+      r[6] = stokes[3];
+      r[7] = weight;
+    }
+    ++ev.n;
+    return;
+  }
+  if (pixel < 0) {
+    c.noutside += 1;
+    return;
+  }
+  const int64_t npixel = (int64_t)cam.nlon * cam.nlat;
+  if (wi != 0.) {
+    atomicAdd(cam.image + pixel, wi);
+    ++c.natomics;
+  }
+  if (wq != 0.) {
+    atomicAdd(cam.image + npixel + pixel, wq);
+    ++c.natomics;
+  }
+  if (wu != 0.) {
+    atomicAdd(cam.image + 2 * npixel + pixel, wu);
+    ++c.natomics;
+  }
+}
+
+/* one event of the point camera (device_dust.h's header comment has the
+ * contract): the direct light of the photon at its emission point (`scattered`
+ * false, w = 1) or the peel-off of a copy of it at a scattering point
+ * (w = the packet's weight so far, albedo included). An event inside the
+ * exclusion radius is counted and adds nothing (a trace gets a row of zeros
+ * at its position: one row per event, as with the parallel camera).
+ * __noinline__ like the functions it calls: one copy serves
+ * the direct light and the peel-offs. */
+template <bool TRACE>
+__device__ __noinline__ void
+dust_sky_event(const GridDev &g, const DustDev &d, const SkyCameraDev &cam,
+               const double2 *__restrict__ opacity, DustPhoton &peel,
+               bool scattered, double weight, double albedo,
+               DustCountersDev &c, DustEvents &ev) {
+  double k[3], r, r2;
+  if (!dust_sky_direction(cam, peel.pos, k, r, r2)) {
+    c.nexcluded += 1;
+    const double nothing[4] = {0., 0., 0., 0.};
+    if (TRACE)
+      dust_sky_add<TRACE>(cam, peel.pos, -1, 0., 0., 0., nothing, 0., ev, c);
+    return;
+  }
+  double w;
+  if (scattered) {
+    const double hgfac = dust_scatter_towards_point(d, peel, k);
+    const double tau = dust_integrate_to(g, opacity, peel.pos, peel.dir,
+                                         peel.inv_dir, r, c.nsteps);
+    if (!cam.pole_is_z)
+      dust_sky_rotate(cam, k, peel.stokes);
+    w = weight * hgfac * albedo * exp(-tau);
+  } else {
+    const double inv_k[3] = {1. / k[0], 1. / k[1], 1. / k[2]};
+    const double tau =
+        dust_integrate_to(g, opacity, peel.pos, k, inv_k, r, c.nsteps);
+    w = 0.25 * exp(-tau) / M_PI;
+  }
+  const double addend = w / r2;
+  const int64_t pixel = TRACE ? -1 : dust_sky_pixel(cam, k);
+  dust_sky_add<TRACE>(cam, peel.pos, pixel, addend * peel.stokes[0],
+                      addend * peel.stokes[1], addend * peel.stokes[2],
+                      peel.stokes, addend, ev, c);
+}
+
 /* DustPhotonShootJob::execute for one packet; SOURCE selects where it
- * starts (at compile time: the galaxy's instantiation has no trace of the
- * other source), everything after the emission is the same */
-template <bool TRACE, int SOURCE>
+ * starts and CAMERA where its peel-offs go (at compile time: the galaxy's
+ * instantiation has no trace of the other source, the parallel camera's
+ * none of the point camera), everything else is the same */
+template <bool TRACE, int SOURCE, int CAMERA>
 __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
                                    const DustSource<SOURCE> &src,
+                                   const DustCamera<CAMERA> &cam,
                                    const double2 *__restrict__ opacity,
                                    uint32_t seed, uint64_t id,
                                    DustCountersDev &c, DustEvents &ev) {
@@ -106,12 +192,19 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   }
 
   /* direct light towards the observer, :127-130 */
-  const double tau_old =
-      dust_integrate(g, opacity, p.pos, d.obs_dir, d.obs_inv_dir, c.nsteps);
-  const double w_direct = 0.25 * exp(-tau_old) / M_PI;
-  const double unpolarised[4] = {1., 0., 0., 0.};
-  dust_add<TRACE>(d, p.pos, w_direct, 0., 0., unpolarised, w_direct, ev,
-                  c.natomics);
+  if constexpr (CAMERA == DUST_CAMERA_POINT) {
+    if (cam.direct_light) {
+      DustPhoton direct = p;
+      dust_sky_event<TRACE>(g, d, cam, opacity, direct, false, 1., 1., c, ev);
+    }
+  } else {
+    const double tau_old =
+        dust_integrate(g, opacity, p.pos, d.obs_dir, d.obs_inv_dir, c.nsteps);
+    const double w_direct = 0.25 * exp(-tau_old) / M_PI;
+    const double unpolarised[4] = {1., 0., 0., 0.};
+    dust_add<TRACE>(d, p.pos, w_direct, 0., 0., unpolarised, w_direct, ev,
+                    c.natomics);
+  }
 
   /* forced first interaction, :132-138 */
   double albedo = 1.;
@@ -124,14 +217,20 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   while (inside) {
     /* peel-off, :141-155 */
     DustPhoton peel = p;
-    const double hgfac = dust_scatter_towards(d, peel);
-    const double tau_new = dust_integrate(g, opacity, peel.pos, peel.dir,
-                                          peel.inv_dir, c.nsteps);
-    albedo *= d.albedo;
-    const double weight_new = weight * hgfac * albedo * exp(-tau_new);
-    dust_add<TRACE>(d, peel.pos, weight_new * peel.stokes[0],
-                    weight_new * peel.stokes[1], weight_new * peel.stokes[2],
-                    peel.stokes, weight_new, ev, c.natomics);
+    if constexpr (CAMERA == DUST_CAMERA_POINT) {
+      albedo *= d.albedo;
+      dust_sky_event<TRACE>(g, d, cam, opacity, peel, true, weight, albedo, c,
+                            ev);
+    } else {
+      const double hgfac = dust_scatter_towards(d, peel);
+      const double tau_new = dust_integrate(g, opacity, peel.pos, peel.dir,
+                                            peel.inv_dir, c.nsteps);
+      albedo *= d.albedo;
+      const double weight_new = weight * hgfac * albedo * exp(-tau_new);
+      dust_add<TRACE>(d, peel.pos, weight_new * peel.stokes[0],
+                      weight_new * peel.stokes[1], weight_new * peel.stokes[2],
+                      peel.stokes, weight_new, ev, c.natomics);
+    }
     /* scatter and fly on, :157-159 */
     dust_scatter(d, rng, p);
     ++nscatter;
@@ -155,17 +254,18 @@ __device__ __forceinline__ void dust_count(unsigned long long *dst,
 }
 
 /* packets [first, first + n) */
-template <int SOURCE>
+template <int SOURCE, int CAMERA>
 __global__ void __launch_bounds__(256)
     dust_shoot_kernel(GridDev g, DustDev d,
                       const double2 *__restrict__ opacity, uint32_t seed,
                       uint64_t first, uint64_t n, DustCountersDev *counters,
-                      DustSource<SOURCE> src) {
+                      DustSource<SOURCE> src, DustCamera<CAMERA> cam) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   DustCountersDev c = {};
   DustEvents ev = {nullptr, 0, 0};
   if (k < n)
-    dust_packet<false, SOURCE>(g, d, src, opacity, seed, first + k, c, ev);
+    dust_packet<false, SOURCE, CAMERA>(g, d, src, cam, opacity, seed,
+                                       first + k, c, ev);
   /* the whole wave reaches the reduction (no early return above) */
   dust_count(&counters->nsteps, c.nsteps);
   dust_count(&counters->nscatter, c.nscatter);
@@ -173,6 +273,10 @@ __global__ void __launch_bounds__(256)
   dust_count(&counters->natomics, c.natomics);
   dust_count(&counters->npackets, c.npackets);
   dust_count(&counters->nsource_capped, c.nsource_capped);
+  if constexpr (CAMERA == DUST_CAMERA_POINT) {
+    dust_count(&counters->nexcluded, c.nexcluded);
+    dust_count(&counters->noutside, c.noutside);
+  }
 }
 
 enum {
@@ -181,15 +285,18 @@ enum {
   DUST_PROBE_SCATTER_TOWARDS = 2,
   DUST_PROBE_OPTICAL_DEPTH = 3,
   DUST_PROBE_TRACE = 4,
-  DUST_PROBE_CELL_SOURCE = 5
+  DUST_PROBE_CELL_SOURCE = 5,
+  DUST_PROBE_SKY_PEEL = 6
 };
 
 /* the parity probes of cmi_gpu_dust_probe (include/cmi_gpu.h gives the row
  * layouts); row k uses the stream of packet first + k. EMIT and TRACE follow
- * SOURCE; CELL_SOURCE exists in the cell source's instantiation only. */
-template <int SOURCE>
+ * SOURCE, TRACE follows CAMERA; CELL_SOURCE exists in the cell source's
+ * instantiations only, SKY_PEEL in the point camera's. */
+template <int SOURCE, int CAMERA>
 __global__ void __launch_bounds__(64)
     dust_probe_kernel(GridDev g, DustDev d, DustSource<SOURCE> src,
+                      DustCamera<CAMERA> cam,
                       const double2 *__restrict__ opacity, int32_t kind,
                       uint32_t seed, uint64_t first, int64_t n, int32_t width,
                       const double *__restrict__ in, double *__restrict__ out,
@@ -250,7 +357,8 @@ __global__ void __launch_bounds__(64)
     /* out: {nevents, nscatter, nsteps, ncapped, rows[max_events][8]} */
     DustCountersDev c = {};
     DustEvents ev = {o + 4, max_events, 0};
-    dust_packet<true, SOURCE>(g, d, src, opacity, seed, first + k, c, ev);
+    dust_packet<true, SOURCE, CAMERA>(g, d, src, cam, opacity, seed,
+                                      first + k, c, ev);
     o[0] = ev.n;
     o[1] = (double)c.nscatter;
     o[2] = (double)c.nsteps;
@@ -263,6 +371,38 @@ __global__ void __launch_bounds__(64)
       for (int a = 0; a < 3; ++a) {
         o[1 + a] = p.pos[a];
         o[4 + a] = p.dir[a];
+      }
+    }
+  } else if (kind == DUST_PROBE_SKY_PEEL) {
+    /* in: {pos[3], dir[3], sin theta, cos theta, phi, sin phi, cos phi, I, Q,
+     * U, V}; out: {hgfac, I, Q, U, V (rotated), r, tau, steps, pixel (-1:
+     * outside the window, -2: excluded, everything but r then 0)} */
+    if constexpr (CAMERA == DUST_CAMERA_POINT) {
+      const double *r = in + k * 15;
+      DustPhoton p;
+      for (int a = 0; a < 3; ++a)
+        p.pos[a] = r[a];
+      dust_set_direction(p, r + 3);
+      for (int j = 0; j < 5; ++j)
+        p.par[j] = r[6 + j];
+      for (int j = 0; j < 4; ++j)
+        p.stokes[j] = r[11 + j];
+      double kv[3], dist, dist2;
+      if (!dust_sky_direction(cam, p.pos, kv, dist, dist2)) {
+        o[5] = dist;
+        o[8] = -2.;
+      } else {
+        unsigned long long nsteps = 0;
+        o[0] = dust_scatter_towards_point(d, p, kv);
+        o[6] = dust_integrate_to(g, opacity, p.pos, p.dir, p.inv_dir, dist,
+                                 nsteps);
+        if (!cam.pole_is_z)
+          dust_sky_rotate(cam, kv, p.stokes);
+        for (int j = 0; j < 4; ++j)
+          o[1 + j] = p.stokes[j];
+        o[5] = dist;
+        o[7] = (double)nsteps;
+        o[8] = (double)dust_sky_pixel(cam, kv);
       }
     }
   }

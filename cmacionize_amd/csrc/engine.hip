@@ -242,6 +242,11 @@ struct cmi_gpu_engine {
   std::vector<double> cell_source_blocks_host;
   bool have_cell_source = false, cell_source_from_cells = false;
   uint64_t cells_epoch = 0, cell_source_epoch = 0;
+  /* the camera the peel-offs go to (have_ccd: one is set): the parallel
+   * camera's parameters are DustDev's, the point camera's these; dust_image
+   * is the image of whichever was set last */
+  int dust_camera = DUST_CAMERA_PARALLEL;
+  SkyCameraDev sky_camera = {};
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -2646,6 +2651,8 @@ int cmi_gpu_set_ccd_image(cmi_gpu_engine *e, double theta, double phi,
   const size_t bytes = 3 * (size_t)nx * ny * sizeof(double);
   HIP_TRY(hipMalloc(&e->dust_image, bytes));
   d.image = e->dust_image;
+  e->dust_camera = DUST_CAMERA_PARALLEL;
+  e->sky_camera.image = nullptr;
   e->have_ccd = true;
   return cmi_gpu_reset_image(e);
 }
@@ -2852,6 +2859,13 @@ int cmi_gpu_get_cell_source(cmi_gpu_engine *e, double *total_luminosity,
   return CMI_GPU_OK;
 }
 
+/* pixels of the selected camera's image */
+static size_t dust_image_pixels(const cmi_gpu_engine *e) {
+  return e->dust_camera == DUST_CAMERA_POINT
+             ? (size_t)e->sky_camera.nlon * e->sky_camera.nlat
+             : (size_t)e->dust.res[0] * e->dust.res[1];
+}
+
 /* everything a dust launch needs; builds the records {n kappa x_H, 0} or
  * {n sigma, 0} */
 static int dust_prepare(cmi_gpu_engine *e) {
@@ -2864,9 +2878,13 @@ static int dust_prepare(cmi_gpu_engine *e) {
   if (!e->have_cells || !e->have_dust_scattering || !e->have_ccd ||
       !have_source)
     return fail(CMI_GPU_ESTATE, "dust: upload_cells, set_dust_scattering, "
-                                "set_ccd_image and "
+                                "set_ccd_image (or set_sky_camera) and "
                                 "set_continuous_source_spiral_galaxy (or a "
                                 "cell source) first");
+  if (e->dust_camera == DUST_CAMERA_POINT &&
+      e->dust_source != DUST_SOURCE_CELLS)
+    return fail(CMI_GPU_ESTATE, "dust: the sky camera serves the cell source "
+                                "only, not the spiral galaxy");
   if (e->dust_source == DUST_SOURCE_CELLS && e->cell_source_from_cells &&
       e->cell_source_epoch != e->cells_epoch)
     return fail(CMI_GPU_ESTATE, "dust: the cells changed after the line "
@@ -2908,14 +2926,23 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
     EventPair ev;
     CMI_TRY(timer_begin(e, ev));
     const unsigned blocks = (unsigned)((chunk + 255) / 256);
-    if (e->dust_source == DUST_SOURCE_CELLS)
-      dust_shoot_kernel<DUST_SOURCE_CELLS><<<blocks, 256, 0, e->stream>>>(
-          e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
-          e->dust_counters, e->cell_source);
+    if (e->dust_camera == DUST_CAMERA_POINT)
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+              chunk, e->dust_counters, e->cell_source, e->sky_camera);
+    else if (e->dust_source == DUST_SOURCE_CELLS)
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+              chunk, e->dust_counters, e->cell_source,
+              DustCamera<DUST_CAMERA_PARALLEL>());
     else
-      dust_shoot_kernel<DUST_SOURCE_GALAXY><<<blocks, 256, 0, e->stream>>>(
-          e->grid, e->dust, e->dust_opacity, seed, first_packet + done, chunk,
-          e->dust_counters, DustSource<DUST_SOURCE_GALAXY>());
+      dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+              chunk, e->dust_counters, DustSource<DUST_SOURCE_GALAXY>(),
+              DustCamera<DUST_CAMERA_PARALLEL>());
     HIP_TRY(hipGetLastError());
     CMI_TRY(timer_end(e, e->shoot_events, ev, chunk));
     done += chunk;
@@ -2953,12 +2980,26 @@ int cmi_gpu_get_dust_counters(cmi_gpu_engine *e, uint64_t *counters) {
   return CMI_GPU_OK;
 }
 
+int cmi_gpu_get_sky_camera_counters(cmi_gpu_engine *e, uint64_t *counters) {
+  if (!e || !counters)
+    return fail(CMI_GPU_EINVAL, "get_sky_camera_counters: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  DustCountersDev c = {};
+  if (e->dust_counters)
+    HIP_TRY(hipMemcpy(&c, e->dust_counters, sizeof c, hipMemcpyDeviceToHost));
+  counters[0] = c.nexcluded;
+  counters[1] = c.noutside;
+  return CMI_GPU_OK;
+}
+
 int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
                            double *U) {
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
   if (!e->have_ccd)
-    return fail(CMI_GPU_ESTATE, "download_image: no image (set_ccd_image)");
+    return fail(CMI_GPU_ESTATE, "download_image: no image (set_ccd_image or "
+                                "set_sky_camera)");
   uint64_t c[6];
   CMI_TRY(cmi_gpu_get_dust_counters(e, c));
   if (c[5])
@@ -2971,7 +3012,7 @@ int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
                 "download_image: %llu packet(s) reached the cap of %d "
                 "scatterings; the image is incomplete",
                 (unsigned long long)c[2], CMI_DUST_MAX_SCATTER);
-  const size_t npixel = (size_t)e->dust.res[0] * e->dust.res[1];
+  const size_t npixel = dust_image_pixels(e);
   double *dst[3] = {I, Q, U};
   for (int k = 0; k < 3; ++k)
     if (dst[k])
@@ -2986,8 +3027,7 @@ int cmi_gpu_reset_image(cmi_gpu_engine *e) {
   HIP_TRY(hipSetDevice(e->device));
   if (e->dust_image)
     HIP_TRY(hipMemsetAsync(e->dust_image, 0,
-                           3 * (size_t)e->dust.res[0] * e->dust.res[1] *
-                               sizeof(double),
+                           3 * dust_image_pixels(e) * sizeof(double),
                            e->stream));
   if (e->dust_counters)
     HIP_TRY(hipMemsetAsync(e->dust_counters, 0, sizeof(DustCountersDev),
@@ -2999,21 +3039,24 @@ int cmi_gpu_reset_image(cmi_gpu_engine *e) {
 int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events) {
-  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_CELL_SOURCE ||
+  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_SKY_PEEL ||
       max_events < 0 || n > (1 << 24))
     return fail(CMI_GPU_EINVAL, "dust_probe: bad argument");
-  static const int in_width[6] = {0, 12, 12, 6, 0, 0};
+  static const int in_width[7] = {0, 12, 12, 6, 0, 0, 15};
   const int width = kind == DUST_PROBE_EMIT              ? 6
                     : kind == DUST_PROBE_SCATTER         ? 12
                     : kind == DUST_PROBE_SCATTER_TOWARDS ? 5
                     : kind == DUST_PROBE_OPTICAL_DEPTH   ? 2 + max_events
                     : kind == DUST_PROBE_CELL_SOURCE     ? 7
+                    : kind == DUST_PROBE_SKY_PEEL        ? 9
                                                          : 4 + 8 * max_events;
   if (in_width[kind] && !in)
     return fail(CMI_GPU_EINVAL, "dust_probe: input rows missing");
   CMI_TRY(dust_prepare(e));
   if (kind == DUST_PROBE_CELL_SOURCE && e->dust_source != DUST_SOURCE_CELLS)
     return fail(CMI_GPU_ESTATE, "dust_probe: no cell source is selected");
+  if (kind == DUST_PROBE_SKY_PEEL && e->dust_camera != DUST_CAMERA_POINT)
+    return fail(CMI_GPU_ESTATE, "dust_probe: no sky camera is selected");
   if (n == 0)
     return CMI_GPU_OK;
   double *din = nullptr, *dout = nullptr;
@@ -3033,15 +3076,24 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
     const unsigned blocks = (unsigned)((m + 63) / 64);
     const double *rows = din ? din + k * in_width[kind] : nullptr;
-    if (e->dust_source == DUST_SOURCE_CELLS)
-      dust_probe_kernel<DUST_SOURCE_CELLS><<<blocks, 64, 0, e->stream>>>(
-          e->grid, e->dust, e->cell_source, e->dust_opacity, kind, seed,
-          first_packet + k, m, width, rows, dout + k * width, max_events);
+    if (e->dust_camera == DUST_CAMERA_POINT)
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
+          <<<blocks, 64, 0, e->stream>>>(
+              e->grid, e->dust, e->cell_source, e->sky_camera, e->dust_opacity,
+              kind, seed, first_packet + k, m, width, rows, dout + k * width,
+              max_events);
+    else if (e->dust_source == DUST_SOURCE_CELLS)
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL>
+          <<<blocks, 64, 0, e->stream>>>(
+              e->grid, e->dust, e->cell_source,
+              DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
+              first_packet + k, m, width, rows, dout + k * width, max_events);
     else
-      dust_probe_kernel<DUST_SOURCE_GALAXY><<<blocks, 64, 0, e->stream>>>(
-          e->grid, e->dust, DustSource<DUST_SOURCE_GALAXY>(), e->dust_opacity,
-          kind, seed, first_packet + k, m, width, rows, dout + k * width,
-          max_events);
+      dust_probe_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL>
+          <<<blocks, 64, 0, e->stream>>>(
+              e->grid, e->dust, DustSource<DUST_SOURCE_GALAXY>(),
+              DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
+              first_packet + k, m, width, rows, dout + k * width, max_events);
     err = hipGetLastError();
     if (err == hipSuccess)
       err = hipStreamSynchronize(e->stream);
@@ -3674,6 +3726,80 @@ int cmi_gpu_render_line_sky_map(cmi_gpu_engine *e, int32_t nlines,
     for (size_t k = 0; k < npixel; ++k)
       maps[(size_t)l * npixel + (size_t)pixel[k]] = rays[(size_t)l * npixel + k];
   return CMI_GPU_OK;
+}
+
+int cmi_gpu_check_sky_camera(const double *box_anchor, const double *box_sides,
+                             const double *origin, const double *frame,
+                             double lon_min, double lon_max, double lat_min,
+                             double lat_max, int32_t nlon, int32_t nlat,
+                             double exclusion_radius) {
+  static const char *what = "set_sky_camera";
+  if (!box_anchor || !box_sides || !origin)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(origin[a]))
+      return fail(CMI_GPU_EINVAL, "%s: the origin is not finite", what);
+  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                        nlat));
+  /* (a Monte Carlo event must land in one pixel: no more than one turn) */
+  if (!(lon_max <= lon_min + 2. * M_PI))
+    return fail(CMI_GPU_EINVAL, "%s: the longitude range must not be wider "
+                "than 2 pi", what);
+  if (!(exclusion_radius >= 0.) || !std::isfinite(exclusion_radius))
+    return fail(CMI_GPU_EINVAL, "%s: the exclusion radius must be finite and "
+                ">= 0", what);
+  bool in_box = true;
+  for (int a = 0; a < 3; ++a)
+    in_box &= origin[a] >= box_anchor[a] &&
+              origin[a] <= box_anchor[a] + box_sides[a];
+  if (in_box && !(exclusion_radius > 0.))
+    return fail(CMI_GPU_EINVAL, "%s: an observer in the box needs an "
+                "exclusion radius above 0 (the estimator's 1 / r^2 diverges "
+                "at the observer)", what);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_sky_camera(cmi_gpu_engine *e, const double *origin,
+                           const double *frame, double lon_min, double lon_max,
+                           double lat_min, double lat_max, int32_t nlon,
+                           int32_t nlat, double exclusion_radius,
+                           int32_t direct_light) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "set_sky_camera: null engine");
+  CMI_TRY(cmi_gpu_check_sky_camera(e->grid.anchor, e->grid.box_sides, origin,
+                                   frame, lon_min, lon_max, lat_min, lat_max,
+                                   nlon, nlat, exclusion_radius));
+  HIP_TRY(hipSetDevice(e->device));
+  SkyCameraDev cam = {};
+  for (int a = 0; a < 3; ++a) {
+    cam.o[a] = origin[a];
+    cam.e1[a] = frame[a];
+    cam.e2[a] = frame[3 + a];
+    cam.e3[a] = frame[6 + a];
+  }
+  cam.lon_min = lon_min;
+  cam.lat_min = lat_min;
+  cam.lon_width = lon_max - lon_min;
+  cam.lat_width = lat_max - lat_min;
+  cam.nlon = nlon;
+  cam.nlat = nlat;
+  cam.r_min2 = exclusion_radius * exclusion_radius;
+  cam.pole_is_z = frame[6] == 0. && frame[7] == 0. && frame[8] == 1.;
+  cam.direct_light = direct_light != 0;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  /* no launch may see the old image once it is freed, whatever follows */
+  e->have_ccd = false;
+  (void)hipFree(e->dust_image);
+  e->dust_image = nullptr;
+  e->dust.image = nullptr;
+  e->sky_camera.image = nullptr;
+  HIP_TRY(hipMalloc(&e->dust_image,
+                    3 * (size_t)nlon * nlat * sizeof(double)));
+  cam.image = e->dust_image;
+  e->sky_camera = cam;
+  e->dust_camera = DUST_CAMERA_POINT;
+  e->have_ccd = true;
+  return cmi_gpu_reset_image(e);
 }
 
 } // extern "C"

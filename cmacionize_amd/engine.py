@@ -34,6 +34,7 @@ TABLE_LINEAR, TABLE_LOGLOG = 0, 1
 DUST_PROBE_EMIT, DUST_PROBE_SCATTER, DUST_PROBE_SCATTER_TOWARDS = 0, 1, 2
 DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
 DUST_PROBE_CELL_SOURCE = 5
+DUST_PROBE_SKY_PEEL = 6
 
 _dp = C.POINTER(C.c_double)
 
@@ -111,6 +112,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_line_sky", "cmi_gpu_render_field_sky",
     "cmi_gpu_sky_probe", "cmi_gpu_render_line_sky_map",
     "cmi_gpu_sky_map_directions",
+    "cmi_gpu_set_sky_camera", "cmi_gpu_check_sky_camera",
+    "cmi_gpu_get_sky_camera_counters",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -288,6 +291,13 @@ def load_library():
     L.cmi_gpu_sky_map_directions.argtypes = [
         _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
         C.c_int32, _dp, _dp]
+    L.cmi_gpu_set_sky_camera.argtypes = [
+        vp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double,
+        C.c_int32, C.c_int32, C.c_double, C.c_int32]
+    L.cmi_gpu_check_sky_camera.argtypes = [
+        _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double,
+        C.c_int32, C.c_int32, C.c_double]
+    L.cmi_gpu_get_sky_camera_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -329,6 +339,38 @@ def sky_map_directions(nlon, nlat, lon_range=FULL_SKY_LONGITUDE,
     if rc != 0:
         raise EngineError(L.cmi_gpu_last_error().decode())
     return d, omega
+
+
+def sky_frame(pole=(0., 0., 1.), zero_longitude=(1., 0., 0.)):
+    """The frame ((e_1, e_2, e_3) as rows) of a pole and a zero of longitude,
+    orthonormalised as the driver's EmissionSkyMaps block does: the pole is
+    kept, the zero of longitude is made perpendicular to it, e_2 = e_3 x e_1.
+    The default pole gives e_3 = (0, 0, 1) exactly."""
+    e3 = np.asarray(pole, dtype=np.float64)
+    zero = np.asarray(zero_longitude, dtype=np.float64)
+    e3 = e3 / np.sqrt(e3 @ e3)
+    e1 = zero - (zero @ e3) * e3
+    norm = np.sqrt(e1 @ e1)
+    if not norm > 1e-8 * np.sqrt(zero @ zero):
+        raise ValueError("the frame's pole and zero of longitude are parallel")
+    e1 = e1 / norm
+    return np.array([e1, np.cross(e3, e1), e3])
+
+
+def check_sky_camera(box_anchor, box_sides, origin, nlon, nlat,
+                     exclusion_radius, lon_range=FULL_SKY_LONGITUDE,
+                     lat_range=FULL_SKY_LATITUDE, frame=IDENTITY_FRAME):
+    """GpuEngine.set_sky_camera's argument checks for a box, run on the host
+    (cmi_gpu_check_sky_camera): raises EngineError as that call would."""
+    L = load_library()
+    rc = L.cmi_gpu_check_sky_camera(
+        _p(_f64(box_anchor).reshape(3)), _p(_f64(box_sides).reshape(3)),
+        _p(_f64(origin).reshape(3)), _p(_f64(frame).reshape(9)),
+        lon_range[0], lon_range[1], lat_range[0], lat_range[1], int(nlon),
+        int(nlat), exclusion_radius)
+    if rc != 0:
+        raise EngineError("cmi_gpu error %d: %s" % (
+            rc, L.cmi_gpu_last_error().decode()))
 
 
 def _p(a):
@@ -916,9 +958,10 @@ class GpuEngine:
                  DUST_PROBE_SCATTER_TOWARDS: 5,
                  DUST_PROBE_OPTICAL_DEPTH: 2 + max_events,
                  DUST_PROBE_TRACE: 4 + 8 * max_events,
-                 DUST_PROBE_CELL_SOURCE: 7}[kind]
+                 DUST_PROBE_CELL_SOURCE: 7, DUST_PROBE_SKY_PEEL: 9}[kind]
         in_width = {DUST_PROBE_SCATTER: 12, DUST_PROBE_SCATTER_TOWARDS: 12,
-                    DUST_PROBE_OPTICAL_DEPTH: 6}.get(kind, 0)
+                    DUST_PROBE_OPTICAL_DEPTH: 6,
+                    DUST_PROBE_SKY_PEEL: 15}.get(kind, 0)
         inp = None
         if in_width:
             inp = _f64(rows).reshape(n, in_width)
@@ -1057,6 +1100,64 @@ class GpuEngine:
             _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
             lat_range[1], int(nlon), int(nlat), dust_cross_section, _p(out)))
         return dict(zip(names, out))
+
+    def set_sky_camera(self, origin, nlon, nlat, exclusion_radius,
+                       lon_range=FULL_SKY_LONGITUDE,
+                       lat_range=FULL_SKY_LATITUDE, frame=IDENTITY_FRAME,
+                       direct_light=True):
+        """The peel-offs of dust_shoot go to an observer at `origin` into an
+        (nlon, nlat) map of the sky around it (include/cmi_gpu.h,
+        cmi_gpu_set_sky_camera); set_ccd_image selects the parallel camera
+        again."""
+        o = _f64(origin).reshape(3)
+        f = _f64(frame).reshape(9)
+        self._check(self._lib.cmi_gpu_set_sky_camera(
+            self._h, _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
+            lat_range[1], int(nlon), int(nlat), exclusion_radius,
+            int(bool(direct_light))))
+        self.image_shape = (int(nlon), int(nlat))
+
+    def get_sky_camera_counters(self):
+        c = (C.c_uint64 * 2)()
+        self._check(self._lib.cmi_gpu_get_sky_camera_counters(self._h, c))
+        return {"nexcluded": int(c[0]), "noutside": int(c[1])}
+
+    def render_scattered_line_sky_map(self, lines, origin, nlon, nlat,
+                                      npackets, seed, dust_cross_section,
+                                      albedo, g, p_l, exclusion_radius,
+                                      lon_range=FULL_SKY_LONGITUDE,
+                                      lat_range=FULL_SKY_LATITUDE,
+                                      frame_pole=(0., 0., 1.),
+                                      frame_zero_longitude=(1., 0., 0.),
+                                      direct_light=True):
+        """Monte Carlo sky maps of emission lines in direct and
+        dust-scattered light around an observer at `origin`: (nlines, 3,
+        nlon, nlat), I, Q and U in W m^-2 sr^-1, the pixels and the unit of
+        render_line_sky_map. Each line is one run of `npackets` packets from
+        the cells' emissivities through dust of `dust_cross_section` m^2 per
+        hydrogen nucleus, peeled off towards the observer with a weight
+        1 / r^2 (events nearer than `exclusion_radius` add nothing); the raw
+        image is scaled by L_total / (npackets omega_ij), omega_ij the exact
+        solid angles of sky_map_directions. At albedo 0 it is the ray-traced
+        map; with direct_light=False it is the scattered light alone, to be
+        added to the ray-traced map. Replaces the engine's camera, dust and
+        dust source."""
+        names = list(EMISSION_LINES if lines is None else lines)
+        frame = sky_frame(frame_pole, frame_zero_longitude)
+        self.set_dust_scattering_per_hydrogen(g, p_l, albedo,
+                                              dust_cross_section)
+        self.set_sky_camera(origin, nlon, nlat, exclusion_radius, lon_range,
+                            lat_range, frame, direct_light)
+        _, omega = sky_map_directions(nlon, nlat, lon_range, lat_range, frame)
+        omega = omega.reshape(int(nlon), int(nlat))
+        out = np.zeros((len(names), 3, int(nlon), int(nlat)))
+        for k, name in enumerate(names):
+            self.set_cell_source_line(name)
+            self.reset_image()
+            self.dust_shoot(seed, 0, int(npackets))
+            total = self.get_cell_source(tables=False)
+            out[k] = self.download_image() * (total / int(npackets)) / omega
+        return out
 
     def get_timing(self, reset=True):
         s = C.c_double()

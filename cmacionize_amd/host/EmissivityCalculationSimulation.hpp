@@ -52,6 +52,21 @@
  *   EmissionSkyMaps:dust cross section per hydrogen   0. m^2
  *   EmissionSkyMaps:type / filename prefix / output folder
  *                                                BinaryArray / sky_map / .
+ * With "EmissionSkyMaps:scattering: true" every flagged line is also shot as
+ * a Monte Carlo run peeled off towards the observer (cmi_gpu_set_sky_camera,
+ * cmi_gpu_set_cell_source_line, cmi_gpu_dust_shoot) through dust of the same
+ * cross section per hydrogen; I, Q and U are written next to the ray-traced
+ * map as <prefix>_<LineName>_scattered_I / _Q / _U, scaled by L_total /
+ * (packets x the pixel's solid angle) to W m^-2 sr^-1 like it. The longitude
+ * range may then not be wider than 360 degrees. Read only then:
+ *   EmissionSkyMaps:number of packets            1000000
+ *   EmissionSkyMaps:random seed                  42
+ *   EmissionSkyMaps:dust albedo / dust asymmetry / dust peak linear
+ *                    polarisation: required if the cross section is > 0
+ *   EmissionSkyMaps:exclusion radius             required, a length: events
+ *                    nearer to the observer than this add nothing
+ *   EmissionSkyMaps:direct light                 true (false: the scattered
+ *                    light alone, to be added to the ray-traced map)
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -172,6 +187,12 @@ class EmissivityCalculationSimulation {
     double frame[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
     double dust_cross_section = 0.;
     std::string type, prefix, folder;
+    /* scattered light (the keys below are read only if scattering is set) */
+    bool scattering = false, direct_light = true;
+    long long npackets = 1000000, seed = 42;
+    double albedo = 0., asymmetry = 0.5, polarisation = 0.;
+    double exclusion_radius = 0.;
+    double camera_lon_max = 0.; /* min(lon[1], lon[0] + 2 pi) */
 
     void read(ParameterFile &params) {
       if (!params.has_value("EmissionSkyMaps:observer position"))
@@ -256,6 +277,52 @@ class EmissivityCalculationSimulation {
         frame[3 + a] = e2[a];
         frame[6 + a] = e3[a];
       }
+      /* (a key that is read shows in the used-values: with the switch
+       * absent or off none of these is, the switch included) */
+      if (!params.peek_bool("EmissionSkyMaps:scattering"))
+        return;
+      scattering = params.get_bool("EmissionSkyMaps:scattering", false);
+      npackets = params.get_integer("EmissionSkyMaps:number of packets",
+                                    1000000);
+      seed = params.get_integer("EmissionSkyMaps:random seed", 42);
+      if (npackets <= 0)
+        throw ParameterError("EmissionSkyMaps:number of packets must be "
+                             "positive");
+      if (seed < 0 || seed > 0xffffffffll)
+        throw ParameterError("EmissionSkyMaps:random seed must fit 32 bits");
+      static const char *keys[3] = {
+          "EmissionSkyMaps:dust albedo", "EmissionSkyMaps:dust asymmetry",
+          "EmissionSkyMaps:dust peak linear polarisation"};
+      double *values[3] = {&albedo, &asymmetry, &polarisation};
+      for (int k = 0; k < 3; ++k) {
+        if (params.has_value(keys[k]))
+          *values[k] = params.get_double(keys[k], *values[k]);
+        else if (dust_cross_section > 0.)
+          throw ParameterError(std::string(keys[k]) +
+                               " is required for scattering off dust with a "
+                               "cross section above 0");
+      }
+      if (!(albedo >= 0. && albedo <= 1.))
+        throw ParameterError("EmissionSkyMaps:dust albedo must be in [0, 1]");
+      if (!(asymmetry != 0. && std::fabs(asymmetry) < 1.))
+        throw ParameterError("EmissionSkyMaps:dust asymmetry must be non-zero "
+                             "and inside (-1, 1)");
+      if (!params.has_value("EmissionSkyMaps:exclusion radius"))
+        throw ParameterError("EmissionSkyMaps:exclusion radius is required "
+                             "for scattering");
+      exclusion_radius = params.get_physical_value(
+          QUANTITY_LENGTH, "EmissionSkyMaps:exclusion radius", "0. m");
+      if (!(exclusion_radius >= 0.) || !std::isfinite(exclusion_radius))
+        throw ParameterError("EmissionSkyMaps:exclusion radius must be "
+                             "finite and not negative");
+      direct_light = params.get_bool("EmissionSkyMaps:direct light", true);
+      /* (360 degrees converted to radians may overshoot 2 pi by an ulp) */
+      if (lon[1] - lon[0] > 2. * M_PI * (1. + 1.e-12))
+        throw ParameterError("EmissionSkyMaps:longitude range must not be "
+                             "wider than 360 degrees with scattering");
+      /* the camera alone gets the clamped end: the ray-traced map keeps the
+       * range as converted, whatever the switch */
+      camera_lon_max = std::min(lon[1], lon[0] + 2. * M_PI);
     }
   };
 
@@ -542,6 +609,55 @@ public:
                 sky.folder + "/" + sky.prefix + "_" +
                     GpuIonizationSimulation::emission_line_name(lines[k]),
                 sky.type, maps.data() + k * npixel, sky.nlon, sky.nlat, 1.);
+        if (rc == CMI_GPU_OK && sky.scattering) {
+          status("Shooting the lines' packets towards the observer...");
+          std::vector<double> omega(npixel), iqu(3 * npixel);
+          rc = cmi_gpu_sky_map_directions(
+              sky.frame, sky.lon[0], sky.camera_lon_max, sky.lat[0], sky.lat[1],
+              (int32_t)sky.nlon, (int32_t)sky.nlat, nullptr, omega.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_dust_scattering_per_hydrogen(
+                engine, sky.asymmetry, sky.polarisation, sky.albedo,
+                sky.dust_cross_section);
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_sky_camera(
+                engine, sky.observer.data(), sky.frame, sky.lon[0],
+                sky.camera_lon_max, sky.lat[0], sky.lat[1], (int32_t)sky.nlon,
+                (int32_t)sky.nlat, sky.exclusion_radius, sky.direct_light ? 1 : 0);
+          for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
+            double total = 0.;
+            rc = cmi_gpu_set_cell_source_line(engine, lines[k]);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_reset_image(engine);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_dust_shoot(engine, (uint32_t)sky.seed, 0,
+                                      (uint64_t)sky.npackets);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
+            if (rc == CMI_GPU_OK)
+              rc = cmi_gpu_download_image(engine, iqu.data(),
+                                          iqu.data() + npixel,
+                                          iqu.data() + 2 * npixel);
+            if (rc != CMI_GPU_OK)
+              break;
+            /* W m^-2 sr^-1: x L_total / packets / the pixel's solid angle,
+             * in the order the Python call multiplies */
+            const double per_packet = total / (double)sky.npackets;
+            for (int j = 0; j < 3; ++j)
+              for (size_t i = 0; i < npixel; ++i)
+                iqu[j * npixel + i] = iqu[j * npixel + i] * per_packet /
+                                      omega[i];
+            static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
+                                            "_scattered_U"};
+            if (write_output)
+              for (int j = 0; j < 3; ++j)
+                written += " " + write_image(
+                    sky.folder + "/" + sky.prefix + "_" +
+                        GpuIonizationSimulation::emission_line_name(lines[k]) +
+                        stokes[j],
+                    sky.type, iqu.data() + j * npixel, sky.nlon, sky.nlat, 1.);
+          }
+        }
       }
       const std::string message = rc ? cmi_gpu_last_error() : "";
       cmi_gpu_destroy(engine);

@@ -928,11 +928,93 @@ int cmi_gpu_get_dust_counters(cmi_gpu_engine *engine, uint64_t *counters);
  *    each peel-off
  *  5 CELL_SOURCE (the cell source must be selected): out {cell, pos[3],
  *    dir[3]}
+ *  6 SKY_PEEL (the sky camera must be selected, CMI_GPU_ESTATE otherwise):
+ *    one peel-off of cmi_gpu_set_sky_camera's contract. in {pos[3], dir[3],
+ *    sin theta, cos theta, phi, sin phi, cos phi, I, Q, U, V}; out {hgfac,
+ *    I, Q, U, V after the rotation to the frame's pole, r, tau to the
+ *    observer, steps, pixel}; pixel is -1 outside the map's window and -2
+ *    inside the exclusion radius (everything but r is then 0)
  * EMIT and TRACE follow the selected source (a cell source always finds a
- * position). */
+ * position). TRACE follows the selected camera as well: with the sky camera
+ * a row's weight is the addend W / r^2 and its Stokes vector the rotated
+ * one; an event inside the exclusion radius gives a row of its position and
+ * zeros, and with the direct light switched off a packet's rows start at its
+ * first peel-off. */
 int cmi_gpu_dust_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events);
+
+/* The sky camera: the peel-offs of cmi_gpu_dust_shoot go to an observer at
+ * `origin` (m), inside or near the box, into an equirectangular map of I, Q,
+ * U: nlon x nlat pixels over [lon_min, lon_max] x [lat_min, lat_max]
+ * (radians) in the frame e_1, e_2, e_3 = the rows of frame[9], pixel (i, j)
+ * at i * nlat + j - the pixels of cmi_gpu_render_line_sky_map below. The
+ * call allocates and clears the image and selects this camera; a later
+ * cmi_gpu_set_ccd_image selects the parallel camera again (and this call
+ * replaces that one's image): cmi_gpu_dust_shoot, cmi_gpu_download_image
+ * ([nlon * nlat] per Stokes parameter), cmi_gpu_reset_image and
+ * cmi_gpu_get_dust_counters work on whichever camera was set last. Only the
+ * cell source has this camera: a shoot or probe with the spiral galaxy
+ * selected is CMI_GPU_ESTATE.
+ * The camera draws no random number: a packet's emission, optical depths and
+ * scatterings are those of the parallel camera for the same seed and id. Per
+ * event - the direct light at the emission point (skipped, with its march, if
+ * direct_light is 0), then every peel-off at a scattering point p:
+ *   v = origin - p, r2 = v . v, r = sqrt(r2), k = v / r (a division per
+ *   axis); the march uses 1 / k per axis.
+ *   r2 < exclusion_radius^2: the event adds nothing and is counted.
+ *   Optical depth to the observer, not to the box edge: the march of 3
+ *   OPTICAL_DEPTH from p along k with the travelled length s summed step by
+ *   step; the step with s + ds >= r adds (r - s) kappa and ends it. Towards
+ *   an observer outside the box the march leaves the grid first.
+ *   Scattering towards k: 2 SCATTER_TOWARDS with the observer's angles from
+ *   k: cos theta = k_z, sin theta = sqrt(max(1 - k_z^2, 0)), phi =
+ *   atan2(k_y, k_x) (0 where sin theta == 0), the skew in degrees.
+ *   Q and U come out referred to the meridian through k and the grid's z
+ *   axis. Unless e_3 is exactly (0, 0, 1) they are rotated to the meridian
+ *   through e_3 by twice the angle chi from N_z = z - (z . k) k to N_e =
+ *   e_3 - (e_3 . k) k (cos chi their normalised dot product, sin chi their
+ *   normalised triple product with k, chi = 0 where either vanishes):
+ *   Q' = Q cos 2 chi - U sin 2 chi, U' = Q sin 2 chi + U cos 2 chi.
+ *   Pixel of the sky direction n = -k: l = atan2(n . e_2, n . e_1), b =
+ *   asin(clamp(n . e_3)); x = l - lon_min wrapped into [0, 2 pi), inside if
+ *   x < lon_max - lon_min; y = b - lat_min, inside if 0 <= y <= lat_max -
+ *   lat_min; i = (int)(nlon x / width), j likewise, each clamped to its last
+ *   index (rounding just below the far edge; b == lat_max is in the last
+ *   row). Events outside the window are counted.
+ *   Addend: W / r2 times (I, Q, U), W = 0.25 exp(-tau) / pi for the direct
+ *   light and weight hgfac albedo exp(-tau) for a peel-off, the parallel
+ *   camera's weights; fp64 atomics, zero terms skipped.
+ * An unnormalised image x L_total / (packets x omega_ij), omega_ij the
+ * pixel's solid angle (cmi_gpu_sky_map_directions), is in W m^-2 sr^-1.
+ * CMI_GPU_EINVAL, nothing allocated or launched: an origin that is not
+ * finite; a frame not orthonormal to 1e-9; not lon_min < lon_max <= lon_min
+ * + 2 pi (an event must land in one pixel); latitudes as in
+ * cmi_gpu_render_line_sky_map; nlon, nlat < 1 or nlon nlat > 2^28; an
+ * exclusion radius that is negative or not finite, or 0 with the origin in
+ * the closed box (the estimator's variance diverges at r -> 0 and an event
+ * at r = 0 would add infinity). Synchronous. */
+int cmi_gpu_set_sky_camera(cmi_gpu_engine *engine, const double origin[3],
+                           const double frame[9], double lon_min,
+                           double lon_max, double lat_min, double lat_max,
+                           int32_t nlon, int32_t nlat, double exclusion_radius,
+                           int32_t direct_light);
+
+/* A validation helper, not part of a run: the argument checks of
+ * cmi_gpu_set_sky_camera for a box (host only, no engine, no device), so
+ * that drivers and tests can check a camera before an engine exists:
+ * CMI_GPU_OK or CMI_GPU_EINVAL with the message that call would give */
+int cmi_gpu_check_sky_camera(const double box_anchor[3],
+                             const double box_sides[3], const double origin[3],
+                             const double frame[9], double lon_min,
+                             double lon_max, double lat_min, double lat_max,
+                             int32_t nlon, int32_t nlat,
+                             double exclusion_radius);
+
+/* counters[2] = {events inside the exclusion radius, events outside the
+ * map's window} since the last reset. Synchronous. */
+int cmi_gpu_get_sky_camera_counters(cmi_gpu_engine *engine,
+                                    uint64_t *counters);
 
 /* ------------------------------------------------ emission-line images -- */
 /* Ray-traced line-of-sight maps of the grid: what an observer in the
