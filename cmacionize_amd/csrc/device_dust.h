@@ -113,7 +113,14 @@ typedef DustSource<DUST_SOURCE_CELLS> CellSourceDev;
 /* where the peel-off goes: template parameter of dust_packet and its kernels.
  * PARALLEL: the CCD image of an observer infinitely far away (DustDev's);
  * POINT: the sky map around an observer at a point */
-enum { DUST_CAMERA_PARALLEL = 0, DUST_CAMERA_POINT = 1 };
+enum {
+  DUST_CAMERA_PARALLEL = 0,
+  DUST_CAMERA_POINT = 1,
+  /* several cameras of one kind that share a packet's walk:
+   * descriptors in device memory, one image stack [view][3][pixels] */
+  DUST_CAMERA_PARALLEL_VIEWS = 2,
+  DUST_CAMERA_POINT_VIEWS = 3
+};
 
 /* what a camera reads beyond DustDev, a kernel argument of its own: nothing
  * for the parallel camera */
@@ -129,6 +136,46 @@ template <> struct DustCamera<DUST_CAMERA_POINT> {
   double *image;        /* [3][nlon * nlat]: I, Q, U */
 };
 typedef DustCamera<DUST_CAMERA_POINT> SkyCameraDev;
+
+/* one parallel view of DUST_CAMERA_PARALLEL_VIEWS: what cmi_gpu_set_ccd_image
+ * puts into DustDev for it (the resolution is shared, DustDev's) */
+struct DustViewDev {
+  double view[5];
+  double obs_dir[3];
+  double obs_inv_dir[3];
+  double img_anchor[2], img_sides[2];
+};
+
+/* one observer of DUST_CAMERA_POINT_VIEWS: what differs between the cameras
+ * (window, resolution and direct_light are shared) */
+struct SkyObserverDev {
+  double o[3];
+  double e1[3], e2[3], e3[3];
+  double r_min2;
+  int32_t pole_is_z;
+};
+
+/* per-view counters: DDA steps of the view's own marches, atomics into its
+ * image, events inside the exclusion radius, events outside the window. On
+ * the device each is spread over CMI_DUST_VIEW_SLOTS words, one per lane of a
+ * wave ([view][counter][slot]), so that a wave's addition is one atomic
+ * instruction to 64 different addresses; the host sums the slots. */
+#define CMI_DUST_VIEW_COUNTERS 4
+#define CMI_DUST_VIEW_SLOTS 64
+
+template <> struct DustCamera<DUST_CAMERA_PARALLEL_VIEWS> {
+  const DustViewDev *views; /* [nviews] */
+  int32_t nviews;
+  double *images;               /* [nviews][3][res[0] * res[1]] */
+  unsigned long long *counters; /* [nviews][4][CMI_DUST_VIEW_SLOTS] */
+};
+template <> struct DustCamera<DUST_CAMERA_POINT_VIEWS> {
+  SkyCameraDev shared; /* window, resolution, direct_light; the rest per view */
+  const SkyObserverDev *views; /* [nviews] */
+  int32_t nviews;
+  double *images;               /* [nviews][3][nlon * nlat] */
+  unsigned long long *counters; /* [nviews][4][CMI_DUST_VIEW_SLOTS] */
+};
 
 /* everything the dust kernels read, by value */
 struct DustDev {

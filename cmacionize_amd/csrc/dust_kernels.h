@@ -167,10 +167,72 @@ dust_sky_event(const GridDev &g, const DustDev &d, const SkyCameraDev &cam,
                       peel.stokes, addend, ev, c);
 }
 
+/* what one view's event added to the thread's counters since `before`, into
+ * the view's own (device_dust.h has the layout) */
+__device__ __forceinline__ void dust_view_count(unsigned long long *counters,
+                                                int v,
+                                                const DustCountersDev &before,
+                                                const DustCountersDev &c) {
+  unsigned long long *dst =
+      counters +
+      (size_t)v * CMI_DUST_VIEW_COUNTERS * CMI_DUST_VIEW_SLOTS +
+      threadIdx.x % CMI_DUST_VIEW_SLOTS;
+  const unsigned long long delta[CMI_DUST_VIEW_COUNTERS] = {
+      c.nsteps - before.nsteps, c.natomics - before.natomics,
+      c.nexcluded - before.nexcluded, c.noutside - before.noutside};
+#pragma unroll
+  for (int j = 0; j < CMI_DUST_VIEW_COUNTERS; ++j)
+    if (delta[j])
+      atomicAdd(dst + j * CMI_DUST_VIEW_SLOTS, delta[j]);
+}
+
+/* view v of the parallel views as the single camera's DustDev: dv is a copy
+ * of the kernel's d, of which only the camera's fields change */
+__device__ __forceinline__ void
+dust_select_view(const DustCamera<DUST_CAMERA_PARALLEL_VIEWS> &cam, int v,
+                 DustDev &dv) {
+  const DustViewDev &w = cam.views[v];
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    dv.view[j] = w.view[j];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    dv.obs_dir[a] = w.obs_dir[a];
+    dv.obs_inv_dir[a] = w.obs_inv_dir[a];
+  }
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    dv.img_anchor[a] = w.img_anchor[a];
+    dv.img_sides[a] = w.img_sides[a];
+  }
+  dv.image = cam.images + (size_t)v * 3 * ((size_t)dv.res[0] * dv.res[1]);
+}
+
+/* observer v of the point views as the single camera's SkyCameraDev: cv is a
+ * copy of cam.shared */
+__device__ __forceinline__ void
+dust_select_view(const DustCamera<DUST_CAMERA_POINT_VIEWS> &cam, int v,
+                 SkyCameraDev &cv) {
+  const SkyObserverDev &w = cam.views[v];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    cv.o[a] = w.o[a];
+    cv.e1[a] = w.e1[a];
+    cv.e2[a] = w.e2[a];
+    cv.e3[a] = w.e3[a];
+  }
+  cv.r_min2 = w.r_min2;
+  cv.pole_is_z = w.pole_is_z;
+  cv.image = cam.images + (size_t)v * 3 * ((size_t)cv.nlon * cv.nlat);
+}
+
 /* DustPhotonShootJob::execute for one packet; SOURCE selects where it
  * starts and CAMERA where its peel-offs go (at compile time: the galaxy's
  * instantiation has no trace of the other source, the parallel camera's
- * none of the point camera), everything else is the same */
+ * none of the point camera), everything else is the same. The two kinds with
+ * several views walk the same walk and repeat each event per view, in the
+ * order 0..K-1, through the single camera's functions with the single
+ * camera's expressions: an addend is the single camera's addend. */
 template <bool TRACE, int SOURCE, int CAMERA>
 __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
                                    const DustSource<SOURCE> &src,
@@ -191,8 +253,39 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
     }
   }
 
+  /* the single camera that the current view is handed to the camera's
+   * functions as (several views only; unused and gone otherwise) */
+  DustDev dv;
+  SkyCameraDev cv;
+  if constexpr (CAMERA == DUST_CAMERA_PARALLEL_VIEWS)
+    dv = d;
+  if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS)
+    cv = cam.shared;
+
   /* direct light towards the observer, :127-130 */
-  if constexpr (CAMERA == DUST_CAMERA_POINT) {
+  if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
+    if (cam.shared.direct_light) {
+      for (int v = 0; v < cam.nviews; ++v) {
+        dust_select_view(cam, v, cv);
+        const DustCountersDev before = c;
+        DustPhoton direct = p;
+        dust_sky_event<TRACE>(g, d, cv, opacity, direct, false, 1., 1., c, ev);
+        dust_view_count(cam.counters, v, before, c);
+      }
+    }
+  } else if constexpr (CAMERA == DUST_CAMERA_PARALLEL_VIEWS) {
+    for (int v = 0; v < cam.nviews; ++v) {
+      dust_select_view(cam, v, dv);
+      const DustCountersDev before = c;
+      const double tau_old = dust_integrate(g, opacity, p.pos, dv.obs_dir,
+                                            dv.obs_inv_dir, c.nsteps);
+      const double w_direct = 0.25 * exp(-tau_old) / M_PI;
+      const double unpolarised[4] = {1., 0., 0., 0.};
+      dust_add<TRACE>(dv, p.pos, w_direct, 0., 0., unpolarised, w_direct, ev,
+                      c.natomics);
+      dust_view_count(cam.counters, v, before, c);
+    }
+  } else if constexpr (CAMERA == DUST_CAMERA_POINT) {
     if (cam.direct_light) {
       DustPhoton direct = p;
       dust_sky_event<TRACE>(g, d, cam, opacity, direct, false, 1., 1., c, ev);
@@ -217,7 +310,33 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   while (inside) {
     /* peel-off, :141-155 */
     DustPhoton peel = p;
-    if constexpr (CAMERA == DUST_CAMERA_POINT) {
+    if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
+      albedo *= d.albedo;
+      for (int v = 0; v < cam.nviews; ++v) {
+        dust_select_view(cam, v, cv);
+        const DustCountersDev before = c;
+        peel = p;
+        dust_sky_event<TRACE>(g, d, cv, opacity, peel, true, weight, albedo, c,
+                              ev);
+        dust_view_count(cam.counters, v, before, c);
+      }
+    } else if constexpr (CAMERA == DUST_CAMERA_PARALLEL_VIEWS) {
+      albedo *= d.albedo;
+      for (int v = 0; v < cam.nviews; ++v) {
+        dust_select_view(cam, v, dv);
+        const DustCountersDev before = c;
+        peel = p;
+        const double hgfac = dust_scatter_towards(dv, peel);
+        const double tau_new = dust_integrate(g, opacity, peel.pos, peel.dir,
+                                              peel.inv_dir, c.nsteps);
+        const double weight_new = weight * hgfac * albedo * exp(-tau_new);
+        dust_add<TRACE>(dv, peel.pos, weight_new * peel.stokes[0],
+                        weight_new * peel.stokes[1],
+                        weight_new * peel.stokes[2], peel.stokes, weight_new,
+                        ev, c.natomics);
+        dust_view_count(cam.counters, v, before, c);
+      }
+    } else if constexpr (CAMERA == DUST_CAMERA_POINT) {
       albedo *= d.albedo;
       dust_sky_event<TRACE>(g, d, cam, opacity, peel, true, weight, albedo, c,
                             ev);
@@ -273,7 +392,8 @@ __global__ void __launch_bounds__(256)
   dust_count(&counters->natomics, c.natomics);
   dust_count(&counters->npackets, c.npackets);
   dust_count(&counters->nsource_capped, c.nsource_capped);
-  if constexpr (CAMERA == DUST_CAMERA_POINT) {
+  if constexpr (CAMERA == DUST_CAMERA_POINT ||
+                CAMERA == DUST_CAMERA_POINT_VIEWS) {
     dust_count(&counters->nexcluded, c.nexcluded);
     dust_count(&counters->noutside, c.noutside);
   }

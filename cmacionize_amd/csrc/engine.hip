@@ -247,6 +247,17 @@ struct cmi_gpu_engine {
    * is the image of whichever was set last */
   int dust_camera = DUST_CAMERA_PARALLEL;
   SkyCameraDev sky_camera = {};
+  /* several views in one run (DUST_CAMERA_PARALLEL_VIEWS, DUST_CAMERA_POINT_
+   * VIEWS; dust_nviews is 1 with a single camera): the descriptors on the
+   * host and on the device, the per-view counters [nviews][4][slots], the
+   * view the camera-dependent probes follow. dust_image is then the stack
+   * [nviews][3][pixels]; dust (view 0's fields) and sky_camera (origin and
+   * frame of observer 0) carry what the views share. */
+  int32_t dust_nviews = 1, dust_probe_view = 0;
+  std::vector<DustViewDev> dust_views;
+  std::vector<SkyObserverDev> sky_views;
+  void *dust_views_dev = nullptr;
+  unsigned long long *dust_view_counters = nullptr;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1136,6 +1147,8 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->tile_counts);
   (void)hipFree(e->launch_steps);
   (void)hipFree(e->dust_image);
+  (void)hipFree(e->dust_views_dev);
+  (void)hipFree(e->dust_view_counters);
   (void)hipFree(e->dust_cdf);
   (void)hipFree(e->dust_opacity);
   (void)hipFree(e->dust_counters);
@@ -2577,6 +2590,17 @@ int cmi_gpu_get_kernel_timing(cmi_gpu_engine *e, double *kernel_ms,
 #define CMI_DUST_MIN_LAUNCH 64ull
 #define CMI_DUST_MAX_LAUNCH (1ull << 20)
 #define CMI_DUST_STEPS_PER_LAUNCH (1ull << 29)
+/* With several views a packet takes K times the peel-off marches, and sized
+ * by steps alone a launch soon holds fewer packets than the device has lanes
+ * for (at K = 16 about 1e5 against 256 CUs x 512 lanes: measured at 0.6 of
+ * the single camera's steps/s). Such a launch is no shorter
+ * for being smaller - its lanes run side by side and it lasts as long as its
+ * longest packets -, so these kinds are not sized below CMI_DUST_VIEWS_FILLS
+ * times the lanes the device holds at once: CMI_DUST_VIEWS_LANES_PER_CU per
+ * CU, 4 SIMDs x 2 waves (the kernels' 170 to 212 VGPRs) x 64 lanes. The
+ * single camera's sizing is as it was. */
+#define CMI_DUST_VIEWS_LANES_PER_CU 512ull
+#define CMI_DUST_VIEWS_FILLS 4ull
 /* rows per dust_probe_kernel launch */
 #define CMI_DUST_PROBE_LAUNCH (1ll << 14)
 
@@ -2617,6 +2641,80 @@ int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *e, double g,
   return CMI_GPU_OK;
 }
 
+/* the views' descriptors and counters go with a camera that is replaced */
+static void dust_free_views(cmi_gpu_engine *e) {
+  (void)hipFree(e->dust_views_dev);
+  (void)hipFree(e->dust_view_counters);
+  e->dust_views_dev = nullptr;
+  e->dust_view_counters = nullptr;
+  e->dust_views.clear();
+  e->sky_views.clear();
+  e->dust_nviews = 1;
+  e->dust_probe_view = 0;
+}
+
+/* the camera's part of DustDev, view by view */
+static void dust_put_view(DustDev &d, const DustViewDev &v) {
+  for (int j = 0; j < 5; ++j)
+    d.view[j] = v.view[j];
+  for (int a = 0; a < 3; ++a) {
+    d.obs_dir[a] = v.obs_dir[a];
+    d.obs_inv_dir[a] = v.obs_inv_dir[a];
+  }
+  for (int a = 0; a < 2; ++a) {
+    d.img_anchor[a] = v.img_anchor[a];
+    d.img_sides[a] = v.img_sides[a];
+  }
+}
+
+/* the same for an observer of the point camera */
+static void sky_put_observer(SkyCameraDev &cam, const SkyObserverDev &v) {
+  for (int a = 0; a < 3; ++a) {
+    cam.o[a] = v.o[a];
+    cam.e1[a] = v.e1[a];
+    cam.e2[a] = v.e2[a];
+    cam.e3[a] = v.e3[a];
+  }
+  cam.r_min2 = v.r_min2;
+  cam.pole_is_z = v.pole_is_z;
+}
+
+static SkyObserverDev sky_make_observer(const double *origin,
+                                        const double *frame,
+                                        double exclusion_radius) {
+  SkyObserverDev v;
+  for (int a = 0; a < 3; ++a) {
+    v.o[a] = origin[a];
+    v.e1[a] = frame[a];
+    v.e2[a] = frame[3 + a];
+    v.e3[a] = frame[6 + a];
+  }
+  v.r_min2 = exclusion_radius * exclusion_radius;
+  v.pole_is_z = frame[6] == 0. && frame[7] == 0. && frame[8] == 1.;
+  return v;
+}
+
+/* CCDImage ctor, src/CCDImage.hpp:123-160 */
+static DustViewDev dust_make_view(double theta, double phi,
+                                  const double *anchor, const double *sides) {
+  DustViewDev v;
+  v.view[0] = std::sin(theta);
+  v.view[1] = std::cos(theta);
+  v.view[2] = phi;
+  v.view[3] = std::sin(phi);
+  v.view[4] = std::cos(phi);
+  v.obs_dir[0] = v.view[0] * v.view[4];
+  v.obs_dir[1] = v.view[0] * v.view[3];
+  v.obs_dir[2] = v.view[1];
+  for (int a = 0; a < 3; ++a)
+    v.obs_inv_dir[a] = 1. / v.obs_dir[a];
+  for (int a = 0; a < 2; ++a) {
+    v.img_anchor[a] = anchor[a];
+    v.img_sides[a] = sides[a];
+  }
+  return v;
+}
+
 int cmi_gpu_set_ccd_image(cmi_gpu_engine *e, double theta, double phi,
                           int32_t nx, int32_t ny, const double *anchor,
                           const double *sides) {
@@ -2624,35 +2722,114 @@ int cmi_gpu_set_ccd_image(cmi_gpu_engine *e, double theta, double phi,
       !(sides[1] > 0.) || (int64_t)nx * ny > (1ll << 28))
     return fail(CMI_GPU_EINVAL, "set_ccd_image: bad argument");
   HIP_TRY(hipSetDevice(e->device));
-  /* CCDImage ctor, src/CCDImage.hpp:123-160 */
   DustDev &d = e->dust;
-  d.view[0] = std::sin(theta);
-  d.view[1] = std::cos(theta);
-  d.view[2] = phi;
-  d.view[3] = std::sin(phi);
-  d.view[4] = std::cos(phi);
-  d.obs_dir[0] = d.view[0] * d.view[4];
-  d.obs_dir[1] = d.view[0] * d.view[3];
-  d.obs_dir[2] = d.view[1];
-  for (int a = 0; a < 3; ++a)
-    d.obs_inv_dir[a] = 1. / d.obs_dir[a];
+  dust_put_view(d, dust_make_view(theta, phi, anchor, sides));
   d.res[0] = nx;
   d.res[1] = ny;
-  for (int a = 0; a < 2; ++a) {
-    d.img_anchor[a] = anchor[a];
-    d.img_sides[a] = sides[a];
-  }
   HIP_TRY(hipStreamSynchronize(e->stream));
   /* no launch may see the old image once it is freed, whatever follows */
   e->have_ccd = false;
   (void)hipFree(e->dust_image);
   e->dust_image = nullptr;
   d.image = nullptr;
+  dust_free_views(e);
   const size_t bytes = 3 * (size_t)nx * ny * sizeof(double);
   HIP_TRY(hipMalloc(&e->dust_image, bytes));
   d.image = e->dust_image;
   e->dust_camera = DUST_CAMERA_PARALLEL;
   e->sky_camera.image = nullptr;
+  e->have_ccd = true;
+  return cmi_gpu_reset_image(e);
+}
+
+/* the stack, the descriptors and the counters of a camera with several
+ * views, allocated before anything of the engine changes: a call that fails
+ * here leaves the camera that was selected */
+extern "C++" {
+namespace {
+struct DustViewBuffers {
+  double *images = nullptr;
+  void *views = nullptr;
+  unsigned long long *counters = nullptr;
+  ~DustViewBuffers() {
+    (void)hipFree(images);
+    (void)hipFree(views);
+    (void)hipFree(counters);
+  }
+};
+} // namespace
+}
+
+static int dust_alloc_views(const char *what, int32_t nviews, size_t npixel,
+                            const void *views, size_t view_bytes,
+                            DustViewBuffers &b) {
+  hipError_t err = hipMalloc(&b.images, (size_t)nviews * 3 * npixel *
+                                            sizeof(double));
+  if (err == hipSuccess)
+    err = hipMalloc(&b.views, (size_t)nviews * view_bytes);
+  if (err == hipSuccess)
+    err = hipMalloc(&b.counters, (size_t)nviews * CMI_DUST_VIEW_COUNTERS *
+                                     CMI_DUST_VIEW_SLOTS *
+                                     sizeof(unsigned long long));
+  if (err == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    return fail(CMI_GPU_ENOMEM, "%s: the stack of %d images of %zu pixels "
+                "does not fit into the device's memory", what, (int)nviews,
+                npixel);
+  }
+  HIP_TRY(err);
+  HIP_TRY(hipMemcpy(b.views, views, (size_t)nviews * view_bytes,
+                    hipMemcpyHostToDevice));
+  return CMI_GPU_OK;
+}
+
+/* the engine takes the buffers over from b */
+static void dust_adopt_views(cmi_gpu_engine *e, int32_t nviews,
+                             DustViewBuffers &b) {
+  e->have_ccd = false;
+  (void)hipFree(e->dust_image);
+  dust_free_views(e);
+  e->dust_image = b.images;
+  e->dust_views_dev = b.views;
+  e->dust_view_counters = b.counters;
+  b.images = nullptr;
+  b.views = nullptr;
+  b.counters = nullptr;
+  e->dust_nviews = nviews;
+}
+
+int cmi_gpu_set_ccd_images(cmi_gpu_engine *e, int32_t nviews,
+                           const double *theta, const double *phi, int32_t nx,
+                           int32_t ny, const double *anchors,
+                           const double *sides) {
+  if (!e || !theta || !phi || !anchors || !sides || nx <= 0 || ny <= 0 ||
+      (int64_t)nx * ny > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "set_ccd_images: bad argument");
+  if (nviews < 1 || nviews > CMI_GPU_MAX_VIEWS)
+    return fail(CMI_GPU_EINVAL, "set_ccd_images: %d views, must be 1 to %d",
+                (int)nviews, CMI_GPU_MAX_VIEWS);
+  std::vector<DustViewDev> views;
+  for (int32_t v = 0; v < nviews; ++v) {
+    if (!(sides[2 * v] > 0.) || !(sides[2 * v + 1] > 0.))
+      return fail(CMI_GPU_EINVAL, "set_ccd_images: view %d: bad argument (the "
+                  "sides must be > 0)", (int)v);
+    views.push_back(
+        dust_make_view(theta[v], phi[v], anchors + 2 * v, sides + 2 * v));
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  DustViewBuffers b;
+  CMI_TRY(dust_alloc_views("set_ccd_images", nviews, (size_t)nx * ny,
+                           views.data(), sizeof(DustViewDev), b));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  dust_adopt_views(e, nviews, b);
+  DustDev &d = e->dust;
+  dust_put_view(d, views[0]);
+  d.res[0] = nx;
+  d.res[1] = ny;
+  d.image = e->dust_image;
+  e->dust_views = views;
+  e->sky_camera.image = nullptr;
+  e->dust_camera = DUST_CAMERA_PARALLEL_VIEWS;
   e->have_ccd = true;
   return cmi_gpu_reset_image(e);
 }
@@ -2859,9 +3036,19 @@ int cmi_gpu_get_cell_source(cmi_gpu_engine *e, double *total_luminosity,
   return CMI_GPU_OK;
 }
 
-/* pixels of the selected camera's image */
+static bool dust_point_camera(const cmi_gpu_engine *e) {
+  return e->dust_camera == DUST_CAMERA_POINT ||
+         e->dust_camera == DUST_CAMERA_POINT_VIEWS;
+}
+
+static bool dust_several_views(const cmi_gpu_engine *e) {
+  return e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS ||
+         e->dust_camera == DUST_CAMERA_POINT_VIEWS;
+}
+
+/* pixels of one image of the selected camera */
 static size_t dust_image_pixels(const cmi_gpu_engine *e) {
-  return e->dust_camera == DUST_CAMERA_POINT
+  return dust_point_camera(e)
              ? (size_t)e->sky_camera.nlon * e->sky_camera.nlat
              : (size_t)e->dust.res[0] * e->dust.res[1];
 }
@@ -2878,11 +3065,11 @@ static int dust_prepare(cmi_gpu_engine *e) {
   if (!e->have_cells || !e->have_dust_scattering || !e->have_ccd ||
       !have_source)
     return fail(CMI_GPU_ESTATE, "dust: upload_cells, set_dust_scattering, "
-                                "set_ccd_image (or set_sky_camera) and "
+                                "a camera (set_ccd_image, set_sky_camera or "
+                                "their several views) and "
                                 "set_continuous_source_spiral_galaxy (or a "
                                 "cell source) first");
-  if (e->dust_camera == DUST_CAMERA_POINT &&
-      e->dust_source != DUST_SOURCE_CELLS)
+  if (dust_point_camera(e) && e->dust_source != DUST_SOURCE_CELLS)
     return fail(CMI_GPU_ESTATE, "dust: the sky camera serves the cell source "
                                 "only, not the spiral galaxy");
   if (e->dust_source == DUST_SOURCE_CELLS && e->cell_source_from_cells &&
@@ -2913,6 +3100,12 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
                        uint64_t n) {
   CMI_TRY(dust_prepare(e));
   uint64_t size = CMI_DUST_FIRST_LAUNCH;
+  const uint64_t min_launch =
+      dust_several_views(e)
+          ? std::max<uint64_t>(CMI_DUST_MIN_LAUNCH,
+                               CMI_DUST_VIEWS_FILLS * (uint64_t)e->num_cu *
+                                   CMI_DUST_VIEWS_LANES_PER_CU)
+          : CMI_DUST_MIN_LAUNCH;
   for (uint64_t done = 0; done < n;) {
     const uint64_t chunk = std::min<uint64_t>(n - done, size);
     /* only a launch that another follows is measured: both copies are
@@ -2926,7 +3119,35 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
     EventPair ev;
     CMI_TRY(timer_begin(e, ev));
     const unsigned blocks = (unsigned)((chunk + 255) / 256);
-    if (e->dust_camera == DUST_CAMERA_POINT)
+    if (e->dust_camera == DUST_CAMERA_POINT_VIEWS) {
+      DustCamera<DUST_CAMERA_POINT_VIEWS> cam;
+      cam.shared = e->sky_camera;
+      cam.views = (const SkyObserverDev *)e->dust_views_dev;
+      cam.nviews = e->dust_nviews;
+      cam.images = e->dust_image;
+      cam.counters = e->dust_view_counters;
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT_VIEWS>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+              chunk, e->dust_counters, e->cell_source, cam);
+    } else if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS) {
+      DustCamera<DUST_CAMERA_PARALLEL_VIEWS> cam;
+      cam.views = (const DustViewDev *)e->dust_views_dev;
+      cam.nviews = e->dust_nviews;
+      cam.images = e->dust_image;
+      cam.counters = e->dust_view_counters;
+      if (e->dust_source == DUST_SOURCE_CELLS)
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL_VIEWS>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, e->cell_source, cam);
+      else
+        dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL_VIEWS>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, DustSource<DUST_SOURCE_GALAXY>(),
+                cam);
+    } else if (e->dust_camera == DUST_CAMERA_POINT)
       dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
@@ -2956,7 +3177,7 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
           std::max(1., (double)(steps_after - steps_before) / (double)chunk);
       size = (uint64_t)std::min<double>(
           (double)CMI_DUST_MAX_LAUNCH,
-          std::max<double>((double)CMI_DUST_MIN_LAUNCH,
+          std::max<double>((double)min_launch,
                            (double)CMI_DUST_STEPS_PER_LAUNCH / per_packet));
     }
   }
@@ -2995,6 +3216,11 @@ int cmi_gpu_get_sky_camera_counters(cmi_gpu_engine *e, uint64_t *counters) {
 
 int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
                            double *U) {
+  return cmi_gpu_download_image_view(e, 0, I, Q, U);
+}
+
+int cmi_gpu_download_image_view(cmi_gpu_engine *e, int32_t view, double *I,
+                                double *Q, double *U) {
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
   if (!e->have_ccd)
@@ -3012,11 +3238,14 @@ int cmi_gpu_download_image(cmi_gpu_engine *e, double *I, double *Q,
                 "download_image: %llu packet(s) reached the cap of %d "
                 "scatterings; the image is incomplete",
                 (unsigned long long)c[2], CMI_DUST_MAX_SCATTER);
+  if (view < 0 || view >= e->dust_nviews)
+    return fail(CMI_GPU_EINVAL, "download_image_view: view %d of %d",
+                (int)view, (int)e->dust_nviews);
   const size_t npixel = dust_image_pixels(e);
   double *dst[3] = {I, Q, U};
   for (int k = 0; k < 3; ++k)
     if (dst[k])
-      HIP_TRY(hipMemcpy(dst[k], e->dust_image + k * npixel,
+      HIP_TRY(hipMemcpy(dst[k], e->dust_image + (3 * (size_t)view + k) * npixel,
                         npixel * sizeof(double), hipMemcpyDeviceToHost));
   return CMI_GPU_OK;
 }
@@ -3027,12 +3256,58 @@ int cmi_gpu_reset_image(cmi_gpu_engine *e) {
   HIP_TRY(hipSetDevice(e->device));
   if (e->dust_image)
     HIP_TRY(hipMemsetAsync(e->dust_image, 0,
-                           3 * dust_image_pixels(e) * sizeof(double),
+                           (size_t)e->dust_nviews * 3 * dust_image_pixels(e) *
+                               sizeof(double),
+                           e->stream));
+  if (e->dust_view_counters)
+    HIP_TRY(hipMemsetAsync(e->dust_view_counters, 0,
+                           (size_t)e->dust_nviews * CMI_DUST_VIEW_COUNTERS *
+                               CMI_DUST_VIEW_SLOTS *
+                               sizeof(unsigned long long),
                            e->stream));
   if (e->dust_counters)
     HIP_TRY(hipMemsetAsync(e->dust_counters, 0, sizeof(DustCountersDev),
                            e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_get_dust_view_counters(cmi_gpu_engine *e, int32_t view,
+                                   uint64_t *counters) {
+  if (!e || !counters)
+    return fail(CMI_GPU_EINVAL, "get_dust_view_counters: bad argument");
+  if (!e->have_ccd || !dust_several_views(e))
+    return fail(CMI_GPU_ESTATE, "get_dust_view_counters: no camera with "
+                                "several views is selected (set_ccd_images "
+                                "or set_sky_cameras)");
+  if (view < 0 || view >= e->dust_nviews)
+    return fail(CMI_GPU_EINVAL, "get_dust_view_counters: view %d of %d",
+                (int)view, (int)e->dust_nviews);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  unsigned long long slots[CMI_DUST_VIEW_COUNTERS][CMI_DUST_VIEW_SLOTS];
+  HIP_TRY(hipMemcpy(slots,
+                    e->dust_view_counters + (size_t)view *
+                                                CMI_DUST_VIEW_COUNTERS *
+                                                CMI_DUST_VIEW_SLOTS,
+                    sizeof slots, hipMemcpyDeviceToHost));
+  for (int j = 0; j < CMI_DUST_VIEW_COUNTERS; ++j) {
+    counters[j] = 0;
+    for (int k = 0; k < CMI_DUST_VIEW_SLOTS; ++k)
+      counters[j] += slots[j][k];
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_select_probe_view(cmi_gpu_engine *e, int32_t view) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (!e->have_ccd)
+    return fail(CMI_GPU_ESTATE, "select_probe_view: no camera is set");
+  if (view < 0 || view >= e->dust_nviews)
+    return fail(CMI_GPU_EINVAL, "select_probe_view: view %d of %d", (int)view,
+                (int)e->dust_nviews);
+  e->dust_probe_view = view;
   return CMI_GPU_OK;
 }
 
@@ -3055,8 +3330,17 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
   CMI_TRY(dust_prepare(e));
   if (kind == DUST_PROBE_CELL_SOURCE && e->dust_source != DUST_SOURCE_CELLS)
     return fail(CMI_GPU_ESTATE, "dust_probe: no cell source is selected");
-  if (kind == DUST_PROBE_SKY_PEEL && e->dust_camera != DUST_CAMERA_POINT)
+  if (kind == DUST_PROBE_SKY_PEEL && !dust_point_camera(e))
     return fail(CMI_GPU_ESTATE, "dust_probe: no sky camera is selected");
+  /* with several views the probes run the single camera's kernels for the
+   * selected view, so a row is the single camera's row (a trace writes to no
+   * image) */
+  DustDev dust = e->dust;
+  SkyCameraDev sky_camera = e->sky_camera;
+  if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
+    dust_put_view(dust, e->dust_views[e->dust_probe_view]);
+  if (e->dust_camera == DUST_CAMERA_POINT_VIEWS)
+    sky_put_observer(sky_camera, e->sky_views[e->dust_probe_view]);
   if (n == 0)
     return CMI_GPU_OK;
   double *din = nullptr, *dout = nullptr;
@@ -3076,22 +3360,22 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
     const unsigned blocks = (unsigned)((m + 63) / 64);
     const double *rows = din ? din + k * in_width[kind] : nullptr;
-    if (e->dust_camera == DUST_CAMERA_POINT)
+    if (dust_point_camera(e))
       dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
           <<<blocks, 64, 0, e->stream>>>(
-              e->grid, e->dust, e->cell_source, e->sky_camera, e->dust_opacity,
+              e->grid, dust, e->cell_source, sky_camera, e->dust_opacity,
               kind, seed, first_packet + k, m, width, rows, dout + k * width,
               max_events);
     else if (e->dust_source == DUST_SOURCE_CELLS)
       dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL>
           <<<blocks, 64, 0, e->stream>>>(
-              e->grid, e->dust, e->cell_source,
+              e->grid, dust, e->cell_source,
               DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
               first_packet + k, m, width, rows, dout + k * width, max_events);
     else
       dust_probe_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL>
           <<<blocks, 64, 0, e->stream>>>(
-              e->grid, e->dust, DustSource<DUST_SOURCE_GALAXY>(),
+              e->grid, dust, DustSource<DUST_SOURCE_GALAXY>(),
               DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
               first_packet + k, m, width, rows, dout + k * width, max_events);
     err = hipGetLastError();
@@ -3771,26 +4055,20 @@ int cmi_gpu_set_sky_camera(cmi_gpu_engine *e, const double *origin,
                                    nlon, nlat, exclusion_radius));
   HIP_TRY(hipSetDevice(e->device));
   SkyCameraDev cam = {};
-  for (int a = 0; a < 3; ++a) {
-    cam.o[a] = origin[a];
-    cam.e1[a] = frame[a];
-    cam.e2[a] = frame[3 + a];
-    cam.e3[a] = frame[6 + a];
-  }
+  sky_put_observer(cam, sky_make_observer(origin, frame, exclusion_radius));
   cam.lon_min = lon_min;
   cam.lat_min = lat_min;
   cam.lon_width = lon_max - lon_min;
   cam.lat_width = lat_max - lat_min;
   cam.nlon = nlon;
   cam.nlat = nlat;
-  cam.r_min2 = exclusion_radius * exclusion_radius;
-  cam.pole_is_z = frame[6] == 0. && frame[7] == 0. && frame[8] == 1.;
   cam.direct_light = direct_light != 0;
   HIP_TRY(hipStreamSynchronize(e->stream));
   /* no launch may see the old image once it is freed, whatever follows */
   e->have_ccd = false;
   (void)hipFree(e->dust_image);
   e->dust_image = nullptr;
+  dust_free_views(e);
   e->dust.image = nullptr;
   e->sky_camera.image = nullptr;
   HIP_TRY(hipMalloc(&e->dust_image,
@@ -3798,6 +4076,55 @@ int cmi_gpu_set_sky_camera(cmi_gpu_engine *e, const double *origin,
   cam.image = e->dust_image;
   e->sky_camera = cam;
   e->dust_camera = DUST_CAMERA_POINT;
+  e->have_ccd = true;
+  return cmi_gpu_reset_image(e);
+}
+
+int cmi_gpu_set_sky_cameras(cmi_gpu_engine *e, int32_t nviews,
+                            const double *origins, const double *frames,
+                            double lon_min, double lon_max, double lat_min,
+                            double lat_max, int32_t nlon, int32_t nlat,
+                            const double *exclusion_radii,
+                            int32_t direct_light) {
+  if (!e || !origins || !frames || !exclusion_radii)
+    return fail(CMI_GPU_EINVAL, "set_sky_cameras: null argument");
+  if (nviews < 1 || nviews > CMI_GPU_MAX_VIEWS)
+    return fail(CMI_GPU_EINVAL, "set_sky_cameras: %d views, must be 1 to %d",
+                (int)nviews, CMI_GPU_MAX_VIEWS);
+  std::vector<SkyObserverDev> views;
+  for (int32_t v = 0; v < nviews; ++v) {
+    if (cmi_gpu_check_sky_camera(e->grid.anchor, e->grid.box_sides,
+                                 origins + 3 * v, frames + 9 * v, lon_min,
+                                 lon_max, lat_min, lat_max, nlon, nlat,
+                                 exclusion_radii[v])) {
+      /* set_sky_camera's message, with the view it is about */
+      const std::string single = g_last_error;
+      return fail(CMI_GPU_EINVAL, "set_sky_cameras: view %d: %s", (int)v,
+                  single.c_str());
+    }
+    views.push_back(sky_make_observer(origins + 3 * v, frames + 9 * v,
+                                      exclusion_radii[v]));
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  DustViewBuffers b;
+  CMI_TRY(dust_alloc_views("set_sky_cameras", nviews, (size_t)nlon * nlat,
+                           views.data(), sizeof(SkyObserverDev), b));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  dust_adopt_views(e, nviews, b);
+  SkyCameraDev cam = {};
+  sky_put_observer(cam, views[0]);
+  cam.lon_min = lon_min;
+  cam.lat_min = lat_min;
+  cam.lon_width = lon_max - lon_min;
+  cam.lat_width = lat_max - lat_min;
+  cam.nlon = nlon;
+  cam.nlat = nlat;
+  cam.direct_light = direct_light != 0;
+  cam.image = e->dust_image;
+  e->sky_camera = cam;
+  e->sky_views = views;
+  e->dust.image = nullptr;
+  e->dust_camera = DUST_CAMERA_POINT_VIEWS;
   e->have_ccd = true;
   return cmi_gpu_reset_image(e);
 }

@@ -35,6 +35,8 @@ DUST_PROBE_EMIT, DUST_PROBE_SCATTER, DUST_PROBE_SCATTER_TOWARDS = 0, 1, 2
 DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
 DUST_PROBE_CELL_SOURCE = 5
 DUST_PROBE_SKY_PEEL = 6
+# CMI_GPU_MAX_VIEWS: the views of one run (set_ccd_images, set_sky_cameras)
+MAX_VIEWS = 64
 
 _dp = C.POINTER(C.c_double)
 
@@ -114,6 +116,9 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_sky_map_directions",
     "cmi_gpu_set_sky_camera", "cmi_gpu_check_sky_camera",
     "cmi_gpu_get_sky_camera_counters",
+    "cmi_gpu_set_ccd_images", "cmi_gpu_set_sky_cameras",
+    "cmi_gpu_download_image_view", "cmi_gpu_get_dust_view_counters",
+    "cmi_gpu_select_probe_view",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -298,6 +303,15 @@ def load_library():
         _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double,
         C.c_int32, C.c_int32, C.c_double]
     L.cmi_gpu_get_sky_camera_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cmi_gpu_set_ccd_images.argtypes = [vp, C.c_int32, _dp, _dp, C.c_int32,
+                                         C.c_int32, _dp, _dp]
+    L.cmi_gpu_set_sky_cameras.argtypes = [
+        vp, C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_double,
+        C.c_double, C.c_int32, C.c_int32, _dp, C.c_int32]
+    L.cmi_gpu_download_image_view.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    L.cmi_gpu_get_dust_view_counters.argtypes = [vp, C.c_int32,
+                                                 C.POINTER(C.c_uint64)]
+    L.cmi_gpu_select_probe_view.argtypes = [vp, C.c_int32]
     _lib = L
     return L
 
@@ -924,6 +938,53 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_set_ccd_image(
             self._h, theta, phi, int(nx), int(ny), _p(a), _p(s)))
         self.image_shape = (int(nx), int(ny))
+        self.nviews = 1
+
+    def set_ccd_images(self, theta, phi, nx, ny, anchors, sides):
+        """Several CCD images filled by one run: view v looks along
+        (theta[v], phi[v]) with anchors[v] and sides[v] ((2,) arrays serve
+        every view); the resolution is shared (include/cmi_gpu.h,
+        cmi_gpu_set_ccd_images). download_images returns the stack."""
+        t = _f64(theta).reshape(-1)
+        f = _f64(phi).reshape(-1)
+        n = len(t)
+        if len(f) != n:
+            raise ValueError("theta and phi differ in length")
+        a = _f64(np.broadcast_to(_f64(anchors), (n, 2)))
+        s = _f64(np.broadcast_to(_f64(sides), (n, 2)))
+        self._check(self._lib.cmi_gpu_set_ccd_images(
+            self._h, n, _p(t), _p(f), int(nx), int(ny), _p(a), _p(s)))
+        self.image_shape = (int(nx), int(ny))
+        self.nviews = n
+
+    def download_images(self):
+        """The images of every view, (nviews, 3, nx, ny), unnormalised"""
+        out = np.zeros((self.nviews, 3) + self.image_shape)
+        for v in range(self.nviews):
+            out[v] = self.download_image_view(v)
+        return out
+
+    def download_image_view(self, view):
+        """I, Q, U of one view, (3, nx, ny), unnormalised"""
+        out = np.zeros((3,) + self.image_shape)
+        self._check(self._lib.cmi_gpu_download_image_view(
+            self._h, int(view), _p(out[0]), _p(out[1]), _p(out[2])))
+        return out
+
+    def get_dust_view_counters(self, view):
+        """One view's share of a run with several views: the DDA steps of its
+        own marches, the atomics into its image, its events inside the
+        exclusion radius and outside the window"""
+        c = (C.c_uint64 * 4)()
+        self._check(self._lib.cmi_gpu_get_dust_view_counters(
+            self._h, int(view), c))
+        return dict(zip(("nsteps", "natomics", "nexcluded", "noutside"),
+                        (int(v) for v in c)))
+
+    def select_probe_view(self, view):
+        """The view that the TRACE and SKY_PEEL probes follow (0 after a
+        camera is set)"""
+        self._check(self._lib.cmi_gpu_select_probe_view(self._h, int(view)))
 
     def set_continuous_source_spiral_galaxy(self, r_stars, h_stars,
                                             bulge_over_total):
@@ -1000,12 +1061,30 @@ class GpuEngine:
         peak linear polarisation p_l); the unnormalised image is scaled by
         L_total / (npackets A_pixel), which makes it comparable with
         render_line_images. Replaces the engine's CCD image, dust and dust
-        source."""
+        source.
+        With sequences of equal length for theta and phi (anchor and sides
+        then (2,) for every view or (nviews, 2)) the views share one run per
+        line, hence its noise: (nlines, nviews, 3, nx, ny)."""
         names = list(EMISSION_LINES if lines is None else lines)
+        self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
+        if np.ndim(theta) or np.ndim(phi):
+            nviews = len(_f64(theta).reshape(-1))
+            a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
+            s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
+            pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
+            self.set_ccd_images(theta, phi, nx, ny, a, s)
+            out = np.zeros((len(names), nviews, 3, int(nx), int(ny)))
+            for k, name in enumerate(names):
+                self.set_cell_source_line(name)
+                self.reset_image()
+                self.dust_shoot(seed, 0, int(npackets))
+                total = self.get_cell_source(tables=False)
+                out[k] = self.download_images() * \
+                    (total / (int(npackets) * pixel_area))[:, None, None, None]
+            return out
         a = _f64(anchor).reshape(2)
         s = _f64(sides).reshape(2)
         pixel_area = s[0] * s[1] / (int(nx) * int(ny))
-        self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
         self.set_ccd_image(theta, phi, nx, ny, a, s)
         out = np.zeros((len(names), 3, int(nx), int(ny)))
         for k, name in enumerate(names):
@@ -1116,6 +1195,26 @@ class GpuEngine:
             lat_range[1], int(nlon), int(nlat), exclusion_radius,
             int(bool(direct_light))))
         self.image_shape = (int(nlon), int(nlat))
+        self.nviews = 1
+
+    def set_sky_cameras(self, origins, nlon, nlat, exclusion_radii,
+                        lon_range=FULL_SKY_LONGITUDE,
+                        lat_range=FULL_SKY_LATITUDE, frames=IDENTITY_FRAME,
+                        direct_light=True):
+        """Several sky cameras filled by one run: observer v at origins[v]
+        with frames[v] and exclusion_radii[v] (one frame or one radius serves
+        every observer); window and resolution are shared (include/cmi_gpu.h,
+        cmi_gpu_set_sky_cameras). download_images returns the stack."""
+        o = _f64(origins).reshape(-1, 3)
+        n = len(o)
+        f = _f64(np.broadcast_to(_f64(frames), (n, 3, 3)))
+        r = _f64(np.broadcast_to(_f64(exclusion_radii), (n,)))
+        self._check(self._lib.cmi_gpu_set_sky_cameras(
+            self._h, n, _p(o), _p(f), lon_range[0], lon_range[1],
+            lat_range[0], lat_range[1], int(nlon), int(nlat), _p(r),
+            int(bool(direct_light))))
+        self.image_shape = (int(nlon), int(nlat))
+        self.nviews = n
 
     def get_sky_camera_counters(self):
         c = (C.c_uint64 * 2)()
@@ -1141,11 +1240,35 @@ class GpuEngine:
         solid angles of sky_map_directions. At albedo 0 it is the ray-traced
         map; with direct_light=False it is the scattered light alone, to be
         added to the ray-traced map. Replaces the engine's camera, dust and
-        dust source."""
+        dust source.
+        With a sequence of observers, origin of shape (nviews, 3)
+        (exclusion_radius, frame_pole and frame_zero_longitude then one for
+        every observer or one each), the observers share one run per line,
+        hence its noise: (nlines, nviews, 3, nlon, nlat)."""
         names = list(EMISSION_LINES if lines is None else lines)
-        frame = sky_frame(frame_pole, frame_zero_longitude)
         self.set_dust_scattering_per_hydrogen(g, p_l, albedo,
                                               dust_cross_section)
+        if np.ndim(origin) == 2:
+            o = _f64(origin).reshape(-1, 3)
+            nviews = len(o)
+            poles = np.broadcast_to(_f64(frame_pole), (nviews, 3))
+            zeros = np.broadcast_to(_f64(frame_zero_longitude), (nviews, 3))
+            frames = np.array([sky_frame(p, z) for p, z in zip(poles, zeros)])
+            self.set_sky_cameras(o, nlon, nlat, exclusion_radius, lon_range,
+                                 lat_range, frames, direct_light)
+            omega = np.array([
+                sky_map_directions(nlon, nlat, lon_range, lat_range, f)[1]
+                for f in frames]).reshape(nviews, 1, int(nlon), int(nlat))
+            out = np.zeros((len(names), nviews, 3, int(nlon), int(nlat)))
+            for k, name in enumerate(names):
+                self.set_cell_source_line(name)
+                self.reset_image()
+                self.dust_shoot(seed, 0, int(npackets))
+                total = self.get_cell_source(tables=False)
+                out[k] = self.download_images() * (total / int(npackets)) \
+                    / omega
+            return out
+        frame = sky_frame(frame_pole, frame_zero_longitude)
         self.set_sky_camera(origin, nlon, nlat, exclusion_radius, lon_range,
                             lat_range, frame, direct_light)
         _, omega = sky_map_directions(nlon, nlat, lon_range, lat_range, frame)

@@ -67,6 +67,23 @@
  *                    nearer to the observer than this add nothing
  *   EmissionSkyMaps:direct light                 true (false: the scattered
  *                    light alone, to be added to the ray-traced map)
+ * Several views in one go (read only if the key is there; 1 to
+ * CMI_GPU_MAX_VIEWS):
+ *   EmissionImages:number of views               1
+ *   EmissionSkyMaps:number of observers          1
+ * View 0 is described by the keys above. View k >= 1 is described by the
+ * same keys with " k" appended: "view theta 1" and "view phi 1" (required),
+ * "anchor x 1", "anchor y 1", "sides x 1", "sides y 1" (a missing one takes
+ * view 0's value if view 0 names one, the bounding rectangle of view k's own
+ * projection otherwise); "observer position 1" (required), "frame pole 1",
+ * "frame zero longitude 1" and "exclusion radius 1" (a missing one takes
+ * observer 0's). Resolution, window, dust, packets and seed are shared. View
+ * 0's files keep their names; view k's carry "_view<k>" after the line's
+ * name: <prefix>_<LineName>_view1.dat, <prefix>_<LineName>_view1_scattered_I.
+ * The ray-traced maps of the further views are further calls of the same
+ * renderer; with scattering all views are filled by one Monte Carlo run per
+ * line (cmi_gpu_set_ccd_images, cmi_gpu_set_sky_cameras), so they share its
+ * noise.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -104,6 +121,63 @@ class EmissivityCalculationSimulation {
     bool scattering = false;
     long long npackets = 1000000, seed = 42;
     double albedo = 0., asymmetry = 0.5, polarisation = 0.;
+    /* several views: views[0] repeats the members above, views[k] is read
+     * from the keys with " k" appended */
+    struct View {
+      double theta = 0., phi = 0.;
+      bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
+      double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
+    };
+    long long nviews = 1;
+    std::vector<View> views;
+
+    void read_views(ParameterFile &params) {
+      static const char *axis[2] = {"x", "y"};
+      if (params.has_value("EmissionImages:number of views"))
+        nviews = params.get_integer("EmissionImages:number of views", 1);
+      if (nviews < 1 || nviews > CMI_GPU_MAX_VIEWS)
+        throw ParameterError("EmissionImages:number of views must be 1.." +
+                             std::to_string(CMI_GPU_MAX_VIEWS));
+      views.assign(1, View());
+      views[0].theta = theta;
+      views[0].phi = phi;
+      for (int a = 0; a < 2; ++a) {
+        views[0].have_anchor[a] = have_anchor[a];
+        views[0].have_sides[a] = have_sides[a];
+        views[0].anchor[a] = anchor[a];
+        views[0].sides[a] = sides[a];
+      }
+      for (long long k = 1; k < nviews; ++k) {
+        const std::string n = " " + std::to_string(k);
+        View v = views[0];
+        const std::string kt = "EmissionImages:view theta" + n;
+        const std::string kp = "EmissionImages:view phi" + n;
+        if (!params.has_value(kt))
+          throw ParameterError(kt + " is required");
+        if (!params.has_value(kp))
+          throw ParameterError(kp + " is required");
+        v.theta = params.get_physical_value(QUANTITY_ANGLE, kt, "0. degrees");
+        v.phi = params.get_physical_value(QUANTITY_ANGLE, kp, "0. degrees");
+        for (int a = 0; a < 2; ++a) {
+          const std::string ka =
+              std::string("EmissionImages:anchor ") + axis[a] + n;
+          const std::string ks =
+              std::string("EmissionImages:sides ") + axis[a] + n;
+          if (params.has_value(ka)) {
+            v.have_anchor[a] = true;
+            v.anchor[a] = params.get_physical_value(QUANTITY_LENGTH, ka, "0. m");
+          }
+          if (params.has_value(ks)) {
+            v.have_sides[a] = true;
+            v.sides[a] = params.get_physical_value(QUANTITY_LENGTH, ks, "1. m");
+          }
+          if (v.have_sides[a] && !(v.sides[a] > 0.))
+            throw ParameterError("EmissionImages: the image sides must be "
+                                 "positive");
+        }
+        views.push_back(v);
+      }
+    }
 
     void read(ParameterFile &params) {
       theta = params.get_physical_value(QUANTITY_ANGLE,
@@ -146,6 +220,7 @@ class EmissivityCalculationSimulation {
         if (have_sides[a] && !(sides[a] > 0.))
           throw ParameterError("EmissionImages: the image sides must be "
                                "positive");
+      read_views(params);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       if (!params.peek_bool("EmissionImages:scattering"))
@@ -193,6 +268,89 @@ class EmissivityCalculationSimulation {
     double albedo = 0., asymmetry = 0.5, polarisation = 0.;
     double exclusion_radius = 0.;
     double camera_lon_max = 0.; /* min(lon[1], lon[0] + 2 pi) */
+    /* several observers: observers[0] repeats the members above,
+     * observers[k] is read from the keys with " k" appended */
+    struct Observer {
+      std::array<double, 3> position = {0., 0., 0.};
+      double frame[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
+      double exclusion_radius = 0.;
+    };
+    long long nobservers = 1;
+    std::vector<Observer> observers;
+
+    /* Gram-Schmidt: e_3 = the pole, e_1 = the zero of longitude made
+     * perpendicular to it, e_2 = e_3 x e_1 */
+    static void make_frame(const std::array<double, 3> &pole,
+                           const std::array<double, 3> &zero,
+                           const std::string &n, double frame[9]) {
+      double e3[3], e1[3];
+      double norm = std::sqrt(pole[0] * pole[0] + pole[1] * pole[1] +
+                              pole[2] * pole[2]);
+      const double zero_norm = std::sqrt(zero[0] * zero[0] + zero[1] * zero[1] +
+                                         zero[2] * zero[2]);
+      if (!(norm > 0.) || !std::isfinite(norm) || !(zero_norm > 0.) ||
+          !std::isfinite(zero_norm))
+        throw ParameterError("EmissionSkyMaps:frame pole" + n +
+                             " and frame zero longitude" + n +
+                             " must be finite vectors, not zero");
+      for (int a = 0; a < 3; ++a)
+        e3[a] = pole[a] / norm;
+      const double along = zero[0] * e3[0] + zero[1] * e3[1] + zero[2] * e3[2];
+      for (int a = 0; a < 3; ++a)
+        e1[a] = zero[a] - along * e3[a];
+      norm = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+      if (!(norm > 1.e-8 * zero_norm))
+        throw ParameterError("EmissionSkyMaps:frame pole" + n +
+                             " and frame zero longitude" + n +
+                             " are parallel");
+      for (int a = 0; a < 3; ++a)
+        e1[a] /= norm;
+      const double e2[3] = {e3[1] * e1[2] - e3[2] * e1[1],
+                            e3[2] * e1[0] - e3[0] * e1[2],
+                            e3[0] * e1[1] - e3[1] * e1[0]};
+      for (int a = 0; a < 3; ++a) {
+        frame[a] = e1[a];
+        frame[3 + a] = e2[a];
+        frame[6 + a] = e3[a];
+      }
+    }
+
+    /* the observers' positions and frames (the exclusion radii are read with
+     * the scattering keys) */
+    void read_observers(ParameterFile &params,
+                        const std::array<double, 3> &pole,
+                        const std::array<double, 3> &zero) {
+      if (params.has_value("EmissionSkyMaps:number of observers"))
+        nobservers =
+            params.get_integer("EmissionSkyMaps:number of observers", 1);
+      if (nobservers < 1 || nobservers > CMI_GPU_MAX_VIEWS)
+        throw ParameterError("EmissionSkyMaps:number of observers must be "
+                             "1.." + std::to_string(CMI_GPU_MAX_VIEWS));
+      observers.assign(1, Observer());
+      observers[0].position = observer;
+      std::copy(frame, frame + 9, observers[0].frame);
+      for (long long k = 1; k < nobservers; ++k) {
+        const std::string n = " " + std::to_string(k);
+        Observer o;
+        const std::string key = "EmissionSkyMaps:observer position" + n;
+        if (!params.has_value(key))
+          throw ParameterError(key + " is required");
+        o.position = params.get_physical_vector(QUANTITY_LENGTH, key, "");
+        for (int a = 0; a < 3; ++a)
+          if (!std::isfinite(o.position[a]))
+            throw ParameterError(key + " must be finite");
+        const std::string kpole = "EmissionSkyMaps:frame pole" + n;
+        const std::string kzero = "EmissionSkyMaps:frame zero longitude" + n;
+        const std::array<double, 3> p =
+            params.has_value(kpole) ? params.get_double_vector(kpole, pole)
+                                    : pole;
+        const std::array<double, 3> z =
+            params.has_value(kzero) ? params.get_double_vector(kzero, zero)
+                                    : zero;
+        make_frame(p, z, n, o.frame);
+        observers.push_back(o);
+      }
+    }
 
     void read(ParameterFile &params) {
       if (!params.has_value("EmissionSkyMaps:observer position"))
@@ -247,36 +405,8 @@ class EmissivityCalculationSimulation {
       if (!(dust_cross_section >= 0.))
         throw ParameterError("EmissionSkyMaps:dust cross section per hydrogen "
                              "must not be negative");
-      /* Gram-Schmidt: e_3 = the pole, e_1 = the zero of longitude made
-       * perpendicular to it, e_2 = e_3 x e_1 */
-      double e3[3], e1[3];
-      double norm = std::sqrt(pole[0] * pole[0] + pole[1] * pole[1] +
-                              pole[2] * pole[2]);
-      const double zero_norm = std::sqrt(zero[0] * zero[0] + zero[1] * zero[1] +
-                                         zero[2] * zero[2]);
-      if (!(norm > 0.) || !std::isfinite(norm) || !(zero_norm > 0.) ||
-          !std::isfinite(zero_norm))
-        throw ParameterError("EmissionSkyMaps:frame pole and frame zero "
-                             "longitude must be finite vectors, not zero");
-      for (int a = 0; a < 3; ++a)
-        e3[a] = pole[a] / norm;
-      const double along = zero[0] * e3[0] + zero[1] * e3[1] + zero[2] * e3[2];
-      for (int a = 0; a < 3; ++a)
-        e1[a] = zero[a] - along * e3[a];
-      norm = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
-      if (!(norm > 1.e-8 * zero_norm))
-        throw ParameterError("EmissionSkyMaps:frame pole and frame zero "
-                             "longitude are parallel");
-      for (int a = 0; a < 3; ++a)
-        e1[a] /= norm;
-      const double e2[3] = {e3[1] * e1[2] - e3[2] * e1[1],
-                            e3[2] * e1[0] - e3[0] * e1[2],
-                            e3[0] * e1[1] - e3[1] * e1[0]};
-      for (int a = 0; a < 3; ++a) {
-        frame[a] = e1[a];
-        frame[3 + a] = e2[a];
-        frame[6 + a] = e3[a];
-      }
+      make_frame(pole, zero, "", frame);
+      read_observers(params, pole, zero);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       if (!params.peek_bool("EmissionSkyMaps:scattering"))
@@ -315,6 +445,17 @@ class EmissivityCalculationSimulation {
       if (!(exclusion_radius >= 0.) || !std::isfinite(exclusion_radius))
         throw ParameterError("EmissionSkyMaps:exclusion radius must be "
                              "finite and not negative");
+      observers[0].exclusion_radius = exclusion_radius;
+      for (long long k = 1; k < nobservers; ++k) {
+        const std::string key =
+            "EmissionSkyMaps:exclusion radius " + std::to_string(k);
+        double r = exclusion_radius;
+        if (params.has_value(key))
+          r = params.get_physical_value(QUANTITY_LENGTH, key, "0. m");
+        if (!(r >= 0.) || !std::isfinite(r))
+          throw ParameterError(key + " must be finite and not negative");
+        observers[(size_t)k].exclusion_radius = r;
+      }
       direct_light = params.get_bool("EmissionSkyMaps:direct light", true);
       /* (360 degrees converted to radians may overshoot 2 pi by an ulp) */
       if (lon[1] - lon[0] > 2. * M_PI * (1. + 1.e-12))
@@ -517,55 +658,79 @@ public:
         values.swap(v2);
       }
       std::string written;
+      /* "" for view 0, whose files keep their names */
+      auto view_tag = [](size_t v) {
+        return v ? "_view" + std::to_string(v) : std::string();
+      };
+      static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
+                                      "_scattered_U"};
       if (rc == CMI_GPU_OK && placed && do_images) {
         status("Rendering emission line images...");
-        /* default image: the rectangle around the box's projected corners */
-        const double st = std::sin(img.theta), ct = std::cos(img.theta),
-                     sp = std::sin(img.phi), cp = std::cos(img.phi);
-        const double ex[3] = {-sp, cp, 0.};
-        const double ey[3] = {-ct * cp, -ct * sp, st};
-        double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
-        for (int corner = 0; corner < 8; ++corner) {
-          double p[2] = {0., 0.};
-          for (int a = 0; a < 3; ++a) {
-            const double x =
-                box_anchor[a] + ((corner >> a) & 1) * box_sides[a];
-            p[0] += x * ex[a];
-            p[1] += x * ey[a];
+        const size_t nviews = img.views.size();
+        /* per view, default image: the rectangle around the box's projected
+         * corners */
+        std::vector<double> theta(nviews), phi(nviews), anchors(2 * nviews),
+            sides(2 * nviews);
+        for (size_t v = 0; v < nviews; ++v) {
+          const ImageSettings::View &view = img.views[v];
+          theta[v] = view.theta;
+          phi[v] = view.phi;
+          const double st = std::sin(view.theta), ct = std::cos(view.theta),
+                       sp = std::sin(view.phi), cp = std::cos(view.phi);
+          const double ex[3] = {-sp, cp, 0.};
+          const double ey[3] = {-ct * cp, -ct * sp, st};
+          double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
+          for (int corner = 0; corner < 8; ++corner) {
+            double p[2] = {0., 0.};
+            for (int a = 0; a < 3; ++a) {
+              const double x =
+                  box_anchor[a] + ((corner >> a) & 1) * box_sides[a];
+              p[0] += x * ex[a];
+              p[1] += x * ey[a];
+            }
+            for (int k = 0; k < 2; ++k) {
+              lo[k] = std::min(lo[k], p[k]);
+              hi[k] = std::max(hi[k], p[k]);
+            }
           }
           for (int k = 0; k < 2; ++k) {
-            lo[k] = std::min(lo[k], p[k]);
-            hi[k] = std::max(hi[k], p[k]);
+            anchors[2 * v + k] = view.have_anchor[k] ? view.anchor[k] : lo[k];
+            sides[2 * v + k] =
+                view.have_sides[k] ? view.sides[k] : hi[k] - anchors[2 * v + k];
           }
-        }
-        double anchor[2], sides[2];
-        for (int k = 0; k < 2; ++k) {
-          anchor[k] = img.have_anchor[k] ? img.anchor[k] : lo[k];
-          sides[k] = img.have_sides[k] ? img.sides[k] : hi[k] - anchor[k];
         }
         const size_t npixel = (size_t)img.nx * (size_t)img.ny;
         std::vector<double> images(lines.size() * npixel);
-        rc = cmi_gpu_render_line_images(
-            engine, (int32_t)lines.size(), lines.data(), img.theta, img.phi,
-            (int32_t)img.nx, (int32_t)img.ny, anchor, sides,
-            (int32_t)img.supersample, img.dust_cross_section, images.data());
-        if (rc == CMI_GPU_OK && write_output)
-          for (size_t k = 0; k < lines.size(); ++k)
-            written += " " + write_image(
-                img.folder + "/" + img.prefix + "_" +
-                    GpuIonizationSimulation::emission_line_name(lines[k]),
-                img.type, images.data() + k * npixel, img.nx, img.ny, 1.);
+        for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+          rc = cmi_gpu_render_line_images(
+              engine, (int32_t)lines.size(), lines.data(), theta[v], phi[v],
+              (int32_t)img.nx, (int32_t)img.ny, anchors.data() + 2 * v,
+              sides.data() + 2 * v, (int32_t)img.supersample,
+              img.dust_cross_section, images.data());
+          if (rc == CMI_GPU_OK && write_output)
+            for (size_t k = 0; k < lines.size(); ++k)
+              written += " " + write_image(
+                  img.folder + "/" + img.prefix + "_" +
+                      GpuIonizationSimulation::emission_line_name(lines[k]) +
+                      view_tag(v),
+                  img.type, images.data() + k * npixel, img.nx, img.ny, 1.);
+        }
         if (rc == CMI_GPU_OK && img.scattering) {
           status("Shooting the lines' packets through the dust...");
           rc = cmi_gpu_set_dust_scattering_per_hydrogen(
               engine, img.asymmetry, img.polarisation, img.albedo,
               img.dust_cross_section);
+          /* one view: the single camera, as ever; several: one run fills
+           * them all */
           if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_ccd_image(engine, img.theta, img.phi,
-                                       (int32_t)img.nx, (int32_t)img.ny,
-                                       anchor, sides);
-          const double pixel_area =
-              sides[0] * sides[1] / ((double)img.nx * (double)img.ny);
+            rc = nviews == 1
+                     ? cmi_gpu_set_ccd_image(engine, theta[0], phi[0],
+                                             (int32_t)img.nx, (int32_t)img.ny,
+                                             anchors.data(), sides.data())
+                     : cmi_gpu_set_ccd_images(
+                           engine, (int32_t)nviews, theta.data(), phi.data(),
+                           (int32_t)img.nx, (int32_t)img.ny, anchors.data(),
+                           sides.data());
           std::vector<double> iqu(3 * npixel);
           for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
             double total = 0.;
@@ -577,53 +742,80 @@ public:
                                       (uint64_t)img.npackets);
             if (rc == CMI_GPU_OK)
               rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
-            if (rc == CMI_GPU_OK)
-              rc = cmi_gpu_download_image(engine, iqu.data(),
-                                          iqu.data() + npixel,
-                                          iqu.data() + 2 * npixel);
-            static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
-                                            "_scattered_U"};
-            if (rc == CMI_GPU_OK && write_output)
-              for (int j = 0; j < 3; ++j)
-                written += " " + write_image(
-                    img.folder + "/" + img.prefix + "_" +
-                        GpuIonizationSimulation::emission_line_name(lines[k]) +
-                        stokes[j],
-                    img.type, iqu.data() + j * npixel, img.nx, img.ny,
-                    total / ((double)img.npackets * pixel_area));
+            for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+              rc = cmi_gpu_download_image_view(engine, (int32_t)v, iqu.data(),
+                                               iqu.data() + npixel,
+                                               iqu.data() + 2 * npixel);
+              const double pixel_area = sides[2 * v] * sides[2 * v + 1] /
+                                        ((double)img.nx * (double)img.ny);
+              if (rc == CMI_GPU_OK && write_output)
+                for (int j = 0; j < 3; ++j)
+                  written += " " + write_image(
+                      img.folder + "/" + img.prefix + "_" +
+                          GpuIonizationSimulation::emission_line_name(
+                              lines[k]) +
+                          view_tag(v) + stokes[j],
+                      img.type, iqu.data() + j * npixel, img.nx, img.ny,
+                      total / ((double)img.npackets * pixel_area));
+            }
           }
         }
       }
       if (rc == CMI_GPU_OK && placed && do_sky) {
         status("Rendering emission line sky maps...");
+        const size_t nviews = sky.observers.size();
         const size_t npixel = (size_t)sky.nlon * (size_t)sky.nlat;
         std::vector<double> maps(lines.size() * npixel);
-        rc = cmi_gpu_render_line_sky_map(
-            engine, (int32_t)lines.size(), lines.data(), sky.observer.data(),
-            sky.frame, sky.lon[0], sky.lon[1], sky.lat[0], sky.lat[1],
-            (int32_t)sky.nlon, (int32_t)sky.nlat, sky.dust_cross_section,
-            maps.data());
-        if (rc == CMI_GPU_OK && write_output)
-          for (size_t k = 0; k < lines.size(); ++k)
-            written += " " + write_image(
-                sky.folder + "/" + sky.prefix + "_" +
-                    GpuIonizationSimulation::emission_line_name(lines[k]),
-                sky.type, maps.data() + k * npixel, sky.nlon, sky.nlat, 1.);
+        for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+          rc = cmi_gpu_render_line_sky_map(
+              engine, (int32_t)lines.size(), lines.data(),
+              sky.observers[v].position.data(), sky.observers[v].frame,
+              sky.lon[0], sky.lon[1], sky.lat[0], sky.lat[1],
+              (int32_t)sky.nlon, (int32_t)sky.nlat, sky.dust_cross_section,
+              maps.data());
+          if (rc == CMI_GPU_OK && write_output)
+            for (size_t k = 0; k < lines.size(); ++k)
+              written += " " + write_image(
+                  sky.folder + "/" + sky.prefix + "_" +
+                      GpuIonizationSimulation::emission_line_name(lines[k]) +
+                      view_tag(v),
+                  sky.type, maps.data() + k * npixel, sky.nlon, sky.nlat, 1.);
+        }
         if (rc == CMI_GPU_OK && sky.scattering) {
           status("Shooting the lines' packets towards the observer...");
-          std::vector<double> omega(npixel), iqu(3 * npixel);
-          rc = cmi_gpu_sky_map_directions(
-              sky.frame, sky.lon[0], sky.camera_lon_max, sky.lat[0], sky.lat[1],
-              (int32_t)sky.nlon, (int32_t)sky.nlat, nullptr, omega.data());
+          std::vector<double> omega(nviews * npixel), iqu(3 * npixel);
+          std::vector<double> origins(3 * nviews), frames(9 * nviews),
+              radii(nviews);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            const SkyMapSettings::Observer &o = sky.observers[v];
+            std::copy(o.position.begin(), o.position.end(),
+                      origins.begin() + 3 * v);
+            std::copy(o.frame, o.frame + 9, frames.begin() + 9 * v);
+            radii[v] = o.exclusion_radius;
+            rc = cmi_gpu_sky_map_directions(
+                o.frame, sky.lon[0], sky.camera_lon_max, sky.lat[0],
+                sky.lat[1], (int32_t)sky.nlon, (int32_t)sky.nlat, nullptr,
+                omega.data() + v * npixel);
+          }
           if (rc == CMI_GPU_OK)
             rc = cmi_gpu_set_dust_scattering_per_hydrogen(
                 engine, sky.asymmetry, sky.polarisation, sky.albedo,
                 sky.dust_cross_section);
+          /* one observer: the single camera, as ever; several: one run fills
+           * them all */
           if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_sky_camera(
-                engine, sky.observer.data(), sky.frame, sky.lon[0],
-                sky.camera_lon_max, sky.lat[0], sky.lat[1], (int32_t)sky.nlon,
-                (int32_t)sky.nlat, sky.exclusion_radius, sky.direct_light ? 1 : 0);
+            rc = nviews == 1
+                     ? cmi_gpu_set_sky_camera(
+                           engine, origins.data(), frames.data(), sky.lon[0],
+                           sky.camera_lon_max, sky.lat[0], sky.lat[1],
+                           (int32_t)sky.nlon, (int32_t)sky.nlat, radii[0],
+                           sky.direct_light ? 1 : 0)
+                     : cmi_gpu_set_sky_cameras(
+                           engine, (int32_t)nviews, origins.data(),
+                           frames.data(), sky.lon[0], sky.camera_lon_max,
+                           sky.lat[0], sky.lat[1], (int32_t)sky.nlon,
+                           (int32_t)sky.nlat, radii.data(),
+                           sky.direct_light ? 1 : 0);
           for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
             double total = 0.;
             rc = cmi_gpu_set_cell_source_line(engine, lines[k]);
@@ -634,28 +826,29 @@ public:
                                       (uint64_t)sky.npackets);
             if (rc == CMI_GPU_OK)
               rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
-            if (rc == CMI_GPU_OK)
-              rc = cmi_gpu_download_image(engine, iqu.data(),
-                                          iqu.data() + npixel,
-                                          iqu.data() + 2 * npixel);
-            if (rc != CMI_GPU_OK)
-              break;
-            /* W m^-2 sr^-1: x L_total / packets / the pixel's solid angle,
-             * in the order the Python call multiplies */
-            const double per_packet = total / (double)sky.npackets;
-            for (int j = 0; j < 3; ++j)
-              for (size_t i = 0; i < npixel; ++i)
-                iqu[j * npixel + i] = iqu[j * npixel + i] * per_packet /
-                                      omega[i];
-            static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
-                                            "_scattered_U"};
-            if (write_output)
+            for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+              rc = cmi_gpu_download_image_view(engine, (int32_t)v, iqu.data(),
+                                               iqu.data() + npixel,
+                                               iqu.data() + 2 * npixel);
+              if (rc != CMI_GPU_OK)
+                break;
+              /* W m^-2 sr^-1: x L_total / packets / the pixel's solid angle,
+               * in the order the Python call multiplies */
+              const double per_packet = total / (double)sky.npackets;
               for (int j = 0; j < 3; ++j)
-                written += " " + write_image(
-                    sky.folder + "/" + sky.prefix + "_" +
-                        GpuIonizationSimulation::emission_line_name(lines[k]) +
-                        stokes[j],
-                    sky.type, iqu.data() + j * npixel, sky.nlon, sky.nlat, 1.);
+                for (size_t i = 0; i < npixel; ++i)
+                  iqu[j * npixel + i] = iqu[j * npixel + i] * per_packet /
+                                        omega[v * npixel + i];
+              if (write_output)
+                for (int j = 0; j < 3; ++j)
+                  written += " " + write_image(
+                      sky.folder + "/" + sky.prefix + "_" +
+                          GpuIonizationSimulation::emission_line_name(
+                              lines[k]) +
+                          view_tag(v) + stokes[j],
+                      sky.type, iqu.data() + j * npixel, sky.nlon, sky.nlat,
+                      1.);
+            }
           }
         }
       }

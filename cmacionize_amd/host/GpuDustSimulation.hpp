@@ -24,6 +24,14 @@
  *   DustSimulation:number of photons          5e5
  *   DustSimulation:random seed                42
  *   DustSimulation:output folder              .
+ * Beyond the reference, the galaxy at several inclinations from one run (the
+ * views share the packets' walk, cmi_gpu_set_ccd_images; read only if the
+ * key is there, 1 to CMI_GPU_MAX_VIEWS):
+ *   CCDImage:number of views                  1
+ * View 0 is described by the keys above; view k >= 1 by "view theta k" and
+ * "view phi k" (required) and "anchor x k", "anchor y k", "sides x k",
+ * "sides y k" (a missing one takes view 0's value). View 0 keeps its file
+ * name, view k's is <filename>_view<k>.
  * A box that does not contain the origin (the galaxy's centre) is refused.
  * A periodic box is refused: the reference's integrate_optical_depth wraps
  * through a periodic face and never reaches the box edge
@@ -76,6 +84,12 @@ private:
   double _image_anchor[2], _image_sides[2];
   std::string _image_type, _image_filename;
   long long _numphoton;
+  /* several views: _views[0] repeats the members above */
+  struct View {
+    double theta, phi;
+    double anchor[2], sides[2];
+  };
+  std::vector<View> _views;
 
 public:
   /* the parameter reads of src/DustSimulation.cpp:79-116 and the
@@ -135,6 +149,38 @@ public:
             "source is centred on it");
     if (_nx <= 0 || _ny <= 0 || _numphoton < 0)
       throw ParameterError("Bad image resolution or number of photons");
+    /* (a key that is read shows in the used values: a file without the key
+     * reads none of the new ones) */
+    long long nviews = 1;
+    if (_params.has_value("CCDImage:number of views"))
+      nviews = _params.get_integer("CCDImage:number of views", 1);
+    if (nviews < 1 || nviews > CMI_GPU_MAX_VIEWS)
+      throw ParameterError("CCDImage:number of views must be 1.." +
+                           std::to_string(CMI_GPU_MAX_VIEWS));
+    _views.push_back({_theta, _phi, {_image_anchor[0], _image_anchor[1]},
+                      {_image_sides[0], _image_sides[1]}});
+    static const char *axis[2] = {"x", "y"};
+    for (long long k = 1; k < nviews; ++k) {
+      const std::string n = " " + std::to_string(k);
+      View v = _views[0];
+      const std::string kt = "CCDImage:view theta" + n;
+      const std::string kp = "CCDImage:view phi" + n;
+      if (!_params.has_value(kt))
+        throw ParameterError(kt + " is required");
+      if (!_params.has_value(kp))
+        throw ParameterError(kp + " is required");
+      v.theta = _params.get_physical_value(QUANTITY_ANGLE, kt, "0. degrees");
+      v.phi = _params.get_physical_value(QUANTITY_ANGLE, kp, "0. degrees");
+      for (int a = 0; a < 2; ++a) {
+        const std::string ka = std::string("CCDImage:anchor ") + axis[a] + n;
+        const std::string ks = std::string("CCDImage:sides ") + axis[a] + n;
+        if (_params.has_value(ka))
+          v.anchor[a] = _params.get_physical_value(QUANTITY_LENGTH, ka, "0. m");
+        if (_params.has_value(ks))
+          v.sides[a] = _params.get_physical_value(QUANTITY_LENGTH, ks, "1. m");
+      }
+      _views.push_back(v);
+    }
   }
 
   /* the bulge-to-total ratio the source samples with
@@ -174,7 +220,20 @@ public:
         << ", \"anchor\": [" << _image_anchor[0] << ", " << _image_anchor[1]
         << "], \"sides\": [" << _image_sides[0] << ", " << _image_sides[1]
         << "], \"type\": \"" << _image_type << "\", \"filename\": \""
-        << _image_filename << "\"}\n}\n";
+        << _image_filename << "\"}";
+    /* (only with several views: one view is described as it always was) */
+    if (_views.size() > 1) {
+      out << ",\n  \"views\": [";
+      for (size_t v = 0; v < _views.size(); ++v)
+        out << (v ? ",\n    " : "\n    ") << "{\"theta\": " << _views[v].theta
+            << ", \"phi\": " << _views[v].phi << ", \"anchor\": ["
+            << _views[v].anchor[0] << ", " << _views[v].anchor[1]
+            << "], \"sides\": [" << _views[v].sides[0] << ", "
+            << _views[v].sides[1] << "], \"filename\": \""
+            << view_filename(v) << "\"}";
+      out << "\n  ]";
+    }
+    out << "\n}\n";
   }
 
   /* src/DustSimulation.cpp:118-186 */
@@ -248,9 +307,23 @@ public:
     check(cmi_gpu_set_dust_scattering(engine, _dust.g, _dust.p_l,
                                       _dust.albedo, _dust.kappa),
           "set_dust_scattering");
-    check(cmi_gpu_set_ccd_image(engine, _theta, _phi, (int32_t)_nx,
-                                (int32_t)_ny, _image_anchor, _image_sides),
-          "set_ccd_image");
+    if (_views.size() == 1) {
+      check(cmi_gpu_set_ccd_image(engine, _theta, _phi, (int32_t)_nx,
+                                  (int32_t)_ny, _image_anchor, _image_sides),
+            "set_ccd_image");
+    } else {
+      std::vector<double> theta, phi, anchors, sides;
+      for (const View &v : _views) {
+        theta.push_back(v.theta);
+        phi.push_back(v.phi);
+        anchors.insert(anchors.end(), v.anchor, v.anchor + 2);
+        sides.insert(sides.end(), v.sides, v.sides + 2);
+      }
+      check(cmi_gpu_set_ccd_images(engine, (int32_t)_views.size(),
+                                   theta.data(), phi.data(), (int32_t)_nx,
+                                   (int32_t)_ny, anchors.data(), sides.data()),
+            "set_ccd_images");
+    }
     check(cmi_gpu_set_continuous_source_spiral_galaxy(
               engine, _r_stars, _h_stars, _bulge_over_total),
           "set_continuous_source_spiral_galaxy");
@@ -267,12 +340,15 @@ public:
     status("Done shooting photons.");
 
     std::vector<double> image(_nx * _ny);
-    check(cmi_gpu_download_image(engine, image.data(), nullptr, nullptr),
-          "download_image");
-    if (write_output) {
-      status("Saving final image...");
-      save(image, 1. / (double)_numphoton);
-      status("Done saving image.");
+    for (size_t v = 0; v < _views.size(); ++v) {
+      check(cmi_gpu_download_image_view(engine, (int32_t)v, image.data(),
+                                        nullptr, nullptr),
+            "download_image");
+      if (write_output) {
+        status("Saving final image...");
+        save(image, 1. / (double)_numphoton, v);
+        status("Done saving image.");
+      }
     }
     const double total_seconds =
         std::chrono::duration<double>(std::chrono::steady_clock::now() -
@@ -292,9 +368,16 @@ private:
   }
 
   /* CCDImage::save, src/CCDImage.hpp:299-362 (ImageWriter.hpp) */
-  void save(const std::vector<double> &image, double normalization) const {
-    (void)write_image(_output_folder + "/" + _image_filename, _image_type,
+  void save(const std::vector<double> &image, double normalization,
+            size_t view) const {
+    (void)write_image(_output_folder + "/" + view_filename(view), _image_type,
                       image.data(), _nx, _ny, normalization);
+  }
+
+  /* view 0 keeps the file's name */
+  std::string view_filename(size_t view) const {
+    return view ? _image_filename + "_view" + std::to_string(view)
+                : _image_filename;
   }
 };
 

@@ -1016,6 +1016,76 @@ int cmi_gpu_check_sky_camera(const double box_anchor[3],
 int cmi_gpu_get_sky_camera_counters(cmi_gpu_engine *engine,
                                     uint64_t *counters);
 
+/* Several cameras in one run: views that share the packets' random walk (no
+ * counterpart in the reference). The cameras above draw no random number, so
+ * a packet's emission, optical depths and scatterings do not depend on the
+ * camera: with K views cmi_gpu_dust_shoot walks each packet once and repeats
+ * only the events - at the direct light and at every scattering, for the
+ * views 0..K-1 in this order, the event of the single camera set with view
+ * v's arguments, with its expressions in its order. View v's image is thus
+ * the single camera's image of the same seed and packets but for the order
+ * in which the atomics add, and the views of one run share their noise. A
+ * run holds cameras of one kind: K parallel views (cmi_gpu_set_ccd_images) or
+ * K point observers (cmi_gpu_set_sky_cameras). */
+#define CMI_GPU_MAX_VIEWS 64
+
+/* K = nviews CCD images of the shared resolution nx x ny: view v looks along
+ * (theta[v], phi[v]) (radians) with the image anchors[2 v + {0, 1}] and
+ * sides[2 v + {0, 1}] (m), as cmi_gpu_set_ccd_image's arguments. Allocates and
+ * clears the stack [nviews][3][nx * ny] and selects these views; a later
+ * cmi_gpu_set_ccd_image or cmi_gpu_set_sky_camera selects that single camera
+ * again, and this call replaces theirs. CMI_GPU_EINVAL, with nothing
+ * allocated and the camera selected before left as it was: nviews outside
+ * [1, CMI_GPU_MAX_VIEWS], or a view that cmi_gpu_set_ccd_image would refuse
+ * (the message names the first such view); CMI_GPU_ENOMEM, likewise, if the
+ * stack does not fit into the device's memory. Synchronous. */
+int cmi_gpu_set_ccd_images(cmi_gpu_engine *engine, int32_t nviews,
+                           const double *theta, const double *phi, int32_t nx,
+                           int32_t ny, const double *anchors,
+                           const double *sides);
+
+/* K = nviews sky cameras that share the window, the resolution and
+ * direct_light: observer v at origins[3 v + a] with the frame frames[9 v + j]
+ * and the exclusion radius exclusion_radii[v], as cmi_gpu_set_sky_camera's
+ * arguments. The stack is [nviews][3][nlon * nlat]. Selection, refusals (per
+ * view those of cmi_gpu_set_sky_camera, the message names the view) and
+ * CMI_GPU_ENOMEM as cmi_gpu_set_ccd_images; like cmi_gpu_set_sky_camera it
+ * serves the cell source only. Synchronous. */
+int cmi_gpu_set_sky_cameras(cmi_gpu_engine *engine, int32_t nviews,
+                            const double *origins, const double *frames,
+                            double lon_min, double lon_max, double lat_min,
+                            double lat_max, int32_t nlon, int32_t nlat,
+                            const double *exclusion_radii,
+                            int32_t direct_light);
+
+/* cmi_gpu_download_image for view `view` of the stack (view 0 with a single
+ * camera; cmi_gpu_download_image itself returns view 0). A view outside
+ * [0, nviews) is CMI_GPU_EINVAL. cmi_gpu_reset_image clears the whole stack
+ * and the counters of every view; cmi_gpu_get_dust_counters counts the walk
+ * and all views, cmi_gpu_get_sky_camera_counters sums over the views.
+ * cmi_gpu_dust_shoot sizes its launches from the steps per packet of the walk
+ * and all views, but with several views not below 4 times the lanes the
+ * device holds at once (2^19 packets on 256 CUs; 2^20 stays the cap): a
+ * smaller launch would leave SIMDs idle without ending sooner. */
+int cmi_gpu_download_image_view(cmi_gpu_engine *engine, int32_t view,
+                                double *I, double *Q, double *U);
+
+/* counters[4] of view `view` since the last reset = {DDA steps of the view's
+ * own marches (the direct light's and the peel-offs'), fp64 atomics into its
+ * image, events inside its exclusion radius, events outside its window}; the
+ * last two are 0 for parallel views. The steps of cmi_gpu_get_dust_counters
+ * are those of the walk (the forced first interaction and the flights
+ * between scatterings) plus these over all views. CMI_GPU_ESTATE unless
+ * several views are selected. Synchronous. */
+int cmi_gpu_get_dust_view_counters(cmi_gpu_engine *engine, int32_t view,
+                                   uint64_t *counters);
+
+/* The view that the camera-dependent probes of cmi_gpu_dust_probe (4 TRACE,
+ * 6 SKY_PEEL) follow: they run the single camera's probe for that view, so a
+ * row is exactly the single camera's row. View 0 after every call that sets
+ * a camera. */
+int cmi_gpu_select_probe_view(cmi_gpu_engine *engine, int32_t view);
+
 /* ------------------------------------------------ emission-line images -- */
 /* Ray-traced line-of-sight maps of the grid: what an observer in the
  * direction (theta, phi) sees of the cells' emissivities, with dust
