@@ -51,6 +51,11 @@ struct PacketRng {
     }
   }
 
+  /* pass over the next two draws without generating their block (the stream
+   * is counter-based: the later draws are what they would have been). Only
+   * on a block boundary - no cached double left. */
+  __device__ __forceinline__ void skip_block() { ++block; }
+
   /* draw d of the packet = word pair (d & 1) of block d / 2; draws are
    * consumed strictly in order, so one cached double is enough */
   __device__ __forceinline__ double next() {
@@ -80,6 +85,43 @@ struct PacketRng {
     cached = to_unit(c2, c3);
     have = 1;
     return to_unit(c0, c1);
+  }
+};
+
+/* Where a new packet comes from - draws 0 and 1 of its stream: the continuous
+ * source or a discrete one (PhotonSource::get_random_photon,
+ * src/PhotonSource.cpp:208-226: drawn also when there is no continuous
+ * source), and which discrete one. With no continuous source and ONE
+ * discrete source both draws can only say "source 0": their block - ten
+ * Philox rounds per packet in the key kernel and again in the transport
+ * kernel - is then passed over, not generated. (A test on the model, the same
+ * for every packet - scalar compares and one scalar load: the key kernels make
+ * it once, ahead of their loop over packets; emit_geometry makes it per
+ * packet, where it is a refill's, not the march's.) */
+struct PacketOrigin {
+  bool fixed; /* draws 0 and 1 cannot matter */
+
+  __device__ __forceinline__ explicit PacketOrigin(const ModelDev &m)
+      : fixed(m.continuous_probability == 0. && m.nsource == 1 &&
+              m.source_cumulative[0] >= 1.) {}
+
+  /* of a stream at its start; returns 0 (a discrete source: `src`) or 1 (the
+   * continuous source: src = nsource, its own draws are the caller's) */
+  __device__ __forceinline__ uint32_t draw(const ModelDev &m, PacketRng &rng,
+                                           uint32_t &src) const {
+    src = 0;
+    if (fixed) {
+      rng.skip_block();
+      return 0;
+    }
+    if (rng.next() >= m.continuous_probability) {
+      const double xs = rng.next();
+      while (xs > m.source_cumulative[src])
+        ++src;
+      return 0;
+    }
+    src = (uint32_t)m.nsource;
+    return 1;
   }
 };
 
@@ -152,6 +194,9 @@ cmi_locate_linear(double x, const double *arr, uint32_t length) {
  * Planck table is sampled in (src/PlanckPhotonSourceSpectrum.cpp:149-165) -;
  * outside [x[0], x[n - 1]] the end values (no extrapolation). A log-log
  * interval with a sample that is not positive falls back to linear. */
+/* (always inlined: called out of line, a table - a member of the model, a
+ * kernel argument - needs an address, and the kernel then keeps a copy of its
+ * arguments in scratch and reads the model from there) */
 /* ... in two steps, so that the 14 rows of a cross-section table share one
  * search: where x lies (the interval and the weight of its upper end), then a
  * row's value there */
@@ -160,8 +205,8 @@ struct TableAt {
   double linear; /* (x - x0) / (x1 - x0), 0 / 1 outside the table */
   double loglog; /* log(x / x0) / log(x1 / x0) where that exists, else < 0 */
 };
-__host__ __device__ inline TableAt cmi_table_locate(const TableDev &t,
-                                                    double x) {
+__host__ __device__ __forceinline__ TableAt
+cmi_table_locate(const TableDev &t, double x) {
   const double *xs = t.x;
   const uint32_t n = (uint32_t)t.n;
   TableAt at;
@@ -193,8 +238,8 @@ __host__ __device__ inline TableAt cmi_table_locate(const TableDev &t,
     at.loglog = log(x / x0) / log(x1 / x0);
   return at;
 }
-__host__ __device__ inline double cmi_table_row(const TableDev &t, int row,
-                                                const TableAt &at) {
+__host__ __device__ __forceinline__ double
+cmi_table_row(const TableDev &t, int row, const TableAt &at) {
   const double *ys = t.y + (size_t)row * (size_t)t.n;
   const double y0 = ys[at.lo], y1 = ys[at.lo + 1];
   if (at.linear <= 0.)
@@ -205,8 +250,8 @@ __host__ __device__ inline double cmi_table_row(const TableDev &t, int row,
     return y0 * exp(log(y1 / y0) * at.loglog);
   return y0 + (y1 - y0) * at.linear;
 }
-__host__ __device__ inline double cmi_table_value(const TableDev &t, int row,
-                                                 double x) {
+__host__ __device__ __forceinline__ double
+cmi_table_value(const TableDev &t, int row, double x) {
   return cmi_table_row(t, row, cmi_table_locate(t, x));
 }
 
@@ -501,39 +546,133 @@ __device__ inline void cmi_ionization_states_hydrogen_helium(
  * (TablesDev::metal_ct; the others are zero rows): one loop body for the 12
  * ions instead of 12 + 19 inlined fit evaluations, then the reference's
  * products and normalisations per element. */
-/* ratio_k of ion ION_C_p1 + k (the loop body below; temp_finish_kernel
- * evaluates the 12 ions of a cell side by side, one lane each) */
+/* What the balance takes from the temperature alone - the recombination
+ * rates and the charge transfer fits, up to four exponentials and a logarithm
+ * each: per metal ion ... */
+struct MetalIonTerms {
+  double alpha; /* cmi_recombination_rate(m, ion, T) */
+  double ct[3]; /* ct_eval(metal_ct[ion][0 / 1 / 2], T4): recombination with
+                   H0, ionization by H+, recombination with He0 */
+};
+/* ... and for a cell (50 doubles: too many to keep per lane, few enough to
+ * keep per wave where the cells of a wave share their temperature -
+ * ionization_kernel) */
+struct MetalTerms {
+  double alpha_H, alpha_He;
+  MetalIonTerms ion[12]; /* of ION_C_p1 + k */
+};
+
+/* the one place that evaluates them */
+__device__ __forceinline__ MetalIonTerms
+cmi_metal_ion_terms(const ModelDev &m, int ion, double T, double T4) {
+  const TablesDev *tb = m.tables;
+  MetalIonTerms t;
+  t.alpha = cmi_recombination_rate(m, ion, T);
+  t.ct[1] = ct_eval(tb->metal_ct[ion][1], T4);
+  t.ct[0] = ct_eval(tb->metal_ct[ion][0], T4);
+  t.ct[2] = ct_eval(tb->metal_ct[ion][2], T4);
+  return t;
+}
+
+/* ... and the one place that uses them: ratio_k from the terms of its ion
+ * and its normalised mean intensity */
+__device__ __forceinline__ double
+cmi_metal_ratio_of(const MetalIonTerms &t, double jion, double ne, double nh0,
+                   double nhe0, double nhp) {
+  const double num = jion + nhp * t.ct[1];
+  const double den = ne * t.alpha + nh0 * t.ct[0] + nhe0 * t.ct[2];
+  return num / den;
+}
+
+/* Where a balance gets its terms from: evaluated where they are used, every
+ * lane at its own temperature ... */
+struct MetalTermsEvaluated {
+  static constexpr bool stored = false;
+  const ModelDev &m;
+  double T, T4;
+  __device__ __forceinline__ double alpha_H() const {
+    return cmi_recombination_rate(m, ION_H_n, T);
+  }
+  __device__ __forceinline__ double alpha_He() const {
+    return cmi_recombination_rate(m, ION_He_n, T);
+  }
+  __device__ __forceinline__ MetalIonTerms ion(int ion) const {
+    return cmi_metal_ion_terms(m, ion, T, T4);
+  }
+};
+/* ... or read from a MetalTerms that cmi_metal_terms filled for the cell's
+ * temperature */
+struct MetalTermsStored {
+  static constexpr bool stored = true;
+  const MetalTerms *t;
+  __device__ __forceinline__ double alpha_H() const { return t->alpha_H; }
+  __device__ __forceinline__ double alpha_He() const { return t->alpha_He; }
+  __device__ __forceinline__ MetalIonTerms ion(int ion) const {
+    return t->ion[ion - ION_C_p1];
+  }
+};
+
+/* every term of a cell at temperature T: the calls of
+ * cmi_ionization_state_cell and cmi_metal_ratio with their arguments (the
+ * helium rate only where there is helium, as there) */
+__device__ inline void cmi_metal_terms(const ModelDev &m, double T,
+                                       MetalTerms &out) {
+  const MetalTermsEvaluated at = {m, T, T * 1.e-4};
+  out.alpha_H = at.alpha_H();
+  out.alpha_He = (m.abundance[0] != 0.) ? at.alpha_He() : 0.;
+#pragma unroll 1
+  for (int k = 0; k < 12; ++k)
+    out.ion[k] = at.ion(ION_C_p1 + k);
+}
+
+/* ratio_k of ion ION_C_p1 + k at the lane's own temperature
+ * (temp_finish_kernel evaluates the 12 ions of a cell side by side, one lane
+ * each) */
 template <class Integrals>
 __device__ __forceinline__ double
 cmi_metal_ratio(const ModelDev &m, const Integrals &j, int ion, double ne,
                 double T, double T4, double nh0, double nhe0, double nhp) {
-  const TablesDev *tb = m.tables;
-  const double alpha = cmi_recombination_rate(m, ion, T);
-  const double num = j(ion) + nhp * ct_eval(tb->metal_ct[ion][1], T4);
-  const double den = ne * alpha + nh0 * ct_eval(tb->metal_ct[ion][0], T4) +
-                     nhe0 * ct_eval(tb->metal_ct[ion][2], T4);
-  return num / den;
+  return cmi_metal_ratio_of(cmi_metal_ion_terms(m, ion, T, T4), j(ion), ne,
+                            nh0, nhe0, nhp);
 }
 
 __device__ __forceinline__ void cmi_metal_fractions(const double (&ratio)[12],
                                                     double x[CMI_NION]);
 
+template <class Terms, class Integrals>
+__device__ inline void
+cmi_ionization_states_metals_from(const Terms &terms, const Integrals &j,
+                                  double ne, double nh0, double nhe0,
+                                  double nhp, double x[CMI_NION]) {
+  double ratio[12];
+  if constexpr (Terms::stored) {
+    /* twelve quotients of loaded terms: straight-line code */
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+      ratio[k] = cmi_metal_ratio_of(terms.ion(ION_C_p1 + k), j(ION_C_p1 + k),
+                                    ne, nh0, nhe0, nhp);
+  } else {
+    /* (one copy of the fits in the code, not twelve) */
+#pragma unroll 1
+    for (int k = 0; k < 12; ++k) {
+      const double r = cmi_metal_ratio_of(terms.ion(ION_C_p1 + k),
+                                          j(ION_C_p1 + k), ne, nh0, nhe0, nhp);
+      /* static indexing keeps ratio[] in registers */
+#pragma unroll
+      for (int i = 0; i < 12; ++i)
+        if (i == k)
+          ratio[i] = r;
+    }
+  }
+  cmi_metal_fractions(ratio, x);
+}
+
 template <class Integrals>
 __device__ inline void cmi_ionization_states_metals(
     const ModelDev &m, const Integrals &j, double ne, double T, double T4,
     double nh0, double nhe0, double nhp, double x[CMI_NION]) {
-  double ratio[12];
-#pragma unroll 1
-  for (int k = 0; k < 12; ++k) {
-    const double r =
-        cmi_metal_ratio(m, j, ION_C_p1 + k, ne, T, T4, nh0, nhe0, nhp);
-    /* static indexing keeps ratio[] in registers */
-#pragma unroll
-    for (int i = 0; i < 12; ++i)
-      if (i == k)
-        ratio[i] = r;
-  }
-  cmi_metal_fractions(ratio, x);
+  const MetalTermsEvaluated terms = {m, T, T4};
+  cmi_ionization_states_metals_from(terms, j, ne, nh0, nhe0, nhp, x);
 }
 
 /* the reference's products and normalisations per element */
@@ -585,22 +724,24 @@ __device__ __forceinline__ void cmi_metal_fractions(const double (&ratio)[12],
 /* IonizationStateCalculator::calculate_ionization_state(jfac, hfac, vars),
  * src/IonizationStateCalculator.cpp:70-272. J[14] un-normalised; heating[2]
  * normalised in place; x[14] out. */
-__device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,
-                                                 double hfac, double ntot,
-                                                 double T,
-                                                 const double J[CMI_NION],
-                                                 double heating[2],
-                                                 double x[CMI_NION]) {
+/* (`terms`: the temperature-only terms of this cell's T, evaluated here or
+ * stored - MetalTermsEvaluated / MetalTermsStored) */
+template <class Terms>
+__device__ inline void
+cmi_ionization_state_cell_from(const ModelDev &m, const Terms &terms,
+                               double jfac, double hfac, double ntot, double T,
+                               const double J[CMI_NION], double heating[2],
+                               double x[CMI_NION]) {
   const double jH = jfac * J[ION_H_n];
   const double jHe = jfac * J[ION_He_n];
   heating[0] = hfac * heating[0];
   heating[1] = hfac * heating[1];
   if (jH > 0. && ntot > 0.) {
-    const double alphaH = cmi_recombination_rate(m, ION_H_n, T);
+    const double alphaH = terms.alpha_H();
     const double AHe = m.abundance[0];
     double h0, he0 = 0.;
     if (AHe != 0.) {
-      const double alphaHe = cmi_recombination_rate(m, ION_He_n, T);
+      const double alphaHe = terms.alpha_He();
       cmi_ionization_states_hydrogen_helium(alphaH, alphaHe, jH, jHe, ntot,
                                             AHe, T, h0, he0);
     } else {
@@ -610,7 +751,6 @@ __device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,
     x[ION_He_n] = he0;
     const double nhp = ntot * (1. - h0);
     const double ne = ntot * (1. - h0 + AHe * (1. - he0));
-    const double T4 = T * 1.e-4;
     const double nh0 = ntot * h0;
     const double nhe0 = ntot * he0 * AHe;
     /* normalised mean intensity of an ion, by ion index */
@@ -625,7 +765,7 @@ __device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,
         return jfac * v;
       }
     } jm = {J, jfac};
-    cmi_ionization_states_metals(m, jm, ne, T, T4, nh0, nhe0, nhp, x);
+    cmi_ionization_states_metals_from(terms, jm, ne, nh0, nhe0, nhp, x);
   } else {
 #pragma unroll
     for (int i = 0; i < CMI_NION; ++i)
@@ -639,6 +779,16 @@ __device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,
       x[ION_Ne_n] = 1.;
     }
   }
+}
+
+__device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,
+                                                 double hfac, double ntot,
+                                                 double T,
+                                                 const double J[CMI_NION],
+                                                 double heating[2],
+                                                 double x[CMI_NION]) {
+  const MetalTermsEvaluated terms = {m, T, T * 1.e-4};
+  cmi_ionization_state_cell_from(m, terms, jfac, hfac, ntot, T, J, heating, x);
 }
 
 #endif

@@ -181,14 +181,11 @@ template <bool FULL, bool EXACT>
 __device__ inline uint32_t emit_geometry(const GridDev &g, const ModelDev &m,
                                          PacketRng &rng, Packet<FULL> &p) {
   /* first uniform: continuous or discrete source (drawn also when there is
-   * no continuous source: continuous_probability = 0) */
-  double x = rng.next();
-  uint32_t origin = 0;
-  if (x >= m.continuous_probability) {
-    x = rng.next();
-    int i = 0;
-    while (x > m.source_cumulative[i])
-      ++i;
+   * no continuous source: continuous_probability = 0), second: which
+   * discrete source - PacketOrigin */
+  uint32_t i;
+  const uint32_t origin = PacketOrigin(m).draw(m, rng, i);
+  if (origin == 0) {
 #pragma unroll
     for (int a = 0; a < 3; ++a)
       p.pos[a] = m.source_position[3 * i + a];
@@ -197,7 +194,6 @@ __device__ inline uint32_t emit_geometry(const GridDev &g, const ModelDev &m,
     /* PlanarContinuousPhotonSource::get_random_incoming_direction
      * (src/PlanarContinuousPhotonSource.hpp:165-188): a point of a rectangle
      * in the plane x[axis] = intercept, an isotropic direction */
-    origin = 1;
     const int i0 = m.continuous_axis == 0 ? 1 : 0;
     const int i1 = m.continuous_axis == 2 ? 1 : 2;
     const double u0 = rng.next();
@@ -215,7 +211,6 @@ __device__ inline uint32_t emit_geometry(const GridDev &g, const ModelDev &m,
      * (src/IsotropicContinuousPhotonSource.hpp:95-191): a focus point in the
      * box, an isotropic direction through it, and the point where that line
      * enters the box */
-    origin = 1;
     double focus[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)

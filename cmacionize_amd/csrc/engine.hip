@@ -190,6 +190,10 @@ struct cmi_gpu_engine {
     int tile_min_per_item = -1; /* flights per unit of work; -1 = auto */
     int tile_refill_threshold = 48;
     bool tile_counting_sort = true; /* false: rocPRIM radix sort of the slots */
+    /* hydrogen-only cell update: the rows of 64 cells that share one
+     * temperature share its temperature-only terms (false: every lane
+     * evaluates them for its own cell) */
+    bool update_reuse = true;
     /* multi-ion runs: the cross sections of re-emitted flights in a kernel of
      * their own (flight_weights_kernel) instead of inside the interaction
      * kernels */
@@ -1688,6 +1692,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.defer_weights = value != 0;
   else if (k == "tile_counting_sort")
     e->tune.tile_counting_sort = value != 0;
+  else if (k == "update_reuse")
+    e->tune.update_reuse = value != 0;
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
   return CMI_GPU_OK;
@@ -1986,9 +1992,11 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
   else if (e->full_ions)
     ionization_kernel<true><<<blocks, CMI_BLOCK, 0, e->stream>>>(a);
   else if (e->config.track_heating)
-    ionization_kernel<false><<<blocks, CMI_BLOCK, 0, e->stream>>>(a);
+    ionization_kernel<false, true>
+        <<<blocks, CMI_BLOCK, 0, e->stream>>>(a, e->tune.update_reuse ? 1 : 0);
   else
-    ionization_kernel<false, false><<<blocks, CMI_BLOCK, 0, e->stream>>>(a);
+    ionization_kernel<false, false>
+        <<<blocks, CMI_BLOCK, 0, e->stream>>>(a, e->tune.update_reuse ? 1 : 0);
   HIP_TRY(hipGetLastError());
   CMI_TRY(timer_end(e, e->update_events, ev, 0));
   return CMI_GPU_OK;

@@ -2933,6 +2933,7 @@ direction_key_batches(const KeyArgs &a) {
   __shared__ uint32_t s_count[CMI_VERNER_NCLASS];
   const uint32_t lo_bits = a.dir_bits - a.dir_hi_bits;
   const uint64_t stride = (uint64_t)gridDim.x * BATCH;
+  const PacketOrigin from(a.model);
   for (uint64_t base = (uint64_t)blockIdx.x * BATCH; base < a.n_packets;
        base += stride) {
     const unsigned int n = a.n_packets - base < BATCH
@@ -2950,15 +2951,9 @@ direction_key_batches(const KeyArgs &a) {
       const uint64_t id =
           a.select ? (uint64_t)a.select[base + local] : base + local;
       rng.init(a.seed, a.iteration, a.first_packet + id);
-      const uint32_t origin =
-          rng.next() >= a.model.continuous_probability ? 0u : 1u;
-      uint32_t src = 0;
-      if (origin == 0) {
-        const double xs = rng.next(); /* source pick */
-        while (xs > a.model.source_cumulative[src])
-          ++src;
-      } else {
-        src = (uint32_t)a.model.nsource;
+      uint32_t src;
+      const uint32_t origin = from.draw(a.model, rng, src);
+      if (origin != 0) {
         (void)rng.next();
         (void)rng.next();
         if (a.model.continuous_type == 1)
@@ -3027,22 +3022,17 @@ __global__ void __launch_bounds__(CMI_BLOCK, 5)
     direction_key_kernel(const KeyArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   const uint32_t lo_bits = a.dir_bits - a.dir_hi_bits;
+  const PacketOrigin from(a.model);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < a.n_packets; i += stride) {
     PacketRng rng;
     const uint64_t id = a.select ? (uint64_t)a.select[i] : i;
     rng.init(a.seed, a.iteration, a.first_packet + id);
-    const uint32_t origin =
-        rng.next() >= a.model.continuous_probability ? 0u : 1u;
-    uint32_t src = 0;
-    if (origin == 0) {
-      const double xs = rng.next(); /* source pick */
-      while (xs > a.model.source_cumulative[src])
-        ++src;
-    } else {
-      /* the continuous source: one more "source", its packets ordered by
-       * direction like the others (they enter all over the box) */
-      src = (uint32_t)a.model.nsource;
+    uint32_t src;
+    const uint32_t origin = from.draw(a.model, rng, src);
+    if (origin != 0) {
+      /* the continuous source: one more "source" (src = nsource), its packets
+       * ordered by direction like the others (they enter all over the box) */
       (void)rng.next(); /* the focus point, or the point in the plane */
       (void)rng.next();
       if (a.model.continuous_type == 1)
@@ -3094,8 +3084,8 @@ struct UpdateArgs {
 };
 
 /* IonizationStateCalculator::calculate_ionization_state over the grid
- * (src/IonizationStateCalculator.cpp:511-530 -> :70-272), one cell per lane,
- * grid-stride; also rebuilds the transport record of each cell. */
+ * (src/IonizationStateCalculator.cpp:511-530 -> :70-272), one cell per lane;
+ * also rebuilds the transport record of each cell. */
 /* HEATING = false: a hydrogen-only run that does not track the heating terms
  * (no transport kernel adds to them, no temperature solve reads them): their
  * two fields are neither read nor normalised. */
@@ -3104,6 +3094,48 @@ struct UpdateArgs {
 #ifndef CMI_IONIZATION_WAVES
 #define CMI_IONIZATION_WAVES 4
 #endif
+/* a cell's integrals in, ... */
+template <bool FULL, bool HEATING>
+__device__ __forceinline__ void
+ionization_load_cell(const UpdateArgs &a, int64_t c, double (&J)[CMI_NION],
+                     double (&heating)[2]) {
+  if (FULL) {
+#pragma unroll
+    for (int i = 0; i < CMI_NION; ++i)
+      J[i] = (*acc_at(a.cells, i, c));
+  } else {
+    J[0] = (*acc_at(a.cells, 0, c));
+#pragma unroll
+    for (int i = 1; i < CMI_NION; ++i)
+      J[i] = 0.;
+  }
+  heating[0] = HEATING ? (*acc_at(a.cells, CMI_NION, c)) : 0.;
+  heating[1] = HEATING ? (*acc_at(a.cells, CMI_NION + 1, c)) : 0.;
+}
+/* ... its balance, from temperature-only terms evaluated per lane or stored,
+ * and its fractions, heating terms and transport record out */
+template <bool HEATING, class Terms>
+__device__ __forceinline__ void
+ionization_update_cell(const UpdateArgs &a, int64_t c, double ntot, double T,
+                       const double (&J)[CMI_NION], double (&heating)[2],
+                       const Terms &terms) {
+  double x[CMI_NION];
+  cmi_ionization_state_cell_from(a.model, terms, a.jfac, a.hfac, ntot, T, J,
+                                 heating, x);
+#pragma unroll
+  for (int i = 0; i < CMI_NION; ++i)
+    a.cells.x[i][c] = x[i];
+  if (HEATING) {
+    (*acc_at(a.cells, CMI_NION, c)) = heating[0];
+    (*acc_at(a.cells, CMI_NION + 1, c)) = heating[1];
+  }
+  a.cells.opacity[c] = (ntot > 0.)
+                           ? make_double2(ntot * x[ION_H_n], ntot * x[ION_He_n])
+                           : make_double2(-1., 0.);
+}
+
+/* every ion (and, before the reuse below, hydrogen only): grid-stride, every
+ * lane evaluates every term of its cell */
 template <bool FULL, bool HEATING = true>
 __global__ void __launch_bounds__(CMI_BLOCK, FULL ? 2 : CMI_IONIZATION_WAVES)
     ionization_kernel(const UpdateArgs a) {
@@ -3112,30 +3144,92 @@ __global__ void __launch_bounds__(CMI_BLOCK, FULL ? 2 : CMI_IONIZATION_WAVES)
        c < a.first + a.count; c += stride) {
     const double ntot = a.cells.number_density[c];
     const double T = a.cells.temperature[c];
-    double J[CMI_NION], heating[2], x[CMI_NION];
-    if (FULL) {
-#pragma unroll
-      for (int i = 0; i < CMI_NION; ++i)
-        J[i] = (*acc_at(a.cells, i, c));
-    } else {
-      J[0] = (*acc_at(a.cells, 0, c));
-#pragma unroll
-      for (int i = 1; i < CMI_NION; ++i)
-        J[i] = 0.;
+    double J[CMI_NION], heating[2];
+    ionization_load_cell<FULL, HEATING>(a, c, J, heating);
+    const MetalTermsEvaluated terms = {a.model, T, T * 1.e-4};
+    ionization_update_cell<HEATING>(a, c, ntot, T, J, heating, terms);
+  }
+}
+
+/* Hydrogen only (the overload with `reuse`): the metals' twelve ratios are
+ * still evaluated and written (x[2..13] are part of the result), and what they
+ * cost is their recombination rates and charge transfer fits - 50 values that
+ * depend on the temperature alone, which no kernel of such a run changes and
+ * which is usually the same in every cell. So a wave takes the cells in
+ * chunks of CMI_UPDATE_CHUNK_ROWS consecutive rows of 64 (chunk after chunk,
+ * grid-stride) and keeps the terms of one temperature in LDS: a row whose
+ * cells all have that temperature, bit for bit, reads them; a row with one
+ * other temperature replaces them; a row whose cells differ among themselves
+ * evaluates them per lane as before. reuse == 0: every row per lane - on the
+ * same walk, so the two settings differ in the reuse alone. The arithmetic is
+ * the same functions on the same values either way (MetalTermsEvaluated /
+ * MetalTermsStored): the results are equal bit for bit. */
+/* (the launch has a lane per cell up to 8 blocks per CU: on a grid that does
+ * not fill it, the waves beyond the number of chunks find none and end) */
+#ifndef CMI_UPDATE_CHUNK_ROWS
+#define CMI_UPDATE_CHUNK_ROWS 8
+#endif
+template <bool FULL, bool HEATING>
+__global__ void __launch_bounds__(CMI_BLOCK, CMI_IONIZATION_WAVES)
+    ionization_kernel(const UpdateArgs a, const int reuse) {
+  static_assert(!FULL, "the reuse path is the hydrogen-only update's");
+  constexpr int WAVES = CMI_BLOCK / 64;
+  __shared__ MetalTerms s_terms[WAVES];
+  const int wave_in_block =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  MetalTerms &stored = s_terms[wave_in_block];
+  const int64_t rows = (a.count + 63) >> 6;
+  const int64_t chunks =
+      (rows + CMI_UPDATE_CHUNK_ROWS - 1) / CMI_UPDATE_CHUNK_ROWS;
+  const int64_t nwaves = (int64_t)gridDim.x * WAVES;
+  const int64_t end = a.first + a.count;
+  /* the temperature the stored terms were made for (its bits; none yet) */
+  unsigned long long stored_for = 0;
+  bool have = false;
+  for (int64_t chunk = (int64_t)blockIdx.x * WAVES + wave_in_block;
+       chunk < chunks; chunk += nwaves) {
+    for (int64_t row = chunk * CMI_UPDATE_CHUNK_ROWS;
+         row < (chunk + 1) * CMI_UPDATE_CHUNK_ROWS && row < rows; ++row) {
+      const int64_t c = a.first + (row << 6) + (int64_t)(threadIdx.x & 63u);
+      if (c >= end)
+        continue; /* (lanes past the end of the last row) */
+      const double ntot = a.cells.number_density[c];
+      const double T = a.cells.temperature[c];
+      double J[CMI_NION], heating[2];
+      ionization_load_cell<FULL, HEATING>(a, c, J, heating);
+      /* one temperature in all of the row's lanes? (wave-uniform answers:
+       * the branches below are scalar) */
+      const unsigned long long bits =
+          (unsigned long long)__double_as_longlong(T);
+      const unsigned long long first =
+          ((unsigned long long)__builtin_amdgcn_readfirstlane(
+               (uint32_t)(bits >> 32))
+           << 32) |
+          __builtin_amdgcn_readfirstlane((uint32_t)bits);
+      bool use_stored = false;
+      if (reuse != 0 && wave_ballot(bits != first) == 0ull) {
+        /* (terms nobody reads are not made: a row of neutral or empty cells) */
+        if (!(have && stored_for == first) &&
+            wave_ballot(a.jfac * J[ION_H_n] > 0. && ntot > 0.) != 0ull) {
+          /* every lane of the row writes the same values: whichever lanes a
+           * later row has, each reads what the wave wrote */
+          cmi_metal_terms(a.model, T, stored);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          stored_for = first;
+          have = true;
+        }
+        use_stored = have && stored_for == first;
+      }
+      if (use_stored) {
+        const MetalTermsStored terms = {&stored};
+        ionization_update_cell<HEATING>(a, c, ntot, T, J, heating, terms);
+      } else {
+        const MetalTermsEvaluated terms = {a.model, T, T * 1.e-4};
+        ionization_update_cell<HEATING>(a, c, ntot, T, J, heating, terms);
+      }
     }
-    heating[0] = HEATING ? (*acc_at(a.cells, CMI_NION, c)) : 0.;
-    heating[1] = HEATING ? (*acc_at(a.cells, CMI_NION + 1, c)) : 0.;
-    cmi_ionization_state_cell(a.model, a.jfac, a.hfac, ntot, T, J, heating, x);
-#pragma unroll
-    for (int i = 0; i < CMI_NION; ++i)
-      a.cells.x[i][c] = x[i];
-    if (HEATING) {
-      (*acc_at(a.cells, CMI_NION, c)) = heating[0];
-      (*acc_at(a.cells, CMI_NION + 1, c)) = heating[1];
-    }
-    a.cells.opacity[c] = (ntot > 0.)
-                             ? make_double2(ntot * x[ION_H_n], ntot * x[ION_He_n])
-                             : make_double2(-1., 0.);
   }
 }
 

@@ -603,6 +603,12 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *   "tile_counting_sort" (1)  the slots are put in tile order by counting
  *                           (per-tile counters in LDS; up to 32768 tiles) -
  *                           0: by rocPRIM's radix sort
+ *   "update_reuse" (1)      hydrogen-only cell update: the recombination rates
+ *                           and charge transfer fits of the metals' balance
+ *                           depend on the temperature alone; a wave keeps
+ *                           those of one temperature and every row of 64
+ *                           cells that all have it, bit for bit, reads them
+ *                           (same results) - 0: every cell evaluates them
  *   "timing" (0)            record HIP events around every launch for
  *                           cmi_gpu_get_timing / _kernel_timing /
  *                           _launch_times (off: a run creates no events)
