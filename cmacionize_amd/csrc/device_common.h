@@ -36,6 +36,8 @@ enum { TYPE_PRIMARY = 0, TYPE_DIFFUSE_HI, TYPE_DIFFUSE_HeI, TYPE_ABSORBED };
 #define CMI_LIGHTSPEED 299792458.
 #define CMI_ELECTRONVOLT 1.6021766208e-19
 #define CMI_ELECTRON_MASS 9.10938356e-31
+/* the atomic mass unit of the same CODATA set (the reference has none) */
+#define CMI_ATOMIC_MASS_UNIT 1.660539040e-27
 
 #define CMI_MAX_SOURCES_INLINE 8
 

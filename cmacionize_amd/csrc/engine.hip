@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include "dust_kernels.h"
 #include "line_image_kernels.h"
+#include "line_cube_kernels.h"
 #include "sky_image_kernels.h"
 #include "sort.h"
 
@@ -243,6 +244,8 @@ struct cmi_gpu_engine {
   int dust_source = DUST_SOURCE_GALAXY;
   CellSourceDev cell_source = {};
   double *cell_source_cells = nullptr, *cell_source_blocks = nullptr;
+  /* cmi_gpu_set_cell_velocities: [3][ncell], m s^-1; null: at rest */
+  double *cell_velocities = nullptr;
   std::vector<double> cell_source_blocks_host;
   bool have_cell_source = false, cell_source_from_cells = false;
   uint64_t cells_epoch = 0, cell_source_epoch = 0;
@@ -1157,6 +1160,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->dust_opacity);
   (void)hipFree(e->dust_counters);
   (void)hipFree(e->cell_source_cells);
+  (void)hipFree(e->cell_velocities);
   (void)hipFree(e->cell_source_blocks);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
@@ -3694,6 +3698,313 @@ int cmi_gpu_line_image_probe(cmi_gpu_engine *e, double theta, double phi,
   (void)hipFree(dxy);
   (void)hipFree(drows);
   HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------------ spectral line cubes -- */
+extern "C++" {
+namespace {
+/* device buffers of one cube call, freed however it ends */
+struct LineCubeBuffers {
+  double *records = nullptr, *samples = nullptr, *cube = nullptr,
+         *fields = nullptr, *widths = nullptr, *extinction = nullptr,
+         *velocity = nullptr;
+  ~LineCubeBuffers() {
+    (void)hipFree(records);
+    (void)hipFree(samples);
+    (void)hipFree(cube);
+    (void)hipFree(fields);
+    (void)hipFree(widths);
+    (void)hipFree(extinction);
+    (void)hipFree(velocity);
+  }
+};
+
+/* the velocity axis of a cube call */
+struct LineCubeAxis {
+  int32_t nchan;
+  double vmin, dv;
+};
+
+int line_cube_axis(const char *what, int32_t nplanes, int32_t nx, int32_t ny,
+                   int32_t nchan, double vmin, double vmax,
+                   LineCubeAxis &axis) {
+  if (nchan < 1)
+    return fail(CMI_GPU_EINVAL, "%s: at least one velocity channel (%d asked "
+                "for)", what, (int)nchan);
+  if (!std::isfinite(vmin) || !std::isfinite(vmax) || !(vmax > vmin) ||
+      !std::isfinite(vmax - vmin))
+    return fail(CMI_GPU_EINVAL, "%s: the velocity range must be finite with "
+                "vmax > vmin", what);
+  /* (nx ny <= 2^28 has been checked, so the products below cannot overflow) */
+  if ((int64_t)nplanes * nchan > (1ll << 28) ||
+      (int64_t)nplanes * nchan * ((int64_t)nx * ny) > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %d x %d pixels: a "
+                "cube has at most 2^28 values", what, (int)nplanes, (int)nchan,
+                (int)nx, (int)ny);
+  axis.nchan = nchan;
+  axis.vmin = vmin;
+  axis.dv = (vmax - vmin) / nchan;
+  return CMI_GPU_OK;
+}
+
+/* refuses a device array of n velocities of which one is not finite */
+int line_cube_check_velocities(cmi_gpu_engine *e, const char *what,
+                               const double *velocity, int64_t n) {
+  unsigned int *ninvalid = nullptr;
+  HIP_TRY(hipMalloc(&ninvalid, sizeof(unsigned int)));
+  unsigned int bad = 0;
+  hipError_t err = hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream);
+  if (err == hipSuccess) {
+    cell_velocity_check_kernel<<<grid_blocks(e, n, 8), 256, 0, e->stream>>>(
+        velocity, n, ninvalid);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                         e->stream);
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  (void)hipFree(ninvalid);
+  HIP_TRY(err);
+  if (bad)
+    return fail(CMI_GPU_EINVAL, "%s: %u velocity component(s) are not finite",
+                what, bad);
+  return CMI_GPU_OK;
+}
+
+/* the cube [nl][nchan][nx * ny] of the records [ncell][2 + 2 nl] into b.cube
+ * (device): per chunk of pixel rows and per block of CB channels one march
+ * launch for the nl lines */
+int line_cube_march(cmi_gpu_engine *e, const LineViewDev &v, int nl,
+                    const LineCubeAxis &axis, LineCubeBuffers &b) {
+  constexpr int CB = CMI_LINE_CUBE_CB;
+  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
+  const int64_t npixel = (int64_t)v.nx * v.ny;
+  const int64_t NY = (int64_t)v.ny * v.s;
+  /* pixel rows per launch: the sample buffer holds CB channels of them */
+  const int64_t rows = std::max<int64_t>(
+      1, std::min<int64_t>(v.nx, (CMI_LINE_IMAGE_LAUNCH_SAMPLES / CB) /
+                                     (NY * v.s)));
+  const int64_t chunk_samples = rows * v.s * NY;
+  if (v.s > 1 && !b.samples)
+    HIP_TRY(hipMalloc(&b.samples, sizeof(double) * (size_t)chunk_samples * CB *
+                                      CMI_LINE_IMAGE_BATCH));
+  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
+  for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
+    const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
+    for (int32_t c0 = 0; c0 < axis.nchan; c0 += CB) {
+      LineCubeMarchArgs a;
+      a.grid = e->grid;
+      a.view = v;
+      a.records = b.records;
+      a.nd = 2 + 2 * nl;
+      a.sx0 = (int32_t)(ix0 * v.s);
+      a.sx1 = (int32_t)(ix1 * v.s);
+      a.c0 = c0;
+      a.nc = std::min<int32_t>(CB, axis.nchan - c0);
+      a.vmin = axis.vmin;
+      a.dv = axis.dv;
+      if (v.s > 1) {
+        a.out = b.samples;
+        a.line_stride = CB * chunk_samples;
+        a.channel_stride = chunk_samples;
+      } else {
+        a.out = b.cube + c0 * npixel + ix0 * v.ny;
+        a.line_stride = axis.nchan * npixel;
+        a.channel_stride = npixel;
+      }
+      const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
+      line_cube_march_kernel<CB>
+          <<<dim3((unsigned)(tiles_x * tiles_y), (unsigned)nl), 256, 0,
+             e->stream>>>(a);
+      HIP_TRY(hipGetLastError());
+      if (v.s > 1) {
+        /* the images' reduction, a line's channels in the place of lines */
+        const int64_t work = (ix1 - ix0) * v.ny * a.nc;
+        for (int l = 0; l < nl; ++l) {
+          line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
+                                     e->stream>>>(
+              b.samples + l * a.line_stride, chunk_samples, a.nc, (int32_t)ix0,
+              (int32_t)ix1, v.ny, v.s, npixel,
+              b.cube + ((int64_t)l * axis.nchan + c0) * npixel);
+          HIP_TRY(hipGetLastError());
+        }
+      }
+    }
+  }
+  return CMI_GPU_OK;
+}
+} // namespace
+} // extern "C++"
+
+double cmi_gpu_emission_line_atomic_weight(int32_t line) {
+  return (line < 0 || line >= CMI_NEMISSIONLINE)
+             ? 0.
+             : cmi_emission_atomic_weight[line];
+}
+
+int cmi_gpu_set_cell_velocities(cmi_gpu_engine *e, const double *velocities) {
+  static const char *what = "set_cell_velocities";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!velocities) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    (void)hipFree(e->cell_velocities);
+    e->cell_velocities = nullptr;
+    return CMI_GPU_OK;
+  }
+  const size_t n = 3 * (size_t)e->ncell;
+  double *fresh = nullptr;
+  HIP_TRY(hipMalloc(&fresh, sizeof(double) * n));
+  hipError_t err =
+      hipMemcpy(fresh, velocities, sizeof(double) * n, hipMemcpyHostToDevice);
+  int rc = CMI_GPU_OK;
+  if (err != hipSuccess)
+    rc = fail(CMI_GPU_EDEVICE, "%s: upload failed: %s", what,
+              hipGetErrorString(err));
+  else
+    rc = line_cube_check_velocities(e, what, fresh, (int64_t)n);
+  if (rc) {
+    /* the previous state is kept */
+    (void)hipFree(fresh);
+    return rc;
+  }
+  (void)hipFree(e->cell_velocities);
+  e->cell_velocities = fresh;
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_line_cube(cmi_gpu_engine *e, int32_t nlines,
+                             const int32_t *lines, double theta, double phi,
+                             int32_t nx, int32_t ny, const double *anchor,
+                             const double *sides, int32_t supersample,
+                             double dust_cross_section, int32_t nchan,
+                             double vmin, double vmax, double sigma_turb,
+                             double *cube) {
+  static const char *what = "render_line_cube";
+  if (!e || !lines || !cube)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
+    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
+                (int)nlines, CMI_NEMISSIONLINE);
+  for (int32_t l = 0; l < nlines; ++l) {
+    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
+      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
+                  (int)lines[l]);
+    if (cmi_emission_atomic_weight[lines[l]] == 0.)
+      return fail(CMI_GPU_EINVAL, "%s: entry %d is not the line of one ion: "
+                  "it has no line profile", what, (int)lines[l]);
+  }
+  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
+    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
+                what);
+  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
+    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
+                "be >= 0 and finite", what);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, nlines, nx, ny, nchan, vmin, vmax, axis));
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t nvalue = (size_t)nx * ny * nchan; /* of one line */
+  LineCubeBuffers b;
+  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records,
+                    sizeof(double) * (size_t)e->ncell * (2 + 2 * nb)));
+  HIP_TRY(hipMalloc(&b.cube, sizeof(double) * nvalue * nb));
+  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
+    LineCubeRecordArgs r;
+    r.model = e->model;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.nlines = nl;
+    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l) {
+      r.lines[l] = l < nl ? lines[first + l] : 0;
+      r.weight[l] = l < nl ? cmi_emission_atomic_weight[lines[first + l]] : 1.;
+    }
+    r.dust_cross_section = dust_cross_section;
+    r.sigma_turb = sigma_turb;
+    for (int a = 0; a < 3; ++a)
+      r.n[a] = v.n[a];
+    r.velocity = e->cell_velocities;
+    r.records = b.records;
+    line_cube_record_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
+                              e->stream>>>(r);
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(line_cube_march(e, v, nl, axis, b));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(cube + (size_t)first * nvalue, b.cube,
+                      sizeof(double) * nvalue * nl, hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_field_cube(cmi_gpu_engine *e, int32_t nfields,
+                              const double *fields, const double *extinction,
+                              const double *velocity, const double *widths,
+                              double theta, double phi, int32_t nx, int32_t ny,
+                              const double *anchor, const double *sides,
+                              int32_t supersample, int32_t nchan, double vmin,
+                              double vmax, double *cube) {
+  static const char *what = "render_field_cube";
+  if (!e || !fields || !widths || !cube)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nfields < 1 || nfields > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
+                what, (int)nfields);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, nfields, nx, ny, nchan, vmin, vmax, axis));
+  const size_t ncell = (size_t)e->ncell;
+  for (size_t i = 0; i < ncell * (size_t)nfields; ++i)
+    if (!(widths[i] >= 0.) || !std::isfinite(widths[i]))
+      return fail(CMI_GPU_EINVAL, "%s: the width of field %lld in cell %lld "
+                  "is negative or not finite", what, (long long)(i / ncell),
+                  (long long)(i % ncell));
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t nvalue = (size_t)nx * ny * nchan; /* of one field */
+  LineCubeBuffers b;
+  if (velocity) {
+    HIP_TRY(hipMalloc(&b.velocity, sizeof(double) * 3 * ncell));
+    HIP_TRY(hipMemcpy(b.velocity, velocity, sizeof(double) * 3 * ncell,
+                      hipMemcpyHostToDevice));
+    CMI_TRY(line_cube_check_velocities(e, what, b.velocity,
+                                       3 * (int64_t)ncell));
+  }
+  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
+  HIP_TRY(hipMalloc(&b.records, sizeof(double) * ncell * (2 + 2 * nb)));
+  HIP_TRY(hipMalloc(&b.cube, sizeof(double) * nvalue * nb));
+  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
+  HIP_TRY(hipMalloc(&b.widths, sizeof(double) * ncell * nb));
+  if (extinction) {
+    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
+    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice));
+  }
+  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
+    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
+    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b.widths, widths + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    field_cube_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
+                               e->stream>>>(
+        b.fields, b.widths, b.extinction, b.velocity, v.n[0], v.n[1], v.n[2],
+        e->ncell, nl, b.records);
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(line_cube_march(e, v, nl, axis, b));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(cube + (size_t)first * nvalue, b.cube,
+                      sizeof(double) * nvalue * nl, hipMemcpyDeviceToHost));
+  }
   return CMI_GPU_OK;
 }
 

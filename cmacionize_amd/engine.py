@@ -119,6 +119,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_set_ccd_images", "cmi_gpu_set_sky_cameras",
     "cmi_gpu_download_image_view", "cmi_gpu_get_dust_view_counters",
     "cmi_gpu_select_probe_view",
+    "cmi_gpu_set_cell_velocities", "cmi_gpu_render_line_cube",
+    "cmi_gpu_render_field_cube", "cmi_gpu_emission_line_atomic_weight",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -132,6 +134,49 @@ EMISSION_LINES = [
     "avg_nH_nHe", "avg_nH_nHe_count", "NeII_12mu", "NIII_57mu", "NeIII_15mu",
     "NII_122mu", "CII_158mu", "CII_2325", "CIII_1908", "OII_7325", "SIV_10mu",
     "HeI_5876", "Hrec_s", "WFC2_F439W", "WFC2_F555W", "WFC2_F675W"]
+
+# standard atomic weights of the emitting elements: the entries of
+# EMISSION_LINES that are the line of one ion, hence have a spectral cube
+_ELEMENT_WEIGHTS = {"H": 1.00794, "He": 4.002602, "C": 12.0107, "N": 14.0067,
+                    "O": 15.9994, "Ne": 20.1797, "S": 32.065}
+
+
+def _line_element(name):
+    if name in ("HAlpha", "HBeta"):
+        return "H"
+    for element in ("He", "Ne", "C", "N", "O", "S"):
+        if name.startswith(element + "I"):
+            return element
+    return None
+
+
+LINE_ATOMIC_WEIGHTS = {name: _ELEMENT_WEIGHTS[_line_element(name)]
+                       for name in EMISSION_LINES
+                       if name != "HII" and _line_element(name)}
+
+
+def cube_channel_centres(nchan, vmin, vmax):
+    """Centres (m s^-1) of the channels of a cube over [vmin, vmax): the
+    means of the edges vmin + c * dv."""
+    dv = (vmax - vmin) / nchan
+    edges = vmin + np.arange(nchan + 1) * dv
+    return 0.5 * (edges[:-1] + edges[1:])
+
+
+def cube_moments(cube, centres):
+    """Moments of a cube (..., nchan, nx, ny) along its channel axis: moment
+    0 (the sum over channels), the intensity-weighted mean velocity and the
+    dispersion about it, each (..., nx, ny); the last two are NaN where
+    moment 0 is 0."""
+    cube = np.asarray(cube, dtype=np.float64)
+    v = np.asarray(centres, dtype=np.float64)[:, None, None]
+    m0 = cube.sum(axis=-3)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(m0 == 0., np.nan, (cube * v).sum(axis=-3) / m0)
+        var = (cube * (v - mean[..., None, :, :]) ** 2).sum(axis=-3) / m0
+        sigma = np.where(m0 == 0., np.nan, np.sqrt(np.maximum(var, 0.)))
+    return m0, mean, sigma
+
 
 _lib = None
 
@@ -277,6 +322,17 @@ def load_library():
     L.cmi_gpu_render_field_images.argtypes = [
         vp, C.c_int32, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp,
         _dp, C.c_int32, _dp, _dp]
+    L.cmi_gpu_set_cell_velocities.argtypes = [vp, _dp]
+    L.cmi_gpu_emission_line_atomic_weight.argtypes = [C.c_int32]
+    L.cmi_gpu_emission_line_atomic_weight.restype = C.c_double
+    L.cmi_gpu_render_line_cube.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), C.c_double, C.c_double,
+        C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double, C.c_int32,
+        C.c_double, C.c_double, C.c_double, _dp]
+    L.cmi_gpu_render_field_cube.argtypes = [
+        vp, C.c_int32, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32,
+        C.c_int32, _dp, _dp, C.c_int32, C.c_int32, C.c_double, C.c_double,
+        _dp]
     L.cmi_gpu_set_dust_scattering_per_hydrogen.argtypes = [
         vp, C.c_double, C.c_double, C.c_double, C.c_double]
     L.cmi_gpu_set_cell_source_line.argtypes = [vp, C.c_int32]
@@ -1118,6 +1174,61 @@ class GpuEngine:
         out = np.zeros((len(xy), 3 + 2 * max_cells))
         self._check(self._lib.cmi_gpu_line_image_probe(
             self._h, theta, phi, len(xy), _p(xy), max_cells, _p(out)))
+        return out
+
+    # spectral line cubes ----------------------------------------------------
+    def set_cell_velocities(self, velocities):
+        """The cells' bulk velocities for render_line_cube: (3, ncell) in
+        m s^-1, in the engine's cell order; None puts every cell at rest."""
+        if velocities is None:
+            self._check(self._lib.cmi_gpu_set_cell_velocities(self._h, None))
+            return
+        v = _f64(velocities).reshape(3, self.n)
+        self._check(self._lib.cmi_gpu_set_cell_velocities(self._h, _p(v)))
+
+    def render_line_cube(self, lines, theta, phi, nx, ny, anchor, sides,
+                         nchan, vmin, vmax, supersample=1,
+                         dust_cross_section=0., sigma_turb=0.):
+        """render_line_images resolved in radial velocity: {name: (nchan, nx,
+        ny) array}, W m^-2 sr^-1 per channel, for `nchan` channels of equal
+        width over [vmin, vmax) m s^-1 (positive: receding). Each cell's
+        emission is shifted by its velocity (set_cell_velocities) along the
+        view and spread by the thermal width of the emitting ion plus
+        `sigma_turb` (include/cmi_gpu.h, cmi_gpu_render_line_cube). Only
+        names of LINE_ATOMIC_WEIGHTS have a cube."""
+        names = list(lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(names), max(int(nchan), 0), max(int(nx), 0),
+                        max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_line_cube(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
+            dust_cross_section, int(nchan), vmin, vmax, sigma_turb, _p(out)))
+        return dict(zip(names, out))
+
+    def render_field_cube(self, fields, widths, theta, phi, nx, ny, anchor,
+                          sides, nchan, vmin, vmax, supersample=1,
+                          extinction=None, velocity=None):
+        """The same cubes of any per-cell sources: fields[nfields][ncell]
+        with the Gaussian widths[nfields][ncell] (b = sqrt(2) sigma, m s^-1),
+        the optional extinction[ncell] (m^-1) and velocity[3][ncell]
+        (m s^-1); (nfields, nchan, nx, ny)."""
+        f = _f64(fields).reshape(-1, self.n)
+        w = _f64(widths).reshape(len(f), self.n)
+        k = None if extinction is None else _f64(extinction).reshape(self.n)
+        v = None if velocity is None else _f64(velocity).reshape(3, self.n)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(f), max(int(nchan), 0), max(int(nx), 0),
+                        max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_field_cube(
+            self._h, len(f), _p(f), _p(k) if k is not None else None,
+            _p(v) if v is not None else None, _p(w), theta, phi, int(nx),
+            int(ny), _p(a), _p(s), int(supersample), int(nchan), vmin, vmax,
+            _p(out)))
         return out
 
     # sky maps ---------------------------------------------------------------

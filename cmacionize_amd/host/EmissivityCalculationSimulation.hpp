@@ -84,6 +84,21 @@
  * renderer; with scattering all views are filled by one Monte Carlo run per
  * line (cmi_gpu_set_ccd_images, cmi_gpu_set_sky_cameras), so they share its
  * noise.
+ * Spectral cubes (read only if "velocity channels" is there):
+ *   EmissionImages:velocity channels             the number of channels
+ *   EmissionImages:velocity minimum / velocity maximum   required, velocities
+ *   EmissionImages:turbulent velocity dispersion 0. m s^-1
+ *   EmissionImages:velocity field type           Static, or one of
+ *     SolidBodyRotation: "angular velocity" (required, a frequency),
+ *       "rotation axis" ([0, 0, 1]), "rotation centre" (the origin);
+ *       v = omega axis x (r - centre)
+ *     RadialExpansion: "expansion velocity" v0 and "expansion radius" r0
+ *       (required), "expansion centre" (the origin); v = v0 (r - centre) / r0
+ *     Snapshot: /PartType0/Velocities of the snapshot
+ * Every flagged line that is the line of one ion is then also written as
+ * <prefix>_<LineName>_cube.dat (_cube_view<k>.dat for view k >= 1): raw
+ * doubles, [channel][ix][iy], next to its integrated image; the other flagged
+ * entries keep their image and are named on stderr. PGM cannot hold a cube.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -130,6 +145,107 @@ class EmissivityCalculationSimulation {
     };
     long long nviews = 1;
     std::vector<View> views;
+
+    /* spectral cubes (read only if "velocity channels" is there) */
+    bool cubes = false;
+    long long nchan = 0;
+    double vmin = 0., vmax = 0., sigma_turb = 0.;
+    std::string velocity_field = "Static";
+    double angular_velocity = 0., expansion_velocity = 0.,
+           expansion_radius = 1.;
+    std::array<double, 3> rotation_axis = {0., 0., 1.},
+                          field_centre = {0., 0., 0.};
+
+    void read_cubes(ParameterFile &params) {
+      if (!params.has_value("EmissionImages:velocity channels"))
+        return;
+      cubes = true;
+      nchan = params.get_integer("EmissionImages:velocity channels", 1);
+      if (nchan < 1)
+        throw ParameterError("EmissionImages:velocity channels must be at "
+                             "least 1");
+      if (type != "BinaryArray")
+        throw ParameterError("EmissionImages:velocity channels needs type "
+                             "BinaryArray: a cube is written as raw doubles");
+      for (const char *key : {"EmissionImages:velocity minimum",
+                              "EmissionImages:velocity maximum"})
+        if (!params.has_value(key))
+          throw ParameterError(std::string(key) + " is required with "
+                               "EmissionImages:velocity channels");
+      vmin = params.get_physical_value(
+          QUANTITY_VELOCITY, "EmissionImages:velocity minimum", "0. m s^-1");
+      vmax = params.get_physical_value(
+          QUANTITY_VELOCITY, "EmissionImages:velocity maximum", "0. m s^-1");
+      if (!(vmax > vmin) || !std::isfinite(vmax - vmin))
+        throw ParameterError("EmissionImages:velocity maximum must be above "
+                             "velocity minimum, both finite");
+      sigma_turb = params.get_physical_value(
+          QUANTITY_VELOCITY, "EmissionImages:turbulent velocity dispersion",
+          "0. m s^-1");
+      if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
+        throw ParameterError("EmissionImages:turbulent velocity dispersion "
+                             "must not be negative");
+      velocity_field =
+          params.get_string("EmissionImages:velocity field type", "Static");
+      const std::string origin = "[0. m, 0. m, 0. m]";
+      if (velocity_field == "SolidBodyRotation") {
+        if (!params.has_value("EmissionImages:angular velocity"))
+          throw ParameterError("EmissionImages:angular velocity is required "
+                               "for SolidBodyRotation");
+        angular_velocity = params.get_physical_value(
+            QUANTITY_FREQUENCY, "EmissionImages:angular velocity", "0. s^-1");
+        rotation_axis = params.get_double_vector(
+            "EmissionImages:rotation axis", {0., 0., 1.});
+        double norm = 0.;
+        for (int a = 0; a < 3; ++a)
+          norm += rotation_axis[a] * rotation_axis[a];
+        norm = std::sqrt(norm);
+        if (!(norm > 0.) || !std::isfinite(norm))
+          throw ParameterError("EmissionImages:rotation axis must be a "
+                               "finite vector that is not zero");
+        for (int a = 0; a < 3; ++a)
+          rotation_axis[a] /= norm;
+        field_centre = params.get_physical_vector(
+            QUANTITY_LENGTH, "EmissionImages:rotation centre", origin);
+      } else if (velocity_field == "RadialExpansion") {
+        for (const char *key : {"EmissionImages:expansion velocity",
+                                "EmissionImages:expansion radius"})
+          if (!params.has_value(key))
+            throw ParameterError(std::string(key) +
+                                 " is required for RadialExpansion");
+        expansion_velocity = params.get_physical_value(
+            QUANTITY_VELOCITY, "EmissionImages:expansion velocity",
+            "0. m s^-1");
+        expansion_radius = params.get_physical_value(
+            QUANTITY_LENGTH, "EmissionImages:expansion radius", "1. m");
+        if (!(expansion_radius > 0.))
+          throw ParameterError("EmissionImages:expansion radius must be "
+                               "positive");
+        field_centre = params.get_physical_vector(
+            QUANTITY_LENGTH, "EmissionImages:expansion centre", origin);
+      } else if (velocity_field != "Static" && velocity_field != "Snapshot") {
+        throw ParameterError(
+            "Unknown EmissionImages:velocity field type \"" + velocity_field +
+            "\" (Static, SolidBodyRotation, RadialExpansion or Snapshot)");
+      }
+    }
+
+    /* the velocity of the matter at r (not for Snapshot) */
+    std::array<double, 3> velocity_at(const std::array<double, 3> &r) const {
+      const double d[3] = {r[0] - field_centre[0], r[1] - field_centre[1],
+                           r[2] - field_centre[2]};
+      if (velocity_field == "SolidBodyRotation") {
+        const std::array<double, 3> &w = rotation_axis;
+        return {angular_velocity * (w[1] * d[2] - w[2] * d[1]),
+                angular_velocity * (w[2] * d[0] - w[0] * d[2]),
+                angular_velocity * (w[0] * d[1] - w[1] * d[0])};
+      }
+      if (velocity_field == "RadialExpansion") {
+        const double scale = expansion_velocity / expansion_radius;
+        return {scale * d[0], scale * d[1], scale * d[2]};
+      }
+      return {0., 0., 0.};
+    }
 
     void read_views(ParameterFile &params) {
       static const char *axis[2] = {"x", "y"};
@@ -221,6 +337,7 @@ class EmissivityCalculationSimulation {
           throw ParameterError("EmissionImages: the image sides must be "
                                "positive");
       read_views(params);
+      read_cubes(params);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       if (!params.peek_bool("EmissionImages:scattering"))
@@ -611,6 +728,50 @@ public:
       }
     }
 
+    /* cubes: the cells' velocities in the engine's cell order, [3][size] */
+    std::vector<double> velocities;
+    if (do_images && img.cubes && !cell_of_row.empty() &&
+        img.velocity_field != "Static") {
+      velocities.assign(3 * size, 0.);
+      if (img.velocity_field == "Snapshot") {
+        if (!file.exists("/PartType0/Velocities"))
+          throw ParameterError("EmissionImages:velocity field type Snapshot: "
+                               "the snapshot has no dataset "
+                               "/PartType0/Velocities");
+        const std::vector<double> rows =
+            file.read_doubles("/PartType0/Velocities");
+        if (rows.size() != 3 * size)
+          throw ParameterError("dataset /PartType0/Velocities has the wrong "
+                               "size");
+        double unit_time_in_SI = 1.;
+        if (file.exists("/Units")) {
+          const Hdf5Reader::Object units = file.open("/Units");
+          const auto it = units.attributes.find("Unit time in cgs (U_t)");
+          if (it != units.attributes.end())
+            unit_time_in_SI = Hdf5Reader::as_doubles(it->second).at(0);
+        }
+        const double unit = unit_length_in_SI / unit_time_in_SI;
+        for (size_t i = 0; i < size; ++i)
+          for (int a = 0; a < 3; ++a)
+            velocities[(size_t)a * size + cell_of_row[i]] =
+                rows[3 * i + a] * unit;
+      } else {
+        size_t c = 0;
+        for (long long i = 0; i < ncell[0]; ++i)
+          for (long long j = 0; j < ncell[1]; ++j)
+            for (long long k = 0; k < ncell[2]; ++k, ++c) {
+              const long long idx[3] = {i, j, k};
+              std::array<double, 3> r;
+              for (int a = 0; a < 3; ++a)
+                r[a] = box_anchor[a] +
+                       (idx[a] + 0.5) * (box_sides[a] / ncell[a]);
+              const std::array<double, 3> v = img.velocity_at(r);
+              for (int a = 0; a < 3; ++a)
+                velocities[(size_t)a * size + c] = v[a];
+            }
+      }
+    }
+
     status("Starting emissivity calculation...");
     std::vector<double> values(lines.size() * size);
     if (!lines.empty()) {
@@ -701,6 +862,29 @@ public:
         }
         const size_t npixel = (size_t)img.nx * (size_t)img.ny;
         std::vector<double> images(lines.size() * npixel);
+        /* cubes: of the flagged entries that are the line of one ion */
+        std::vector<int32_t> cube_lines;
+        std::vector<double> cube;
+        if (img.cubes) {
+          for (const int32_t line : lines)
+            if (cmi_gpu_emission_line_atomic_weight(line) > 0.)
+              cube_lines.push_back(line);
+            else
+              std::cerr << "EmissionImages: "
+                        << GpuIonizationSimulation::emission_line_name(line)
+                        << " is not the line of one ion: no cube, the image "
+                           "alone" << std::endl;
+          if ((double)cube_lines.size() * (double)img.nchan * (double)npixel >
+              (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionImages: " + std::to_string(cube_lines.size()) +
+                " cubes of " + std::to_string(img.nchan) + " channels of " +
+                std::to_string(img.nx) + " x " + std::to_string(img.ny) +
+                " pixels: more than 2^28 values in one call");
+          cube.resize(cube_lines.size() * (size_t)img.nchan * npixel);
+          if (!cube_lines.empty() && !velocities.empty())
+            rc = cmi_gpu_set_cell_velocities(engine, velocities.data());
+        }
         for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
           rc = cmi_gpu_render_line_images(
               engine, (int32_t)lines.size(), lines.data(), theta[v], phi[v],
@@ -714,6 +898,24 @@ public:
                       GpuIonizationSimulation::emission_line_name(lines[k]) +
                       view_tag(v),
                   img.type, images.data() + k * npixel, img.nx, img.ny, 1.);
+          if (rc == CMI_GPU_OK && !cube_lines.empty()) {
+            rc = cmi_gpu_render_line_cube(
+                engine, (int32_t)cube_lines.size(), cube_lines.data(),
+                theta[v], phi[v], (int32_t)img.nx, (int32_t)img.ny,
+                anchors.data() + 2 * v, sides.data() + 2 * v,
+                (int32_t)img.supersample, img.dust_cross_section,
+                (int32_t)img.nchan, img.vmin, img.vmax, img.sigma_turb,
+                cube.data());
+            if (rc == CMI_GPU_OK && write_output)
+              for (size_t k = 0; k < cube_lines.size(); ++k)
+                written += " " + write_cube(
+                    img.folder + "/" + img.prefix + "_" +
+                        GpuIonizationSimulation::emission_line_name(
+                            cube_lines[k]) +
+                        "_cube" + view_tag(v),
+                    cube.data() + k * (size_t)img.nchan * npixel, img.nchan,
+                    img.nx, img.ny);
+          }
         }
         if (rc == CMI_GPU_OK && img.scattering) {
           status("Shooting the lines' packets through the dust...");

@@ -65,6 +65,13 @@ inline std::string write_image(std::string filename, const std::string &type,
   return filename;
 }
 
+/* a cube of nchan images, [channel][ix][iy], as raw doubles into <name>.dat
+ * (the extension is added unless it is there). Returns the file's name. */
+inline std::string write_cube(const std::string &filename, const double *cube,
+                              long long nchan, long long nx, long long ny) {
+  return write_image(filename, "BinaryArray", cube, nchan * nx, ny, 1.);
+}
+
 } // namespace cmi
 
 #endif

@@ -1154,6 +1154,97 @@ int cmi_gpu_line_image_probe(cmi_gpu_engine *engine, double theta, double phi,
                              int64_t n, const double *xy, int32_t max_cells,
                              double *out);
 
+/* ------------------------------------------------ spectral line cubes -- */
+/* The images of cmi_gpu_render_line_images / cmi_gpu_render_field_images
+ * resolved in radial velocity: an image per velocity channel. Geometry, the
+ * sample grid, supersampling, the slab test, the march order (far side to
+ * observer) and the cell and path-length arithmetic are the images',
+ * unchanged. The extinction stays grey dust: no line opacity. Parallel camera
+ * only.
+ *
+ * Velocity axis: nchan >= 1 channels of equal width cover the radial
+ * velocities [vmin, vmax) in m s^-1, vmax > vmin, both finite; edge
+ *   e_c = vmin + c * dv   for c = 0 .. nchan,   dv = (vmax - vmin) / nchan,
+ * computed in exactly this form. Radial velocity is positive for matter that
+ * recedes from the observer: with n the unit vector to the observer a cell of
+ * velocity v has u = -((v_x n_x + v_y n_y) + v_z n_z).
+ *
+ * Line profile: a cell has the Gaussian width b = sqrt(2) sigma, sigma^2 =
+ * k_B T / (A m_u) + sigma_turb^2 (computed as b = sqrt(2 (k_B T / (A m_u) +
+ * sigma_turb sigma_turb)), k_B = 1.38064852e-23 J K^-1, m_u = 1.660539040e-27
+ * kg), A the standard atomic weight of the emitting element:
+ *   H 1.00794  He 4.002602  C 12.0107  N 14.0067  O 15.9994  Ne 20.1797
+ *   S 32.065
+ * A blended entry (OII_3727, SII_6725, ...) is one line at one rest velocity.
+ * The fraction of a cell's emission in channel c is
+ *   f_c = 0.5 * (E((e_{c+1} - u) / b) - E((e_c - u) / b)),
+ *   E(z) = 1 for z >= 6, -1 for z <= -6, erf(z) otherwise
+ * (fp64 erf is exactly 1 from |z| = 5.95 on: the clamp is no approximation).
+ * For b == 0 E is the step function with the lower edge inclusive: E = 1 for
+ * e > u and -1 for e <= u, all emission goes to the channel with e_c <= u <
+ * e_{c+1}, and no NaN arises.
+ *
+ * Per step of length ds in a cell with the images' record {k, s} (s = j / 4
+ * pi, or j / 4 pi / k where k != 0), the product in parentheses first:
+ *   k == 0:  I_c += (s ds) f_c
+ *   else:    dtau = k ds,  I_c = I_c exp(-dtau) + (s * -expm1(-dtau)) f_c
+ *
+ * Output: channel-integrated surface brightness, W m^-2 sr^-1 per channel
+ * (not per m s^-1: dividing by dv is the caller's), cube[(l * nchan + c) * nx
+ * * ny + ix * ny + iy]; a pixel is the mean of its s^2 samples, summed a
+ * outer, b inner. No atomics: the same call gives the same bits.
+ *
+ * What follows from these definitions: (1) with nchan = 1, vmin <= u - 6 b
+ * and vmax >= u + 6 b for every cell, f_0 = 1 exactly and the cube is the
+ * image of the same view, bit for bit; (2) adding one constant to every u,
+ * vmin and vmax leaves the cube unchanged (bit for bit where every e - u
+ * stays exact); (3) the sum over channels is at most the image, and equal to
+ * it up to rounding when the range covers u +- 6 b of every emitting cell.
+ *
+ * Preconditions and errors of the image calls; also CMI_GPU_EINVAL for nchan
+ * < 1, vmax <= vmin or a range that is not finite, and for nlines * nchan *
+ * nx * ny > 2^28. All calls are synchronous; a call that fails leaves the
+ * engine usable. */
+
+/* A of the element that emits emission line `line` (numbered as in
+ * cmi_gpu_compute_emissivities); 0 for an entry that has no cube, and for a
+ * number that is no entry. Host only, no engine. */
+double cmi_gpu_emission_line_atomic_weight(int32_t line);
+
+/* The bulk velocities of the cells, v[3][ncell] (host, m s^-1, the engine's
+ * cell order), for cmi_gpu_render_line_cube. NULL drops the array: every cell
+ * is then at rest, as before the first call. A component that is not finite
+ * is CMI_GPU_EINVAL (checked on the device) and the previous state is kept. */
+int cmi_gpu_set_cell_velocities(cmi_gpu_engine *engine,
+                                const double *velocities);
+
+/* cube (host) of the emission lines lines[l]: lines, dust_cross_section and
+ * preconditions as in cmi_gpu_render_line_images, velocities from
+ * cmi_gpu_set_cell_velocities, widths from the cells' temperatures and
+ * sigma_turb (m s^-1; negative or NaN: EINVAL). Entries that are not the
+ * line of one ion (HII, BALMER_JUMP_*, avg_*, Hrec_s, WFC2_*) are
+ * CMI_GPU_EINVAL. The emissivities are computed once per batch of 7 lines,
+ * not per channel. */
+int cmi_gpu_render_line_cube(cmi_gpu_engine *engine, int32_t nlines,
+                             const int32_t *lines, double theta, double phi,
+                             int32_t nx, int32_t ny, const double *anchor,
+                             const double *sides, int32_t supersample,
+                             double dust_cross_section, int32_t nchan,
+                             double vmin, double vmax, double sigma_turb,
+                             double *cube);
+
+/* the same for any per-cell sources: fields[nfields][ncell] and the optional
+ * extinction[ncell] as in cmi_gpu_render_field_images, velocity[3][ncell]
+ * (m s^-1; NULL: at rest; not finite: EINVAL) and widths[nfields][ncell] (b
+ * in m s^-1, >= 0 and finite, else EINVAL). Needs only cmi_gpu_create. */
+int cmi_gpu_render_field_cube(cmi_gpu_engine *engine, int32_t nfields,
+                              const double *fields, const double *extinction,
+                              const double *velocity, const double *widths,
+                              double theta, double phi, int32_t nx, int32_t ny,
+                              const double *anchor, const double *sides,
+                              int32_t supersample, int32_t nchan, double vmin,
+                              double vmax, double *cube);
+
 /* ------------------------------------------------------------ sky maps -- */
 /* Line images for an observer inside or near the grid: the other camera. The
  * calls above see the box from infinitely far away, one direction for all
