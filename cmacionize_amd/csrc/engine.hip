@@ -12,6 +12,7 @@
 #include "line_image_kernels.h"
 #include "line_cube_kernels.h"
 #include "sky_image_kernels.h"
+#include "sky_cube_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -4328,6 +4329,284 @@ int cmi_gpu_render_line_sky_map(cmi_gpu_engine *e, int32_t nlines,
   for (int32_t l = 0; l < nlines; ++l)
     for (size_t k = 0; k < npixel; ++k)
       maps[(size_t)l * npixel + (size_t)pixel[k]] = rays[(size_t)l * npixel + k];
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------------------ sky cubes -- */
+extern "C++" {
+namespace {
+/* device buffers of one sky cube call, freed however it ends */
+struct SkyCubeBuffers {
+  double *records = nullptr, *directions = nullptr, *out = nullptr,
+         *fields = nullptr, *widths = nullptr, *extinction = nullptr,
+         *velocity = nullptr;
+  ~SkyCubeBuffers() {
+    (void)hipFree(records);
+    (void)hipFree(directions);
+    (void)hipFree(out);
+    (void)hipFree(fields);
+    (void)hipFree(widths);
+    (void)hipFree(extinction);
+    (void)hipFree(velocity);
+  }
+};
+
+/* values of one march's result buffer (bounds the rays per launch) */
+constexpr int64_t CMI_SKY_CUBE_LAUNCH_VALUES = 1ll << 26;
+
+/* the size, the velocity axis and the observer's velocity of a sky cube call
+ * (sky_check has bounded nrays) */
+int sky_cube_check(const char *what, int32_t nplanes, int64_t nrays,
+                   int32_t nchan, double vmin, double vmax,
+                   const double *observer_velocity, LineCubeAxis &axis,
+                   double v_obs[3]) {
+  if (nchan >= 1 &&
+      ((int64_t)nplanes * nchan > (1ll << 28) ||
+       (int64_t)nplanes * nchan * nrays > (1ll << 28)))
+    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %lld rays: a cube has "
+                "at most 2^28 values", what, (int)nplanes, (int)nchan,
+                (long long)nrays);
+  CMI_TRY(line_cube_axis(what, nplanes, 1, 1, nchan, vmin, vmax, axis));
+  for (int a = 0; a < 3; ++a) {
+    v_obs[a] = observer_velocity ? observer_velocity[a] : 0.;
+    if (!std::isfinite(v_obs[a]))
+      return fail(CMI_GPU_EINVAL, "%s: component %d of the observer's velocity "
+                  "is not finite", what, a);
+  }
+  return CMI_GPU_OK;
+}
+
+/* out[(l * nchan + c) * nrays + r] (host), l < nl, of the records
+ * [ncell][4 + 2 nl] in b.records: per chunk of rays and per block of CB
+ * channels one march launch for the nl lines, directions up, results down */
+int sky_cube_march(cmi_gpu_engine *e, const double *origin, int64_t nrays,
+                   const double *directions, int nl, int nb,
+                   const LineCubeAxis &axis, SkyCubeBuffers &b, double *out) {
+  constexpr int CB = CMI_SKY_CUBE_CB;
+  const int64_t chunk = std::max<int64_t>(
+      1, std::min<int64_t>(std::min<int64_t>(nrays, CMI_SKY_LAUNCH_RAYS),
+                           CMI_SKY_CUBE_LAUNCH_VALUES /
+                               ((int64_t)nb * axis.nchan)));
+  if (!b.directions)
+    HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
+  if (!b.out)
+    HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk * axis.nchan * nb));
+  for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
+    const int64_t n = std::min<int64_t>(chunk, nrays - r0);
+    HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
+                      sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
+    for (int32_t c0 = 0; c0 < axis.nchan; c0 += CB) {
+      SkyCubeMarchArgs a;
+      a.grid = e->grid;
+      for (int k = 0; k < 3; ++k)
+        a.origin[k] = origin[k];
+      a.directions = b.directions;
+      a.records = b.records;
+      a.nrays = n;
+      a.nd = 4 + 2 * nl;
+      a.c0 = c0;
+      a.nc = std::min<int32_t>(CB, axis.nchan - c0);
+      a.pad = 0;
+      a.vmin = axis.vmin;
+      a.dv = axis.dv;
+      a.line_stride = (int64_t)axis.nchan * chunk;
+      a.channel_stride = chunk;
+      a.out = b.out;
+      sky_cube_march_kernel<CB>
+          <<<dim3((unsigned)((n + 255) / 256), (unsigned)nl), 256, 0,
+             e->stream>>>(a);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (n == nrays) {
+      HIP_TRY(hipMemcpy(out, b.out,
+                        sizeof(double) * (size_t)nl * axis.nchan * (size_t)n,
+                        hipMemcpyDeviceToHost));
+    } else {
+      for (int64_t p = 0; p < (int64_t)nl * axis.nchan; ++p)
+        HIP_TRY(hipMemcpy(out + (size_t)p * nrays + r0,
+                          b.out + (size_t)p * chunk,
+                          sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+  }
+  return CMI_GPU_OK;
+}
+} // namespace
+} // extern "C++"
+
+int cmi_gpu_render_line_sky_cube(cmi_gpu_engine *e, int32_t nlines,
+                                 const int32_t *lines, const double *origin,
+                                 const double *observer_velocity,
+                                 int64_t nrays, const double *directions,
+                                 double dust_cross_section, int32_t nchan,
+                                 double vmin, double vmax, double sigma_turb,
+                                 double *out) {
+  static const char *what = "render_line_sky_cube";
+  if (!e || !lines || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
+    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
+                (int)nlines, CMI_NEMISSIONLINE);
+  for (int32_t l = 0; l < nlines; ++l) {
+    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
+      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
+                  (int)lines[l]);
+    if (cmi_emission_atomic_weight[lines[l]] == 0.)
+      return fail(CMI_GPU_EINVAL, "%s: entry %d is not the line of one ion: "
+                  "it has no line profile", what, (int)lines[l]);
+  }
+  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
+    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
+                what);
+  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
+    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
+                "be >= 0 and finite", what);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  LineCubeAxis axis;
+  double v_obs[3];
+  CMI_TRY(sky_cube_check(what, nlines, nrays, nchan, vmin, vmax,
+                         observer_velocity, axis, v_obs));
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  HIP_TRY(hipSetDevice(e->device));
+  SkyCubeBuffers b;
+  const int nb = std::min<int>(nlines, CMI_SKY_CUBE_BATCH);
+  HIP_TRY(hipMalloc(&b.records,
+                    sizeof(double) * (size_t)e->ncell * (4 + 2 * nb)));
+  for (int32_t first = 0; first < nlines; first += CMI_SKY_CUBE_BATCH) {
+    const int nl = std::min<int>(nlines - first, CMI_SKY_CUBE_BATCH);
+    SkyCubeRecordArgs r;
+    r.model = e->model;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.nlines = nl;
+    for (int l = 0; l < CMI_SKY_CUBE_BATCH; ++l) {
+      r.lines[l] = l < nl ? lines[first + l] : 0;
+      r.weight[l] = l < nl ? cmi_emission_atomic_weight[lines[first + l]] : 1.;
+    }
+    r.dust_cross_section = dust_cross_section;
+    r.sigma_turb = sigma_turb;
+    for (int a = 0; a < 3; ++a)
+      r.v_obs[a] = v_obs[a];
+    r.velocity = e->cell_velocities;
+    r.records = b.records;
+    sky_cube_record_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
+                             e->stream>>>(r);
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(sky_cube_march(e, origin, nrays, directions, nl, nb, axis, b,
+                           out + (size_t)first * nchan * (size_t)nrays));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_field_sky_cube(cmi_gpu_engine *e, int32_t nfields,
+                                  const double *fields,
+                                  const double *extinction,
+                                  const double *velocity, const double *widths,
+                                  const double *origin,
+                                  const double *observer_velocity,
+                                  int64_t nrays, const double *directions,
+                                  int32_t nchan, double vmin, double vmax,
+                                  double *out) {
+  static const char *what = "render_field_sky_cube";
+  if (!e || !fields || !widths || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (nfields < 1 || nfields > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
+                what, (int)nfields);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  LineCubeAxis axis;
+  double v_obs[3];
+  CMI_TRY(sky_cube_check(what, nfields, nrays, nchan, vmin, vmax,
+                         observer_velocity, axis, v_obs));
+  const size_t ncell = (size_t)e->ncell;
+  for (size_t i = 0; i < ncell * (size_t)nfields; ++i)
+    if (!(widths[i] >= 0.) || !std::isfinite(widths[i]))
+      return fail(CMI_GPU_EINVAL, "%s: the width of field %lld in cell %lld "
+                  "is negative or not finite", what, (long long)(i / ncell),
+                  (long long)(i % ncell));
+  HIP_TRY(hipSetDevice(e->device));
+  SkyCubeBuffers b;
+  if (velocity) {
+    HIP_TRY(hipMalloc(&b.velocity, sizeof(double) * 3 * ncell));
+    HIP_TRY(hipMemcpy(b.velocity, velocity, sizeof(double) * 3 * ncell,
+                      hipMemcpyHostToDevice));
+    CMI_TRY(line_cube_check_velocities(e, what, b.velocity,
+                                       3 * (int64_t)ncell));
+  }
+  const int nb = std::min<int>(nfields, CMI_SKY_CUBE_BATCH);
+  HIP_TRY(hipMalloc(&b.records, sizeof(double) * ncell * (4 + 2 * nb)));
+  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
+  HIP_TRY(hipMalloc(&b.widths, sizeof(double) * ncell * nb));
+  if (extinction) {
+    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
+    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice));
+  }
+  for (int32_t first = 0; first < nfields; first += CMI_SKY_CUBE_BATCH) {
+    const int nl = std::min<int>(nfields - first, CMI_SKY_CUBE_BATCH);
+    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b.widths, widths + (size_t)first * ncell,
+                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
+    field_sky_cube_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
+                                   e->stream>>>(
+        b.fields, b.widths, b.extinction, b.velocity, v_obs[0], v_obs[1],
+        v_obs[2], e->ncell, nl, b.records);
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(sky_cube_march(e, origin, nrays, directions, nl, nb, axis, b,
+                           out + (size_t)first * nchan * (size_t)nrays));
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_line_sky_map_cube(cmi_gpu_engine *e, int32_t nlines,
+                                     const int32_t *lines,
+                                     const double *origin, const double *frame,
+                                     double lon_min, double lon_max,
+                                     double lat_min, double lat_max,
+                                     int32_t nlon, int32_t nlat,
+                                     double dust_cross_section,
+                                     const double *observer_velocity,
+                                     int32_t nchan, double vmin, double vmax,
+                                     double sigma_turb, double *cubes) {
+  static const char *what = "render_line_sky_map_cube";
+  if (!e || !lines || !cubes || nlines < 1)
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                        nlat));
+  const size_t npixel = (size_t)nlon * nlat;
+  if (nchan >= 1 && ((int64_t)nlines * nchan > (1ll << 28) ||
+                     (int64_t)nlines * nchan * (int64_t)npixel > (1ll << 28)))
+    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %d x %d pixels: a "
+                "cube has at most 2^28 values", what, (int)nlines, (int)nchan,
+                (int)nlon, (int)nlat);
+  /* the map call's ray order: 8 x 8 tiles; pixel[k] is the pixel of ray k */
+  const size_t nplane = (size_t)nlines * (size_t)std::max<int32_t>(nchan, 1);
+  std::vector<int64_t> pixel;
+  std::vector<double> directions, rays;
+  try {
+    pixel.reserve(npixel);
+    directions.resize(3 * npixel);
+    rays.resize(nplane * npixel);
+  } catch (const std::bad_alloc &) {
+    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
+  }
+  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
+    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
+      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
+        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
+          sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                            nlat, i, j, directions.data() + 3 * pixel.size());
+          pixel.push_back((int64_t)i * nlat + j);
+        }
+  CMI_TRY(cmi_gpu_render_line_sky_cube(
+      e, nlines, lines, origin, observer_velocity, (int64_t)npixel,
+      directions.data(), dust_cross_section, nchan, vmin, vmax, sigma_turb,
+      rays.data()));
+  for (size_t p = 0; p < nplane; ++p)
+    for (size_t k = 0; k < npixel; ++k)
+      cubes[p * npixel + (size_t)pixel[k]] = rays[p * npixel + k];
   return CMI_GPU_OK;
 }
 

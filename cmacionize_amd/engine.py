@@ -121,6 +121,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_select_probe_view",
     "cmi_gpu_set_cell_velocities", "cmi_gpu_render_line_cube",
     "cmi_gpu_render_field_cube", "cmi_gpu_emission_line_atomic_weight",
+    "cmi_gpu_render_field_sky_cube", "cmi_gpu_render_line_sky_cube",
+    "cmi_gpu_render_line_sky_map_cube",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -349,6 +351,16 @@ def load_library():
     L.cmi_gpu_render_line_sky_map.argtypes = [
         vp, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.c_double, C.c_double,
         C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp]
+    L.cmi_gpu_render_field_sky_cube.argtypes = [
+        vp, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int64, _dp,
+        C.c_int32, C.c_double, C.c_double, _dp]
+    L.cmi_gpu_render_line_sky_cube.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.c_int64, _dp,
+        C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double, _dp]
+    L.cmi_gpu_render_line_sky_map_cube.argtypes = [
+        vp, C.c_int32, C.POINTER(C.c_int32), _dp, _dp, C.c_double, C.c_double,
+        C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _dp,
+        C.c_int32, C.c_double, C.c_double, C.c_double, _dp]
     L.cmi_gpu_sky_map_directions.argtypes = [
         _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
         C.c_int32, _dp, _dp]
@@ -1289,6 +1301,79 @@ class GpuEngine:
             self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
             _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
             lat_range[1], int(nlon), int(nlat), dust_cross_section, _p(out)))
+        return dict(zip(names, out))
+
+    # sky cubes --------------------------------------------------------------
+    def render_field_sky_cube(self, fields, widths, origin, directions, nchan,
+                              vmin, vmax, extinction=None, velocity=None,
+                              observer_velocity=None):
+        """render_field_sky resolved in radial velocity: (nfields, nchan,
+        nrays), W m^-2 sr^-1 per channel, for `nchan` channels of equal width
+        over [vmin, vmax) m s^-1. A cell of velocity[3][ncell] seen along the
+        ray direction d by an observer of `observer_velocity` (m s^-1; None:
+        at rest) has the radial velocity (v - v_obs) . d, positive for matter
+        that recedes; widths[nfields][ncell] are the Gaussian b = sqrt(2)
+        sigma (include/cmi_gpu.h, "sky cubes")."""
+        f = _f64(fields).reshape(-1, self.n)
+        w = _f64(widths).reshape(len(f), self.n)
+        k = None if extinction is None else _f64(extinction).reshape(self.n)
+        v = None if velocity is None else _f64(velocity).reshape(3, self.n)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(f), max(int(nchan), 0), len(d)))
+        self._check(self._lib.cmi_gpu_render_field_sky_cube(
+            self._h, len(f), _p(f), _p(k) if k is not None else None,
+            _p(v) if v is not None else None, _p(w), _p(o),
+            _p(vo) if vo is not None else None, len(d), _p(d), int(nchan),
+            vmin, vmax, _p(out)))
+        return out
+
+    def render_line_sky_cube(self, lines, origin, directions, nchan, vmin,
+                             vmax, dust_cross_section=0., sigma_turb=0.,
+                             observer_velocity=None):
+        """render_line_sky resolved in radial velocity, a spectrum per ray:
+        {name: (nchan, nrays) array}. Velocities from set_cell_velocities,
+        widths from the cells' temperatures and `sigma_turb` as in
+        render_line_cube. Only names of LINE_ATOMIC_WEIGHTS have a cube."""
+        names = list(lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(names), max(int(nchan), 0), len(d)))
+        self._check(self._lib.cmi_gpu_render_line_sky_cube(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            _p(o), _p(vo) if vo is not None else None, len(d), _p(d),
+            dust_cross_section, int(nchan), vmin, vmax, sigma_turb, _p(out)))
+        return dict(zip(names, out))
+
+    def render_line_sky_map_cube(self, lines, origin, nlon, nlat, nchan, vmin,
+                                 vmax, lon_range=FULL_SKY_LONGITUDE,
+                                 lat_range=FULL_SKY_LATITUDE,
+                                 frame=IDENTITY_FRAME, dust_cross_section=0.,
+                                 sigma_turb=0., observer_velocity=None):
+        """render_line_sky_map per velocity channel: {name: (nchan, nlon,
+        nlat) array}, the longitude-latitude-velocity cube of an observer at
+        `origin`. cube_moments and cube_channel_centres work on it."""
+        names = list(lines)
+        idx = np.array([EMISSION_LINES.index(n) for n in names],
+                       dtype=np.int32)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        f = _f64(frame).reshape(9)
+        out = np.zeros((len(names), max(int(nchan), 0), max(int(nlon), 0),
+                        max(int(nlat), 0)))
+        self._check(self._lib.cmi_gpu_render_line_sky_map_cube(
+            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
+            lat_range[1], int(nlon), int(nlat), dust_cross_section,
+            _p(vo) if vo is not None else None, int(nchan), vmin, vmax,
+            sigma_turb, _p(out)))
         return dict(zip(names, out))
 
     def set_sky_camera(self, origin, nlon, nlat, exclusion_radius,

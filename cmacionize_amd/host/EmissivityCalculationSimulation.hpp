@@ -99,6 +99,12 @@
  * <prefix>_<LineName>_cube.dat (_cube_view<k>.dat for view k >= 1): raw
  * doubles, [channel][ix][iy], next to its integrated image; the other flagged
  * entries keep their image and are named on stderr. PGM cannot hold a cube.
+ * Sky cubes: the same keys in the EmissionSkyMaps: block,
+ * "velocity channels" as the switch, with the block's own velocity field, and
+ *   EmissionSkyMaps:observer velocity            [0., 0., 0.] m s^-1
+ * ("observer velocity k" for observer k >= 1; observer 0's if absent). Every
+ * flagged single-ion line is then also written as <prefix>_<LineName>_cube.dat
+ * (_cube_view<k>.dat), raw doubles [channel][i][j], next to its map.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -124,29 +130,9 @@ class EmissivityCalculationSimulation {
                                cmi_gpu_last_error());
   }
 
-  /* the EmissionImages: block (read only if the file has one) */
-  struct ImageSettings {
-    double theta = 0., phi = 0.;
-    long long nx = 200, ny = 200, supersample = 1;
-    bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
-    double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
-    double dust_cross_section = 0.;
-    std::string type, prefix, folder;
-    /* scattered light (the keys below are read only if scattering is set) */
-    bool scattering = false;
-    long long npackets = 1000000, seed = 42;
-    double albedo = 0., asymmetry = 0.5, polarisation = 0.;
-    /* several views: views[0] repeats the members above, views[k] is read
-     * from the keys with " k" appended */
-    struct View {
-      double theta = 0., phi = 0.;
-      bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
-      double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
-    };
-    long long nviews = 1;
-    std::vector<View> views;
-
-    /* spectral cubes (read only if "velocity channels" is there) */
+  /* the spectral cube keys of a block, "EmissionImages" or "EmissionSkyMaps"
+   * (read only if the block has "velocity channels") */
+  struct CubeSettings {
     bool cubes = false;
     long long nchan = 0;
     double vmin = 0., vmax = 0., sigma_turb = 0.;
@@ -156,76 +142,75 @@ class EmissivityCalculationSimulation {
     std::array<double, 3> rotation_axis = {0., 0., 1.},
                           field_centre = {0., 0., 0.};
 
-    void read_cubes(ParameterFile &params) {
-      if (!params.has_value("EmissionImages:velocity channels"))
+    void read_cubes(ParameterFile &params, const std::string &block,
+                    const std::string &type) {
+      if (!params.has_value(block + ":velocity channels"))
         return;
       cubes = true;
-      nchan = params.get_integer("EmissionImages:velocity channels", 1);
+      nchan = params.get_integer(block + ":velocity channels", 1);
       if (nchan < 1)
-        throw ParameterError("EmissionImages:velocity channels must be at "
+        throw ParameterError(block + ":velocity channels must be at "
                              "least 1");
       if (type != "BinaryArray")
-        throw ParameterError("EmissionImages:velocity channels needs type "
+        throw ParameterError(block + ":velocity channels needs type "
                              "BinaryArray: a cube is written as raw doubles");
-      for (const char *key : {"EmissionImages:velocity minimum",
-                              "EmissionImages:velocity maximum"})
-        if (!params.has_value(key))
-          throw ParameterError(std::string(key) + " is required with "
-                               "EmissionImages:velocity channels");
+      for (const char *name : {":velocity minimum", ":velocity maximum"})
+        if (!params.has_value(block + name))
+          throw ParameterError(block + name + " is required with " + block +
+                               ":velocity channels");
       vmin = params.get_physical_value(
-          QUANTITY_VELOCITY, "EmissionImages:velocity minimum", "0. m s^-1");
+          QUANTITY_VELOCITY, block + ":velocity minimum", "0. m s^-1");
       vmax = params.get_physical_value(
-          QUANTITY_VELOCITY, "EmissionImages:velocity maximum", "0. m s^-1");
+          QUANTITY_VELOCITY, block + ":velocity maximum", "0. m s^-1");
       if (!(vmax > vmin) || !std::isfinite(vmax - vmin))
-        throw ParameterError("EmissionImages:velocity maximum must be above "
+        throw ParameterError(block + ":velocity maximum must be above "
                              "velocity minimum, both finite");
       sigma_turb = params.get_physical_value(
-          QUANTITY_VELOCITY, "EmissionImages:turbulent velocity dispersion",
+          QUANTITY_VELOCITY, block + ":turbulent velocity dispersion",
           "0. m s^-1");
       if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
-        throw ParameterError("EmissionImages:turbulent velocity dispersion "
+        throw ParameterError(block + ":turbulent velocity dispersion "
                              "must not be negative");
       velocity_field =
-          params.get_string("EmissionImages:velocity field type", "Static");
+          params.get_string(block + ":velocity field type", "Static");
       const std::string origin = "[0. m, 0. m, 0. m]";
       if (velocity_field == "SolidBodyRotation") {
-        if (!params.has_value("EmissionImages:angular velocity"))
-          throw ParameterError("EmissionImages:angular velocity is required "
+        if (!params.has_value(block + ":angular velocity"))
+          throw ParameterError(block + ":angular velocity is required "
                                "for SolidBodyRotation");
         angular_velocity = params.get_physical_value(
-            QUANTITY_FREQUENCY, "EmissionImages:angular velocity", "0. s^-1");
+            QUANTITY_FREQUENCY, block + ":angular velocity", "0. s^-1");
         rotation_axis = params.get_double_vector(
-            "EmissionImages:rotation axis", {0., 0., 1.});
+            block + ":rotation axis", {0., 0., 1.});
         double norm = 0.;
         for (int a = 0; a < 3; ++a)
           norm += rotation_axis[a] * rotation_axis[a];
         norm = std::sqrt(norm);
         if (!(norm > 0.) || !std::isfinite(norm))
-          throw ParameterError("EmissionImages:rotation axis must be a "
+          throw ParameterError(block + ":rotation axis must be a "
                                "finite vector that is not zero");
         for (int a = 0; a < 3; ++a)
           rotation_axis[a] /= norm;
         field_centre = params.get_physical_vector(
-            QUANTITY_LENGTH, "EmissionImages:rotation centre", origin);
+            QUANTITY_LENGTH, block + ":rotation centre", origin);
       } else if (velocity_field == "RadialExpansion") {
-        for (const char *key : {"EmissionImages:expansion velocity",
-                                "EmissionImages:expansion radius"})
-          if (!params.has_value(key))
-            throw ParameterError(std::string(key) +
+        for (const char *name : {":expansion velocity", ":expansion radius"})
+          if (!params.has_value(block + name))
+            throw ParameterError(block + name +
                                  " is required for RadialExpansion");
         expansion_velocity = params.get_physical_value(
-            QUANTITY_VELOCITY, "EmissionImages:expansion velocity",
+            QUANTITY_VELOCITY, block + ":expansion velocity",
             "0. m s^-1");
         expansion_radius = params.get_physical_value(
-            QUANTITY_LENGTH, "EmissionImages:expansion radius", "1. m");
+            QUANTITY_LENGTH, block + ":expansion radius", "1. m");
         if (!(expansion_radius > 0.))
-          throw ParameterError("EmissionImages:expansion radius must be "
+          throw ParameterError(block + ":expansion radius must be "
                                "positive");
         field_centre = params.get_physical_vector(
-            QUANTITY_LENGTH, "EmissionImages:expansion centre", origin);
+            QUANTITY_LENGTH, block + ":expansion centre", origin);
       } else if (velocity_field != "Static" && velocity_field != "Snapshot") {
         throw ParameterError(
-            "Unknown EmissionImages:velocity field type \"" + velocity_field +
+            "Unknown " + block + ":velocity field type \"" + velocity_field +
             "\" (Static, SolidBodyRotation, RadialExpansion or Snapshot)");
       }
     }
@@ -246,6 +231,29 @@ class EmissivityCalculationSimulation {
       }
       return {0., 0., 0.};
     }
+  };
+
+  /* the EmissionImages: block (read only if the file has one) */
+  struct ImageSettings : CubeSettings {
+    double theta = 0., phi = 0.;
+    long long nx = 200, ny = 200, supersample = 1;
+    bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
+    double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
+    double dust_cross_section = 0.;
+    std::string type, prefix, folder;
+    /* scattered light (the keys below are read only if scattering is set) */
+    bool scattering = false;
+    long long npackets = 1000000, seed = 42;
+    double albedo = 0., asymmetry = 0.5, polarisation = 0.;
+    /* several views: views[0] repeats the members above, views[k] is read
+     * from the keys with " k" appended */
+    struct View {
+      double theta = 0., phi = 0.;
+      bool have_anchor[2] = {false, false}, have_sides[2] = {false, false};
+      double anchor[2] = {0., 0.}, sides[2] = {0., 0.};
+    };
+    long long nviews = 1;
+    std::vector<View> views;
 
     void read_views(ParameterFile &params) {
       static const char *axis[2] = {"x", "y"};
@@ -337,7 +345,7 @@ class EmissivityCalculationSimulation {
           throw ParameterError("EmissionImages: the image sides must be "
                                "positive");
       read_views(params);
-      read_cubes(params);
+      read_cubes(params, "EmissionImages", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       if (!params.peek_bool("EmissionImages:scattering"))
@@ -372,7 +380,7 @@ class EmissivityCalculationSimulation {
   };
 
   /* the EmissionSkyMaps: block (read only if the file has one) */
-  struct SkyMapSettings {
+  struct SkyMapSettings : CubeSettings {
     std::array<double, 3> observer = {0., 0., 0.};
     long long nlon = 360, nlat = 180;
     std::array<double, 2> lon = {0., 0.}, lat = {0., 0.};
@@ -391,6 +399,7 @@ class EmissivityCalculationSimulation {
       std::array<double, 3> position = {0., 0., 0.};
       double frame[9] = {1., 0., 0., 0., 1., 0., 0., 0., 1.};
       double exclusion_radius = 0.;
+      std::array<double, 3> velocity = {0., 0., 0.}; /* sky cubes */
     };
     long long nobservers = 1;
     std::vector<Observer> observers;
@@ -469,6 +478,24 @@ class EmissivityCalculationSimulation {
       }
     }
 
+    /* sky cubes: "observer velocity", and "observer velocity k" for observer
+     * k >= 1 (observer 0's where the key is absent) */
+    void read_observer_velocities(ParameterFile &params) {
+      for (long long k = 0; k < nobservers; ++k) {
+        const std::string key = "EmissionSkyMaps:observer velocity" +
+                                (k ? " " + std::to_string(k) : std::string());
+        Observer &o = observers[(size_t)k];
+        if (k == 0 || params.has_value(key))
+          o.velocity = params.get_physical_vector(
+              QUANTITY_VELOCITY, key, "[0. m s^-1, 0. m s^-1, 0. m s^-1]");
+        else
+          o.velocity = observers[0].velocity;
+        for (int a = 0; a < 3; ++a)
+          if (!std::isfinite(o.velocity[a]))
+            throw ParameterError(key + " must be finite");
+      }
+    }
+
     void read(ParameterFile &params) {
       if (!params.has_value("EmissionSkyMaps:observer position"))
         throw ParameterError("EmissionSkyMaps:observer position is required");
@@ -524,6 +551,9 @@ class EmissivityCalculationSimulation {
                              "must not be negative");
       make_frame(pole, zero, "", frame);
       read_observers(params, pole, zero);
+      read_cubes(params, "EmissionSkyMaps", type);
+      if (cubes)
+        read_observer_velocities(params);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       if (!params.peek_bool("EmissionSkyMaps:scattering"))
@@ -729,13 +759,15 @@ public:
     }
 
     /* cubes: the cells' velocities in the engine's cell order, [3][size] */
-    std::vector<double> velocities;
-    if (do_images && img.cubes && !cell_of_row.empty() &&
-        img.velocity_field != "Static") {
+    auto cell_velocities = [&](const CubeSettings &cs,
+                               const std::string &block) {
+      std::vector<double> velocities;
+      if (!cs.cubes || cell_of_row.empty() || cs.velocity_field == "Static")
+        return velocities;
       velocities.assign(3 * size, 0.);
-      if (img.velocity_field == "Snapshot") {
+      if (cs.velocity_field == "Snapshot") {
         if (!file.exists("/PartType0/Velocities"))
-          throw ParameterError("EmissionImages:velocity field type Snapshot: "
+          throw ParameterError(block + ":velocity field type Snapshot: "
                                "the snapshot has no dataset "
                                "/PartType0/Velocities");
         const std::vector<double> rows =
@@ -765,12 +797,19 @@ public:
               for (int a = 0; a < 3; ++a)
                 r[a] = box_anchor[a] +
                        (idx[a] + 0.5) * (box_sides[a] / ncell[a]);
-              const std::array<double, 3> v = img.velocity_at(r);
+              const std::array<double, 3> v = cs.velocity_at(r);
               for (int a = 0; a < 3; ++a)
                 velocities[(size_t)a * size + c] = v[a];
             }
       }
-    }
+      return velocities;
+    };
+    const std::vector<double> velocities =
+        do_images ? cell_velocities(img, "EmissionImages")
+                  : std::vector<double>();
+    const std::vector<double> sky_velocities =
+        do_sky ? cell_velocities(sky, "EmissionSkyMaps")
+               : std::vector<double>();
 
     status("Starting emissivity calculation...");
     std::vector<double> values(lines.size() * size);
@@ -968,6 +1007,32 @@ public:
         const size_t nviews = sky.observers.size();
         const size_t npixel = (size_t)sky.nlon * (size_t)sky.nlat;
         std::vector<double> maps(lines.size() * npixel);
+        /* cubes: of the flagged entries that are the line of one ion */
+        std::vector<int32_t> cube_lines;
+        std::vector<double> cube;
+        if (sky.cubes) {
+          for (const int32_t line : lines)
+            if (cmi_gpu_emission_line_atomic_weight(line) > 0.)
+              cube_lines.push_back(line);
+            else
+              std::cerr << "EmissionSkyMaps: "
+                        << GpuIonizationSimulation::emission_line_name(line)
+                        << " is not the line of one ion: no cube, the map "
+                           "alone" << std::endl;
+          if ((double)cube_lines.size() * (double)sky.nchan * (double)npixel >
+              (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionSkyMaps: " + std::to_string(cube_lines.size()) +
+                " cubes of " + std::to_string(sky.nchan) + " channels of " +
+                std::to_string(sky.nlon) + " x " + std::to_string(sky.nlat) +
+                " pixels: more than 2^28 values in one call");
+          cube.resize(cube_lines.size() * (size_t)sky.nchan * npixel);
+          /* (the block's own field, whatever EmissionImages: left) */
+          if (!cube_lines.empty())
+            rc = cmi_gpu_set_cell_velocities(
+                engine,
+                sky_velocities.empty() ? nullptr : sky_velocities.data());
+        }
         for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
           rc = cmi_gpu_render_line_sky_map(
               engine, (int32_t)lines.size(), lines.data(),
@@ -982,6 +1047,24 @@ public:
                       GpuIonizationSimulation::emission_line_name(lines[k]) +
                       view_tag(v),
                   sky.type, maps.data() + k * npixel, sky.nlon, sky.nlat, 1.);
+          if (rc == CMI_GPU_OK && !cube_lines.empty()) {
+            rc = cmi_gpu_render_line_sky_map_cube(
+                engine, (int32_t)cube_lines.size(), cube_lines.data(),
+                sky.observers[v].position.data(), sky.observers[v].frame,
+                sky.lon[0], sky.lon[1], sky.lat[0], sky.lat[1],
+                (int32_t)sky.nlon, (int32_t)sky.nlat, sky.dust_cross_section,
+                sky.observers[v].velocity.data(), (int32_t)sky.nchan, sky.vmin,
+                sky.vmax, sky.sigma_turb, cube.data());
+            if (rc == CMI_GPU_OK && write_output)
+              for (size_t k = 0; k < cube_lines.size(); ++k)
+                written += " " + write_cube(
+                    sky.folder + "/" + sky.prefix + "_" +
+                        GpuIonizationSimulation::emission_line_name(
+                            cube_lines[k]) +
+                        "_cube" + view_tag(v),
+                    cube.data() + k * (size_t)sky.nchan * npixel, sky.nchan,
+                    sky.nlon, sky.nlat);
+          }
         }
         if (rc == CMI_GPU_OK && sky.scattering) {
           status("Shooting the lines' packets towards the observer...");

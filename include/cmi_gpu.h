@@ -1160,7 +1160,7 @@ int cmi_gpu_line_image_probe(cmi_gpu_engine *engine, double theta, double phi,
  * sample grid, supersampling, the slab test, the march order (far side to
  * observer) and the cell and path-length arithmetic are the images',
  * unchanged. The extinction stays grey dust: no line opacity. Parallel camera
- * only.
+ * only (the camera inside the model: "sky cubes" below).
  *
  * Velocity axis: nchan >= 1 channels of equal width cover the radial
  * velocities [vmin, vmax) in m s^-1, vmax > vmin, both finite; edge
@@ -1337,6 +1337,94 @@ int cmi_gpu_sky_map_directions(const double frame[9], double lon_min,
                                double lon_max, double lat_min, double lat_max,
                                int32_t nlon, int32_t nlat, double *directions,
                                double *solid_angles);
+
+/* ----------------------------------------------------------- sky cubes -- */
+/* The sky maps above resolved in radial velocity: a sky value per velocity
+ * channel, for an observer inside or near the grid - the longitude-latitude-
+ * velocity cube such an observer records, or a spectrum per pencil beam.
+ *
+ * Rays: the ray list o + t d_r, the origin, the checks of the directions, the
+ * slab test, the start cell, the step and the end of the march are those of
+ * "sky maps", unchanged, and so are the refusals of periodic boxes
+ * (CMI_GPU_EINVAL) and of blocks of a decomposed grid (CMI_GPU_ESTATE).
+ *
+ * Velocity axis: the edges e_c = vmin + c * dv, E(z) and f_c are those of
+ * "spectral line cubes", unchanged, b == 0 as the step function with the
+ * lower edge inclusive included, and so are the atomic weights and b =
+ * sqrt(2 (k_B T / (A m_u) + sigma_turb sigma_turb)).
+ *
+ * Radial velocity: this is what is new. A cell of velocity v seen by an
+ * observer of velocity v_obs along the ray direction d (which points away
+ * from the observer) has
+ *   w = v - v_obs   per component, formed once per cell,
+ *   u = (w_x d_x + w_y d_y) + w_z d_z
+ * in exactly this form, no contraction. u is positive for matter that
+ * recedes. There is no minus sign: d points away from the observer, where the
+ * parallel camera's n points towards it.
+ *
+ * Per step of length ds, from the observer outwards, T = 1 and I_c = 0 at the
+ * start, with the sky march's own products:
+ *   k == 0:  I_c += T * ((s * ds) * f_c)
+ *   else:    dtau = k * ds;  I_c += T * ((s * -expm1(-dtau)) * f_c);
+ *            T = T * exp(-dtau)
+ * in this order of multiplications.
+ *
+ * Output: channel-integrated surface brightness, W m^-2 sr^-1 per channel,
+ * out[(l * nchan + c) * nrays + r]. No atomics: the same call on the same
+ * state gives the same bits.
+ *
+ * What follows: (1) with nchan = 1 and a range that covers u +- 6 b of every
+ * cell on every ray the result is that of cmi_gpu_render_field_sky /
+ * cmi_gpu_render_line_sky, bit for bit; (2) adding one vector to every cell's
+ * velocity and to v_obs changes nothing, bit for bit where the subtractions
+ * are exact; (3) the channels sum to at most the sky value, and to it up to
+ * rounding when the range covers everything; (4) the map call equals the
+ * ray-list call on the map's directions, bit for bit.
+ *
+ * Errors: those of the sky calls and of the cube calls; also CMI_GPU_EINVAL
+ * for an observer velocity that is not finite and for nlines * nchan * nrays
+ * > 2^28. observer_velocity may be NULL (at rest). All calls are synchronous;
+ * a call that fails leaves the engine usable and the state of
+ * cmi_gpu_set_cell_velocities untouched. 6 sources per march. */
+
+/* fields, extinction and origin / rays as in cmi_gpu_render_field_sky,
+ * velocity and widths as in cmi_gpu_render_field_cube. Needs only
+ * cmi_gpu_create. */
+int cmi_gpu_render_field_sky_cube(cmi_gpu_engine *engine, int32_t nfields,
+                                  const double *fields,
+                                  const double *extinction,
+                                  const double *velocity /* [3][ncell] or NULL */,
+                                  const double *widths, const double origin[3],
+                                  const double *observer_velocity /* [3] or NULL */,
+                                  int64_t nrays, const double *directions,
+                                  int32_t nchan, double vmin, double vmax,
+                                  double *out /* [nfields][nchan][nrays] */);
+
+/* lines, rays and dust_cross_section as in cmi_gpu_render_line_sky; the
+ * velocities come from cmi_gpu_set_cell_velocities, the widths from the
+ * cells' temperatures and sigma_turb as in cmi_gpu_render_line_cube. Entries
+ * that are not the line of one ion are CMI_GPU_EINVAL. */
+int cmi_gpu_render_line_sky_cube(cmi_gpu_engine *engine, int32_t nlines,
+                                 const int32_t *lines, const double origin[3],
+                                 const double *observer_velocity,
+                                 int64_t nrays, const double *directions,
+                                 double dust_cross_section, int32_t nchan,
+                                 double vmin, double vmax, double sigma_turb,
+                                 double *out /* [nlines][nchan][nrays] */);
+
+/* The map of cmi_gpu_render_line_sky_map per channel: host code over
+ * cmi_gpu_render_line_sky_cube with the map's 8 x 8 tile order;
+ * cubes[(l * nchan + c) * nlon * nlat + i * nlat + j]. */
+int cmi_gpu_render_line_sky_map_cube(cmi_gpu_engine *engine, int32_t nlines,
+                                     const int32_t *lines,
+                                     const double origin[3],
+                                     const double frame[9], double lon_min,
+                                     double lon_max, double lat_min,
+                                     double lat_max, int32_t nlon,
+                                     int32_t nlat, double dust_cross_section,
+                                     const double *observer_velocity,
+                                     int32_t nchan, double vmin, double vmax,
+                                     double sigma_turb, double *cubes);
 
 #ifdef __cplusplus
 }
