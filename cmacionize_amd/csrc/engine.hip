@@ -114,6 +114,15 @@ struct cmi_gpu_engine {
   void *sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
   uint64_t sort_capacity = 0;
+  /* the span cursors of a first-generation launch (ShootArgs::span_cursor) */
+  uint32_t *span_cursor = nullptr;
+#ifdef CMI_EXPERIMENTS
+  /* ShootArgs::phase_clock of the last first-generation launch, and its
+   * blocks */
+  unsigned long long *phase_clock = nullptr;
+  size_t phase_clock_capacity = 0;
+  unsigned phase_blocks = 0;
+#endif
 
   /* re-emission queues (ping-pong) */
   double *queue_block = nullptr;
@@ -225,6 +234,12 @@ struct cmi_gpu_engine {
     /* the first generation parks an absorbed packet at the place of its
      * position in the launch's order (no queue counter) */
     bool park_in_place = true;
+    /* the kernels with the hydrogen-only block table: how their bundles are
+     * scheduled (ShootArgs::span_claim and what follows it; the defaults
+     * are what DESIGN_LOG.md 13 measured) */
+    bool span_claim = CMI_SPAN_CLAIM_DEFAULT;
+    bool emit_before_flush = CMI_EMIT_BEFORE_FLUSH_DEFAULT;
+    bool phase_stamps = false; /* experiments build: ShootArgs::phase_clock */
   } tune;
 
   /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
@@ -1140,6 +1155,10 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->source_cumulative);
   (void)hipFree(e->sort_keys[0]);
   (void)hipFree(e->select_count);
+  (void)hipFree(e->span_cursor);
+#ifdef CMI_EXPERIMENTS
+  (void)hipFree(e->phase_clock);
+#endif
   (void)hipFree(e->select_ids);
   (void)hipFree(e->select_rows);
   (void)hipFree(e->sort_temp);
@@ -1699,6 +1718,12 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.tile_counting_sort = value != 0;
   else if (k == "update_reuse")
     e->tune.update_reuse = value != 0;
+  else if (k == "span_claim")
+    e->tune.span_claim = value != 0;
+  else if (k == "emit_before_flush")
+    e->tune.emit_before_flush = value != 0;
+  else if (k == "phase_stamps")
+    e->tune.phase_stamps = value != 0;
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
   return CMI_GPU_OK;
@@ -1862,6 +1887,29 @@ int cmi_gpu_get_atomic_count(cmi_gpu_engine *e, uint64_t *natomics) {
   CMI_TRY(download_counters(e, host));
   *natomics = host.natomics;
   return CMI_GPU_OK;
+}
+
+int cmi_gpu_get_phase_clocks(cmi_gpu_engine *e, uint64_t *out,
+                             int64_t capacity, int64_t *count) {
+  if (!e || !count || capacity < 0 || (!out && capacity))
+    return fail(CMI_GPU_EINVAL, "get_phase_clocks: bad argument");
+#ifdef CMI_EXPERIMENTS
+  if (!e->phase_clock || !e->phase_blocks)
+    return fail(CMI_GPU_ESTATE,
+                "get_phase_clocks: no launch with phase_stamps yet");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const int64_t n = CMI_PHASE_COUNT + 1 + (int64_t)e->phase_blocks;
+  *count = n;
+  if (capacity)
+    HIP_TRY(hipMemcpy(out, e->phase_clock,
+                      sizeof(uint64_t) * (size_t)(capacity < n ? capacity : n),
+                      hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+#else
+  return fail(CMI_GPU_ESTATE,
+              "get_phase_clocks: not a build with -DCMI_EXPERIMENTS");
+#endif
 }
 
 int cmi_gpu_get_wave_steps(cmi_gpu_engine *e, uint64_t *nwavesteps) {

@@ -102,6 +102,14 @@ constexpr int shoot_block_threads() {
  * 223/152/88/29 ms per 2e7 packets; the idle lanes cost far less than the
  * atomics they save). */
 #define CMI_REFILL_THRESHOLD 64
+/* scheduling of the hydrogen-only table kernels (ShootArgs::span_claim,
+ * emit_before_flush): what the engine starts with */
+#ifndef CMI_SPAN_CLAIM_DEFAULT
+#define CMI_SPAN_CLAIM_DEFAULT true
+#endif
+#ifndef CMI_EMIT_BEFORE_FLUSH_DEFAULT
+#define CMI_EMIT_BEFORE_FLUSH_DEFAULT true
+#endif
 
 /* hardware fp64 atomic add (global_atomic_add_f64), no CAS loop */
 __device__ __forceinline__ void atomic_add_f64(double *address, double value) {
@@ -220,6 +228,41 @@ struct ShootArgs {
    * reciprocals of (ny + 2 L)(nz + 2 L) and nz + 2 L */
   int32_t pad_ny, pad_nz;
   double pad_inv_yz, pad_inv_z;
+  /* Scheduling of the kernels with the hydrogen-only block table (TABLE &&
+   * !FULL). None of it changes which packet flies with which random numbers.
+   * span_claim: a block takes its positions a span - one chunk per wave,
+   * consecutive in the launch's order - at a time from span_cursor (one
+   * cursor per XCD with xcd_remap, over that XCD's contiguous part of the
+   * spans; zeroed before every launch) instead of the static split by block
+   * index. */
+  uint32_t *span_cursor;
+  uint32_t n_spans; /* of (block's waves) x chunk positions; the last is short */
+  int32_t span_claim;
+  /* the refill ahead of the flush point: an early wave emits while it would
+   * wait at the barrier */
+  int32_t emit_before_flush;
+#ifdef CMI_EXPERIMENTS
+  /* cycles per section of the outer loop, summed over the waves
+   * [CMI_PHASE_*], then the 100 MHz clock at the first wave's start and at
+   * every block's end [CMI_PHASE_COUNT + 1 + block]; NULL: no stamps */
+  unsigned long long *phase_clock;
+#endif
+};
+
+/* a block's held span (LDS): none yet - wave 0 claims one before the next
+ * barrier -, or no span left in the launch */
+#define CMI_SPAN_WANTED 0xfffffffeu
+#define CMI_SPAN_NONE 0xffffffffu
+#define CMI_SPAN_CURSORS 8
+
+/* sections of the first generation's outer loop (ShootArgs::phase_clock) */
+enum {
+  CMI_PHASE_BARRIER = 0, /* waiting at the flush point's first barrier */
+  CMI_PHASE_FLUSH,       /* the flush and its second barrier */
+  CMI_PHASE_REFILL,
+  CMI_PHASE_MARCH,
+  CMI_PHASE_END, /* end of flights */
+  CMI_PHASE_COUNT
 };
 
 /* waves per SIMD the multi-ion first generation is built for (128 VGPRs and
@@ -1140,6 +1183,45 @@ __global__ void
                                                        : a.n_packets;
   if (pos > pos_end)
     pos = pos_end;
+  /* Claimed spans (ShootArgs::span_claim): the wave starts without positions;
+   * the block takes spans of BLOCK / 64 chunks at the flush points, wave w
+   * flies chunk w of a span - the waves of a block stay on one pencil. */
+  constexpr bool CLAIM = TABLE && !FULL;
+  const bool claim = CLAIM && a.span_claim != 0;
+  __shared__ uint32_t s_span, s_span_part;
+  if (claim) {
+    chunk_begin = 0;
+    pos = 0;
+    pos_end = 0;
+    if (threadIdx.x == 0) {
+      s_span = CMI_SPAN_WANTED;
+      s_span_part = a.xcd_remap ? (blockIdx.x & (CMI_SPAN_CURSORS - 1)) : 0u;
+    }
+  }
+#ifdef CMI_EXPERIMENTS
+  /* cycle stamps per section (the experiments build only) */
+  unsigned long long phase_cycles[CMI_PHASE_COUNT] = {0, 0, 0, 0, 0};
+  unsigned long long phase_stamp = 0;
+  const bool stamps = CLAIM && a.phase_clock != nullptr;
+  if (stamps) {
+    phase_stamp = __builtin_amdgcn_s_memtime();
+    if (threadIdx.x == 0)
+      atomicMin(a.phase_clock + CMI_PHASE_COUNT,
+                (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  }
+#define CMI_PHASE_MARK(section)                                               \
+  do {                                                                        \
+    if (stamps) {                                                             \
+      const unsigned long long now = __builtin_amdgcn_s_memtime();            \
+      phase_cycles[section] += now - phase_stamp;                             \
+      phase_stamp = now;                                                      \
+    }                                                                         \
+  } while (0)
+#else
+#define CMI_PHASE_MARK(section)                                               \
+  do {                                                                        \
+  } while (0)
+#endif
 
   Packet<FULL> p;
   /* Lanes without a packet take part in the cross-lane sums with a path
@@ -1251,10 +1333,47 @@ __global__ void
    * work left. Waves may arrive from different places in the code - the
    * points are interchangeable - but every wave must keep arriving until the
    * block is done: a wave never exits while others may wait at a barrier. */
+  /* Wave 0, before the barrier: the block's next span, unless it still holds
+   * one no wave has taken. One lane asks the cursor of the block's XCD - and,
+   * once that part of the spans is used up, the next XCD's; the answer goes
+   * to LDS, where every wave reads it after the barrier. */
+  auto claim_span = [&]() {
+    if (__builtin_amdgcn_readfirstlane(s_span) != CMI_SPAN_WANTED)
+      return;
+    const uint32_t nparts = a.xcd_remap ? CMI_SPAN_CURSORS : 1u;
+    const uint32_t q = a.xcd_remap ? a.n_spans / CMI_SPAN_CURSORS : a.n_spans;
+    const uint32_t r = a.xcd_remap ? a.n_spans % CMI_SPAN_CURSORS : 0u;
+    uint32_t part =
+        __builtin_amdgcn_readfirstlane(s_span_part);
+    uint32_t got = CMI_SPAN_NONE;
+    for (uint32_t tried = 0; tried < nparts; ++tried) {
+      const uint32_t begin = part * q + (part < r ? part : r);
+      const uint32_t count = q + (part < r ? 1u : 0u);
+      uint32_t v = 0;
+      if (lane == 0)
+        v = atomicAdd(a.span_cursor + part, 1u);
+      v = __builtin_amdgcn_readfirstlane(v);
+      if (v < count) {
+        got = begin + v;
+        break;
+      }
+      part = part + 1u == nparts ? 0u : part + 1u;
+    }
+    if (lane == 0) {
+      s_span = got;
+      s_span_part = part;
+    }
+  };
   auto flush_point = [&](bool has_work) -> bool {
+    if (CLAIM && claim && __builtin_amdgcn_readfirstlane(wib) == 0)
+      claim_span();
+    /* (bit 1: the wave has used up its chunk) */
     if (lane == 0)
-      block_has_work[wib] = has_work ? 1 : 0;
+      block_has_work[wib] =
+          (has_work ? 1 : 0) | ((CLAIM && claim && pos == pos_end) ? 2 : 0);
+    CMI_PHASE_MARK(CMI_PHASE_END);
     __syncthreads();
+    CMI_PHASE_MARK(CMI_PHASE_BARRIER);
     if (FULL) {
       const int i = threadIdx.x & 15;
       for (int k = threadIdx.x >> 4; k < lds_slots; k += BLOCK / 16) {
@@ -1290,11 +1409,39 @@ __global__ void
         }
       }
     }
-    int any_work = 0;
+    int any_work = 0, all_waves = 2;
 #pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w)
+    for (int w = 0; w < BLOCK / 64; ++w) {
       any_work |= block_has_work[w];
+      all_waves &= block_has_work[w];
+    }
+    any_work &= 1;
+    bool took = false;
+    if (CLAIM && claim) {
+      /* the span the block holds: once every wave has used up its chunk, wave
+       * w takes chunk w of it (a short last span leaves some waves without
+       * positions: they keep arriving here) */
+      const uint32_t span =
+          __builtin_amdgcn_readfirstlane(s_span);
+      if (span != CMI_SPAN_NONE)
+        any_work = 1;
+      took = span != CMI_SPAN_NONE &&
+             __builtin_amdgcn_readfirstlane(all_waves) != 0;
+      if (took) {
+        chunk_begin =
+            ((uint64_t)span * (BLOCK / 64) +
+             (uint64_t)__builtin_amdgcn_readfirstlane(wib)) *
+            chunk;
+        pos = chunk_begin < a.n_packets ? chunk_begin : a.n_packets;
+        pos_end = chunk_begin + chunk < a.n_packets ? chunk_begin + chunk
+                                                    : a.n_packets;
+      }
+    }
     __syncthreads();
+    /* (after every wave has read it) */
+    if (CLAIM && took && threadIdx.x == 0)
+      s_span = CMI_SPAN_WANTED;
+    CMI_PHASE_MARK(CMI_PHASE_FLUSH);
     return any_work != 0;
   };
   /* add (v0[, v1]) to `cell` through the block table, for the lanes given as
@@ -1378,21 +1525,25 @@ __global__ void
   for (;;) {
     const unsigned long long active_mask = __ballot(active);
     const unsigned long long idle_mask = ~active_mask;
-    if (pos == pos_end && chunk_begin + nwaves * chunk < a.n_packets) {
+    if (!claim && pos == pos_end &&
+        chunk_begin + nwaves * chunk < a.n_packets) {
       /* current chunk used up: jump to this wave's next one */
       chunk_begin += nwaves * chunk;
       pos = chunk_begin;
       pos_end = chunk_begin + chunk < a.n_packets ? chunk_begin + chunk
                                                   : a.n_packets;
     }
-    const uint64_t avail = pos_end - pos;
+    const bool refill_first = CLAIM && a.emit_before_flush != 0;
+    const bool has_work = active_mask != 0ull || pos_end != pos;
     if (use_table) {
-      /* between two bundles */
-      if (!flush_point(active_mask != 0ull || avail != 0))
+      /* between two bundles (a block that claims its spans takes the next
+       * one here) */
+      if (!refill_first && !flush_point(has_work))
         break;
-    } else if (active_mask == 0ull && avail == 0) {
+    } else if (!has_work) {
       break;
     }
+    const uint64_t avail = pos_end - pos;
     if (avail != 0 && idle_mask != 0ull &&
         (active_mask == 0ull || (int)__popcll(idle_mask) >= a.refill_threshold)) {
       const uint64_t rank = __popcll(idle_mask & lane_lt);
@@ -1544,9 +1695,18 @@ __global__ void
       const uint64_t taken = __popcll(idle_mask);
       pos += taken < avail ? taken : avail;
     }
-    /* more positions left for this wave (in this or a later chunk)? */
+    CMI_PHASE_MARK(CMI_PHASE_REFILL);
+    /* emit_before_flush: the flush point after the refill, with what the wave
+     * knew before it */
+    if (CLAIM && refill_first && !flush_point(has_work))
+      break;
+    /* more positions left for this wave (in this or a later chunk)? (A wave
+     * of a block that claims its spans flies what it has to the end once its
+     * chunk is used up: the next span comes when all the block's waves are
+     * through theirs.) */
     const uint64_t avail_after =
-        (pos_end - pos) + (chunk_begin + nwaves * chunk < a.n_packets ? 1 : 0);
+        (pos_end - pos) +
+        (!claim && chunk_begin + nwaves * chunk < a.n_packets ? 1 : 0);
 
     /* ---- hot loop: only the march and the accumulation. It runs until so
      * few lanes are still in flight that the wave is due for a refill (or
@@ -1883,6 +2043,7 @@ __global__ void
       }
     }
 
+    CMI_PHASE_MARK(CMI_PHASE_MARCH);
     /* ---- end of flight for every lane that cannot step any more ---- */
     if (active) {
       bool inside_now;
@@ -2013,7 +2174,19 @@ __global__ void
         }
       }
     }
+    CMI_PHASE_MARK(CMI_PHASE_END);
   }
+#ifdef CMI_EXPERIMENTS
+  if (stamps && lane == 0) {
+    for (int k = 0; k < CMI_PHASE_COUNT; ++k)
+      atomicAdd(a.phase_clock + k, phase_cycles[k]);
+    /* (the block's waves leave the last flush point together) */
+    if (threadIdx.x == 0)
+      a.phase_clock[CMI_PHASE_COUNT + 1 + blockIdx.x] =
+          __builtin_amdgcn_s_memrealtime();
+  }
+#endif
+#undef CMI_PHASE_MARK
   /* IonizationPhotonShootJobMarket::update_counters */
   double s0 = wave_sum((double)tc0);
   double s1 = wave_sum((double)tc1);

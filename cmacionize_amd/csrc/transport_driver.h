@@ -490,6 +490,8 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
 
 /* the buffers of a launch of at most `cap` flights */
 static int reserve_for(cmi_gpu_engine *e, const LaunchPlan &p, uint64_t cap) {
+  if (!e->span_cursor)
+    HIP_TRY(hipMalloc(&e->span_cursor, sizeof(uint32_t) * CMI_SPAN_CURSORS));
   if (p.sorted || p.tiles)
     CMI_TRY(reserve_sort_buffers(e, cap));
   if (p.passes)
@@ -562,6 +564,14 @@ static ShootArgs shoot_args(const cmi_gpu_engine *e, const LaunchPlan &p,
   a.qin = no_queue();
   a.qout = no_queue();
   a.park_in_place = 0;
+  /* (launch_first_generation turns the claimed spans on) */
+  a.span_cursor = nullptr;
+  a.n_spans = 0;
+  a.span_claim = 0;
+  a.emit_before_flush = e->tune.emit_before_flush ? 1 : 0;
+#ifdef CMI_EXPERIMENTS
+  a.phase_clock = nullptr;
+#endif
   return a;
 }
 
@@ -682,9 +692,38 @@ static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
 
 /* the first generation: one timed launch over the launch's flights */
 static int launch_first_generation(cmi_gpu_engine *e, const LaunchPlan &p,
-                                   const ShootArgs &a) {
+                                   const ShootArgs &args) {
+  ShootArgs a = args;
   const unsigned blocks = transport_blocks(
       e, a.n_packets, a.chunk, p.blocks_per_cu_first, p.first_threads);
+  if (e->tune.span_claim) {
+    /* the cursors start at 0 in every launch (kernels without the
+     * hydrogen-only block table do not look at them) */
+    HIP_TRY(hipMemsetAsync(e->span_cursor, 0,
+                           sizeof(uint32_t) * CMI_SPAN_CURSORS, e->stream));
+    const uint64_t span = (uint64_t)(p.first_threads / 64) * a.chunk;
+    a.span_cursor = e->span_cursor;
+    a.n_spans = (uint32_t)((a.n_packets + span - 1) / span);
+    a.span_claim = 1;
+  }
+#ifdef CMI_EXPERIMENTS
+  if (e->tune.phase_stamps) {
+    const size_t words = CMI_PHASE_COUNT + 1 + (size_t)blocks;
+    if (e->phase_clock_capacity < words) {
+      (void)hipFree(e->phase_clock);
+      e->phase_clock = nullptr;
+      e->phase_clock_capacity = 0;
+      HIP_TRY(hipMalloc(&e->phase_clock, sizeof(unsigned long long) * words));
+      e->phase_clock_capacity = words;
+    }
+    HIP_TRY(hipMemsetAsync(e->phase_clock, 0,
+                           sizeof(unsigned long long) * words, e->stream));
+    HIP_TRY(hipMemsetAsync(e->phase_clock + CMI_PHASE_COUNT, 0xff,
+                           sizeof(unsigned long long), e->stream));
+    e->phase_blocks = blocks;
+    a.phase_clock = e->phase_clock;
+  }
+#endif
   EventPair kev;
   CMI_TRY(timer_begin(e, kev));
   p.kernel_first<<<blocks, p.first_threads, 0, e->stream>>>(a);

@@ -123,6 +123,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_field_cube", "cmi_gpu_emission_line_atomic_weight",
     "cmi_gpu_render_field_sky_cube", "cmi_gpu_render_line_sky_cube",
     "cmi_gpu_render_line_sky_map_cube",
+    "cmi_gpu_get_phase_clocks",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -256,6 +257,12 @@ def load_library():
     L.cmi_gpu_get_kernel_timing.argtypes = [vp, _dp, C.POINTER(C.c_uint64)]
     L.cmi_gpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int64]
     L.cmi_gpu_get_atomic_count.argtypes = [vp, C.POINTER(C.c_uint64)]
+    # (a build from before the stamps, loaded through CMI_GPU_LIBRARY for a
+    # comparison, does not have it)
+    if hasattr(L, "cmi_gpu_get_phase_clocks"):
+        L.cmi_gpu_get_phase_clocks.argtypes = [vp, C.POINTER(C.c_uint64),
+                                               C.c_int64,
+                                               C.POINTER(C.c_int64)]
     L.cmi_gpu_get_wave_steps.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.cmi_gpu_set_export_buffer.argtypes = [vp, vp, C.c_uint64]
     L.cmi_gpu_get_export_count.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -731,6 +738,19 @@ class GpuEngine:
         n = C.c_uint64()
         self._check(self._lib.cmi_gpu_get_atomic_count(self._h, C.byref(n)))
         return n.value
+
+    def get_phase_clocks(self):
+        """Experiment builds with set_tuning(phase_stamps=1): the stamps of
+        the last first-generation launch - (cycles per section [5], the
+        100 MHz clock at the launch's start, ... at every block's end)."""
+        n = C.c_int64()
+        self._check(self._lib.cmi_gpu_get_phase_clocks(self._h, None, 0,
+                                                       C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint64)
+        self._check(self._lib.cmi_gpu_get_phase_clocks(
+            self._h, out.ctypes.data_as(C.POINTER(C.c_uint64)), n.value,
+            C.byref(n)))
+        return out[:5], int(out[5]), out[6:]
 
     def get_launch_times(self):
         """[(ms, flights)] of the transport launches since the last

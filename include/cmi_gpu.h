@@ -374,6 +374,17 @@ int cmi_gpu_get_atomic_count(cmi_gpu_engine *engine, uint64_t *natomics);
  * did a step in an average iteration (diagnostic of the packet ordering) */
 int cmi_gpu_get_wave_steps(cmi_gpu_engine *engine, uint64_t *nwavesteps);
 
+/* EXPERIMENT ONLY (builds with -DCMI_EXPERIMENTS and the tuning key
+ * "phase_stamps"; CMI_GPU_ESTATE otherwise): the stamps of the last
+ * first-generation launch of a hydrogen-only table kernel. out[0..4]: shader
+ * cycles the waves spent waiting at the flush point's first barrier, in the
+ * flush, in the refill, in the march loop and at the end of flights;
+ * out[5]: the 100 MHz clock when the first block started; out[6 + b]: when
+ * block b left the kernel. *count: the values the launch wrote (6 + its
+ * blocks); at most `capacity` are copied. Synchronous. */
+int cmi_gpu_get_phase_clocks(cmi_gpu_engine *engine, uint64_t *out,
+                             int64_t capacity, int64_t *count);
+
 /* replaces: TemperatureCalculator::calculate_temperature(loop, totweight,
  * grid, block) (src/TemperatureCalculator.cpp:944-970), i.e. per cell either
  * IonizationStateCalculator::calculate_ionization_state
@@ -615,6 +626,16 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *   "exact_dda" (0)         march with the reference's per-step arithmetic
  *                           (bit-identical path lengths) instead of the
  *                           incremental marcher (equal up to rounding)
+ *   "span_claim" (1)        first generation of the hydrogen-only runs that
+ *                           use the block table: a block takes its packets a
+ *                           span (one chunk per wave) at a time from a cursor
+ *                           in device memory - one cursor per XCD with
+ *                           "xcd_remap" - instead of a fixed share by block
+ *                           index
+ *   "emit_before_flush" (1) the same kernels: the refill ahead of the flush
+ *                           point's barrier - a wave that arrives early emits
+ *                           its next bundle while it would wait
+ *   "phase_stamps" (0)      EXPERIMENT ONLY: cmi_gpu_get_phase_clocks
  *   "exp_no_atomics" (0)    EXPERIMENT ONLY, builds with -DCMI_EXPERIMENTS
  *                           (results are wrong): 1 = skip the
  *                           accumulation; multi-ion kernels: 2 = post
