@@ -226,17 +226,55 @@ dust_select_view(const DustCamera<DUST_CAMERA_POINT_VIEWS> &cam, int v,
   cv.image = cam.images + (size_t)v * 3 * ((size_t)cv.nlon * cv.nlat);
 }
 
+/* Cube mode (scattered-light line cubes; include/cmi_gpu.h,
+ * "scattered-light line cubes", has the contract): the compile-time switch
+ * CUBE of dust_packet and its kernels, and what a cube run reads beyond the
+ * image run, a kernel argument of its own. Only the cell source has it. The
+ * events of a cube run are dust_cube_kernels.h's. */
+template <bool CUBE> struct DustCube {};
+template <> struct DustCube<true> {
+  const double *velocity;     /* [3][ncell] or null: at rest */
+  int64_t ncell;
+  const double *s2;           /* [ncell]: the variance of a cell's profile */
+  const double *obs_velocity; /* [nviews][3]; the point camera's */
+  double two_sigma2;          /* 2 sigma_t sigma_t */
+  int32_t nchan;
+  double vmin, dv;
+  int64_t npixel; /* of one view's image */
+  double *cube;   /* [nviews][3][npixel][nchan]: the channel runs fastest */
+};
+typedef DustCube<true> DustCubeDev;
+
+template <bool TRACE, int CAMERA>
+__device__ __forceinline__ void
+dust_cube_events(const GridDev &g, const DustDev &d,
+                 const DustCamera<CAMERA> &cam, const DustCubeDev &cube,
+                 const double2 *__restrict__ opacity, const DustPhoton &p,
+                 bool scattered, double weight, double albedo, double q,
+                 double s2, int64_t cell, DustDev &dv, SkyCameraDev &cv,
+                 DustCountersDev &c, DustEvents &ev);
+__device__ __forceinline__ double dust_cube_doppler(const DustCubeDev &cube,
+                                                    int64_t cell,
+                                                    const double k[3]);
+__device__ __forceinline__ int64_t dust_cube_cell(const GridDev &g,
+                                                  const double pos[3]);
+
 /* DustPhotonShootJob::execute for one packet; SOURCE selects where it
  * starts and CAMERA where its peel-offs go (at compile time: the galaxy's
  * instantiation has no trace of the other source, the parallel camera's
  * none of the point camera), everything else is the same. The two kinds with
  * several views walk the same walk and repeat each event per view, in the
  * order 0..K-1, through the single camera's functions with the single
- * camera's expressions: an addend is the single camera's addend. */
-template <bool TRACE, int SOURCE, int CAMERA>
+ * camera's expressions: an addend is the single camera's addend. With CUBE
+ * the packet carries its Doppler velocity q and the variance s2 of its
+ * profile, and every event goes through dust_cube_events, which fills the
+ * image with the same addends and the cube with their shares per channel;
+ * the walk and its random numbers do not change. */
+template <bool TRACE, int SOURCE, int CAMERA, bool CUBE>
 __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
                                    const DustSource<SOURCE> &src,
                                    const DustCamera<CAMERA> &cam,
+                                   const DustCube<CUBE> &cube,
                                    const double2 *__restrict__ opacity,
                                    uint32_t seed, uint64_t id,
                                    DustCountersDev &c, DustEvents &ev) {
@@ -244,8 +282,17 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   rng.init(seed, 0u, id);
   DustPhoton p;
   c.npackets += 1;
+  /* cube mode's two scalars */
+  [[maybe_unused]] double q = 0., s2 = 0.;
+  [[maybe_unused]] int64_t ecell = 0;
   if constexpr (SOURCE == DUST_SOURCE_CELLS) {
-    (void)dust_emit_cells(g, src, rng, p);
+    if constexpr (CUBE) {
+      ecell = dust_emit_cells(g, src, rng, p);
+      q = dust_cube_doppler(cube, ecell, p.dir);
+      s2 = cube.s2[ecell];
+    } else {
+      (void)dust_emit_cells(g, src, rng, p);
+    }
   } else {
     if (!dust_emit(d, rng, p)) {
       c.nsource_capped += 1;
@@ -263,7 +310,10 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
     cv = cam.shared;
 
   /* direct light towards the observer, :127-130 */
-  if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
+  if constexpr (CUBE) {
+    dust_cube_events<TRACE, CAMERA>(g, d, cam, cube, opacity, p, false, 1., 1.,
+                                    q, s2, ecell, dv, cv, c, ev);
+  } else if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
     if (cam.shared.direct_light) {
       for (int v = 0; v < cam.nviews; ++v) {
         dust_select_view(cam, v, cv);
@@ -310,7 +360,12 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
   while (inside) {
     /* peel-off, :141-155 */
     DustPhoton peel = p;
-    if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
+    if constexpr (CUBE) {
+      albedo *= d.albedo;
+      dust_cube_events<TRACE, CAMERA>(g, d, cam, cube, opacity, p, true,
+                                      weight, albedo, q, s2,
+                                      dust_cube_cell(g, p.pos), dv, cv, c, ev);
+    } else if constexpr (CAMERA == DUST_CAMERA_POINT_VIEWS) {
       albedo *= d.albedo;
       for (int v = 0; v < cam.nviews; ++v) {
         dust_select_view(cam, v, cv);
@@ -351,7 +406,18 @@ __device__ inline void dust_packet(const GridDev &g, const DustDev &d,
                       peel.stokes, weight_new, ev, c.natomics);
     }
     /* scatter and fly on, :157-159 */
-    dust_scatter(d, rng, p);
+    if constexpr (CUBE) {
+      const int64_t scell = dust_cube_cell(g, p.pos);
+      const double k[3] = {p.dir[0], p.dir[1], p.dir[2]};
+      dust_scatter(d, rng, p);
+      q += dust_cube_doppler(cube, scell, p.dir) -
+           dust_cube_doppler(cube, scell, k);
+      s2 += cube.two_sigma2 *
+            fmax(0., 1. - ((k[0] * p.dir[0] + k[1] * p.dir[1]) +
+                           k[2] * p.dir[2]));
+    } else {
+      dust_scatter(d, rng, p);
+    }
     ++nscatter;
     if (nscatter >= CMI_DUST_MAX_SCATTER) {
       c.ncapped += 1;
@@ -373,18 +439,19 @@ __device__ __forceinline__ void dust_count(unsigned long long *dst,
 }
 
 /* packets [first, first + n) */
-template <int SOURCE, int CAMERA>
+template <int SOURCE, int CAMERA, bool CUBE>
 __global__ void __launch_bounds__(256)
     dust_shoot_kernel(GridDev g, DustDev d,
                       const double2 *__restrict__ opacity, uint32_t seed,
                       uint64_t first, uint64_t n, DustCountersDev *counters,
-                      DustSource<SOURCE> src, DustCamera<CAMERA> cam) {
+                      DustSource<SOURCE> src, DustCamera<CAMERA> cam,
+                      DustCube<CUBE> cube) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   DustCountersDev c = {};
   DustEvents ev = {nullptr, 0, 0};
   if (k < n)
-    dust_packet<false, SOURCE, CAMERA>(g, d, src, cam, opacity, seed,
-                                       first + k, c, ev);
+    dust_packet<false, SOURCE, CAMERA, CUBE>(g, d, src, cam, cube, opacity,
+                                             seed, first + k, c, ev);
   /* the whole wave reaches the reduction (no early return above) */
   dust_count(&counters->nsteps, c.nsteps);
   dust_count(&counters->nscatter, c.nscatter);
@@ -406,17 +473,20 @@ enum {
   DUST_PROBE_OPTICAL_DEPTH = 3,
   DUST_PROBE_TRACE = 4,
   DUST_PROBE_CELL_SOURCE = 5,
-  DUST_PROBE_SKY_PEEL = 6
+  DUST_PROBE_SKY_PEEL = 6,
+  DUST_PROBE_CUBE_TRACE = 7
 };
 
 /* the parity probes of cmi_gpu_dust_probe (include/cmi_gpu.h gives the row
  * layouts); row k uses the stream of packet first + k. EMIT and TRACE follow
  * SOURCE, TRACE follows CAMERA; CELL_SOURCE exists in the cell source's
- * instantiations only, SKY_PEEL in the point camera's. */
-template <int SOURCE, int CAMERA>
+ * instantiations only, SKY_PEEL in the point camera's. The CUBE
+ * instantiations serve CUBE_TRACE alone: TRACE with rows of 10, {u, b} after
+ * the 8. */
+template <int SOURCE, int CAMERA, bool CUBE>
 __global__ void __launch_bounds__(64)
     dust_probe_kernel(GridDev g, DustDev d, DustSource<SOURCE> src,
-                      DustCamera<CAMERA> cam,
+                      DustCamera<CAMERA> cam, DustCube<CUBE> cube,
                       const double2 *__restrict__ opacity, int32_t kind,
                       uint32_t seed, uint64_t first, int64_t n, int32_t width,
                       const double *__restrict__ in, double *__restrict__ out,
@@ -427,6 +497,19 @@ __global__ void __launch_bounds__(64)
   PacketRng rng;
   rng.init(seed, 0u, first + k);
   double *o = out + k * width;
+  if constexpr (CUBE) {
+    if (kind == DUST_PROBE_CUBE_TRACE) {
+      DustCountersDev c = {};
+      DustEvents ev = {o + 4, max_events, 0};
+      dust_packet<true, SOURCE, CAMERA, true>(g, d, src, cam, cube, opacity,
+                                              seed, first + k, c, ev);
+      o[0] = ev.n;
+      o[1] = (double)c.nscatter;
+      o[2] = (double)c.nsteps;
+      o[3] = (double)(c.ncapped + c.nsource_capped);
+    }
+    return;
+  }
   if (kind == DUST_PROBE_EMIT) {
     DustPhoton p;
     bool ok = true;
@@ -477,8 +560,8 @@ __global__ void __launch_bounds__(64)
     /* out: {nevents, nscatter, nsteps, ncapped, rows[max_events][8]} */
     DustCountersDev c = {};
     DustEvents ev = {o + 4, max_events, 0};
-    dust_packet<true, SOURCE, CAMERA>(g, d, src, cam, opacity, seed,
-                                      first + k, c, ev);
+    dust_packet<true, SOURCE, CAMERA, false>(g, d, src, cam, DustCube<false>(),
+                                             opacity, seed, first + k, c, ev);
     o[0] = ev.n;
     o[1] = (double)c.nscatter;
     o[2] = (double)c.nsteps;

@@ -13,6 +13,7 @@
 #include "line_cube_kernels.h"
 #include "sky_image_kernels.h"
 #include "sky_cube_kernels.h"
+#include "dust_cube_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -281,6 +282,15 @@ struct cmi_gpu_engine {
   std::vector<SkyObserverDev> sky_views;
   void *dust_views_dev = nullptr;
   unsigned long long *dust_view_counters = nullptr;
+  /* cube mode (cmi_gpu_set_scattered_cube; nchan 0: off): the kernels'
+   * argument with the engine's buffers s2 [ncell], obs_velocity [nviews][3]
+   * and cube [nviews][3][npixel][nchan], the views the cube was made for, and
+   * why it is stale (null: it is not) */
+  DustCubeDev dust_cube = {};
+  int32_t dust_cube_nviews = 0;
+  const char *dust_cube_stale = nullptr;
+  /* the line of cmi_gpu_set_cell_source_line */
+  int32_t cell_source_line = -1;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1181,6 +1191,9 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->dust_counters);
   (void)hipFree(e->cell_source_cells);
   (void)hipFree(e->cell_velocities);
+  (void)hipFree(const_cast<double *>(e->dust_cube.s2));
+  (void)hipFree(const_cast<double *>(e->dust_cube.obs_velocity));
+  (void)hipFree(e->dust_cube.cube);
   (void)hipFree(e->cell_source_blocks);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
@@ -2702,6 +2715,14 @@ int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *e, double g,
   return CMI_GPU_OK;
 }
 
+/* cube mode does not outlive what it was built from (the cameras, the cell
+ * source, the velocities): the next shoot or probe fails until
+ * cmi_gpu_set_scattered_cube is called again */
+static void dust_cube_mark_stale(cmi_gpu_engine *e, const char *why) {
+  if (e->dust_cube.nchan)
+    e->dust_cube_stale = why;
+}
+
 /* the views' descriptors and counters go with a camera that is replaced */
 static void dust_free_views(cmi_gpu_engine *e) {
   (void)hipFree(e->dust_views_dev);
@@ -2800,6 +2821,7 @@ int cmi_gpu_set_ccd_image(cmi_gpu_engine *e, double theta, double phi,
   e->dust_camera = DUST_CAMERA_PARALLEL;
   e->sky_camera.image = nullptr;
   e->have_ccd = true;
+  dust_cube_mark_stale(e, "the camera was set again");
   return cmi_gpu_reset_image(e);
 }
 
@@ -2892,6 +2914,7 @@ int cmi_gpu_set_ccd_images(cmi_gpu_engine *e, int32_t nviews,
   e->sky_camera.image = nullptr;
   e->dust_camera = DUST_CAMERA_PARALLEL_VIEWS;
   e->have_ccd = true;
+  dust_cube_mark_stale(e, "the cameras were set again");
   return cmi_gpu_reset_image(e);
 }
 
@@ -2950,6 +2973,7 @@ int cmi_gpu_set_continuous_source_spiral_galaxy(cmi_gpu_engine *e,
   d.cdf_n = nbin + 1;
   e->have_dust_source = true;
   e->dust_source = DUST_SOURCE_GALAXY;
+  dust_cube_mark_stale(e, "the source was replaced");
   return CMI_GPU_OK;
 }
 
@@ -3038,6 +3062,7 @@ static int cell_source_begin(cmi_gpu_engine *e) {
    * leaves no source */
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->have_cell_source = false;
+  dust_cube_mark_stale(e, "the cell source was replaced");
   if (!e->cell_source_cells)
     HIP_TRY(hipMalloc(&e->cell_source_cells,
                       (size_t)e->ncell * sizeof(double)));
@@ -3062,6 +3087,7 @@ int cmi_gpu_set_cell_source_line(cmi_gpu_engine *e, int32_t line) {
   cell_source_line_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
                             e->stream>>>(a);
   HIP_TRY(hipGetLastError());
+  e->cell_source_line = line;
   return cell_source_build(e, what, true);
 }
 
@@ -3137,6 +3163,9 @@ static int dust_prepare(cmi_gpu_engine *e) {
       e->cell_source_epoch != e->cells_epoch)
     return fail(CMI_GPU_ESTATE, "dust: the cells changed after the line "
                                 "source was set; set_cell_source_line again");
+  if (e->dust_cube.nchan && e->dust_cube_stale)
+    return fail(CMI_GPU_ESTATE, "dust: %s after cube mode was set; "
+                "set_scattered_cube again", e->dust_cube_stale);
   HIP_TRY(hipSetDevice(e->device));
   if (!e->dust_opacity)
     HIP_TRY(hipMalloc(&e->dust_opacity, (size_t)e->ncell * sizeof(double2)));
@@ -3180,17 +3209,55 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
     EventPair ev;
     CMI_TRY(timer_begin(e, ev));
     const unsigned blocks = (unsigned)((chunk + 255) / 256);
-    if (e->dust_camera == DUST_CAMERA_POINT_VIEWS) {
+    const DustCube<false> no_cube;
+    if (e->dust_cube.nchan) {
+      /* cube mode: the cube instantiation of the selected camera (the cell
+       * source is selected, cmi_gpu_set_scattered_cube and dust_prepare saw
+       * to it) */
+      const DustCubeDev cube = e->dust_cube;
+      if (e->dust_camera == DUST_CAMERA_POINT_VIEWS) {
+        DustCamera<DUST_CAMERA_POINT_VIEWS> cam;
+        cam.shared = e->sky_camera;
+        cam.views = (const SkyObserverDev *)e->dust_views_dev;
+        cam.nviews = e->dust_nviews;
+        cam.images = e->dust_image;
+        cam.counters = e->dust_view_counters;
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT_VIEWS, true>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, e->cell_source, cam, cube);
+      } else if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS) {
+        DustCamera<DUST_CAMERA_PARALLEL_VIEWS> cam;
+        cam.views = (const DustViewDev *)e->dust_views_dev;
+        cam.nviews = e->dust_nviews;
+        cam.images = e->dust_image;
+        cam.counters = e->dust_view_counters;
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL_VIEWS, true>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, e->cell_source, cam, cube);
+      } else if (e->dust_camera == DUST_CAMERA_POINT)
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT, true>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, e->cell_source, e->sky_camera, cube);
+      else
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL, true>
+            <<<blocks, 256, 0, e->stream>>>(
+                e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
+                chunk, e->dust_counters, e->cell_source,
+                DustCamera<DUST_CAMERA_PARALLEL>(), cube);
+    } else if (e->dust_camera == DUST_CAMERA_POINT_VIEWS) {
       DustCamera<DUST_CAMERA_POINT_VIEWS> cam;
       cam.shared = e->sky_camera;
       cam.views = (const SkyObserverDev *)e->dust_views_dev;
       cam.nviews = e->dust_nviews;
       cam.images = e->dust_image;
       cam.counters = e->dust_view_counters;
-      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT_VIEWS>
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT_VIEWS, false>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
-              chunk, e->dust_counters, e->cell_source, cam);
+              chunk, e->dust_counters, e->cell_source, cam, no_cube);
     } else if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS) {
       DustCamera<DUST_CAMERA_PARALLEL_VIEWS> cam;
       cam.views = (const DustViewDev *)e->dust_views_dev;
@@ -3198,33 +3265,34 @@ int cmi_gpu_dust_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
       cam.images = e->dust_image;
       cam.counters = e->dust_view_counters;
       if (e->dust_source == DUST_SOURCE_CELLS)
-        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL_VIEWS>
+        dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL_VIEWS, false>
             <<<blocks, 256, 0, e->stream>>>(
                 e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
-                chunk, e->dust_counters, e->cell_source, cam);
+                chunk, e->dust_counters, e->cell_source, cam, no_cube);
       else
-        dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL_VIEWS>
+        dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL_VIEWS, false>
             <<<blocks, 256, 0, e->stream>>>(
                 e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
                 chunk, e->dust_counters, DustSource<DUST_SOURCE_GALAXY>(),
-                cam);
+                cam, no_cube);
     } else if (e->dust_camera == DUST_CAMERA_POINT)
-      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT, false>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
-              chunk, e->dust_counters, e->cell_source, e->sky_camera);
+              chunk, e->dust_counters, e->cell_source, e->sky_camera,
+              no_cube);
     else if (e->dust_source == DUST_SOURCE_CELLS)
-      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL>
+      dust_shoot_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL, false>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
               chunk, e->dust_counters, e->cell_source,
-              DustCamera<DUST_CAMERA_PARALLEL>());
+              DustCamera<DUST_CAMERA_PARALLEL>(), no_cube);
     else
-      dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL>
+      dust_shoot_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL, false>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, e->dust, e->dust_opacity, seed, first_packet + done,
               chunk, e->dust_counters, DustSource<DUST_SOURCE_GALAXY>(),
-              DustCamera<DUST_CAMERA_PARALLEL>());
+              DustCamera<DUST_CAMERA_PARALLEL>(), no_cube);
     HIP_TRY(hipGetLastError());
     CMI_TRY(timer_end(e, e->shoot_events, ev, chunk));
     done += chunk;
@@ -3326,6 +3394,12 @@ int cmi_gpu_reset_image(cmi_gpu_engine *e) {
                                CMI_DUST_VIEW_SLOTS *
                                sizeof(unsigned long long),
                            e->stream));
+  if (e->dust_cube.nchan)
+    HIP_TRY(hipMemsetAsync(e->dust_cube.cube, 0,
+                           (size_t)e->dust_cube_nviews * 3 *
+                               (size_t)e->dust_cube.npixel *
+                               e->dust_cube.nchan * sizeof(double),
+                           e->stream));
   if (e->dust_counters)
     HIP_TRY(hipMemsetAsync(e->dust_counters, 0, sizeof(DustCountersDev),
                            e->stream));
@@ -3375,16 +3449,17 @@ int cmi_gpu_select_probe_view(cmi_gpu_engine *e, int32_t view) {
 int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
                        uint64_t first_packet, int64_t n, const double *in,
                        double *out, int32_t max_events) {
-  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_SKY_PEEL ||
+  if (!e || n < 0 || !out || kind < 0 || kind > DUST_PROBE_CUBE_TRACE ||
       max_events < 0 || n > (1 << 24))
     return fail(CMI_GPU_EINVAL, "dust_probe: bad argument");
-  static const int in_width[7] = {0, 12, 12, 6, 0, 0, 15};
+  static const int in_width[8] = {0, 12, 12, 6, 0, 0, 15, 0};
   const int width = kind == DUST_PROBE_EMIT              ? 6
                     : kind == DUST_PROBE_SCATTER         ? 12
                     : kind == DUST_PROBE_SCATTER_TOWARDS ? 5
                     : kind == DUST_PROBE_OPTICAL_DEPTH   ? 2 + max_events
                     : kind == DUST_PROBE_CELL_SOURCE     ? 7
                     : kind == DUST_PROBE_SKY_PEEL        ? 9
+                    : kind == DUST_PROBE_CUBE_TRACE      ? 4 + 10 * max_events
                                                          : 4 + 8 * max_events;
   if (in_width[kind] && !in)
     return fail(CMI_GPU_EINVAL, "dust_probe: input rows missing");
@@ -3393,6 +3468,13 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     return fail(CMI_GPU_ESTATE, "dust_probe: no cell source is selected");
   if (kind == DUST_PROBE_SKY_PEEL && !dust_point_camera(e))
     return fail(CMI_GPU_ESTATE, "dust_probe: no sky camera is selected");
+  if (kind == DUST_PROBE_CUBE_TRACE && !e->dust_cube.nchan)
+    return fail(CMI_GPU_ESTATE, "dust_probe: cube mode is not set "
+                                "(set_scattered_cube)");
+  /* the selected view's observer velocity goes with its camera */
+  DustCubeDev cube = e->dust_cube;
+  if (cube.nchan)
+    cube.obs_velocity += 3 * (size_t)e->dust_probe_view;
   /* with several views the probes run the single camera's kernels for the
    * selected view, so a row is the single camera's row (a trace writes to no
    * image) */
@@ -3421,24 +3503,40 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
     const unsigned blocks = (unsigned)((m + 63) / 64);
     const double *rows = din ? din + k * in_width[kind] : nullptr;
-    if (dust_point_camera(e))
-      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT>
+    const DustCube<false> no_cube;
+    if (kind == DUST_PROBE_CUBE_TRACE && dust_point_camera(e))
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT, true>
           <<<blocks, 64, 0, e->stream>>>(
-              e->grid, dust, e->cell_source, sky_camera, e->dust_opacity,
-              kind, seed, first_packet + k, m, width, rows, dout + k * width,
-              max_events);
-    else if (e->dust_source == DUST_SOURCE_CELLS)
-      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL>
+              e->grid, dust, e->cell_source, sky_camera, cube,
+              e->dust_opacity, kind, seed, first_packet + k, m, width, rows,
+              dout + k * width, max_events);
+    else if (kind == DUST_PROBE_CUBE_TRACE)
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL, true>
           <<<blocks, 64, 0, e->stream>>>(
               e->grid, dust, e->cell_source,
-              DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
-              first_packet + k, m, width, rows, dout + k * width, max_events);
+              DustCamera<DUST_CAMERA_PARALLEL>(), cube, e->dust_opacity, kind,
+              seed, first_packet + k, m, width, rows, dout + k * width,
+              max_events);
+    else if (dust_point_camera(e))
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_POINT, false>
+          <<<blocks, 64, 0, e->stream>>>(
+              e->grid, dust, e->cell_source, sky_camera, no_cube,
+              e->dust_opacity, kind, seed, first_packet + k, m, width, rows,
+              dout + k * width, max_events);
+    else if (e->dust_source == DUST_SOURCE_CELLS)
+      dust_probe_kernel<DUST_SOURCE_CELLS, DUST_CAMERA_PARALLEL, false>
+          <<<blocks, 64, 0, e->stream>>>(
+              e->grid, dust, e->cell_source,
+              DustCamera<DUST_CAMERA_PARALLEL>(), no_cube, e->dust_opacity,
+              kind, seed, first_packet + k, m, width, rows, dout + k * width,
+              max_events);
     else
-      dust_probe_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL>
+      dust_probe_kernel<DUST_SOURCE_GALAXY, DUST_CAMERA_PARALLEL, false>
           <<<blocks, 64, 0, e->stream>>>(
               e->grid, dust, DustSource<DUST_SOURCE_GALAXY>(),
-              DustCamera<DUST_CAMERA_PARALLEL>(), e->dust_opacity, kind, seed,
-              first_packet + k, m, width, rows, dout + k * width, max_events);
+              DustCamera<DUST_CAMERA_PARALLEL>(), no_cube, e->dust_opacity,
+              kind, seed, first_packet + k, m, width, rows, dout + k * width,
+              max_events);
     err = hipGetLastError();
     if (err == hipSuccess)
       err = hipStreamSynchronize(e->stream);
@@ -3902,6 +4000,7 @@ int cmi_gpu_set_cell_velocities(cmi_gpu_engine *e, const double *velocities) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     (void)hipFree(e->cell_velocities);
     e->cell_velocities = nullptr;
+    dust_cube_mark_stale(e, "the cell velocities were replaced");
     return CMI_GPU_OK;
   }
   const size_t n = 3 * (size_t)e->ncell;
@@ -3920,8 +4019,18 @@ int cmi_gpu_set_cell_velocities(cmi_gpu_engine *e, const double *velocities) {
     (void)hipFree(fresh);
     return rc;
   }
+  /* a cube launch may still be enqueued and reads the old array (with cube
+   * mode off nothing enqueued does, and the call is what it was) */
+  if (e->dust_cube.nchan) {
+    const hipError_t busy = hipStreamSynchronize(e->stream);
+    if (busy != hipSuccess) {
+      (void)hipFree(fresh);
+      HIP_TRY(busy);
+    }
+  }
   (void)hipFree(e->cell_velocities);
   e->cell_velocities = fresh;
+  dust_cube_mark_stale(e, "the cell velocities were replaced");
   return CMI_GPU_OK;
 }
 
@@ -4723,6 +4832,7 @@ int cmi_gpu_set_sky_camera(cmi_gpu_engine *e, const double *origin,
   e->sky_camera = cam;
   e->dust_camera = DUST_CAMERA_POINT;
   e->have_ccd = true;
+  dust_cube_mark_stale(e, "the camera was set again");
   return cmi_gpu_reset_image(e);
 }
 
@@ -4772,7 +4882,184 @@ int cmi_gpu_set_sky_cameras(cmi_gpu_engine *e, int32_t nviews,
   e->dust.image = nullptr;
   e->dust_camera = DUST_CAMERA_POINT_VIEWS;
   e->have_ccd = true;
+  dust_cube_mark_stale(e, "the cameras were set again");
   return cmi_gpu_reset_image(e);
+}
+
+/* --------------------------------------- scattered-light line cubes -- */
+
+static void dust_cube_free(cmi_gpu_engine *e) {
+  (void)hipFree(const_cast<double *>(e->dust_cube.s2));
+  (void)hipFree(const_cast<double *>(e->dust_cube.obs_velocity));
+  (void)hipFree(e->dust_cube.cube);
+  e->dust_cube = DustCubeDev{};
+  e->dust_cube_nviews = 0;
+  e->dust_cube_stale = nullptr;
+}
+
+int cmi_gpu_set_scattered_cube(cmi_gpu_engine *e, int32_t nchan, double vmin,
+                               double vmax, double sigma_turb,
+                               const double *widths,
+                               const double *observer_velocities) {
+  static const char *what = "set_scattered_cube";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  HIP_TRY(hipSetDevice(e->device));
+  if (nchan == 0) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    dust_cube_free(e);
+    return CMI_GPU_OK;
+  }
+  if (!e->have_ccd)
+    return fail(CMI_GPU_ESTATE, "%s: a camera must be set first", what);
+  if (e->dust_source != DUST_SOURCE_CELLS || !e->have_cell_source)
+    return fail(CMI_GPU_ESTATE, "%s: a cell source must be selected (the "
+                "spiral galaxy has no line)", what);
+  const bool line = e->cell_source_from_cells;
+  if (line && e->cell_source_epoch != e->cells_epoch)
+    return fail(CMI_GPU_ESTATE, "%s: the cells changed after the line source "
+                "was set; set_cell_source_line again", what);
+  if (line && widths)
+    return fail(CMI_GPU_ESTATE, "%s: a line source takes its widths from the "
+                "cells' temperatures; widths must be NULL", what);
+  if (!line && !widths)
+    return fail(CMI_GPU_ESTATE, "%s: a field source needs widths[ncell]",
+                what);
+  if (line && cmi_emission_atomic_weight[e->cell_source_line] == 0.)
+    return fail(CMI_GPU_EINVAL, "%s: entry %d is not the line of one ion: it "
+                "has no line profile", what, (int)e->cell_source_line);
+  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
+    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
+                "be >= 0 and finite", what);
+  const int32_t nviews = e->dust_nviews;
+  if (observer_velocities)
+    for (int32_t i = 0; i < 3 * nviews; ++i)
+      if (!std::isfinite(observer_velocities[i]))
+        return fail(CMI_GPU_EINVAL, "%s: the velocity of observer %d is not "
+                    "finite", what, (int)(i / 3));
+  const bool point = dust_point_camera(e);
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, nviews,
+                         point ? e->sky_camera.nlon : e->dust.res[0],
+                         point ? e->sky_camera.nlat : e->dust.res[1], nchan,
+                         vmin, vmax, axis));
+  const size_t npixel = dust_image_pixels(e);
+  const size_t ncell = (size_t)e->ncell;
+  /* everything new is built aside: a call that fails leaves the previous
+   * state in place */
+  double *s2 = nullptr, *vobs = nullptr, *cube = nullptr, *dwidths = nullptr;
+  unsigned int *ninvalid = nullptr;
+  unsigned int bad = 0;
+  std::vector<double> vo(3 * (size_t)nviews, 0.);
+  if (observer_velocities)
+    std::copy(observer_velocities, observer_velocities + vo.size(),
+              vo.begin());
+  hipError_t err = hipMalloc(&s2, sizeof(double) * ncell);
+  if (err == hipSuccess)
+    err = hipMalloc(&vobs, sizeof(double) * vo.size());
+  if (err == hipSuccess)
+    err = hipMalloc(&cube, sizeof(double) * 3 * (size_t)nviews * npixel * nchan);
+  if (err == hipSuccess)
+    err = hipMemcpy(vobs, vo.data(), sizeof(double) * vo.size(),
+                    hipMemcpyHostToDevice);
+  if (err == hipSuccess && line) {
+    dust_cube_line_variance_kernel<<<(unsigned)((ncell + 255) / 256), 256, 0,
+                                     e->stream>>>(
+        e->cells.temperature, cmi_emission_atomic_weight[e->cell_source_line],
+        sigma_turb, e->ncell, s2);
+    err = hipGetLastError();
+  } else if (err == hipSuccess) {
+    err = hipMalloc(&dwidths, sizeof(double) * ncell);
+    if (err == hipSuccess)
+      err = hipMalloc(&ninvalid, sizeof(unsigned int));
+    if (err == hipSuccess)
+      err = hipMemcpy(dwidths, widths, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice);
+    if (err == hipSuccess)
+      err = hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream);
+    if (err == hipSuccess) {
+      dust_cube_field_variance_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0,
+                                        e->stream>>>(dwidths, e->ncell, s2,
+                                                     ninvalid);
+      err = hipGetLastError();
+    }
+    if (err == hipSuccess)
+      err = hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                           e->stream);
+  }
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  (void)hipFree(dwidths);
+  (void)hipFree(ninvalid);
+  int rc = CMI_GPU_OK;
+  if (err == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    rc = fail(CMI_GPU_ENOMEM, "%s: %d cubes of %d channels of %zu pixels do "
+              "not fit into the device's memory", what, (int)nviews,
+              (int)nchan, npixel);
+  } else if (err != hipSuccess) {
+    rc = fail(CMI_GPU_EDEVICE, "%s: %s", what, hipGetErrorString(err));
+  } else if (bad) {
+    rc = fail(CMI_GPU_EINVAL, "%s: %u width(s) are negative or not finite",
+              what, bad);
+  }
+  if (rc) {
+    (void)hipFree(s2);
+    (void)hipFree(vobs);
+    (void)hipFree(cube);
+    return rc;
+  }
+  dust_cube_free(e);
+  DustCubeDev &c = e->dust_cube;
+  c.velocity = e->cell_velocities;
+  c.ncell = e->ncell;
+  c.s2 = s2;
+  c.obs_velocity = vobs;
+  c.two_sigma2 = 2. * sigma_turb * sigma_turb;
+  c.nchan = nchan;
+  c.vmin = axis.vmin;
+  c.dv = axis.dv;
+  c.npixel = (int64_t)npixel;
+  c.cube = cube;
+  e->dust_cube_nviews = nviews;
+  return cmi_gpu_reset_image(e);
+}
+
+int cmi_gpu_download_cube_view(cmi_gpu_engine *e, int32_t view, double *I,
+                               double *Q, double *U) {
+  static const char *what = "download_cube_view";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (!e->dust_cube.nchan)
+    return fail(CMI_GPU_ESTATE, "%s: cube mode is not set "
+                "(set_scattered_cube)", what);
+  /* the image's own refusals: no camera, a capped or dropped packet, the view */
+  CMI_TRY(cmi_gpu_download_image_view(e, view, nullptr, nullptr, nullptr));
+  if (e->dust_cube_stale)
+    return fail(CMI_GPU_ESTATE, "%s: %s after cube mode was set", what,
+                e->dust_cube_stale);
+  const DustCubeDev &c = e->dust_cube;
+  const size_t nvalue = (size_t)c.npixel * c.nchan;
+  double *ordered = nullptr;
+  HIP_TRY(hipMalloc(&ordered, sizeof(double) * nvalue));
+  double *dst[3] = {I, Q, U};
+  hipError_t err = hipSuccess;
+  for (int k = 0; k < 3 && err == hipSuccess; ++k) {
+    if (!dst[k])
+      continue;
+    dust_cube_reorder_kernel<<<(unsigned)((nvalue + 255) / 256), 256, 0,
+                               e->stream>>>(
+        c.cube + (3 * (size_t)view + k) * nvalue, c.npixel, c.nchan, ordered);
+    err = hipGetLastError();
+    if (err == hipSuccess)
+      err = hipStreamSynchronize(e->stream);
+    if (err == hipSuccess)
+      err = hipMemcpy(dst[k], ordered, sizeof(double) * nvalue,
+                      hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(ordered);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
 }
 
 } // extern "C"

@@ -35,6 +35,7 @@ DUST_PROBE_EMIT, DUST_PROBE_SCATTER, DUST_PROBE_SCATTER_TOWARDS = 0, 1, 2
 DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
 DUST_PROBE_CELL_SOURCE = 5
 DUST_PROBE_SKY_PEEL = 6
+DUST_PROBE_CUBE_TRACE = 7
 # CMI_GPU_MAX_VIEWS: the views of one run (set_ccd_images, set_sky_cameras)
 MAX_VIEWS = 64
 
@@ -123,6 +124,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_field_cube", "cmi_gpu_emission_line_atomic_weight",
     "cmi_gpu_render_field_sky_cube", "cmi_gpu_render_line_sky_cube",
     "cmi_gpu_render_line_sky_map_cube",
+    "cmi_gpu_set_scattered_cube", "cmi_gpu_download_cube_view",
     "cmi_gpu_get_phase_clocks",
 ]
 
@@ -387,6 +389,9 @@ def load_library():
     L.cmi_gpu_get_dust_view_counters.argtypes = [vp, C.c_int32,
                                                  C.POINTER(C.c_uint64)]
     L.cmi_gpu_select_probe_view.argtypes = [vp, C.c_int32]
+    L.cmi_gpu_set_scattered_cube.argtypes = [
+        vp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, _dp]
+    L.cmi_gpu_download_cube_view.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
     _lib = L
     return L
 
@@ -549,6 +554,7 @@ class GpuEngine:
         self.ncell = tuple(int(n) for n in
                            (sub_ncell if sub_ncell is not None else ncell))
         self.n = int(np.prod(self.ncell))
+        self.cube_channels = 0  # set_scattered_cube's nchan; 0: off
         # tests, bench and tools read device timings; the engine records them
         # only on request
         self.set_tuning(timing=1)
@@ -1107,7 +1113,8 @@ class GpuEngine:
                  DUST_PROBE_SCATTER_TOWARDS: 5,
                  DUST_PROBE_OPTICAL_DEPTH: 2 + max_events,
                  DUST_PROBE_TRACE: 4 + 8 * max_events,
-                 DUST_PROBE_CELL_SOURCE: 7, DUST_PROBE_SKY_PEEL: 9}[kind]
+                 DUST_PROBE_CELL_SOURCE: 7, DUST_PROBE_SKY_PEEL: 9,
+                 DUST_PROBE_CUBE_TRACE: 4 + 10 * max_events}[kind]
         in_width = {DUST_PROBE_SCATTER: 12, DUST_PROBE_SCATTER_TOWARDS: 12,
                     DUST_PROBE_OPTICAL_DEPTH: 6,
                     DUST_PROBE_SKY_PEEL: 15}.get(kind, 0)
@@ -1497,6 +1504,137 @@ class GpuEngine:
             total = self.get_cell_source(tables=False)
             out[k] = self.download_image() * (total / int(npackets)) / omega
         return out
+
+    # scattered-light line cubes ---------------------------------------------
+    def set_scattered_cube(self, nchan, vmin, vmax, sigma_turb=0.,
+                           widths=None, observer_velocities=None):
+        """Cube mode of dust_shoot for the cameras as currently set: every
+        event also goes, channel by channel, into a velocity cube per view
+        (include/cmi_gpu.h, cmi_gpu_set_scattered_cube). `widths` (ncell,) is
+        b per cell for a field source (a line source takes the cells'
+        temperatures); `observer_velocities` (nviews, 3) the point cameras'.
+        nchan = 0 switches cube mode off."""
+        w = None if widths is None else _f64(widths).reshape(self.n)
+        vo = None if observer_velocities is None else \
+            _f64(observer_velocities).reshape(self.nviews, 3)
+        self._check(self._lib.cmi_gpu_set_scattered_cube(
+            self._h, int(nchan), vmin, vmax, sigma_turb,
+            _p(w) if w is not None else None,
+            _p(vo) if vo is not None else None))
+        self.cube_channels = int(nchan)
+
+    def download_cubes(self):
+        """The cubes of every view, (nviews, 3, nchan, nx, ny), unnormalised"""
+        if not self.cube_channels:
+            # the engine's own refusal (cube mode is not set)
+            self._check(self._lib.cmi_gpu_download_cube_view(
+                self._h, 0, None, None, None))
+        out = np.zeros((self.nviews, 3, self.cube_channels) +
+                       self.image_shape)
+        for v in range(self.nviews):
+            self._check(self._lib.cmi_gpu_download_cube_view(
+                self._h, v, _p(out[v, 0]), _p(out[v, 1]), _p(out[v, 2])))
+        return out
+
+    def render_scattered_line_cube(self, lines, theta, phi, nx, ny, anchor,
+                                   sides, npackets, seed, sigma, albedo, g,
+                                   p_l, nchan, vmin, vmax, sigma_turb=0.):
+        """render_scattered_line_images resolved in radial velocity: the
+        images (nlines, 3, nx, ny) and the cubes (nlines, 3, nchan, nx, ny)
+        of one run per line, both scaled by L_total / (npackets A_pixel):
+        W m^-2 sr^-1, per channel for the cubes, the unit of
+        render_line_cube. The profile of scattered light carries the
+        velocity of the emitting gas as the dust sees it
+        (set_cell_velocities) and widens with sigma_turb per scattering.
+        With sequences for theta and phi the views share one run per line:
+        (nlines, nviews, 3, nx, ny) and (nlines, nviews, 3, nchan, nx, ny).
+        Only names of LINE_ATOMIC_WEIGHTS have a cube. Replaces the engine's
+        CCD image, dust and dust source, and leaves cube mode off."""
+        names = list(lines)
+        self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
+        several = bool(np.ndim(theta) or np.ndim(phi))
+        nviews = len(_f64(theta).reshape(-1)) if several else 1
+        a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
+        s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
+        pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
+        if several:
+            self.set_ccd_images(theta, phi, nx, ny, a, s)
+        else:
+            self.set_ccd_image(theta, phi, nx, ny, a[0], s[0])
+        images = np.zeros((len(names), nviews, 3, int(nx), int(ny)))
+        cubes = np.zeros((len(names), nviews, 3, int(nchan), int(nx),
+                          int(ny)))
+        try:
+            for k, name in enumerate(names):
+                self.set_cell_source_line(name)
+                self.set_scattered_cube(nchan, vmin, vmax, sigma_turb)
+                self.dust_shoot(seed, 0, int(npackets))
+                total = self.get_cell_source(tables=False)
+                scale = total / (int(npackets) * pixel_area)
+                images[k] = self.download_images() * \
+                    scale[:, None, None, None]
+                cubes[k] = self.download_cubes() * \
+                    scale[:, None, None, None, None]
+        finally:
+            self.set_scattered_cube(0, 0., 1.)
+        if several:
+            return images, cubes
+        return images[:, 0], cubes[:, 0]
+
+    def render_scattered_line_sky_map_cube(
+            self, lines, origin, nlon, nlat, npackets, seed,
+            dust_cross_section, albedo, g, p_l, exclusion_radius, nchan,
+            vmin, vmax, sigma_turb=0., observer_velocity=None,
+            lon_range=FULL_SKY_LONGITUDE, lat_range=FULL_SKY_LATITUDE,
+            frame_pole=(0., 0., 1.), frame_zero_longitude=(1., 0., 0.),
+            direct_light=True):
+        """render_scattered_line_sky_map resolved in radial velocity, for
+        observers of velocity `observer_velocity` ((3,), or (nviews, 3) with
+        several observers; None: at rest): the maps (nlines, 3, nlon, nlat)
+        and the cubes (nlines, 3, nchan, nlon, nlat), scaled by L_total /
+        (npackets omega_ij): the unit of render_line_sky_map_cube. With
+        origin of shape (nviews, 3) both gain an axis after the lines'.
+        Replaces the engine's camera, dust and dust source, and leaves cube
+        mode off."""
+        names = list(lines)
+        self.set_dust_scattering_per_hydrogen(g, p_l, albedo,
+                                              dust_cross_section)
+        several = np.ndim(origin) == 2
+        o = _f64(origin).reshape(-1, 3)
+        nviews = len(o)
+        poles = np.broadcast_to(_f64(frame_pole), (nviews, 3))
+        zeros = np.broadcast_to(_f64(frame_zero_longitude), (nviews, 3))
+        frames = np.array([sky_frame(p, z) for p, z in zip(poles, zeros)])
+        if several:
+            self.set_sky_cameras(o, nlon, nlat, exclusion_radius, lon_range,
+                                 lat_range, frames, direct_light)
+        else:
+            self.set_sky_camera(o[0], nlon, nlat, exclusion_radius, lon_range,
+                                lat_range, frames[0], direct_light)
+        vo = None if observer_velocity is None else \
+            _f64(np.broadcast_to(_f64(observer_velocity), (nviews, 3)))
+        omega = np.array([
+            sky_map_directions(nlon, nlat, lon_range, lat_range, f)[1]
+            for f in frames]).reshape(nviews, 1, int(nlon), int(nlat))
+        images = np.zeros((len(names), nviews, 3, int(nlon), int(nlat)))
+        cubes = np.zeros((len(names), nviews, 3, int(nchan), int(nlon),
+                          int(nlat)))
+        try:
+            for k, name in enumerate(names):
+                self.set_cell_source_line(name)
+                self.set_scattered_cube(nchan, vmin, vmax, sigma_turb,
+                                        observer_velocities=vo)
+                self.dust_shoot(seed, 0, int(npackets))
+                total = self.get_cell_source(tables=False)
+                images[k] = self.download_images() * \
+                    (total / int(npackets)) / omega
+                cubes[k] = self.download_cubes() * \
+                    (total / int(npackets)) / omega[:, :, None]
+        finally:
+            self.set_scattered_cube(0, 0., 1.)
+        if several:
+            return images, cubes
+        return images[:, 0], cubes[:, 0]
 
     def get_timing(self, reset=True):
         s = C.c_double()

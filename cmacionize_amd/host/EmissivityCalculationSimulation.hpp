@@ -105,6 +105,15 @@
  * ("observer velocity k" for observer k >= 1; observer 0's if absent). Every
  * flagged single-ion line is then also written as <prefix>_<LineName>_cube.dat
  * (_cube_view<k>.dat), raw doubles [channel][i][j], next to its map.
+ * Scattered-light cubes: "scattered cubes: true" in either
+ * block (default false; looked at like "scattering", so a file without it
+ * has the used-values it had) needs "scattering: true" and "velocity
+ * channels" of that block. Every flagged single-ion line's Monte Carlo run
+ * then also fills a velocity cube per view, written as
+ * <prefix>_<LineName>_scattered_cube_I / _Q / _U (_view<k> before
+ * _scattered): raw doubles [channel][ix][iy] in the unit of the ray-traced
+ * cube, with the block's velocity field, turbulent dispersion and observer
+ * velocities.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -243,6 +252,9 @@ class EmissivityCalculationSimulation {
     std::string type, prefix, folder;
     /* scattered light (the keys below are read only if scattering is set) */
     bool scattering = false;
+    /* "scattered cubes": every flagged single-ion line's scattered light
+     * also per velocity channel */
+    bool scattered_cubes = false;
     long long npackets = 1000000, seed = 42;
     double albedo = 0., asymmetry = 0.5, polarisation = 0.;
     /* several views: views[0] repeats the members above, views[k] is read
@@ -348,6 +360,18 @@ class EmissivityCalculationSimulation {
       read_cubes(params, "EmissionImages", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
+      /* (looked at like the switch above: a file without it, or with it
+       * false, has the used-values it had) */
+      if (params.peek_bool("EmissionImages:scattered cubes")) {
+        if (!params.peek_bool("EmissionImages:scattering"))
+          throw ParameterError("EmissionImages:scattered cubes needs "
+                               "scattering: true");
+        if (!cubes)
+          throw ParameterError("EmissionImages:scattered cubes needs "
+                               "velocity channels");
+        scattered_cubes =
+            params.get_bool("EmissionImages:scattered cubes", false);
+      }
       if (!params.peek_bool("EmissionImages:scattering"))
         return;
       scattering = params.get_bool("EmissionImages:scattering", false);
@@ -389,6 +413,7 @@ class EmissivityCalculationSimulation {
     std::string type, prefix, folder;
     /* scattered light (the keys below are read only if scattering is set) */
     bool scattering = false, direct_light = true;
+    bool scattered_cubes = false; /* as ImageSettings' */
     long long npackets = 1000000, seed = 42;
     double albedo = 0., asymmetry = 0.5, polarisation = 0.;
     double exclusion_radius = 0.;
@@ -556,6 +581,18 @@ class EmissivityCalculationSimulation {
         read_observer_velocities(params);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
+      /* (looked at like the switch above: a file without it, or with it
+       * false, has the used-values it had) */
+      if (params.peek_bool("EmissionSkyMaps:scattered cubes")) {
+        if (!params.peek_bool("EmissionSkyMaps:scattering"))
+          throw ParameterError("EmissionSkyMaps:scattered cubes needs "
+                               "scattering: true");
+        if (!cubes)
+          throw ParameterError("EmissionSkyMaps:scattered cubes needs "
+                               "velocity channels");
+        scattered_cubes =
+            params.get_bool("EmissionSkyMaps:scattered cubes", false);
+      }
       if (!params.peek_bool("EmissionSkyMaps:scattering"))
         return;
       scattering = params.get_bool("EmissionSkyMaps:scattering", false);
@@ -864,6 +901,8 @@ public:
       };
       static const char *stokes[3] = {"_scattered_I", "_scattered_Q",
                                       "_scattered_U"};
+      static const char *cube_stokes[3] = {
+          "_scattered_cube_I", "_scattered_cube_Q", "_scattered_cube_U"};
       if (rc == CMI_GPU_OK && placed && do_images) {
         status("Rendering emission line images...");
         const size_t nviews = img.views.size();
@@ -973,9 +1012,20 @@ public:
                            (int32_t)img.nx, (int32_t)img.ny, anchors.data(),
                            sides.data());
           std::vector<double> iqu(3 * npixel);
+          std::vector<double> scattered_cube(
+              img.scattered_cubes ? 3 * (size_t)img.nchan * npixel : 0);
           for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
             double total = 0.;
             rc = cmi_gpu_set_cell_source_line(engine, lines[k]);
+            /* cube mode for the lines of one ion (it resets the image); the
+             * velocities are those the ray-traced cubes were given */
+            const bool with_cube =
+                img.scattered_cubes &&
+                cmi_gpu_emission_line_atomic_weight(lines[k]) > 0.;
+            if (rc == CMI_GPU_OK && img.scattered_cubes)
+              rc = cmi_gpu_set_scattered_cube(
+                  engine, with_cube ? (int32_t)img.nchan : 0, img.vmin,
+                  img.vmax, img.sigma_turb, nullptr, nullptr);
             if (rc == CMI_GPU_OK)
               rc = cmi_gpu_reset_image(engine);
             if (rc == CMI_GPU_OK)
@@ -998,8 +1048,31 @@ public:
                           view_tag(v) + stokes[j],
                       img.type, iqu.data() + j * npixel, img.nx, img.ny,
                       total / ((double)img.npackets * pixel_area));
+              if (rc == CMI_GPU_OK && with_cube) {
+                const size_t nvalue = (size_t)img.nchan * npixel;
+                rc = cmi_gpu_download_cube_view(
+                    engine, (int32_t)v, scattered_cube.data(),
+                    scattered_cube.data() + nvalue,
+                    scattered_cube.data() + 2 * nvalue);
+                const double scale =
+                    total / ((double)img.npackets * pixel_area);
+                for (double &value : scattered_cube)
+                  value *= scale;
+                if (rc == CMI_GPU_OK && write_output)
+                  for (int j = 0; j < 3; ++j)
+                    written += " " + write_cube(
+                        img.folder + "/" + img.prefix + "_" +
+                            GpuIonizationSimulation::emission_line_name(
+                                lines[k]) +
+                            view_tag(v) + cube_stokes[j],
+                        scattered_cube.data() + j * nvalue, img.nchan, img.nx,
+                        img.ny);
+              }
             }
           }
+          if (rc == CMI_GPU_OK && img.scattered_cubes)
+            rc = cmi_gpu_set_scattered_cube(engine, 0, 0., 1., 0., nullptr,
+                                            nullptr);
         }
       }
       if (rc == CMI_GPU_OK && placed && do_sky) {
@@ -1101,9 +1174,24 @@ public:
                            sky.lat[0], sky.lat[1], (int32_t)sky.nlon,
                            (int32_t)sky.nlat, radii.data(),
                            sky.direct_light ? 1 : 0);
+          std::vector<double> scattered_cube(
+              sky.scattered_cubes ? 3 * (size_t)sky.nchan * npixel : 0);
+          std::vector<double> observer_velocities(3 * nviews);
+          for (size_t v = 0; v < nviews; ++v)
+            std::copy(sky.observers[v].velocity.begin(),
+                      sky.observers[v].velocity.end(),
+                      observer_velocities.begin() + 3 * v);
           for (size_t k = 0; rc == CMI_GPU_OK && k < lines.size(); ++k) {
             double total = 0.;
             rc = cmi_gpu_set_cell_source_line(engine, lines[k]);
+            const bool with_cube =
+                sky.scattered_cubes &&
+                cmi_gpu_emission_line_atomic_weight(lines[k]) > 0.;
+            if (rc == CMI_GPU_OK && sky.scattered_cubes)
+              rc = cmi_gpu_set_scattered_cube(
+                  engine, with_cube ? (int32_t)sky.nchan : 0, sky.vmin,
+                  sky.vmax, sky.sigma_turb, nullptr,
+                  observer_velocities.data());
             if (rc == CMI_GPU_OK)
               rc = cmi_gpu_reset_image(engine);
             if (rc == CMI_GPU_OK)
@@ -1133,8 +1221,32 @@ public:
                           view_tag(v) + stokes[j],
                       sky.type, iqu.data() + j * npixel, sky.nlon, sky.nlat,
                       1.);
+              if (with_cube) {
+                const size_t nvalue = (size_t)sky.nchan * npixel;
+                rc = cmi_gpu_download_cube_view(
+                    engine, (int32_t)v, scattered_cube.data(),
+                    scattered_cube.data() + nvalue,
+                    scattered_cube.data() + 2 * nvalue);
+                if (rc != CMI_GPU_OK)
+                  break;
+                for (size_t i = 0; i < 3 * nvalue; ++i)
+                  scattered_cube[i] = scattered_cube[i] * per_packet /
+                                      omega[v * npixel + i % npixel];
+                if (write_output)
+                  for (int j = 0; j < 3; ++j)
+                    written += " " + write_cube(
+                        sky.folder + "/" + sky.prefix + "_" +
+                            GpuIonizationSimulation::emission_line_name(
+                                lines[k]) +
+                            view_tag(v) + cube_stokes[j],
+                        scattered_cube.data() + j * nvalue, sky.nchan,
+                        sky.nlon, sky.nlat);
+              }
             }
           }
+          if (rc == CMI_GPU_OK && sky.scattered_cubes)
+            rc = cmi_gpu_set_scattered_cube(engine, 0, 0., 1., 0., nullptr,
+                                            nullptr);
         }
       }
       const std::string message = rc ? cmi_gpu_last_error() : "";

@@ -1447,6 +1447,112 @@ int cmi_gpu_render_line_sky_map_cube(cmi_gpu_engine *engine, int32_t nlines,
                                      int32_t nchan, double vmin, double vmax,
                                      double sigma_turb, double *cubes);
 
+/* ------------------------------------------ scattered-light line cubes -- */
+/* The Monte Carlo images of cmi_gpu_dust_shoot resolved in radial velocity:
+ * the line profile of the direct and the dust-scattered light per pixel, for
+ * the cell source and any of the cameras above (parallel or point, one view or
+ * several). No counterpart in the reference.
+ *
+ * Grey dust makes the walk independent of frequency: cube mode draws no
+ * random number, a cube run walks the image run's walk, and its image is the
+ * image run's image but for the order of the atomics.
+ *
+ * Conventions. Channels, the edges e_c = vmin + c * dv, E(z), f_c, the case
+ * b == 0 and "positive = receding" are exactly those of "spectral line cubes"
+ * above. dot3(a, b) = (a_x b_x + a_y b_y) + a_z b_z in this order, no
+ * contraction. v_c is the bulk velocity of cell c from
+ * cmi_gpu_set_cell_velocities, zero for every cell when none was set; sigma_t
+ * the turbulent dispersion; s2_c a per-cell variance built when cube mode is
+ * set:
+ *   line source:  s2_c = k_B T_c / (A m_u) + sigma_t * sigma_t, with the
+ *                 constants and atomic weights of "spectral line cubes";
+ *   field source: s2_c = 0.5 * b_c * b_c from the caller's widths[ncell].
+ *
+ * A packet carries two more scalars: q, its Doppler velocity (positive =
+ * blue-shifted in the lab frame), and s2, the variance of its profile.
+ *   Emission in cell e along k:  q = dot3(v_e, k);  s2 = s2_e.
+ *   Direct light from e towards the observer along d (the parallel camera's
+ *   direction to the observer; for the point camera the unit vector k = v / r
+ *   from the event to the observer):
+ *     parallel:  u = -dot3(v_e, d)   (the u of "spectral line cubes", bit for
+ *                bit);
+ *     point:     u = -(dot3(v_e, d) - dot3(v_obs, d));
+ *     b = sqrt(2 * s2_e).
+ *   Peel-off at a scattering in cell s, incoming direction k, towards d:
+ *     u = -((q + (dot3(v_s, d) - dot3(v_s, k))) - dot3(v_obs, d)), the v_obs
+ *     term absent for the parallel camera;
+ *     b = sqrt(2 * (s2 + (2 * sigma_t * sigma_t) * fmax(0, 1 - dot3(k, d)))).
+ *   Flying on after the scattering gave k':
+ *     q += dot3(v_s, k') - dot3(v_s, k);
+ *     s2 += (2 * sigma_t * sigma_t) * fmax(0, 1 - dot3(k, k')).
+ * The emission cell e is the cell the source selected. The scattering cell s
+ * is floor((pos - anchor) * inv_cellside) per axis, clamped into the grid -
+ * not whatever index a march ended with.
+ *
+ * Dust that shares the gas's turbulence: the scattering grain moves with the
+ * bulk velocity of its cell plus a turbulent velocity of dispersion sigma_t
+ * per component. A grain of velocity w shifts the light it redirects from k
+ * to k' by w . (k' - k); over the turbulent part that is a Gaussian of
+ * variance sigma_t^2 |k' - k|^2 = 2 sigma_t^2 (1 - k . k'), which is what
+ * s2 grows by per scattering. With sigma_t = 0 the profile keeps the
+ * emitting cell's thermal width.
+ *
+ * Deposit. An event that adds (wI, wQ, wU) to a pixel of the image also adds
+ * (wI f_c, wQ f_c, wU f_c) to channel c of that pixel's spectrum, for every c
+ * with f_c != 0; zero addends cost no atomic. Every cube atomic is counted in
+ * natomics (and in the view's). The image is filled as before in the same
+ * run. Events that add nothing to the image (outside the window, inside the
+ * exclusion radius, missed pixels) add nothing to the cube and are counted as
+ * before.
+ *
+ * What follows: (1) one channel that covers every u +- 6 b has f_0 = 1
+ * exactly, and the cube is the image of the same run up to the order of the
+ * atomics; (2) the channels of a covering cube sum to the image up to
+ * rounding; (3) adding one vector V to every cell velocity changes every u by
+ * -dot3(V, d) and nothing else (the sum over scatterings telescopes): for the
+ * parallel camera shifting vmin and vmax by that amount gives the same cube
+ * up to rounding, for the point camera adding V to the observer's velocity
+ * as well changes nothing; (4) with all cells at rest, sigma_t = 0 and one
+ * temperature the cube is the image times the constant f_c(0, b); (5) at
+ * albedo 0 the cube converges to the ray-traced cube of
+ * cmi_gpu_render_line_cube / cmi_gpu_render_line_sky_map_cube in the unit of
+ * the scattered-light images' scaling. */
+
+/* Switches cube mode on for the cameras as currently set: allocates and
+ * zeroes the cubes, builds s2, and resets the image and the counters.
+ * observer_velocities is [nviews][3] (m s^-1; the point cameras', ignored by
+ * parallel ones) or NULL (at rest). nchan = 0 switches cube mode off and
+ * frees the buffers (the other arguments are then not looked at).
+ * CMI_GPU_ESTATE: no camera; no cell source selected (the spiral galaxy has
+ * no line) or a stale one; widths given with a line source, or missing with a
+ * field source. CMI_GPU_EINVAL: the line source's entry is not the line of
+ * one ion; nchan < 0, a range that is not finite with vmax > vmin; a
+ * sigma_turb that is negative or not finite; a width that is negative or not
+ * finite; an observer velocity that is not finite; nviews * nchan * npixel >
+ * 2^28. CMI_GPU_ENOMEM if the cubes do not fit. A call that fails leaves the
+ * previous state in place.
+ * Cube mode is stale, and the next shoot or probe fails with CMI_GPU_ESTATE
+ * until this call is made again, once the cell source is stale or set again,
+ * a camera is set again, or the velocities are replaced. Synchronous. */
+int cmi_gpu_set_scattered_cube(cmi_gpu_engine *engine, int32_t nchan,
+                               double vmin, double vmax, double sigma_turb,
+                               const double *widths /* [ncell] or NULL */,
+                               const double *observer_velocities
+                               /* [nviews][3] or NULL */);
+
+/* The cube of view `view` (0 with a single camera), unnormalised: I, Q, U
+ * host [nchan][npixel] each, in the pixel order of the view's image; any of
+ * the three may be NULL. Fails where cmi_gpu_download_image_view fails, and
+ * with CMI_GPU_ESTATE if cube mode is off or stale. cmi_gpu_reset_image also
+ * zeroes the cubes. With cube mode on cmi_gpu_dust_shoot launches the cube
+ * kernels (same signature, same launch sizing), and cmi_gpu_dust_probe has
+ *  7 CUBE_TRACE: 4 TRACE with rows of 10 doubles, the 8 of TRACE and then
+ *    {u, b} of the event (0, 0 for an event inside the exclusion radius);
+ *    CMI_GPU_ESTATE unless cube mode is on.
+ * Synchronous. */
+int cmi_gpu_download_cube_view(cmi_gpu_engine *engine, int32_t view, double *I,
+                               double *Q, double *U);
+
 #ifdef __cplusplus
 }
 #endif
