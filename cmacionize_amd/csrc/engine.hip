@@ -14,6 +14,7 @@
 #include "sky_image_kernels.h"
 #include "sky_cube_kernels.h"
 #include "dust_cube_kernels.h"
+#include "continuum_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -241,6 +242,10 @@ struct cmi_gpu_engine {
     bool span_claim = CMI_SPAN_CLAIM_DEFAULT;
     bool emit_before_flush = CMI_EMIT_BEFORE_FLUSH_DEFAULT;
     bool phase_stamps = false; /* experiments build: ShootArgs::phase_clock */
+    /* continuum images: channels per march launch (4, 8 or 16) and the rays
+     * per launch (0: the images' and the sky maps' own bounds) */
+    int continuum_channel_block = CMI_CONTINUUM_FB;
+    int64_t continuum_launch_rays = 0;
   } tune;
 
   /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
@@ -1737,6 +1742,13 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.emit_before_flush = value != 0;
   else if (k == "phase_stamps")
     e->tune.phase_stamps = value != 0;
+  else if (k == "continuum_channel_block") {
+    if (value != 4 && value != 8 && value != 16)
+      return fail(CMI_GPU_EINVAL, "set_tuning: continuum_channel_block is 4, "
+                  "8 or 16 (%lld asked for)", (long long)value);
+    e->tune.continuum_channel_block = (int)value;
+  } else if (k == "continuum_launch_rays")
+    e->tune.continuum_launch_rays = value < 0 ? 0 : value;
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
   return CMI_GPU_OK;
@@ -4764,6 +4776,511 @@ int cmi_gpu_render_line_sky_map_cube(cmi_gpu_engine *e, int32_t nlines,
   for (size_t p = 0; p < nplane; ++p)
     for (size_t k = 0; k < npixel; ++k)
       cubes[p * npixel + (size_t)pixel[k]] = rays[p * npixel + k];
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------------- continuum images -- */
+extern "C++" {
+namespace {
+/* device buffers of one continuum call, freed however it ends */
+struct ContinuumBuffers {
+  double *records = nullptr, *samples = nullptr, *image = nullptr,
+         *kappa = nullptr, *source = nullptr, *directions = nullptr,
+         *out = nullptr;
+  unsigned int *ninvalid = nullptr;
+  ~ContinuumBuffers() {
+    (void)hipFree(records);
+    (void)hipFree(samples);
+    (void)hipFree(image);
+    (void)hipFree(kappa);
+    (void)hipFree(source);
+    (void)hipFree(directions);
+    (void)hipFree(out);
+    (void)hipFree(ninvalid);
+  }
+};
+
+/* where the channels of a continuum call come from: the free-free
+ * coefficients of the cells at freq[nf], or the caller's kappa[nf][ncell] and
+ * source[nf][ncell] (host) */
+struct ContinuumInput {
+  const double *freq = nullptr;
+  const double *kappa = nullptr, *source = nullptr;
+};
+
+/* f(std::integral_constant<int, FB>) for the channel block of the engine */
+template <class F> void continuum_for_block(int fb, F &&f) {
+  switch (fb) {
+  case 4: f(std::integral_constant<int, 4>()); break;
+  case 16: f(std::integral_constant<int, 16>()); break;
+  default: f(std::integral_constant<int, 8>()); break;
+  }
+}
+
+/* what every continuum call asks of its channels before a launch; nvalue is
+ * the number of pixels or rays of one channel */
+int continuum_check(const cmi_gpu_engine *e, const char *what, int32_t nf,
+                    int64_t nvalue, const ContinuumInput &in,
+                    const double *background) {
+  if (nf < 1)
+    return fail(CMI_GPU_EINVAL, "%s: at least one channel (%d asked for)",
+                what, (int)nf);
+  if ((int64_t)nf > (1ll << 28) || (int64_t)nf * nvalue > (1ll << 28))
+    return fail(CMI_GPU_EINVAL, "%s: %d channels of %lld values: a call "
+                "renders at most 2^28 values", what, (int)nf,
+                (long long)nvalue);
+  if (in.freq) {
+    for (int32_t f = 0; f < nf; ++f)
+      if (!std::isfinite(in.freq[f]) || !(in.freq[f] > 0.))
+        return fail(CMI_GPU_EINVAL, "%s: frequency %d is not finite and "
+                    "positive (%.17g)", what, (int)f, in.freq[f]);
+    if (!e->have_cells)
+      return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  }
+  if (background)
+    for (int32_t f = 0; f < nf; ++f)
+      if (!std::isfinite(background[f]))
+        return fail(CMI_GPU_EINVAL, "%s: the background of channel %d is not "
+                    "finite", what, (int)f);
+  return CMI_GPU_OK;
+}
+
+/* the channels [c0, c0 + nc) of the caller's fields into b.kappa and b.source
+ * (device, [nc][ncell]) */
+int continuum_upload(cmi_gpu_engine *e, const ContinuumInput &in, int32_t c0,
+                     int32_t nc, ContinuumBuffers &b) {
+  const size_t ncell = (size_t)e->ncell;
+  HIP_TRY(hipMemcpy(b.kappa, in.kappa + (size_t)c0 * ncell,
+                    sizeof(double) * ncell * nc, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b.source, in.source + (size_t)c0 * ncell,
+                    sizeof(double) * ncell * nc, hipMemcpyHostToDevice));
+  return CMI_GPU_OK;
+}
+
+/* allocates the records (and the staging of the caller's fields) and refuses
+ * fields with a value out of range: every block is uploaded and counted
+ * before anything is marched. With one block it stays uploaded. */
+int continuum_begin(cmi_gpu_engine *e, const char *what,
+                    const ContinuumInput &in, int32_t nf, int fb,
+                    ContinuumBuffers &b) {
+  const size_t ncell = (size_t)e->ncell;
+  HIP_TRY(hipMalloc(&b.records, sizeof(double) * 2 * ncell * fb));
+  if (in.freq)
+    return CMI_GPU_OK;
+  const int nb = std::min<int>(nf, fb);
+  HIP_TRY(hipMalloc(&b.kappa, sizeof(double) * ncell * nb));
+  HIP_TRY(hipMalloc(&b.source, sizeof(double) * ncell * nb));
+  HIP_TRY(hipMalloc(&b.ninvalid, 2 * sizeof(unsigned int)));
+  HIP_TRY(hipMemsetAsync(b.ninvalid, 0, 2 * sizeof(unsigned int), e->stream));
+  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
+    const int32_t nc = std::min<int32_t>(fb, nf - c0);
+    CMI_TRY(continuum_upload(e, in, c0, nc, b));
+    const int64_t n = (int64_t)ncell * nc;
+    continuum_field_check_kernel<<<grid_blocks(e, n, 8), 256, 0, e->stream>>>(
+        b.kappa, b.source, n, b.ninvalid);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  unsigned int bad[2] = {0, 0};
+  HIP_TRY(hipMemcpy(bad, b.ninvalid, sizeof bad, hipMemcpyDeviceToHost));
+  if (bad[0])
+    return fail(CMI_GPU_EINVAL, "%s: %u absorption coefficient(s) are "
+                "negative or not finite", what, bad[0]);
+  if (bad[1])
+    return fail(CMI_GPU_EINVAL, "%s: %u source function value(s) are not "
+                "finite", what, bad[1]);
+  return CMI_GPU_OK;
+}
+
+/* the records of the channels [c0, c0 + nc) into b.records */
+int continuum_records(cmi_gpu_engine *e, const ContinuumInput &in, int32_t nf,
+                      int32_t c0, int32_t nc, int fb, ContinuumBuffers &b) {
+  if (in.freq) {
+    FreeFreeRecordArgs r;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.helium_abundance = e->model.abundance[0];
+    r.fb = fb;
+    r.nfreq = nc;
+    for (int f = 0; f < CMI_CONTINUUM_MAX_FB; ++f)
+      r.freq[f] = f < nc ? in.freq[c0 + f] : 1.;
+    r.records = b.records;
+    free_free_record_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0,
+                              e->stream>>>(r);
+  } else {
+    /* (a single block is still there from the check) */
+    if (nf > fb)
+      CMI_TRY(continuum_upload(e, in, c0, nc, b));
+    field_continuum_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
+                                    e->stream>>>(b.kappa, b.source, e->ncell,
+                                                 nc, fb, b.records);
+  }
+  HIP_TRY(hipGetLastError());
+  return CMI_GPU_OK;
+}
+
+/* images[nf][nx * ny] (host) of the parallel camera: per block of FB channels
+ * the records, then per chunk of pixel rows one march launch */
+int continuum_images(cmi_gpu_engine *e, const char *what,
+                     const ContinuumInput &in, int32_t nf,
+                     const double *background, const LineViewDev &v,
+                     double *images) {
+  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
+  const int fb = e->tune.continuum_channel_block;
+  HIP_TRY(hipSetDevice(e->device));
+  ContinuumBuffers b;
+  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
+  const int64_t npixel = (int64_t)v.nx * v.ny;
+  const int64_t NY = (int64_t)v.ny * v.s;
+  const int64_t launch = e->tune.continuum_launch_rays
+                             ? e->tune.continuum_launch_rays
+                             : CMI_LINE_IMAGE_LAUNCH_SAMPLES / fb;
+  /* pixel rows per launch: the sample buffer holds FB channels of them */
+  const int64_t rows = std::max<int64_t>(
+      1, std::min<int64_t>(v.nx, launch / (NY * v.s)));
+  const int64_t chunk_samples = rows * v.s * NY;
+  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel *
+                                  std::min<int>(nf, fb)));
+  if (v.s > 1)
+    HIP_TRY(hipMalloc(&b.samples,
+                      sizeof(double) * (size_t)chunk_samples * fb));
+  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
+  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
+    const int32_t nc = std::min<int32_t>(fb, nf - c0);
+    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
+    for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
+      const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
+      ContinuumMarchArgs a;
+      a.grid = e->grid;
+      a.view = v;
+      a.records = b.records;
+      a.sx0 = (int32_t)(ix0 * v.s);
+      a.sx1 = (int32_t)(ix1 * v.s);
+      a.nc = nc;
+      a.pad = 0;
+      for (int i = 0; i < CMI_CONTINUUM_MAX_FB; ++i)
+        a.background[i] = (background && i < nc) ? background[c0 + i] : 0.;
+      if (v.s > 1) {
+        a.out = b.samples;
+        a.channel_stride = chunk_samples;
+      } else {
+        a.out = b.image + ix0 * v.ny;
+        a.channel_stride = npixel;
+      }
+      const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
+      /* (with the tuning key timing the march launches are timed like the
+       * transport launches: cmi_gpu_get_kernel_timing) */
+      EventPair ev;
+      CMI_TRY(timer_begin(e, ev));
+      continuum_for_block(fb, [&](auto width) {
+        continuum_march_kernel<decltype(width)::value>
+            <<<(unsigned)(tiles_x * tiles_y), 256, 0, e->stream>>>(a);
+      });
+      HIP_TRY(hipGetLastError());
+      CMI_TRY(timer_end(e, e->kernel_events, ev,
+                        (uint64_t)((a.sx1 - a.sx0) * NY)));
+      if (v.s > 1) {
+        /* the images' reduction, channels in the place of lines */
+        const int64_t work = (ix1 - ix0) * v.ny * nc;
+        line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
+                                   e->stream>>>(
+            b.samples, chunk_samples, nc, (int32_t)ix0, (int32_t)ix1, v.ny,
+            v.s, npixel, b.image);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(images + (size_t)c0 * npixel, b.image,
+                      sizeof(double) * (size_t)npixel * nc,
+                      hipMemcpyDeviceToHost));
+  }
+  return CMI_GPU_OK;
+}
+
+/* out[nf][nrays] (host) of the rays from a point: per block of FB channels
+ * the records, then per chunk of rays one march launch, directions up,
+ * results down */
+int continuum_sky(cmi_gpu_engine *e, const char *what, const ContinuumInput &in,
+                  int32_t nf, const double *background, const double *origin,
+                  int64_t nrays, const double *directions, double *out) {
+  const int fb = e->tune.continuum_channel_block;
+  HIP_TRY(hipSetDevice(e->device));
+  ContinuumBuffers b;
+  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
+  const int64_t launch = e->tune.continuum_launch_rays
+                             ? e->tune.continuum_launch_rays
+                             : CMI_SKY_LAUNCH_RAYS;
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nrays, launch));
+  HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
+  HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk * fb));
+  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
+    const int32_t nc = std::min<int32_t>(fb, nf - c0);
+    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
+    for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
+      const int64_t n = std::min<int64_t>(chunk, nrays - r0);
+      HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
+                        sizeof(double) * 3 * (size_t)n,
+                        hipMemcpyHostToDevice));
+      ContinuumSkyMarchArgs a;
+      a.grid = e->grid;
+      for (int k = 0; k < 3; ++k)
+        a.origin[k] = origin[k];
+      a.directions = b.directions;
+      a.records = b.records;
+      a.nrays = n;
+      a.nc = nc;
+      a.pad = 0;
+      a.channel_stride = chunk;
+      a.out = b.out;
+      for (int i = 0; i < CMI_CONTINUUM_MAX_FB; ++i)
+        a.background[i] = (background && i < nc) ? background[c0 + i] : 0.;
+      EventPair ev;
+      CMI_TRY(timer_begin(e, ev));
+      continuum_for_block(fb, [&](auto width) {
+        continuum_sky_march_kernel<decltype(width)::value>
+            <<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(a);
+      });
+      HIP_TRY(hipGetLastError());
+      CMI_TRY(timer_end(e, e->kernel_events, ev, (uint64_t)n));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      for (int32_t i = 0; i < nc; ++i)
+        HIP_TRY(hipMemcpy(out + (size_t)(c0 + i) * nrays + r0,
+                          b.out + (size_t)i * chunk,
+                          sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+  }
+  return CMI_GPU_OK;
+}
+} // namespace
+} // extern "C++"
+
+int cmi_gpu_free_free_coefficients(cmi_gpu_engine *e, int32_t nf,
+                                   const double *freq, double *kappa_out,
+                                   double *source_out) {
+  static const char *what = "free_free_coefficients";
+  if (!e || !freq || !kappa_out || !source_out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  ContinuumInput in;
+  in.freq = freq;
+  CMI_TRY(continuum_check(e, what, nf, 1, in, nullptr));
+  HIP_TRY(hipSetDevice(e->device));
+  const int fb = e->tune.continuum_channel_block;
+  const size_t ncell = (size_t)e->ncell;
+  ContinuumBuffers b;
+  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
+  std::vector<double> host;
+  try {
+    host.resize(2 * ncell * fb);
+  } catch (const std::bad_alloc &) {
+    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
+  }
+  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
+    const int32_t nc = std::min<int32_t>(fb, nf - c0);
+    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(host.data(), b.records, sizeof(double) * 2 * ncell * fb,
+                      hipMemcpyDeviceToHost));
+    for (int32_t i = 0; i < nc; ++i)
+      for (size_t c = 0; c < ncell; ++c) {
+        kappa_out[(size_t)(c0 + i) * ncell + c] = host[2 * (c * fb + i)];
+        source_out[(size_t)(c0 + i) * ncell + c] = host[2 * (c * fb + i) + 1];
+      }
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_continuum_images(cmi_gpu_engine *e, int32_t nf,
+                                    const double *freq,
+                                    const double *background, double theta,
+                                    double phi, int32_t nx, int32_t ny,
+                                    const double *anchor, const double *sides,
+                                    int32_t supersample, double *out) {
+  static const char *what = "render_continuum_images";
+  if (!e || !freq || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  ContinuumInput in;
+  in.freq = freq;
+  CMI_TRY(continuum_check(e, what, nf, (int64_t)nx * ny, in, background));
+  return continuum_images(e, what, in, nf, background, v, out);
+}
+
+int cmi_gpu_render_field_continuum_images(
+    cmi_gpu_engine *e, int32_t nf, const double *kappa, const double *source,
+    const double *background, double theta, double phi, int32_t nx,
+    int32_t ny, const double *anchor, const double *sides,
+    int32_t supersample, double *out) {
+  static const char *what = "render_field_continuum_images";
+  if (!e || !kappa || !source || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  ContinuumInput in;
+  in.kappa = kappa;
+  in.source = source;
+  CMI_TRY(continuum_check(e, what, nf, (int64_t)nx * ny, in, background));
+  return continuum_images(e, what, in, nf, background, v, out);
+}
+
+int cmi_gpu_render_continuum_sky(cmi_gpu_engine *e, int32_t nf,
+                                 const double *freq, const double *background,
+                                 const double *origin, int64_t nrays,
+                                 const double *directions, double *out) {
+  static const char *what = "render_continuum_sky";
+  if (!e || !freq || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  ContinuumInput in;
+  in.freq = freq;
+  CMI_TRY(continuum_check(e, what, nf, nrays, in, background));
+  return continuum_sky(e, what, in, nf, background, origin, nrays, directions,
+                       out);
+}
+
+int cmi_gpu_render_field_continuum_sky(cmi_gpu_engine *e, int32_t nf,
+                                       const double *kappa,
+                                       const double *source,
+                                       const double *background,
+                                       const double *origin, int64_t nrays,
+                                       const double *directions, double *out) {
+  static const char *what = "render_field_continuum_sky";
+  if (!e || !kappa || !source || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  ContinuumInput in;
+  in.kappa = kappa;
+  in.source = source;
+  CMI_TRY(continuum_check(e, what, nf, nrays, in, background));
+  return continuum_sky(e, what, in, nf, background, origin, nrays, directions,
+                       out);
+}
+
+int cmi_gpu_render_continuum_sky_map(cmi_gpu_engine *e, int32_t nf,
+                                     const double *freq,
+                                     const double *background,
+                                     const double *origin, int32_t nlon,
+                                     int32_t nlat, const double *lon_range,
+                                     const double *lat_range,
+                                     const double *frame, double *out) {
+  static const char *what = "render_continuum_sky_map";
+  if (!e || !freq || !out || !lon_range || !lat_range)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(sky_map_check(what, frame, lon_range[0], lon_range[1], lat_range[0],
+                        lat_range[1], nlon, nlat));
+  const size_t npixel = (size_t)nlon * nlat;
+  ContinuumInput in;
+  in.freq = freq;
+  CMI_TRY(continuum_check(e, what, nf, (int64_t)npixel, in, background));
+  /* the map call's ray order: 8 x 8 tiles; pixel[k] is the pixel of ray k */
+  std::vector<int64_t> pixel;
+  std::vector<double> directions, rays;
+  try {
+    pixel.reserve(npixel);
+    directions.resize(3 * npixel);
+    rays.resize((size_t)nf * npixel);
+  } catch (const std::bad_alloc &) {
+    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
+  }
+  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
+    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
+      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
+        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
+          sky_map_direction(frame, lon_range[0], lon_range[1], lat_range[0],
+                            lat_range[1], nlon, nlat, i, j,
+                            directions.data() + 3 * pixel.size());
+          pixel.push_back((int64_t)i * nlat + j);
+        }
+  CMI_TRY(sky_check(e, what, origin, (int64_t)npixel, 1ll << 28,
+                    directions.data()));
+  CMI_TRY(continuum_sky(e, what, in, nf, background, origin, (int64_t)npixel,
+                        directions.data(), rays.data()));
+  for (size_t p = 0; p < (size_t)nf; ++p)
+    for (size_t k = 0; k < npixel; ++k)
+      out[p * npixel + (size_t)pixel[k]] = rays[p * npixel + k];
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_continuum_probe(cmi_gpu_engine *e, int32_t nf, const double *kappa,
+                            const double *source, const double *background,
+                            int32_t point, const double *view, int64_t n,
+                            const double *rays, int32_t max_cells,
+                            double *out) {
+  static const char *what = "continuum_probe";
+  if (!e || !kappa || !source || !view || !out || max_cells < 0 ||
+      (point != 0 && point != 1))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  if (nf < 1 || nf > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 channels (%d asked "
+                "for)", what, (int)nf);
+  LineViewDev v;
+  double origin[3] = {0., 0., 0.};
+  if (point) {
+    CMI_TRY(sky_check(e, what, view, n, 1ll << 20, rays));
+    for (int a = 0; a < 3; ++a)
+      origin[a] = view[a];
+    /* (not read by the kernel; set so that it is passed initialised) */
+    std::memset(&v, 0, sizeof v);
+  } else {
+    if (n <= 0 || n > (1ll << 20) || !rays)
+      return fail(CMI_GPU_EINVAL, "%s: between 1 and 2^20 rays (%lld asked "
+                  "for)", what, (long long)n);
+    CMI_TRY(line_image_view(e, what, view[0], view[1], v));
+    for (int64_t k = 0; k < 2 * n; ++k)
+      if (!std::isfinite(rays[k]))
+        return fail(CMI_GPU_EINVAL, "%s: image coordinate %lld of ray %lld is "
+                    "not finite", what, (long long)(k % 2),
+                    (long long)(k / 2));
+  }
+  ContinuumInput in;
+  in.kappa = kappa;
+  in.source = source;
+  CMI_TRY(continuum_check(e, what, nf, 1, in, background));
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t ncell = (size_t)e->ncell;
+  const size_t width = 3 + (2 + (size_t)nf) * (size_t)max_cells + (size_t)nf;
+  const size_t nray_values = (point ? 3 : 2) * (size_t)n;
+  ContinuumBuffers b;
+  double *dbg = nullptr;
+  HIP_TRY(hipMalloc(&b.kappa, sizeof(double) * ncell * nf));
+  HIP_TRY(hipMalloc(&b.source, sizeof(double) * ncell * nf));
+  HIP_TRY(hipMalloc(&b.ninvalid, 2 * sizeof(unsigned int)));
+  HIP_TRY(hipMalloc(&b.directions, sizeof(double) * nray_values));
+  HIP_TRY(hipMalloc(&b.out, sizeof(double) * width * (size_t)n));
+  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)nf));
+  dbg = b.image; /* the background on the device */
+  HIP_TRY(hipMemsetAsync(b.ninvalid, 0, 2 * sizeof(unsigned int), e->stream));
+  CMI_TRY(continuum_upload(e, in, 0, nf, b));
+  continuum_field_check_kernel<<<grid_blocks(e, (int64_t)ncell * nf, 8), 256,
+                                 0, e->stream>>>(b.kappa, b.source,
+                                                 (int64_t)ncell * nf,
+                                                 b.ninvalid);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  unsigned int bad[2] = {0, 0};
+  HIP_TRY(hipMemcpy(bad, b.ninvalid, sizeof bad, hipMemcpyDeviceToHost));
+  if (bad[0] || bad[1])
+    return fail(CMI_GPU_EINVAL, "%s: %u absorption coefficient(s) are "
+                "negative or not finite, %u source function value(s) are not "
+                "finite", what, bad[0], bad[1]);
+  std::vector<double> bg((size_t)nf, 0.);
+  if (background)
+    std::copy(background, background + nf, bg.begin());
+  HIP_TRY(hipMemcpy(dbg, bg.data(), sizeof(double) * (size_t)nf,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b.directions, rays, sizeof(double) * nray_values,
+                    hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(b.out, 0, sizeof(double) * width * (size_t)n,
+                         e->stream));
+  continuum_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
+      e->grid, v, point, origin[0], origin[1], origin[2], b.directions, n,
+      b.kappa, b.source, dbg, nf, e->ncell, max_cells, b.out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, b.out, sizeof(double) * width * (size_t)n,
+                    hipMemcpyDeviceToHost));
   return CMI_GPU_OK;
 }
 

@@ -126,6 +126,10 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_line_sky_map_cube",
     "cmi_gpu_set_scattered_cube", "cmi_gpu_download_cube_view",
     "cmi_gpu_get_phase_clocks",
+    "cmi_gpu_free_free_coefficients", "cmi_gpu_render_continuum_images",
+    "cmi_gpu_render_field_continuum_images", "cmi_gpu_render_continuum_sky",
+    "cmi_gpu_render_field_continuum_sky",
+    "cmi_gpu_render_continuum_sky_map", "cmi_gpu_continuum_probe",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -181,6 +185,63 @@ def cube_moments(cube, centres):
         var = (cube * (v - mean[..., None, :, :]) ** 2).sum(axis=-3) / m0
         sigma = np.where(m0 == 0., np.nan, np.sqrt(np.maximum(var, 0.)))
     return m0, mean, sigma
+
+
+# the constants of the continuum images (csrc/device_common.h)
+PLANCK = 6.626070040e-34
+BOLTZMANN = 1.38064852e-23
+LIGHTSPEED = 299792458.
+
+
+def planck_function(nu, T):
+    """B_nu(T) = 2 h nu^3 / c^2 / expm1(h nu / (k T)) in W m^-2 Hz^-1 sr^-1;
+    0 for T <= 0. nu (Hz) and T (K) broadcast."""
+    nu, T = np.broadcast_arrays(np.asarray(nu, dtype=np.float64),
+                                np.asarray(T, dtype=np.float64))
+    out = np.zeros(nu.shape)
+    ok = T > 0.
+    with np.errstate(over="ignore"):
+        out[ok] = (2. * PLANCK * nu[ok] * nu[ok] * nu[ok] /
+                   (LIGHTSPEED * LIGHTSPEED)) / \
+            np.expm1((PLANCK * nu[ok]) / (BOLTZMANN * T[ok]))
+    return out if out.ndim else float(out)
+
+
+def brightness_temperature(I, nu):
+    """The Rayleigh-Jeans brightness temperature c^2 I / (2 k nu^2) (K) of
+    the specific intensity I (W m^-2 Hz^-1 sr^-1) at nu (Hz). With I of shape
+    (nf, ...) and nu of shape (nf,) the frequencies go with the first axis."""
+    I = np.asarray(I, dtype=np.float64)
+    nu = np.asarray(nu, dtype=np.float64)
+    if nu.ndim == 1 and I.ndim > 1:
+        nu = nu.reshape((-1,) + (1,) * (I.ndim - 1))
+    return LIGHTSPEED * LIGHTSPEED * I / (2. * BOLTZMANN * nu * nu)
+
+
+def continuum_spectral_index(I, freq):
+    """The slope of log I against log nu between neighbouring frequencies,
+    per pixel: (nf - 1, ...) from I of shape (nf, ...) and freq[nf]; NaN
+    where either intensity is not positive. -0.1 for thin free-free emission,
+    2 for thick."""
+    I = np.asarray(I, dtype=np.float64)
+    nu = np.asarray(freq, dtype=np.float64).reshape(-1)
+    if len(nu) != I.shape[0] or len(nu) < 2:
+        raise ValueError("continuum_spectral_index needs I[nf][...] and "
+                         "freq[nf], nf >= 2")
+    dlognu = np.log(nu[1:] / nu[:-1]).reshape((-1,) + (1,) * (I.ndim - 1))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ok = (I[1:] > 0.) & (I[:-1] > 0.)
+        ratio = np.where(ok, I[1:] / np.where(ok, I[:-1], 1.), np.nan)
+        return np.log(ratio) / dlognu
+
+
+def continuum_flux_density(I, pixel_solid_angle):
+    """The flux density (W m^-2 Hz^-1; 1e26 of them are a jansky) per
+    channel: the sum over the pixels of I (nf, nx, ny) times their solid
+    angle (a scalar, or (nx, ny) as from sky_map_directions)."""
+    I = np.asarray(I, dtype=np.float64)
+    w = np.asarray(pixel_solid_angle, dtype=np.float64)
+    return (I * w).reshape(I.shape[0], -1).sum(axis=1)
 
 
 _lib = None
@@ -392,6 +453,27 @@ def load_library():
     L.cmi_gpu_set_scattered_cube.argtypes = [
         vp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, _dp]
     L.cmi_gpu_download_cube_view.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    # (a build from before the continuum images, loaded through
+    # CMI_GPU_LIBRARY for a comparison, does not have them)
+    if hasattr(L, "cmi_gpu_free_free_coefficients"):
+        L.cmi_gpu_free_free_coefficients.argtypes = [vp, C.c_int32, _dp,
+                                                     _dp, _dp]
+        L.cmi_gpu_render_continuum_images.argtypes = [
+            vp, C.c_int32, _dp, _dp, C.c_double, C.c_double, C.c_int32, C.c_int32,
+            _dp, _dp, C.c_int32, _dp]
+        L.cmi_gpu_render_field_continuum_images.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32,
+            C.c_int32, _dp, _dp, C.c_int32, _dp]
+        L.cmi_gpu_render_continuum_sky.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, C.c_int64, _dp, _dp]
+        L.cmi_gpu_render_field_continuum_sky.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, _dp, C.c_int64, _dp, _dp]
+        L.cmi_gpu_render_continuum_sky_map.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp,
+            _dp]
+        L.cmi_gpu_continuum_probe.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, C.c_int64, _dp,
+            C.c_int32, _dp]
     _lib = L
     return L
 
@@ -1329,6 +1411,127 @@ class GpuEngine:
             _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
             lat_range[1], int(nlon), int(nlat), dust_cross_section, _p(out)))
         return dict(zip(names, out))
+
+    # continuum images ---------------------------------------------------------
+    def _background(self, background, nf):
+        if background is None:
+            return None
+        return _f64(np.broadcast_to(_f64(background), (nf,)))
+
+    def free_free_coefficients(self, freq):
+        """The thermal free-free absorption coefficient (m^-1) and source
+        function B_nu(T) (W m^-2 Hz^-1 sr^-1) of the cells as they are at the
+        frequencies freq[nf] (Hz): two (nf, ncell) arrays in the engine's
+        cell order (include/cmi_gpu.h, "continuum images")."""
+        nu = _f64(freq).reshape(-1)
+        kappa = np.zeros((len(nu), self.n))
+        source = np.zeros((len(nu), self.n))
+        self._check(self._lib.cmi_gpu_free_free_coefficients(
+            self._h, len(nu), _p(nu), _p(kappa), _p(source)))
+        return kappa, source
+
+    def render_continuum_images(self, freq, theta, phi, nx, ny, anchor, sides,
+                                supersample=1, background=None):
+        """Radio continuum images of the ionized gas for the view (theta,
+        phi): (nf, nx, ny), the specific intensity in W m^-2 Hz^-1 sr^-1 at
+        freq[nf] (Hz), free-free emission with its own absorption along the
+        ray, in front of `background` (a scalar or [nf]; None: nothing). The
+        view arguments are those of render_line_images."""
+        nu = _f64(freq).reshape(-1)
+        bg = self._background(background, len(nu))
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(nu), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_continuum_images(
+            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
+            _p(out)))
+        return out
+
+    def render_field_continuum_images(self, kappa, source, theta, phi, nx, ny,
+                                      anchor, sides, supersample=1,
+                                      background=None):
+        """The same images of any channels: kappa[nf][ncell] (m^-1) and
+        source[nf][ncell], the per-cell absorption coefficient and source
+        function of each channel; (nf, nx, ny)."""
+        k = _f64(kappa).reshape(-1, self.n)
+        S = _f64(source).reshape(len(k), self.n)
+        bg = self._background(background, len(k))
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((len(k), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_field_continuum_images(
+            self._h, len(k), _p(k), _p(S),
+            _p(bg) if bg is not None else None, theta, phi, int(nx), int(ny),
+            _p(a), _p(s), int(supersample), _p(out)))
+        return out
+
+    def render_continuum_sky(self, freq, origin, directions, background=None):
+        """The free-free continuum seen from `origin` (m) along the unit
+        vectors directions[nrays][3]: (nf, nrays) in W m^-2 Hz^-1 sr^-1."""
+        nu = _f64(freq).reshape(-1)
+        bg = self._background(background, len(nu))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(nu), len(d)))
+        self._check(self._lib.cmi_gpu_render_continuum_sky(
+            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            _p(o), len(d), _p(d), _p(out)))
+        return out
+
+    def render_field_continuum_sky(self, kappa, source, origin, directions,
+                                   background=None):
+        """The same of any channels kappa[nf][ncell], source[nf][ncell];
+        (nf, nrays)."""
+        k = _f64(kappa).reshape(-1, self.n)
+        S = _f64(source).reshape(len(k), self.n)
+        bg = self._background(background, len(k))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((len(k), len(d)))
+        self._check(self._lib.cmi_gpu_render_field_continuum_sky(
+            self._h, len(k), _p(k), _p(S),
+            _p(bg) if bg is not None else None, _p(o), len(d), _p(d),
+            _p(out)))
+        return out
+
+    def render_continuum_sky_map(self, freq, origin, nlon, nlat,
+                                 lon_range=FULL_SKY_LONGITUDE,
+                                 lat_range=FULL_SKY_LATITUDE,
+                                 frame=IDENTITY_FRAME, background=None):
+        """Equirectangular free-free maps around `origin`: (nf, nlon, nlat),
+        the pixels of sky_map_directions."""
+        nu = _f64(freq).reshape(-1)
+        bg = self._background(background, len(nu))
+        o = _f64(origin).reshape(3)
+        f = _f64(frame).reshape(9)
+        lon = _f64(lon_range).reshape(2)
+        lat = _f64(lat_range).reshape(2)
+        out = np.zeros((len(nu), max(int(nlon), 0), max(int(nlat), 0)))
+        self._check(self._lib.cmi_gpu_render_continuum_sky_map(
+            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            _p(o), int(nlon), int(nlat), _p(lon), _p(lat), _p(f), _p(out)))
+        return out
+
+    def continuum_probe(self, kappa, source, rays, max_cells, theta=None,
+                        phi=None, origin=None, background=None):
+        """The march of chosen rays through kappa[nf][ncell] and
+        source[nf][ncell], cell by cell: rows {t0, t1, steps,
+        cells[max_cells], ds[max_cells], I[nf][max_cells], I_end[nf]}. With
+        theta and phi the rays are image coordinates [n][2] of the parallel
+        camera, with origin directions [n][3]."""
+        k = _f64(kappa).reshape(-1, self.n)
+        S = _f64(source).reshape(len(k), self.n)
+        nf = len(k)
+        bg = self._background(background, nf)
+        point = origin is not None
+        view = _f64(origin).reshape(3) if point else _f64([theta, phi])
+        r = _f64(rays).reshape(-1, 3 if point else 2)
+        out = np.zeros((len(r), 3 + (2 + nf) * max_cells + nf))
+        self._check(self._lib.cmi_gpu_continuum_probe(
+            self._h, nf, _p(k), _p(S), _p(bg) if bg is not None else None,
+            int(point), _p(view), len(r), _p(r), int(max_cells), _p(out)))
+        return out
 
     # sky cubes --------------------------------------------------------------
     def render_field_sky_cube(self, fields, widths, origin, directions, nchan,

@@ -114,6 +114,19 @@
  * _scattered): raw doubles [channel][ix][iy] in the unit of the ray-traced
  * cube, with the block's velocity field, turbulent dispersion and observer
  * velocities.
+ * Radio continuum (read only if "continuum frequencies" is
+ * there, in either block):
+ *   EmissionImages:continuum frequencies         N, the number of frequencies
+ *   EmissionImages:continuum frequency minimum / continuum frequency maximum
+ *                    required, frequencies (wavelengths and photon energies
+ *                    convert); nu_f = nu_min * pow(nu_max / nu_min, f / (N -
+ *                    1)), N == 1 uses the minimum
+ *   EmissionImages:continuum background temperature   0. K: bg_f = B_nu(T_bg)
+ * The thermal free-free emission of the cells with its own absorption is
+ * then written as <prefix>_continuum.dat (_continuum_view<k>.dat for view or
+ * observer k >= 1), raw doubles [f][ix][iy] in W m^-2 Hz^-1 sr^-1, and the
+ * frequencies as <prefix>_continuum_frequencies.txt, one line "nu bg" per
+ * frequency with 17 significant digits. Needs type BinaryArray.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -222,6 +235,83 @@ class EmissivityCalculationSimulation {
             "Unknown " + block + ":velocity field type \"" + velocity_field +
             "\" (Static, SolidBodyRotation, RadialExpansion or Snapshot)");
       }
+    }
+
+    /* the radio continuum keys of a block (read only if the block has
+     * "continuum frequencies") */
+    bool continuum = false;
+    double continuum_background_temperature = 0.;
+    std::vector<double> continuum_frequencies, continuum_background;
+
+    void read_continuum(ParameterFile &params, const std::string &block,
+                        const std::string &type) {
+      if (!params.has_value(block + ":continuum frequencies"))
+        return;
+      continuum = true;
+      const long long n =
+          params.get_integer(block + ":continuum frequencies", 1);
+      /* (the images of one call hold at most 2^28 values, checked against
+       * the pixels where they are rendered; this bounds the ladder itself) */
+      if (n < 1 || n > (1ll << 20))
+        throw ParameterError(block + ":continuum frequencies must be between "
+                             "1 and 2^20 (" + std::to_string(n) +
+                             " asked for)");
+      if (type != "BinaryArray")
+        throw ParameterError(block + ":continuum frequencies needs type "
+                             "BinaryArray: the images of all frequencies are "
+                             "written as raw doubles");
+      for (const char *name :
+           {":continuum frequency minimum", ":continuum frequency maximum"})
+        if (!params.has_value(block + name))
+          throw ParameterError(block + name + " is required with " + block +
+                               ":continuum frequencies");
+      const double nu_min = params.get_physical_value(
+          QUANTITY_FREQUENCY, block + ":continuum frequency minimum", "1. Hz");
+      const double nu_max = params.get_physical_value(
+          QUANTITY_FREQUENCY, block + ":continuum frequency maximum", "1. Hz");
+      if (!(nu_min > 0.) || !std::isfinite(nu_min) || !(nu_max > 0.) ||
+          !std::isfinite(nu_max))
+        throw ParameterError(block + ":continuum frequency minimum and "
+                             "maximum must be positive and finite");
+      if (n > 1 && !(nu_max > nu_min))
+        throw ParameterError(block + ":continuum frequency maximum must be "
+                             "above continuum frequency minimum");
+      continuum_background_temperature = params.get_physical_value(
+          QUANTITY_TEMPERATURE, block + ":continuum background temperature",
+          "0. K");
+      if (!(continuum_background_temperature >= 0.) ||
+          !std::isfinite(continuum_background_temperature))
+        throw ParameterError(block + ":continuum background temperature must "
+                             "not be negative");
+      continuum_frequencies.resize((size_t)n);
+      continuum_background.resize((size_t)n);
+      for (long long f = 0; f < n; ++f) {
+        const double nu =
+            n == 1 ? nu_min
+                   : nu_min * std::pow(nu_max / nu_min,
+                                       (double)f / (double)(n - 1));
+        continuum_frequencies[(size_t)f] = nu;
+        const double T = continuum_background_temperature;
+        continuum_background[(size_t)f] =
+            T > 0. ? (2. * constants::planck * nu * nu * nu /
+                      (constants::lightspeed * constants::lightspeed)) /
+                         std::expm1((constants::planck * nu) /
+                                    (constants::boltzmann * T))
+                   : 0.;
+      }
+    }
+
+    /* <name>.txt: one line "nu bg" per frequency. Returns the file's name. */
+    std::string write_continuum_frequencies(const std::string &name) const {
+      const std::string filename = name + ".txt";
+      std::FILE *file = std::fopen(filename.c_str(), "w");
+      if (!file)
+        throw std::runtime_error("Could not write " + filename);
+      for (size_t f = 0; f < continuum_frequencies.size(); ++f)
+        std::fprintf(file, "%.17g %.17g\n", continuum_frequencies[f],
+                     continuum_background[f]);
+      std::fclose(file);
+      return filename;
     }
 
     /* the velocity of the matter at r (not for Snapshot) */
@@ -358,6 +448,7 @@ class EmissivityCalculationSimulation {
                                "positive");
       read_views(params);
       read_cubes(params, "EmissionImages", type);
+      read_continuum(params, "EmissionImages", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       /* (looked at like the switch above: a file without it, or with it
@@ -579,6 +670,7 @@ class EmissivityCalculationSimulation {
       read_cubes(params, "EmissionSkyMaps", type);
       if (cubes)
         read_observer_velocities(params);
+      read_continuum(params, "EmissionSkyMaps", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       /* (looked at like the switch above: a file without it, or with it
@@ -995,6 +1087,34 @@ public:
                     img.nx, img.ny);
           }
         }
+        if (rc == CMI_GPU_OK && img.continuum) {
+          status("Rendering radio continuum images...");
+          const size_t nf = img.continuum_frequencies.size();
+          if ((double)nf * (double)npixel > (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionImages: " + std::to_string(nf) +
+                " continuum frequencies of " + std::to_string(img.nx) +
+                " x " + std::to_string(img.ny) +
+                " pixels: more than 2^28 values in one call");
+          std::vector<double> continuum(nf * npixel);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_render_continuum_images(
+                engine, (int32_t)nf, img.continuum_frequencies.data(),
+                img.continuum_background.data(), theta[v], phi[v],
+                (int32_t)img.nx, (int32_t)img.ny, anchors.data() + 2 * v,
+                sides.data() + 2 * v, (int32_t)img.supersample,
+                continuum.data());
+            if (rc == CMI_GPU_OK && write_output)
+              written += " " + write_cube(img.folder + "/" + img.prefix +
+                                              "_continuum" + view_tag(v),
+                                          continuum.data(), (long long)nf,
+                                          img.nx, img.ny);
+          }
+          if (rc == CMI_GPU_OK && write_output)
+            written += " " + img.write_continuum_frequencies(
+                                 img.folder + "/" + img.prefix +
+                                 "_continuum_frequencies");
+        }
         if (rc == CMI_GPU_OK && img.scattering) {
           status("Shooting the lines' packets through the dust...");
           rc = cmi_gpu_set_dust_scattering_per_hydrogen(
@@ -1138,6 +1258,34 @@ public:
                     cube.data() + k * (size_t)sky.nchan * npixel, sky.nchan,
                     sky.nlon, sky.nlat);
           }
+        }
+        if (rc == CMI_GPU_OK && sky.continuum) {
+          status("Rendering radio continuum sky maps...");
+          const size_t nf = sky.continuum_frequencies.size();
+          if ((double)nf * (double)npixel > (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionSkyMaps: " + std::to_string(nf) +
+                " continuum frequencies of " + std::to_string(sky.nlon) +
+                " x " + std::to_string(sky.nlat) +
+                " pixels: more than 2^28 values in one call");
+          std::vector<double> continuum(nf * npixel);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_render_continuum_sky_map(
+                engine, (int32_t)nf, sky.continuum_frequencies.data(),
+                sky.continuum_background.data(),
+                sky.observers[v].position.data(), (int32_t)sky.nlon,
+                (int32_t)sky.nlat, sky.lon.data(), sky.lat.data(),
+                sky.observers[v].frame, continuum.data());
+            if (rc == CMI_GPU_OK && write_output)
+              written += " " + write_cube(sky.folder + "/" + sky.prefix +
+                                              "_continuum" + view_tag(v),
+                                          continuum.data(), (long long)nf,
+                                          sky.nlon, sky.nlat);
+          }
+          if (rc == CMI_GPU_OK && write_output)
+            written += " " + sky.write_continuum_frequencies(
+                                 sky.folder + "/" + sky.prefix +
+                                 "_continuum_frequencies");
         }
         if (rc == CMI_GPU_OK && sky.scattering) {
           status("Shooting the lines' packets towards the observer...");

@@ -127,6 +127,12 @@ inline Unit single_unit(const std::string &name) {
     return Unit(M_PI / 180., 0, 0, 0, 0, 0, 1);
   if (name == "Hz")
     return Unit(1., 0, -1, 0, 0, 0, 0);
+  if (name == "kHz")
+    return Unit(1.e3, 0, -1, 0, 0, 0, 0);
+  if (name == "MHz")
+    return Unit(1.e6, 0, -1, 0, 0, 0, 0);
+  if (name == "GHz")
+    return Unit(1.e9, 0, -1, 0, 0, 0, 0);
   if (name == "J")
     return Unit(1., 2, -2, 1, 0, 0, 0);
   if (name == "erg")

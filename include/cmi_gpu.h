@@ -1553,6 +1553,158 @@ int cmi_gpu_set_scattered_cube(cmi_gpu_engine *engine, int32_t nchan,
 int cmi_gpu_download_cube_view(cmi_gpu_engine *engine, int32_t view, double *I,
                                double *Q, double *U);
 
+/* --------------------------------------------------- continuum images -- */
+/* The formal solution of the transfer equation with an absorption coefficient
+ * and a source function of their own in every channel, and thermal free-free
+ * emission of the ionized gas as its first client: radio continuum images of
+ * an H II region, optically thin at high frequency and with T_b = T_e below
+ * the turnover. Every product above shares one grey exp(-k ds) among its
+ * channels and emits what the cell does not absorb itself; here the cell
+ * absorbs its own emission. No counterpart in the reference.
+ *
+ * Channels: nf >= 1, in the caller's order. Channel f has a per-cell
+ * absorption coefficient kappa_f (m^-1, finite, >= 0), a per-cell source
+ * function S_f (W m^-2 Hz^-1 sr^-1, finite) and a background intensity bg_f
+ * (finite; background == NULL means all zero).
+ *
+ * Arithmetic: every product and sum below is one IEEE operation
+ * (-ffp-contract=off) in the order written, with one expm1 per cell and
+ * channel and no exp.
+ *
+ * Parallel camera: the view, the sample grid, the supersampling and the
+ * average of the samples into pixels are those of cmi_gpu_render_field_images
+ * ("emission-line images"), unchanged. The march runs from the far side to
+ * the near side. I_f starts at bg_f; per cell with path ds
+ *   em = expm1(-(kappa_f * ds));  I_f = I_f + em * (I_f - S_f)
+ * A ray that misses the box returns bg_f. Two consequences are exact:
+ * kappa == 0 leaves I_f untouched, and I_f == S_f stays S_f - a medium in
+ * equilibrium with its background is invisible, bit for bit.
+ *
+ * Rays from a point: the origin, the direction list and their checks, the
+ * slab test, the start cell and the step are those of cmi_gpu_render_field_sky
+ * ("sky maps"), unchanged. The march runs from the observer outwards. T_f = 1
+ * and I_f = 0 at the start; per cell
+ *   em = expm1(-(kappa_f * ds));  I_f = I_f + T_f * (S_f * -em);
+ *   T_f = T_f + T_f * em
+ * and after the last cell, or for a ray that misses, I_f = I_f + T_f * bg_f.
+ *
+ * Free-free coefficients of the cells as they are, with the constants h, k_B
+ * and c of the engine (CODATA 2014: 6.626070040e-34, 1.38064852e-23,
+ * 299792458):
+ *   n_e = n * ((1 - x_H0) + A_He * (1 - x_He0)),  n_i = n_e
+ *     (A_He from cmi_gpu_set_abundances; both ions have charge 1),
+ *   x   = (h * nu) / (k_B * T),
+ *   S   = (2 * h * nu * nu * nu / (c * c)) / expm1(x)           = B_nu(T),
+ *   g   = log(exp(5.960 - (sqrt(3) / pi) * log((nu / 1e9) * pow(T / 1e4,
+ *         -1.5))) + e)                        (Draine 2011, eq. 10.9),
+ *   j   = 5.444364709e-52 * g * n_e * n_i / sqrt(T) * exp(-x)
+ *         (W m^-3 Hz^-1 sr^-1; the Gaussian (2^5 pi e^6 / (3 m_e c^3))
+ *         sqrt(2 pi / (3 k_B m_e)) / (4 pi) times 1e-13 for SI densities),
+ *   kappa = j / S                                      (Kirchhoff's law),
+ * the products from left to right. A cell with n_e == 0, without a positive
+ * temperature or with S == 0 has kappa = 0 and S = 0 exactly: vacuum and
+ * neutral cells give no NaN.
+ *
+ * Frequencies: finite and > 0 (Hz). The Gaunt factor is Draine's fit for
+ * the radio to sub-millimetre range, nu_p << nu <~ k_B T / h: it is the
+ * classical logarithm at low frequency and tends to 1 at high frequency.
+ * Nothing is done about the plasma frequency nu_p = 8.98 kHz sqrt(n_e /
+ * cm^-3), below which there is no propagation; at optical frequencies the
+ * continuum of an H II region is bound-free and two-photon emission, which
+ * this is not.
+ *
+ * Output: specific intensity, W m^-2 Hz^-1 sr^-1, out[f * npixel + ix * ny +
+ * iy] or out[f * nrays + r]. No atomics: the same call on the same state
+ * gives the same bits, and a channel's bits do not depend on how many other
+ * channels the call has or where in the list it is.
+ *
+ * Errors, each with a message for cmi_gpu_last_error, before any march and
+ * with `out` untouched: CMI_GPU_EINVAL for nf < 1 or nf * npixel (nf * nrays)
+ * > 2^28, the cube calls' limit; for a frequency that is not finite and
+ * positive; for a kappa that is negative or not finite, an S or a background
+ * that is not finite (the fields are counted on the device once uploaded);
+ * and everything cmi_gpu_render_field_images or cmi_gpu_render_field_sky
+ * refuses for its view or rays. CMI_GPU_ESTATE for the free-free calls
+ * without cell data. All calls are synchronous; a call that fails leaves the
+ * engine usable.
+ *
+ * Tuning (cmi_gpu_set_tuning): continuum_channel_block = 4, 8 or 16 channels
+ * per march launch; continuum_launch_rays = sample rays or rays per march
+ * launch (0: the images' and the sky maps' own bounds). Neither changes a
+ * bit of the result. */
+
+/* The free-free {kappa, S} of the cells at freq[nf]: host arrays [nf][ncell]
+ * in the engine's cell order - what the free-free calls below march. */
+int cmi_gpu_free_free_coefficients(cmi_gpu_engine *engine, int32_t nf,
+                                   const double *freq, double *kappa_out,
+                                   double *source_out);
+
+/* Free-free images of the parallel camera; view arguments as in
+ * cmi_gpu_render_field_images. */
+int cmi_gpu_render_continuum_images(cmi_gpu_engine *engine, int32_t nf,
+                                    const double *freq,
+                                    const double *background /* [nf] or NULL */,
+                                    double theta, double phi, int32_t nx,
+                                    int32_t ny, const double anchor[2],
+                                    const double sides[2], int32_t supersample,
+                                    double *out /* [nf][nx][ny] */);
+
+/* The general solver: kappa[nf][ncell], source[nf][ncell] (host) in the
+ * engine's cell order. Frequencies are the caller's concern. Needs only
+ * cmi_gpu_create. */
+int cmi_gpu_render_field_continuum_images(
+    cmi_gpu_engine *engine, int32_t nf, const double *kappa,
+    const double *source, const double *background /* [nf] or NULL */,
+    double theta, double phi, int32_t nx, int32_t ny, const double anchor[2],
+    const double sides[2], int32_t supersample,
+    double *out /* [nf][nx][ny] */);
+
+/* Free-free along rays from a point; origin and rays as in
+ * cmi_gpu_render_field_sky. */
+int cmi_gpu_render_continuum_sky(cmi_gpu_engine *engine, int32_t nf,
+                                 const double *freq, const double *background,
+                                 const double origin[3], int64_t nrays,
+                                 const double *directions,
+                                 double *out /* [nf][nrays] */);
+
+int cmi_gpu_render_field_continuum_sky(cmi_gpu_engine *engine, int32_t nf,
+                                       const double *kappa,
+                                       const double *source,
+                                       const double *background,
+                                       const double origin[3], int64_t nrays,
+                                       const double *directions,
+                                       double *out /* [nf][nrays] */);
+
+/* The equirectangular map of cmi_gpu_render_line_sky_map in free-free: the
+ * same pixel centres and the same 8 x 8 tile order of the rays, lon_range =
+ * {lon_min, lon_max}, lat_range likewise; out[f * nlon * nlat + i * nlat +
+ * j]. Equals cmi_gpu_render_continuum_sky on the map's directions, bit for
+ * bit. */
+int cmi_gpu_render_continuum_sky_map(cmi_gpu_engine *engine, int32_t nf,
+                                     const double *freq,
+                                     const double *background,
+                                     const double origin[3], int32_t nlon,
+                                     int32_t nlat, const double lon_range[2],
+                                     const double lat_range[2],
+                                     const double frame[9], double *out);
+
+/* Test hook: the march of n <= 2^20 chosen rays through the caller's fields
+ * (nf <= 1024), cell by cell. point == 0: the parallel camera, view = {theta,
+ * phi} and rays[n][2] image coordinates as in cmi_gpu_line_image_probe;
+ * point == 1: view = the origin[3] and rays[n][3] directions as in
+ * cmi_gpu_sky_probe. Row k of `out` has 3 + (2 + nf) * max_cells + nf doubles:
+ * {t0, t1, steps, cells[max_cells], ds[max_cells], I[nf][max_cells],
+ * I_end[nf]}; t0, t1 and the cell list are the geometry probes', I[f][i] is
+ * I_f after step i (for point == 1 before the background is added) and
+ * I_end[f] what the render call returns. A ray that misses has NaN, NaN, 0
+ * and I_end = bg. A tolerance failure can be traced to a cell from this
+ * without running a kernel under a tool. */
+int cmi_gpu_continuum_probe(cmi_gpu_engine *engine, int32_t nf,
+                            const double *kappa, const double *source,
+                            const double *background, int32_t point,
+                            const double *view, int64_t n, const double *rays,
+                            int32_t max_cells, double *out);
+
 #ifdef __cplusplus
 }
 #endif
