@@ -276,7 +276,11 @@ struct CellIntegrals {
    * stand in threshold order (cmi_acc_column), not in the ions' */
   bool row = false;
   __device__ __forceinline__ double operator()(int ion) const {
-    return jfac * J[row ? cmi_acc_column(ion) : ion * stride];
+    return jfac * raw(ion);
+  }
+  /* the accumulator itself (un-normalised), wherever the layout keeps it */
+  __device__ __forceinline__ double raw(int ion) const {
+    return J[row ? cmi_acc_column(ion) : ion * stride];
   }
 };
 
@@ -503,9 +507,9 @@ __device__ inline void temperature_end(const ModelDev &m, double ntot,
     cmi_ionization_states_metals(m, j, ne, s.Tlast, s.Tlast * 1.e-4, nh0, nhe0,
                                  nhp, x);
   }
-  if (j.J[ION_H_n * j.stride] == 0.)
+  if (j.raw(ION_H_n) == 0.)
     h0 = 1.;
-  if (j.J[ION_He_n * j.stride] == 0.)
+  if (j.raw(ION_He_n) == 0.)
     he0 = 1.;
   x[ION_H_n] = h0;
   x[ION_He_n] = he0;

@@ -457,6 +457,37 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
                            double ntot, double midpoint_z, double *temperature,
                            const double J[CMIO_NION], double heating[2],
                            double x[CMIO_NION]);
+/* the branches of the solve a cell can take (the trace of
+ * cmio_temperature_cell_traced) */
+enum {
+  CMIO_TB_NO_RADIATION = 1 << 0,   /* J_H = J_He = 0 or vacuum: neutral, 500 K */
+  CMIO_TB_CRLIM = 1 << 1,          /* too neutral for cosmic ray heating */
+  CMIO_TB_RESTART = 1 << 2,        /* T <= 4000 K on entry: starts at 8000 K */
+  CMIO_TB_GAIN_M99 = 1 << 3,       /* gain slope: gain1 <= 0 < gain2 */
+  CMIO_TB_GAIN_P99 = 1 << 4,       /*             gain2 <= 0 < gain1 */
+  CMIO_TB_GAIN_ZERO = 1 << 5,      /*             both <= 0 */
+  CMIO_TB_LOSS_M99 = 1 << 6,       /* loss slope: loss1 <= 0 < loss2 */
+  CMIO_TB_LOSS_P99 = 1 << 7,       /*             loss2 <= 0 < loss1 */
+  CMIO_TB_LOSS_ZERO = 1 << 8,      /*             both <= 0 */
+  CMIO_TB_T1_FALLBACK = 1 << 9,    /* no secant step possible: T0 = 1.1 T0 */
+  CMIO_TB_BELOW_TMIN = 1 << 10,    /* T0 < t_min_ionized */
+  CMIO_TB_ABOVE_1E10 = 1 << 11,    /* T0 > 1e10 K */
+  CMIO_TB_MAX_ITERATIONS = 1 << 12, /* ended by t_max_iterations, unconverged */
+  CMIO_TB_JH_ZERO = 1 << 13,       /* J_H = 0 at the end: h0 = 1 */
+  CMIO_TB_JHE_ZERO = 1 << 14,      /* J_He = 0 at the end: he0 = 1 */
+  CMIO_TB_METALS_ZEROED = 1 << 15, /* h0 = 1 or h0 <= 1e-10 at the end */
+  CMIO_TB_CLIPPED = 1 << 16,       /* T clipped at 30000 K */
+  CMIO_TB_COSMIC_RAY_GAIN = 1 << 17, /* balance evaluated with crfac > 0 */
+  CMIO_TB_NBRANCH = 18
+};
+/* cmio_temperature_cell that also reports the number of secant steps and the
+ * CMIO_TB_* bits of the branches taken (either pointer may be NULL) */
+void cmio_temperature_cell_traced(const cmio_model *model, double jfac,
+                                  double hfac, double ntot, double midpoint_z,
+                                  double *temperature,
+                                  const double J[CMIO_NION], double heating[2],
+                                  double x[CMIO_NION], int32_t *nsteps,
+                                  uint32_t *branches);
 /* src/TemperatureCalculator.cpp:944-970, temperature branch */
 void cmio_calculate_temperature(const cmio_grid *grid, const cmio_model *model,
                                 cmio_cells *cells, double totweight);
@@ -477,6 +508,14 @@ void cmio_calculate_temperature_range(const cmio_grid *grid,
                                       const cmio_model *model,
                                       cmio_cells *cells, double totweight,
                                       int64_t first, int64_t count);
+/* ... that also fills nsteps[count] and branches[count] (the trace of
+ * cmio_temperature_cell_traced per cell; either may be NULL) */
+void cmio_calculate_temperature_range_traced(const cmio_grid *grid,
+                                             const cmio_model *model,
+                                             cmio_cells *cells,
+                                             double totweight, int64_t first,
+                                             int64_t count, int32_t *nsteps,
+                                             uint32_t *branches);
 void cmio_update_cells_range(const cmio_grid *grid, const cmio_model *model,
                              cmio_cells *cells, uint32_t loop,
                              double totweight, int64_t first, int64_t count);

@@ -111,15 +111,25 @@ static void set_neutral(double x[CMIO_NION], double heating[2]) {
   heating[1] = 0.;
 }
 
-void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
-                           double ntot, double midpoint_z, double *temperature,
-                           const double J[CMIO_NION], double heating[2],
-                           double x[CMIO_NION]) {
+/* the one copy of the solve; nsteps / branches (either may be NULL) receive
+ * the number of secant steps and the CMIO_TB_* bits of the branches taken */
+static void temperature_cell(const cmio_model *model, double jfac, double hfac,
+                             double ntot, double midpoint_z,
+                             double *temperature, const double J[CMIO_NION],
+                             double heating[2], double x[CMIO_NION],
+                             int32_t *nsteps, uint32_t *branches) {
+  uint32_t taken = 0;
+  if (nsteps)
+    *nsteps = 0;
+  if (branches)
+    *branches = 0;
   const double jH = jfac * J[CMIO_ION_H_n];
   const double jHe = jfac * J[CMIO_ION_He_n];
   if ((jH == 0. && jHe == 0.) || ntot == 0.) {
     *temperature = 500.;
     set_neutral(x, heating);
+    if (branches)
+      *branches = CMIO_TB_NO_RADIATION;
     return;
   }
   /* cosmic ray factor of the cell: DensityValues default, i.e. the global
@@ -136,6 +146,8 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
     if (h0 > model->crlim) {
       *temperature = 500.;
       set_neutral(x, heating);
+      if (branches)
+        *branches = CMIO_TB_CRLIM;
       return;
     }
   }
@@ -143,6 +155,7 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
   double T0 = *temperature;
   if (*temperature <= 4000.) {
     T0 = 8000.;
+    taken |= CMIO_TB_RESTART;
   }
   double j[CMIO_NION];
   for (int ion = 0; ion < CMIO_NION; ++ion)
@@ -177,22 +190,28 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
     double expgain;
     if (gain2 > 0.) {
       expgain = (gain1 > 0.) ? log(gain1 / gain2) : -99.;
+      taken |= (gain1 > 0.) ? 0 : CMIO_TB_GAIN_M99;
     } else {
       expgain = (gain1 > 0.) ? 99. : 0.;
+      taken |= (gain1 > 0.) ? CMIO_TB_GAIN_P99 : CMIO_TB_GAIN_ZERO;
     }
     double exploss;
     if (loss2 > 0.) {
       exploss = (loss1 > 0.) ? log(loss1 / loss2) : -99.;
+      taken |= (loss1 > 0.) ? 0 : CMIO_TB_LOSS_M99;
     } else {
       exploss = (loss1 > 0.) ? 99. : 0.;
+      taken |= (loss1 > 0.) ? CMIO_TB_LOSS_P99 : CMIO_TB_LOSS_ZERO;
     }
     const double expdiff = expgain - exploss;
     if (gain0 > 0. && expdiff != 0.) {
       T0 *= pow(loss0 / gain0, logtt / expdiff);
     } else {
       T0 = T1;
+      taken |= CMIO_TB_T1_FALLBACK;
     }
     if (T0 < model->t_min_ionized) {
+      taken |= CMIO_TB_BELOW_TMIN;
       T0 = 500.;
       h0 = 1.;
       he0 = 1.;
@@ -200,6 +219,7 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
       loss0 = 1.;
     }
     if (T0 > 1.e10) {
+      taken |= CMIO_TB_ABOVE_1E10;
       T0 = 1.e10;
       h0 = 1.e-10;
       he0 = 1.e-10;
@@ -207,22 +227,58 @@ void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
       loss0 = 1.;
     }
   }
+  if (niter == (uint_fast32_t)model->t_max_iterations &&
+      fabs(gain0 - loss0) > model->t_epsilon * gain0) {
+    taken |= CMIO_TB_MAX_ITERATIONS;
+  }
+  /* (every balance evaluation of a model with cosmic rays adds their gain) */
+  if (crfac > 0. && niter > 0) {
+    taken |= CMIO_TB_COSMIC_RAY_GAIN;
+  }
+  if (T0 > 30000.) {
+    taken |= CMIO_TB_CLIPPED;
+  }
   T0 = fmin(30000., T0);
   *temperature = T0;
   if (J[CMIO_ION_H_n] == 0.) {
     h0 = 1.;
+    taken |= CMIO_TB_JH_ZERO;
   }
   if (J[CMIO_ION_He_n] == 0.) {
     he0 = 1.;
+    taken |= CMIO_TB_JHE_ZERO;
   }
   x[CMIO_ION_H_n] = h0;
   x[CMIO_ION_He_n] = he0;
   if (h0 == 1. || h0 <= 1.e-10) {
+    taken |= CMIO_TB_METALS_ZEROED;
     for (int ion = CMIO_ION_C_p1; ion < CMIO_NION; ++ion)
       x[ion] = 0.;
   }
   heating[0] = h[0];
   heating[1] = h[1];
+  if (nsteps)
+    *nsteps = (int32_t)niter;
+  if (branches)
+    *branches = taken;
+}
+
+void cmio_temperature_cell(const cmio_model *model, double jfac, double hfac,
+                           double ntot, double midpoint_z, double *temperature,
+                           const double J[CMIO_NION], double heating[2],
+                           double x[CMIO_NION]) {
+  temperature_cell(model, jfac, hfac, ntot, midpoint_z, temperature, J,
+                   heating, x, NULL, NULL);
+}
+
+void cmio_temperature_cell_traced(const cmio_model *model, double jfac,
+                                  double hfac, double ntot, double midpoint_z,
+                                  double *temperature,
+                                  const double J[CMIO_NION], double heating[2],
+                                  double x[CMIO_NION], int32_t *nsteps,
+                                  uint32_t *branches) {
+  temperature_cell(model, jfac, hfac, ntot, midpoint_z, temperature, J,
+                   heating, x, nsteps, branches);
 }
 
 void cmio_calculate_temperature(const cmio_grid *grid, const cmio_model *model,
@@ -238,6 +294,18 @@ void cmio_calculate_temperature_range(const cmio_grid *grid,
                                       const cmio_model *model,
                                       cmio_cells *cells, double totweight,
                                       int64_t first, int64_t count) {
+  cmio_calculate_temperature_range_traced(grid, model, cells, totweight, first,
+                                          count, NULL, NULL);
+}
+
+/* ... with the trace of every cell: nsteps[count], branches[count] (either may
+ * be NULL), indexed by cell - first */
+void cmio_calculate_temperature_range_traced(const cmio_grid *grid,
+                                             const cmio_model *model,
+                                             cmio_cells *cells,
+                                             double totweight, int64_t first,
+                                             int64_t count, int32_t *nsteps,
+                                             uint32_t *branches) {
   const double jfac = model->total_luminosity / totweight;
   const double hfac = jfac * CMIO_PLANCK;
   const double cellside_z = grid->sides[2] / grid->ncell[2];
@@ -257,8 +325,10 @@ void cmio_calculate_temperature_range(const cmio_grid *grid,
     const int64_t iz = i % grid->ncell[2];
     const double zmid = (grid->anchor[2] + cellside_z * iz) + 0.5 * cellside_z;
     double T = cells->temperature[i];
-    cmio_temperature_cell(model, jfac / volume, hfac / volume,
-                          cells->number_density[i], zmid, &T, J, heating, x);
+    temperature_cell(model, jfac / volume, hfac / volume,
+                     cells->number_density[i], zmid, &T, J, heating, x,
+                     nsteps ? &nsteps[i - first] : NULL,
+                     branches ? &branches[i - first] : NULL);
     cells->temperature[i] = T;
     for (int ion = 0; ion < CMIO_NION; ++ion)
       cells->ionic_fraction[ion][i] = x[ion];

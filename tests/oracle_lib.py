@@ -219,6 +219,12 @@ def lib():
     L.cmio_temperature_cell.argtypes = [
         C.POINTER(Model), C.c_double, C.c_double, C.c_double, C.c_double, dp,
         dp, dp, dp]
+    L.cmio_temperature_cell_traced.argtypes = \
+        L.cmio_temperature_cell.argtypes + [C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_uint32)]
+    L.cmio_calculate_temperature_range_traced.argtypes = [
+        C.POINTER(Grid), C.POINTER(Model), C.POINTER(Cells), C.c_double,
+        C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     for name in ("cmio_verner_cross_section",
                  "cmio_verner_recombination_rate",
                  "cmio_ct_recombination_rate_H", "cmio_ct_ionization_rate_H",
@@ -468,6 +474,19 @@ class OracleSimulation:
                                       C.byref(self.cells), loop, totweight,
                                       first, count)
 
+    def calculate_temperature_traced(self, totweight, first=0, count=None):
+        """The temperature solve for cells [first, first + count) with its
+        trace: (secant steps, TB_* branch bits) per cell."""
+        count = self.n - first if count is None else count
+        nsteps = np.zeros(count, dtype=np.int32)
+        branches = np.zeros(count, dtype=np.uint32)
+        lib().cmio_calculate_temperature_range_traced(
+            C.byref(self.grid), C.byref(self.model), C.byref(self.cells),
+            totweight, first, count,
+            nsteps.ctypes.data_as(C.POINTER(C.c_int32)),
+            branches.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return nsteps, branches
+
     def run(self, n_packets, n_iterations, seed=42):
         for loop in range(n_iterations):
             self.reset()
@@ -475,6 +494,15 @@ class OracleSimulation:
             self.typecount[:] = 0.
             self.shoot(seed, loop, 0, n_packets)
             self.update(loop, self.totweight)
+
+
+# CMIO_TB_*: the branches of the temperature solve (oracle/cmio.h), bit k
+TEMPERATURE_BRANCHES = [
+    "NO_RADIATION", "CRLIM", "RESTART", "GAIN_M99", "GAIN_P99", "GAIN_ZERO",
+    "LOSS_M99", "LOSS_P99", "LOSS_ZERO", "T1_FALLBACK", "BELOW_TMIN",
+    "ABOVE_1E10", "MAX_ITERATIONS", "JH_ZERO", "JHE_ZERO", "METALS_ZEROED",
+    "CLIPPED", "COSMIC_RAY_GAIN"]
+TB = {name: 1 << k for k, name in enumerate(TEMPERATURE_BRANCHES)}
 
 
 NEMISSIONLINE = 42
