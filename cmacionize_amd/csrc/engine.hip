@@ -178,6 +178,10 @@ struct cmi_gpu_engine {
     /* direction bits of the sort key (2 x 11 at most); -1 = auto: one or two
      * fewer than 22 where that saves the radix sort a pass of 8 bits */
     int sort_dir_bits = -1;
+    /* the tau classes of every second direction bin the other way round
+     * (KeyArgs::class_order); -1 = the default of the run's kind, hydrogen-only
+     * or multi-ion (DESIGN_LOG.md 14) */
+    int class_order = -1;
     int aggregate = CMI_AGG_BLOCK;      /* first generation (sorted bundles) */
     int aggregate_reemit = CMI_AGG_NONE; /* later generations (random flights) */
     int refill_threshold = CMI_REFILL_THRESHOLD;
@@ -1677,6 +1681,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
         (int)(value < 0 ? -1 : (value < 2 ? 2 : (value > 22 ? 22 : value)));
   else if (k == "sort_tau_bits")
     e->tune.sort_tau_bits = (int)(value < 0 ? -1 : (value > 3 ? 3 : value));
+  else if (k == "class_order")
+    e->tune.class_order = (int)(value < 0 ? -1 : (value != 0 ? 1 : 0));
   else if (k == "aggregate")
     e->tune.aggregate = (int)(value < 0 ? 0 : (value > 2 ? 2 : value));
   else if (k == "aggregate_reemit")

@@ -110,6 +110,14 @@ constexpr int shoot_block_threads() {
 #ifndef CMI_EMIT_BEFORE_FLUSH_DEFAULT
 #define CMI_EMIT_BEFORE_FLUSH_DEFAULT true
 #endif
+/* the order of the tau classes in the sort key (KeyArgs::class_order) of
+ * hydrogen-only and of multi-ion runs: what the engine starts with */
+#ifndef CMI_CLASS_ORDER_DEFAULT
+#define CMI_CLASS_ORDER_DEFAULT 1
+#endif
+#ifndef CMI_CLASS_ORDER_FULL_DEFAULT
+#define CMI_CLASS_ORDER_FULL_DEFAULT 0
+#endif
 
 /* hardware fp64 atomic add (global_atomic_add_f64), no CAS loop */
 __device__ __forceinline__ void atomic_add_f64(double *address, double value) {
@@ -2913,7 +2921,15 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_WEIGHTS_WAVES)
  * instead of idling behind the longest flight, while the waves of a block
  * still share the bin's cells for the combining table. Inside a group the
  * packets keep their fine direction order, so neighbouring lanes are
- * neighbouring rays. tau_bits = 0 gives the plain direction order. */
+ * neighbouring rays. tau_bits = 0 gives the plain direction order.
+ *
+ * class_order: the classes run from the longest flights to the shortest
+ * inside a bin, so at every bin boundary the order would wrap from the
+ * shortest flights of one bin to the longest of the next - a bundle whose
+ * short lanes idle through a long march, once per bin. With class_order the
+ * bins of odd index hold their classes the other way round (serpentine):
+ * neighbouring bins meet at equal classes. Only a packet's place in the
+ * launch's order moves. */
 struct KeyArgs {
   ModelDev model;
   uint64_t first_packet;
@@ -2923,6 +2939,7 @@ struct KeyArgs {
   uint32_t dir_hi_bits; /* 0..dir_bits */
   uint32_t dir_bits;    /* direction bits kept in the key: <= 22 */
   uint32_t tau_bits;    /* 0..3 */
+  uint32_t class_order; /* not 0: the bins of odd index count down */
   /* multi-ion transport: a packet's range also depends on its frequency; the
    * class is then the octave of tau sigma_ref / (sigma_H + A_He sigma_He) */
   int32_t full_ions;
@@ -3040,6 +3057,16 @@ __device__ inline float approximate_opacity_cross_section(const ModelDev &m,
     sum += (t.ion == ION_H_n) ? s : (float)m.abundance[0] * s;
   }
   return sum;
+}
+
+/* the class field of a key: the packet's tau class, counted down in the
+ * coarse bins of odd index with KeyArgs::class_order (top - class is top ^
+ * class: top is all ones) */
+__device__ __forceinline__ uint32_t key_class_field(const KeyArgs &a,
+                                                    uint32_t hi,
+                                                    uint32_t tau_class) {
+  const uint32_t top = (1u << a.tau_bits) - 1u;
+  return tau_class ^ ((a.class_order != 0u && (hi & 1u) != 0u) ? top : 0u);
 }
 
 #ifndef CMI_KEY_WAVES
@@ -3175,7 +3202,8 @@ direction_key_batches(const KeyArgs &a) {
       const uint32_t lo = morton & ((1u << lo_bits) - 1u);
       a.keys[i] = ((s_src[local] & a.source_mask)
                    << (a.dir_bits + a.tau_bits)) |
-                  (hi << (a.tau_bits + lo_bits)) | (tau_class << lo_bits) | lo;
+                  (hi << (a.tau_bits + lo_bits)) |
+                  (key_class_field(a, hi, tau_class) << lo_bits) | lo;
       a.ids[i] = id;
     }
     __syncthreads(); /* the batch's arrays are rewritten by the next one */
@@ -3237,7 +3265,8 @@ __global__ void __launch_bounds__(CMI_BLOCK, 5)
     const uint32_t hi = morton >> lo_bits;
     const uint32_t lo = morton & ((1u << lo_bits) - 1u);
     a.keys[i] = ((src & a.source_mask) << (a.dir_bits + a.tau_bits)) |
-                (hi << (a.tau_bits + lo_bits)) | (tau_class << lo_bits) | lo;
+                (hi << (a.tau_bits + lo_bits)) |
+                (key_class_field(a, hi, tau_class) << lo_bits) | lo;
     a.ids[i] = (uint32_t)id;
   }
 }

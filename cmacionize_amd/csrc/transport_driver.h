@@ -646,6 +646,12 @@ static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
   k.seed = a.seed;
   k.iteration = a.iteration;
   k.tau_bits = p.tau_bits;
+  /* (-1: the default of the branch that sets the class) */
+  k.class_order =
+      e->tune.class_order >= 0
+          ? (uint32_t)e->tune.class_order
+          : (e->full_ions ? CMI_CLASS_ORDER_FULL_DEFAULT
+                          : CMI_CLASS_ORDER_DEFAULT);
   k.full_ions = e->full_ions ? 1 : 0;
   k.sigma_ref = p.sigma_ref;
   k.source_mask = (1u << p.source_bits) - 1u;

@@ -534,6 +534,14 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *                           their flights at about the same step (0 = plain
  *                           direction order, -1 = chosen from the number of
  *                           packets per launch)
+ *   "class_order" (-1)      with tau classes: 1 = the coarse direction bins of
+ *                           odd index hold their classes the other way round,
+ *                           so that neighbouring bins meet at equal classes
+ *                           and no bundle mixes one bin's shortest flights
+ *                           with the next one's longest; 0 = every bin from
+ *                           the longest flights to the shortest; -1 = the
+ *                           default of the run's kind (hydrogen-only: 1,
+ *                           multi-ion: 0)
  *   "sort_dir_bits" (-1)    direction bits of the sort key, 2 .. 22 (an equal-area
  *                           2048 x 2048 lattice, Morton order); -1 = auto: 22,
  *                           or one or two fewer where that saves the radix

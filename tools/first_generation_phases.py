@@ -64,8 +64,13 @@ def main():
         ms = float(np.median([m for m, _ in plain]))
         steps = plain[0][1]
         points.append((steps, ms))
-        print("ncell %d: first generation %.2f ms (%s), %.1f steps/packet"
-              % (ncell, ms, " ".join("%.2f" % m for m, _ in plain), steps),
+        # (the counters are those of the last launch: one first generation)
+        trips = eng.get_wave_steps()
+        print("ncell %d: first generation %.2f ms (%s), %.1f steps/packet, "
+              "%.2f lanes stepping per wave iteration, %.4f wave iterations "
+              "per packet"
+              % (ncell, ms, " ".join("%.2f" % m for m, _ in plain), steps,
+                 steps * npk / max(trips, 1), trips / npk),
               flush=True)
         if ncell != args.ncell[-1]:
             eng.close()
