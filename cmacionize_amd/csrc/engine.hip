@@ -3569,1726 +3569,9 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
   return CMI_GPU_OK;
 }
 
-/* --------------------------------------------------- line images -- */
-extern "C++" {
-namespace {
-/* device buffers of one render call, freed however it ends */
-struct LineImageBuffers {
-  double *records = nullptr, *samples = nullptr, *image = nullptr,
-         *fields = nullptr, *extinction = nullptr;
-  ~LineImageBuffers() {
-    (void)hipFree(records);
-    (void)hipFree(samples);
-    (void)hipFree(image);
-    (void)hipFree(fields);
-    (void)hipFree(extinction);
-  }
-};
-
-int line_image_view(const cmi_gpu_engine *e, const char *what, double theta,
-                    double phi, LineViewDev &v) {
-  const GridDev &g = e->grid;
-  if (g.decomposed)
-    return fail(CMI_GPU_ESTATE, "%s: not available on a block of a decomposed "
-                "grid (an image of one block is not an image)", what);
-  if (g.periodic[0] || g.periodic[1] || g.periodic[2])
-    return fail(CMI_GPU_EINVAL, "%s: periodic boxes are not supported (a line "
-                "of sight through a periodic box has no end)", what);
-  if (!std::isfinite(theta) || !std::isfinite(phi))
-    return fail(CMI_GPU_EINVAL, "%s: view angles must be finite", what);
-  const double st = std::sin(theta), ct = std::cos(theta);
-  const double sp = std::sin(phi), cp = std::cos(phi);
-  v.n[0] = st * cp;
-  v.n[1] = st * sp;
-  v.n[2] = ct;
-  v.ex[0] = -sp;
-  v.ex[1] = cp;
-  v.ex[2] = 0.;
-  v.ey[0] = -ct * cp;
-  v.ey[1] = -ct * sp;
-  v.ey[2] = st;
-  for (int a = 0; a < 3; ++a)
-    v.inv_n[a] = 1. / v.n[a];
-  v.nx = v.ny = v.s = 1;
-  v.pad = 0;
-  v.img_anchor[0] = v.img_anchor[1] = 0.;
-  v.img_sides[0] = v.img_sides[1] = 1.;
-  return CMI_GPU_OK;
-}
-
-int line_image_geometry(const cmi_gpu_engine *e, const char *what,
-                        double theta, double phi, int32_t nx, int32_t ny,
-                        const double *anchor, const double *sides,
-                        int32_t supersample, LineViewDev &v) {
-  if (!anchor || !sides)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nx <= 0 || ny <= 0 || (int64_t)nx * ny > (1ll << 28))
-    return fail(CMI_GPU_EINVAL, "%s: the image must have between 1 and 2^28 "
-                "pixels (%d x %d asked for)", what, (int)nx, (int)ny);
-  if (supersample < 1 || supersample > CMI_LINE_IMAGE_MAX_SUPERSAMPLE)
-    return fail(CMI_GPU_EINVAL, "%s: supersampling must be 1..%d (%d asked "
-                "for)", what, CMI_LINE_IMAGE_MAX_SUPERSAMPLE, (int)supersample);
-  /* the sample grid is indexed with 32-bit integers */
-  if ((int64_t)nx * supersample > (1ll << 30) ||
-      (int64_t)ny * supersample > (1ll << 30))
-    return fail(CMI_GPU_EINVAL, "%s: %d x %d pixels at supersampling %d: more "
-                "than 2^30 samples along an axis", what, (int)nx, (int)ny,
-                (int)supersample);
-  if (!(sides[0] > 0.) || !(sides[1] > 0.) || !std::isfinite(sides[0]) ||
-      !std::isfinite(sides[1]) || !std::isfinite(anchor[0]) ||
-      !std::isfinite(anchor[1]))
-    return fail(CMI_GPU_EINVAL, "%s: the image sides must be positive", what);
-  CMI_TRY(line_image_view(e, what, theta, phi, v));
-  v.nx = nx;
-  v.ny = ny;
-  v.s = supersample;
-  for (int a = 0; a < 2; ++a) {
-    v.img_anchor[a] = anchor[a];
-    v.img_sides[a] = sides[a];
-  }
-  return CMI_GPU_OK;
-}
-
-/* f(std::integral_constant<int, ND>) for the record of nd doubles: 2, 4, 6
- * or 8 (line_image_record_doubles) */
-template <class F> void line_image_for_record(int nd, F &&f) {
-  switch (nd) {
-  case 2: f(std::integral_constant<int, 2>()); break;
-  case 4: f(std::integral_constant<int, 4>()); break;
-  case 6: f(std::integral_constant<int, 6>()); break;
-  default: f(std::integral_constant<int, 8>()); break;
-  }
-}
-
-template <int ND>
-void line_image_launch_march(cmi_gpu_engine *e, const LineMarchArgs &a) {
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const int64_t NY = (int64_t)a.view.ny * a.view.s;
-  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
-  line_image_march_kernel<ND>
-      <<<(unsigned)(tiles_x * tiles_y), 256, 0, e->stream>>>(a);
-}
-
-/* images [nl][nx * ny] of the records [ncell][nd] into b.image (device) */
-int line_image_march(cmi_gpu_engine *e, const LineViewDev &v, int nd, int nl,
-                     LineImageBuffers &b) {
-  const int64_t npixel = (int64_t)v.nx * v.ny;
-  const int64_t NY = (int64_t)v.ny * v.s;
-  /* pixel rows per launch */
-  const int64_t rows = std::max<int64_t>(
-      1, std::min<int64_t>(v.nx, CMI_LINE_IMAGE_LAUNCH_SAMPLES / (NY * v.s)));
-  const int64_t chunk_samples = rows * v.s * NY;
-  if (v.s > 1 && !b.samples)
-    HIP_TRY(hipMalloc(&b.samples, sizeof(double) * (size_t)chunk_samples *
-                                      CMI_LINE_IMAGE_BATCH));
-  for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
-    const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
-    LineMarchArgs a;
-    a.grid = e->grid;
-    a.view = v;
-    a.records = b.records;
-    a.sx0 = (int32_t)(ix0 * v.s);
-    a.sx1 = (int32_t)(ix1 * v.s);
-    a.nlines = nl;
-    if (v.s > 1) {
-      a.out = b.samples;
-      a.line_stride = chunk_samples;
-    } else {
-      a.out = b.image + ix0 * v.ny;
-      a.line_stride = npixel;
-    }
-    line_image_for_record(nd, [&](auto width) {
-      line_image_launch_march<decltype(width)::value>(e, a);
-    });
-    HIP_TRY(hipGetLastError());
-    if (v.s > 1) {
-      const int64_t work = (ix1 - ix0) * v.ny * nl;
-      line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
-                                 e->stream>>>(
-          b.samples, chunk_samples, nl, (int32_t)ix0, (int32_t)ix1, v.ny, v.s,
-          npixel, b.image);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return CMI_GPU_OK;
-}
-
-/* doubles of the record of a batch of nl lines: {k, s[nl]} padded to 16 B */
-inline int line_image_record_doubles(int nl) { return (nl + 2) & ~1; }
-} // namespace
-} // extern "C++"
-
-int cmi_gpu_render_line_images(cmi_gpu_engine *e, int32_t nlines,
-                               const int32_t *lines, double theta, double phi,
-                               int32_t nx, int32_t ny, const double *anchor,
-                               const double *sides, int32_t supersample,
-                               double dust_cross_section, double *images) {
-  static const char *what = "render_line_images";
-  if (!e || !lines || !images)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
-    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
-                (int)nlines, CMI_NEMISSIONLINE);
-  for (int32_t l = 0; l < nlines; ++l)
-    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
-      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
-                  (int)lines[l]);
-  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
-    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
-                what);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  if (!e->have_cells)
-    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t npixel = (int64_t)nx * ny;
-  LineImageBuffers b;
-  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records, sizeof(double) * (size_t)e->ncell *
-                                    line_image_record_doubles(nb)));
-  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel * nb));
-  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
-    const int nd = line_image_record_doubles(nl);
-    LineRecordArgs r;
-    r.model = e->model;
-    r.cells = e->cells;
-    r.ncell = e->ncell;
-    r.nlines = nl;
-    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l)
-      r.lines[l] = l < nl ? lines[first + l] : 0;
-    r.dust_cross_section = dust_cross_section;
-    r.records = b.records;
-    const int blocks = grid_blocks(e, e->ncell, 8);
-    line_image_for_record(nd, [&](auto width) {
-      line_record_kernel<decltype(width)::value>
-          <<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
-    });
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(line_image_march(e, v, nd, nl, b));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(images + (size_t)first * npixel, b.image,
-                      sizeof(double) * (size_t)npixel * nl,
-                      hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_field_images(cmi_gpu_engine *e, int32_t nfields,
-                                const double *fields, double theta, double phi,
-                                int32_t nx, int32_t ny, const double *anchor,
-                                const double *sides, int32_t supersample,
-                                const double *extinction, double *images) {
-  static const char *what = "render_field_images";
-  if (!e || !fields || !images)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nfields < 1 || nfields > 1024)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
-                what, (int)nfields);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  HIP_TRY(hipSetDevice(e->device));
-  const int64_t npixel = (int64_t)nx * ny;
-  const size_t ncell = (size_t)e->ncell;
-  LineImageBuffers b;
-  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records,
-                    sizeof(double) * ncell * line_image_record_doubles(nb)));
-  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel * nb));
-  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
-  if (extinction) {
-    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
-    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
-                      hipMemcpyHostToDevice));
-  }
-  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
-    const int nd = line_image_record_doubles(nl);
-    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
-    line_image_for_record(nd, [&](auto width) {
-      field_record_kernel<decltype(width)::value><<<blocks, 256, 0, e->stream>>>(
-          b.fields, b.extinction, e->ncell, nl, b.records);
-    });
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(line_image_march(e, v, nd, nl, b));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(images + (size_t)first * npixel, b.image,
-                      sizeof(double) * (size_t)npixel * nl,
-                      hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_line_image_probe(cmi_gpu_engine *e, double theta, double phi,
-                             int64_t n, const double *xy, int32_t max_cells,
-                             double *out) {
-  static const char *what = "line_image_probe";
-  if (!e || n < 0 || n > (1 << 24) || max_cells < 0 || (n && (!xy || !out)))
-    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
-  LineViewDev v;
-  CMI_TRY(line_image_view(e, what, theta, phi, v));
-  for (int64_t k = 0; k < 2 * n; ++k)
-    if (!std::isfinite(xy[k]))
-      return fail(CMI_GPU_EINVAL, "%s: image coordinate %lld of ray %lld is "
-                  "not finite", what, (long long)(k % 2), (long long)(k / 2));
-  if (n == 0)
-    return CMI_GPU_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  double *dxy = nullptr, *drows = nullptr;
-  const size_t width = 3 + 2 * (size_t)max_cells;
-  hipError_t err = hipMalloc(&dxy, sizeof(double) * 2 * (size_t)n);
-  if (err == hipSuccess)
-    err = hipMalloc(&drows, sizeof(double) * width * (size_t)n);
-  if (err == hipSuccess)
-    err = hipMemcpy(dxy, xy, sizeof(double) * 2 * (size_t)n,
-                    hipMemcpyHostToDevice);
-  if (err == hipSuccess)
-    err = hipMemsetAsync(drows, 0, sizeof(double) * width * (size_t)n,
-                         e->stream);
-  if (err == hipSuccess) {
-    line_image_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
-        e->grid, v, dxy, n, max_cells, drows);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess)
-    err = hipStreamSynchronize(e->stream);
-  if (err == hipSuccess)
-    err = hipMemcpy(out, drows, sizeof(double) * width * (size_t)n,
-                    hipMemcpyDeviceToHost);
-  (void)hipFree(dxy);
-  (void)hipFree(drows);
-  HIP_TRY(err);
-  return CMI_GPU_OK;
-}
-
-/* ------------------------------------------------ spectral line cubes -- */
-extern "C++" {
-namespace {
-/* device buffers of one cube call, freed however it ends */
-struct LineCubeBuffers {
-  double *records = nullptr, *samples = nullptr, *cube = nullptr,
-         *fields = nullptr, *widths = nullptr, *extinction = nullptr,
-         *velocity = nullptr;
-  ~LineCubeBuffers() {
-    (void)hipFree(records);
-    (void)hipFree(samples);
-    (void)hipFree(cube);
-    (void)hipFree(fields);
-    (void)hipFree(widths);
-    (void)hipFree(extinction);
-    (void)hipFree(velocity);
-  }
-};
-
-/* the velocity axis of a cube call */
-struct LineCubeAxis {
-  int32_t nchan;
-  double vmin, dv;
-};
-
-int line_cube_axis(const char *what, int32_t nplanes, int32_t nx, int32_t ny,
-                   int32_t nchan, double vmin, double vmax,
-                   LineCubeAxis &axis) {
-  if (nchan < 1)
-    return fail(CMI_GPU_EINVAL, "%s: at least one velocity channel (%d asked "
-                "for)", what, (int)nchan);
-  if (!std::isfinite(vmin) || !std::isfinite(vmax) || !(vmax > vmin) ||
-      !std::isfinite(vmax - vmin))
-    return fail(CMI_GPU_EINVAL, "%s: the velocity range must be finite with "
-                "vmax > vmin", what);
-  /* (nx ny <= 2^28 has been checked, so the products below cannot overflow) */
-  if ((int64_t)nplanes * nchan > (1ll << 28) ||
-      (int64_t)nplanes * nchan * ((int64_t)nx * ny) > (1ll << 28))
-    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %d x %d pixels: a "
-                "cube has at most 2^28 values", what, (int)nplanes, (int)nchan,
-                (int)nx, (int)ny);
-  axis.nchan = nchan;
-  axis.vmin = vmin;
-  axis.dv = (vmax - vmin) / nchan;
-  return CMI_GPU_OK;
-}
-
-/* refuses a device array of n velocities of which one is not finite */
-int line_cube_check_velocities(cmi_gpu_engine *e, const char *what,
-                               const double *velocity, int64_t n) {
-  unsigned int *ninvalid = nullptr;
-  HIP_TRY(hipMalloc(&ninvalid, sizeof(unsigned int)));
-  unsigned int bad = 0;
-  hipError_t err = hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream);
-  if (err == hipSuccess) {
-    cell_velocity_check_kernel<<<grid_blocks(e, n, 8), 256, 0, e->stream>>>(
-        velocity, n, ninvalid);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess)
-    err = hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
-                         e->stream);
-  if (err == hipSuccess)
-    err = hipStreamSynchronize(e->stream);
-  (void)hipFree(ninvalid);
-  HIP_TRY(err);
-  if (bad)
-    return fail(CMI_GPU_EINVAL, "%s: %u velocity component(s) are not finite",
-                what, bad);
-  return CMI_GPU_OK;
-}
-
-/* the cube [nl][nchan][nx * ny] of the records [ncell][2 + 2 nl] into b.cube
- * (device): per chunk of pixel rows and per block of CB channels one march
- * launch for the nl lines */
-int line_cube_march(cmi_gpu_engine *e, const LineViewDev &v, int nl,
-                    const LineCubeAxis &axis, LineCubeBuffers &b) {
-  constexpr int CB = CMI_LINE_CUBE_CB;
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const int64_t npixel = (int64_t)v.nx * v.ny;
-  const int64_t NY = (int64_t)v.ny * v.s;
-  /* pixel rows per launch: the sample buffer holds CB channels of them */
-  const int64_t rows = std::max<int64_t>(
-      1, std::min<int64_t>(v.nx, (CMI_LINE_IMAGE_LAUNCH_SAMPLES / CB) /
-                                     (NY * v.s)));
-  const int64_t chunk_samples = rows * v.s * NY;
-  if (v.s > 1 && !b.samples)
-    HIP_TRY(hipMalloc(&b.samples, sizeof(double) * (size_t)chunk_samples * CB *
-                                      CMI_LINE_IMAGE_BATCH));
-  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
-    const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
-    for (int32_t c0 = 0; c0 < axis.nchan; c0 += CB) {
-      LineCubeMarchArgs a;
-      a.grid = e->grid;
-      a.view = v;
-      a.records = b.records;
-      a.nd = 2 + 2 * nl;
-      a.sx0 = (int32_t)(ix0 * v.s);
-      a.sx1 = (int32_t)(ix1 * v.s);
-      a.c0 = c0;
-      a.nc = std::min<int32_t>(CB, axis.nchan - c0);
-      a.vmin = axis.vmin;
-      a.dv = axis.dv;
-      if (v.s > 1) {
-        a.out = b.samples;
-        a.line_stride = CB * chunk_samples;
-        a.channel_stride = chunk_samples;
-      } else {
-        a.out = b.cube + c0 * npixel + ix0 * v.ny;
-        a.line_stride = axis.nchan * npixel;
-        a.channel_stride = npixel;
-      }
-      const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
-      line_cube_march_kernel<CB>
-          <<<dim3((unsigned)(tiles_x * tiles_y), (unsigned)nl), 256, 0,
-             e->stream>>>(a);
-      HIP_TRY(hipGetLastError());
-      if (v.s > 1) {
-        /* the images' reduction, a line's channels in the place of lines */
-        const int64_t work = (ix1 - ix0) * v.ny * a.nc;
-        for (int l = 0; l < nl; ++l) {
-          line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
-                                     e->stream>>>(
-              b.samples + l * a.line_stride, chunk_samples, a.nc, (int32_t)ix0,
-              (int32_t)ix1, v.ny, v.s, npixel,
-              b.cube + ((int64_t)l * axis.nchan + c0) * npixel);
-          HIP_TRY(hipGetLastError());
-        }
-      }
-    }
-  }
-  return CMI_GPU_OK;
-}
-} // namespace
-} // extern "C++"
-
-double cmi_gpu_emission_line_atomic_weight(int32_t line) {
-  return (line < 0 || line >= CMI_NEMISSIONLINE)
-             ? 0.
-             : cmi_emission_atomic_weight[line];
-}
-
-int cmi_gpu_set_cell_velocities(cmi_gpu_engine *e, const double *velocities) {
-  static const char *what = "set_cell_velocities";
-  if (!e)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  HIP_TRY(hipSetDevice(e->device));
-  if (!velocities) {
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(e->cell_velocities);
-    e->cell_velocities = nullptr;
-    dust_cube_mark_stale(e, "the cell velocities were replaced");
-    return CMI_GPU_OK;
-  }
-  const size_t n = 3 * (size_t)e->ncell;
-  double *fresh = nullptr;
-  HIP_TRY(hipMalloc(&fresh, sizeof(double) * n));
-  hipError_t err =
-      hipMemcpy(fresh, velocities, sizeof(double) * n, hipMemcpyHostToDevice);
-  int rc = CMI_GPU_OK;
-  if (err != hipSuccess)
-    rc = fail(CMI_GPU_EDEVICE, "%s: upload failed: %s", what,
-              hipGetErrorString(err));
-  else
-    rc = line_cube_check_velocities(e, what, fresh, (int64_t)n);
-  if (rc) {
-    /* the previous state is kept */
-    (void)hipFree(fresh);
-    return rc;
-  }
-  /* a cube launch may still be enqueued and reads the old array (with cube
-   * mode off nothing enqueued does, and the call is what it was) */
-  if (e->dust_cube.nchan) {
-    const hipError_t busy = hipStreamSynchronize(e->stream);
-    if (busy != hipSuccess) {
-      (void)hipFree(fresh);
-      HIP_TRY(busy);
-    }
-  }
-  (void)hipFree(e->cell_velocities);
-  e->cell_velocities = fresh;
-  dust_cube_mark_stale(e, "the cell velocities were replaced");
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_line_cube(cmi_gpu_engine *e, int32_t nlines,
-                             const int32_t *lines, double theta, double phi,
-                             int32_t nx, int32_t ny, const double *anchor,
-                             const double *sides, int32_t supersample,
-                             double dust_cross_section, int32_t nchan,
-                             double vmin, double vmax, double sigma_turb,
-                             double *cube) {
-  static const char *what = "render_line_cube";
-  if (!e || !lines || !cube)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
-    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
-                (int)nlines, CMI_NEMISSIONLINE);
-  for (int32_t l = 0; l < nlines; ++l) {
-    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
-      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
-                  (int)lines[l]);
-    if (cmi_emission_atomic_weight[lines[l]] == 0.)
-      return fail(CMI_GPU_EINVAL, "%s: entry %d is not the line of one ion: "
-                  "it has no line profile", what, (int)lines[l]);
-  }
-  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
-    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
-                what);
-  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
-    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
-                "be >= 0 and finite", what);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  LineCubeAxis axis;
-  CMI_TRY(line_cube_axis(what, nlines, nx, ny, nchan, vmin, vmax, axis));
-  if (!e->have_cells)
-    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t nvalue = (size_t)nx * ny * nchan; /* of one line */
-  LineCubeBuffers b;
-  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records,
-                    sizeof(double) * (size_t)e->ncell * (2 + 2 * nb)));
-  HIP_TRY(hipMalloc(&b.cube, sizeof(double) * nvalue * nb));
-  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
-    LineCubeRecordArgs r;
-    r.model = e->model;
-    r.cells = e->cells;
-    r.ncell = e->ncell;
-    r.nlines = nl;
-    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l) {
-      r.lines[l] = l < nl ? lines[first + l] : 0;
-      r.weight[l] = l < nl ? cmi_emission_atomic_weight[lines[first + l]] : 1.;
-    }
-    r.dust_cross_section = dust_cross_section;
-    r.sigma_turb = sigma_turb;
-    for (int a = 0; a < 3; ++a)
-      r.n[a] = v.n[a];
-    r.velocity = e->cell_velocities;
-    r.records = b.records;
-    line_cube_record_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
-                              e->stream>>>(r);
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(line_cube_march(e, v, nl, axis, b));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(cube + (size_t)first * nvalue, b.cube,
-                      sizeof(double) * nvalue * nl, hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_field_cube(cmi_gpu_engine *e, int32_t nfields,
-                              const double *fields, const double *extinction,
-                              const double *velocity, const double *widths,
-                              double theta, double phi, int32_t nx, int32_t ny,
-                              const double *anchor, const double *sides,
-                              int32_t supersample, int32_t nchan, double vmin,
-                              double vmax, double *cube) {
-  static const char *what = "render_field_cube";
-  if (!e || !fields || !widths || !cube)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nfields < 1 || nfields > 1024)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
-                what, (int)nfields);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  LineCubeAxis axis;
-  CMI_TRY(line_cube_axis(what, nfields, nx, ny, nchan, vmin, vmax, axis));
-  const size_t ncell = (size_t)e->ncell;
-  for (size_t i = 0; i < ncell * (size_t)nfields; ++i)
-    if (!(widths[i] >= 0.) || !std::isfinite(widths[i]))
-      return fail(CMI_GPU_EINVAL, "%s: the width of field %lld in cell %lld "
-                  "is negative or not finite", what, (long long)(i / ncell),
-                  (long long)(i % ncell));
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t nvalue = (size_t)nx * ny * nchan; /* of one field */
-  LineCubeBuffers b;
-  if (velocity) {
-    HIP_TRY(hipMalloc(&b.velocity, sizeof(double) * 3 * ncell));
-    HIP_TRY(hipMemcpy(b.velocity, velocity, sizeof(double) * 3 * ncell,
-                      hipMemcpyHostToDevice));
-    CMI_TRY(line_cube_check_velocities(e, what, b.velocity,
-                                       3 * (int64_t)ncell));
-  }
-  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records, sizeof(double) * ncell * (2 + 2 * nb)));
-  HIP_TRY(hipMalloc(&b.cube, sizeof(double) * nvalue * nb));
-  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
-  HIP_TRY(hipMalloc(&b.widths, sizeof(double) * ncell * nb));
-  if (extinction) {
-    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
-    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
-                      hipMemcpyHostToDevice));
-  }
-  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
-    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.widths, widths + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    field_cube_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
-                               e->stream>>>(
-        b.fields, b.widths, b.extinction, b.velocity, v.n[0], v.n[1], v.n[2],
-        e->ncell, nl, b.records);
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(line_cube_march(e, v, nl, axis, b));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(cube + (size_t)first * nvalue, b.cube,
-                      sizeof(double) * nvalue * nl, hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-/* ------------------------------------------------------- sky maps -- */
-extern "C++" {
-namespace {
-/* device buffers of one sky call, freed however it ends */
-struct SkyBuffers {
-  double *records = nullptr, *directions = nullptr, *out = nullptr,
-         *fields = nullptr, *extinction = nullptr;
-  ~SkyBuffers() {
-    (void)hipFree(records);
-    (void)hipFree(directions);
-    (void)hipFree(out);
-    (void)hipFree(fields);
-    (void)hipFree(extinction);
-  }
-};
-
-/* what every sky call asks of the engine and of its rays before a launch */
-int sky_check(const cmi_gpu_engine *e, const char *what, const double *origin,
-              int64_t nrays, int64_t max_rays, const double *directions) {
-  const GridDev &g = e->grid;
-  if (g.decomposed)
-    return fail(CMI_GPU_ESTATE, "%s: not available on a block of a decomposed "
-                "grid (the sky of one block is not a sky)", what);
-  if (g.periodic[0] || g.periodic[1] || g.periodic[2])
-    return fail(CMI_GPU_EINVAL, "%s: periodic boxes are not supported (a line "
-                "of sight through a periodic box has no end)", what);
-  if (nrays <= 0 || nrays > max_rays)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and %lld rays (%lld asked for)",
-                what, (long long)max_rays, (long long)nrays);
-  if (!origin || !directions)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  for (int a = 0; a < 3; ++a)
-    if (!std::isfinite(origin[a]))
-      return fail(CMI_GPU_EINVAL, "%s: component %d of the origin is not "
-                  "finite", what, a);
-  for (int64_t r = 0; r < nrays; ++r) {
-    const double *d = directions + 3 * r;
-    if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]))
-      return fail(CMI_GPU_EINVAL, "%s: the direction of ray %lld is not "
-                  "finite", what, (long long)r);
-    const double norm2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-    if (!(std::fabs(norm2 - 1.) <= 1.e-9))
-      return fail(CMI_GPU_EINVAL, "%s: the direction of ray %lld is not a "
-                  "unit vector (|d|^2 = %.17g)", what, (long long)r, norm2);
-  }
-  return CMI_GPU_OK;
-}
-
-/* out[l * nrays + r] (host), l < nl, of the records [ncell][nd] in b.records:
- * launches of at most CMI_SKY_LAUNCH_RAYS rays, directions up, results down */
-int sky_march(cmi_gpu_engine *e, const double *origin, int64_t nrays,
-              const double *directions, int nd, int nl, SkyBuffers &b,
-              double *out) {
-  const int64_t chunk = std::min<int64_t>(nrays, CMI_SKY_LAUNCH_RAYS);
-  if (!b.directions)
-    HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
-  if (!b.out)
-    HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk *
-                                  CMI_LINE_IMAGE_BATCH));
-  for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
-    const int64_t n = std::min<int64_t>(chunk, nrays - r0);
-    HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
-                      sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    SkyMarchArgs a;
-    a.grid = e->grid;
-    for (int k = 0; k < 3; ++k)
-      a.origin[k] = origin[k];
-    a.directions = b.directions;
-    a.records = b.records;
-    a.nrays = n;
-    a.nlines = nl;
-    a.pad = 0;
-    a.line_stride = chunk;
-    a.out = b.out;
-    line_image_for_record(nd, [&](auto width) {
-      sky_march_kernel<decltype(width)::value>
-          <<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(a);
-    });
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (int l = 0; l < nl; ++l)
-      HIP_TRY(hipMemcpy(out + (size_t)l * nrays + r0, b.out + (size_t)l * chunk,
-                        sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-/* rows of a 3 x 3 frame orthonormal to 1e-9? */
-bool sky_frame_is_orthonormal(const double *frame) {
-  for (int i = 0; i < 3; ++i)
-    for (int j = i; j < 3; ++j) {
-      double dot = 0.;
-      for (int a = 0; a < 3; ++a)
-        dot += frame[3 * i + a] * frame[3 * j + a];
-      if (!(std::fabs(dot - (i == j ? 1. : 0.)) <= 1.e-9))
-        return false;
-    }
-  return true;
-}
-
-int sky_map_check(const char *what, const double *frame, double lon_min,
-                  double lon_max, double lat_min, double lat_max,
-                  int32_t nlon, int32_t nlat) {
-  if (!frame)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nlon <= 0 || nlat <= 0 || (int64_t)nlon * nlat > (1ll << 28))
-    return fail(CMI_GPU_EINVAL, "%s: the map must have between 1 and 2^28 "
-                "pixels (%d x %d asked for)", what, (int)nlon, (int)nlat);
-  if (!std::isfinite(lon_min) || !std::isfinite(lon_max) ||
-      !(lon_min < lon_max))
-    return fail(CMI_GPU_EINVAL, "%s: the longitude range must be finite and "
-                "increasing", what);
-  if (!(lat_min < lat_max) || !(lat_min >= -0.5 * M_PI) ||
-      !(lat_max <= 0.5 * M_PI))
-    return fail(CMI_GPU_EINVAL, "%s: the latitude range must be increasing "
-                "and within [-pi / 2, pi / 2]", what);
-  if (!sky_frame_is_orthonormal(frame))
-    return fail(CMI_GPU_EINVAL, "%s: the frame is not orthonormal to 1e-9",
-                what);
-  return CMI_GPU_OK;
-}
-
-/* direction of the centre of pixel (i, j) */
-void sky_map_direction(const double *frame, double lon_min, double lon_max,
-                       double lat_min, double lat_max, int32_t nlon,
-                       int32_t nlat, int32_t i, int32_t j, double *d) {
-  const double l = lon_min + (lon_max - lon_min) * (i + 0.5) / nlon;
-  const double b = lat_min + (lat_max - lat_min) * (j + 0.5) / nlat;
-  const double cb = std::cos(b), sb = std::sin(b);
-  const double c1 = cb * std::cos(l), c2 = cb * std::sin(l);
-  for (int a = 0; a < 3; ++a)
-    d[a] = c1 * frame[a] + c2 * frame[3 + a] + sb * frame[6 + a];
-}
-} // namespace
-} // extern "C++"
-
-int cmi_gpu_render_line_sky(cmi_gpu_engine *e, int32_t nlines,
-                            const int32_t *lines, const double *origin,
-                            int64_t nrays, const double *directions,
-                            double dust_cross_section, double *out) {
-  static const char *what = "render_line_sky";
-  if (!e || !lines || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
-    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
-                (int)nlines, CMI_NEMISSIONLINE);
-  for (int32_t l = 0; l < nlines; ++l)
-    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
-      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
-                  (int)lines[l]);
-  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
-    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
-                what);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  if (!e->have_cells)
-    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
-  HIP_TRY(hipSetDevice(e->device));
-  SkyBuffers b;
-  const int nb = std::min<int>(nlines, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records, sizeof(double) * (size_t)e->ncell *
-                                    line_image_record_doubles(nb)));
-  for (int32_t first = 0; first < nlines; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nlines - first, CMI_LINE_IMAGE_BATCH);
-    const int nd = line_image_record_doubles(nl);
-    LineRecordArgs r;
-    r.model = e->model;
-    r.cells = e->cells;
-    r.ncell = e->ncell;
-    r.nlines = nl;
-    for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l)
-      r.lines[l] = l < nl ? lines[first + l] : 0;
-    r.dust_cross_section = dust_cross_section;
-    r.records = b.records;
-    const int blocks = grid_blocks(e, e->ncell, 8);
-    line_image_for_record(nd, [&](auto width) {
-      line_record_kernel<decltype(width)::value>
-          <<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
-    });
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(sky_march(e, origin, nrays, directions, nd, nl, b,
-                      out + (size_t)first * nrays));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_field_sky(cmi_gpu_engine *e, int32_t nfields,
-                             const double *fields, const double *origin,
-                             int64_t nrays, const double *directions,
-                             const double *extinction, double *out) {
-  static const char *what = "render_field_sky";
-  if (!e || !fields || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nfields < 1 || nfields > 1024)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
-                what, (int)nfields);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t ncell = (size_t)e->ncell;
-  SkyBuffers b;
-  const int nb = std::min<int>(nfields, CMI_LINE_IMAGE_BATCH);
-  HIP_TRY(hipMalloc(&b.records,
-                    sizeof(double) * ncell * line_image_record_doubles(nb)));
-  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
-  if (extinction) {
-    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
-    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
-                      hipMemcpyHostToDevice));
-  }
-  for (int32_t first = 0; first < nfields; first += CMI_LINE_IMAGE_BATCH) {
-    const int nl = std::min<int>(nfields - first, CMI_LINE_IMAGE_BATCH);
-    const int nd = line_image_record_doubles(nl);
-    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
-    line_image_for_record(nd, [&](auto width) {
-      field_record_kernel<decltype(width)::value><<<blocks, 256, 0, e->stream>>>(
-          b.fields, b.extinction, e->ncell, nl, b.records);
-    });
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(sky_march(e, origin, nrays, directions, nd, nl, b,
-                      out + (size_t)first * nrays));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_sky_probe(cmi_gpu_engine *e, const double *origin, int64_t n,
-                      const double *directions, int32_t max_cells,
-                      double *out) {
-  static const char *what = "sky_probe";
-  if (!e || !out || max_cells < 0)
-    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
-  CMI_TRY(sky_check(e, what, origin, n, 1ll << 24, directions));
-  HIP_TRY(hipSetDevice(e->device));
-  double *ddir = nullptr, *drows = nullptr;
-  const size_t width = 3 + 2 * (size_t)max_cells;
-  hipError_t err = hipMalloc(&ddir, sizeof(double) * 3 * (size_t)n);
-  if (err == hipSuccess)
-    err = hipMalloc(&drows, sizeof(double) * width * (size_t)n);
-  if (err == hipSuccess)
-    err = hipMemcpy(ddir, directions, sizeof(double) * 3 * (size_t)n,
-                    hipMemcpyHostToDevice);
-  if (err == hipSuccess)
-    err = hipMemsetAsync(drows, 0, sizeof(double) * width * (size_t)n,
-                         e->stream);
-  if (err == hipSuccess) {
-    sky_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
-        e->grid, origin[0], origin[1], origin[2], ddir, n, max_cells, drows);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess)
-    err = hipStreamSynchronize(e->stream);
-  if (err == hipSuccess)
-    err = hipMemcpy(out, drows, sizeof(double) * width * (size_t)n,
-                    hipMemcpyDeviceToHost);
-  (void)hipFree(ddir);
-  (void)hipFree(drows);
-  HIP_TRY(err);
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_sky_map_directions(const double *frame, double lon_min,
-                               double lon_max, double lat_min, double lat_max,
-                               int32_t nlon, int32_t nlat, double *directions,
-                               double *solid_angles) {
-  static const char *what = "sky_map_directions";
-  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                        nlat));
-  const double dl = (lon_max - lon_min) / nlon;
-  for (int32_t i = 0; i < nlon; ++i)
-    for (int32_t j = 0; j < nlat; ++j) {
-      const size_t p = (size_t)i * nlat + j;
-      if (directions)
-        sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                          nlat, i, j, directions + 3 * p);
-      if (solid_angles) {
-        const double b_lo = lat_min + (lat_max - lat_min) * j / nlat;
-        const double b_hi = lat_min + (lat_max - lat_min) * (j + 1) / nlat;
-        solid_angles[p] = dl * (std::sin(b_hi) - std::sin(b_lo));
-      }
-    }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_line_sky_map(cmi_gpu_engine *e, int32_t nlines,
-                                const int32_t *lines, const double *origin,
-                                const double *frame, double lon_min,
-                                double lon_max, double lat_min, double lat_max,
-                                int32_t nlon, int32_t nlat,
-                                double dust_cross_section, double *maps) {
-  static const char *what = "render_line_sky_map";
-  if (!e || !lines || !maps || nlines < 1)
-    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
-  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                        nlat));
-  /* the rays in 8 x 8 tiles of the map, so that a wave's 64 rays are
-   * neighbours on the sky; pixel[k] is the pixel of ray k */
-  const size_t npixel = (size_t)nlon * nlat;
-  std::vector<int64_t> pixel;
-  std::vector<double> directions, rays;
-  try {
-    pixel.reserve(npixel);
-    directions.resize(3 * npixel);
-    rays.resize((size_t)nlines * npixel);
-  } catch (const std::bad_alloc &) {
-    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
-  }
-  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
-    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
-      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
-        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
-          sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                            nlat, i, j, directions.data() + 3 * pixel.size());
-          pixel.push_back((int64_t)i * nlat + j);
-        }
-  CMI_TRY(cmi_gpu_render_line_sky(e, nlines, lines, origin, (int64_t)npixel,
-                                  directions.data(), dust_cross_section,
-                                  rays.data()));
-  for (int32_t l = 0; l < nlines; ++l)
-    for (size_t k = 0; k < npixel; ++k)
-      maps[(size_t)l * npixel + (size_t)pixel[k]] = rays[(size_t)l * npixel + k];
-  return CMI_GPU_OK;
-}
-
-/* ------------------------------------------------------ sky cubes -- */
-extern "C++" {
-namespace {
-/* device buffers of one sky cube call, freed however it ends */
-struct SkyCubeBuffers {
-  double *records = nullptr, *directions = nullptr, *out = nullptr,
-         *fields = nullptr, *widths = nullptr, *extinction = nullptr,
-         *velocity = nullptr;
-  ~SkyCubeBuffers() {
-    (void)hipFree(records);
-    (void)hipFree(directions);
-    (void)hipFree(out);
-    (void)hipFree(fields);
-    (void)hipFree(widths);
-    (void)hipFree(extinction);
-    (void)hipFree(velocity);
-  }
-};
-
-/* values of one march's result buffer (bounds the rays per launch) */
-constexpr int64_t CMI_SKY_CUBE_LAUNCH_VALUES = 1ll << 26;
-
-/* the size, the velocity axis and the observer's velocity of a sky cube call
- * (sky_check has bounded nrays) */
-int sky_cube_check(const char *what, int32_t nplanes, int64_t nrays,
-                   int32_t nchan, double vmin, double vmax,
-                   const double *observer_velocity, LineCubeAxis &axis,
-                   double v_obs[3]) {
-  if (nchan >= 1 &&
-      ((int64_t)nplanes * nchan > (1ll << 28) ||
-       (int64_t)nplanes * nchan * nrays > (1ll << 28)))
-    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %lld rays: a cube has "
-                "at most 2^28 values", what, (int)nplanes, (int)nchan,
-                (long long)nrays);
-  CMI_TRY(line_cube_axis(what, nplanes, 1, 1, nchan, vmin, vmax, axis));
-  for (int a = 0; a < 3; ++a) {
-    v_obs[a] = observer_velocity ? observer_velocity[a] : 0.;
-    if (!std::isfinite(v_obs[a]))
-      return fail(CMI_GPU_EINVAL, "%s: component %d of the observer's velocity "
-                  "is not finite", what, a);
-  }
-  return CMI_GPU_OK;
-}
-
-/* out[(l * nchan + c) * nrays + r] (host), l < nl, of the records
- * [ncell][4 + 2 nl] in b.records: per chunk of rays and per block of CB
- * channels one march launch for the nl lines, directions up, results down */
-int sky_cube_march(cmi_gpu_engine *e, const double *origin, int64_t nrays,
-                   const double *directions, int nl, int nb,
-                   const LineCubeAxis &axis, SkyCubeBuffers &b, double *out) {
-  constexpr int CB = CMI_SKY_CUBE_CB;
-  const int64_t chunk = std::max<int64_t>(
-      1, std::min<int64_t>(std::min<int64_t>(nrays, CMI_SKY_LAUNCH_RAYS),
-                           CMI_SKY_CUBE_LAUNCH_VALUES /
-                               ((int64_t)nb * axis.nchan)));
-  if (!b.directions)
-    HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
-  if (!b.out)
-    HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk * axis.nchan * nb));
-  for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
-    const int64_t n = std::min<int64_t>(chunk, nrays - r0);
-    HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
-                      sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice));
-    for (int32_t c0 = 0; c0 < axis.nchan; c0 += CB) {
-      SkyCubeMarchArgs a;
-      a.grid = e->grid;
-      for (int k = 0; k < 3; ++k)
-        a.origin[k] = origin[k];
-      a.directions = b.directions;
-      a.records = b.records;
-      a.nrays = n;
-      a.nd = 4 + 2 * nl;
-      a.c0 = c0;
-      a.nc = std::min<int32_t>(CB, axis.nchan - c0);
-      a.pad = 0;
-      a.vmin = axis.vmin;
-      a.dv = axis.dv;
-      a.line_stride = (int64_t)axis.nchan * chunk;
-      a.channel_stride = chunk;
-      a.out = b.out;
-      sky_cube_march_kernel<CB>
-          <<<dim3((unsigned)((n + 255) / 256), (unsigned)nl), 256, 0,
-             e->stream>>>(a);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (n == nrays) {
-      HIP_TRY(hipMemcpy(out, b.out,
-                        sizeof(double) * (size_t)nl * axis.nchan * (size_t)n,
-                        hipMemcpyDeviceToHost));
-    } else {
-      for (int64_t p = 0; p < (int64_t)nl * axis.nchan; ++p)
-        HIP_TRY(hipMemcpy(out + (size_t)p * nrays + r0,
-                          b.out + (size_t)p * chunk,
-                          sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    }
-  }
-  return CMI_GPU_OK;
-}
-} // namespace
-} // extern "C++"
-
-int cmi_gpu_render_line_sky_cube(cmi_gpu_engine *e, int32_t nlines,
-                                 const int32_t *lines, const double *origin,
-                                 const double *observer_velocity,
-                                 int64_t nrays, const double *directions,
-                                 double dust_cross_section, int32_t nchan,
-                                 double vmin, double vmax, double sigma_turb,
-                                 double *out) {
-  static const char *what = "render_line_sky_cube";
-  if (!e || !lines || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nlines < 1 || nlines > CMI_NEMISSIONLINE)
-    return fail(CMI_GPU_EINVAL, "%s: %d lines asked for, there are %d", what,
-                (int)nlines, CMI_NEMISSIONLINE);
-  for (int32_t l = 0; l < nlines; ++l) {
-    if (lines[l] < 0 || lines[l] >= CMI_NEMISSIONLINE)
-      return fail(CMI_GPU_EINVAL, "%s: no emission line %d", what,
-                  (int)lines[l]);
-    if (cmi_emission_atomic_weight[lines[l]] == 0.)
-      return fail(CMI_GPU_EINVAL, "%s: entry %d is not the line of one ion: "
-                  "it has no line profile", what, (int)lines[l]);
-  }
-  if (!(dust_cross_section >= 0.) || !std::isfinite(dust_cross_section))
-    return fail(CMI_GPU_EINVAL, "%s: the dust cross section must be >= 0",
-                what);
-  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
-    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
-                "be >= 0 and finite", what);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  LineCubeAxis axis;
-  double v_obs[3];
-  CMI_TRY(sky_cube_check(what, nlines, nrays, nchan, vmin, vmax,
-                         observer_velocity, axis, v_obs));
-  if (!e->have_cells)
-    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
-  HIP_TRY(hipSetDevice(e->device));
-  SkyCubeBuffers b;
-  const int nb = std::min<int>(nlines, CMI_SKY_CUBE_BATCH);
-  HIP_TRY(hipMalloc(&b.records,
-                    sizeof(double) * (size_t)e->ncell * (4 + 2 * nb)));
-  for (int32_t first = 0; first < nlines; first += CMI_SKY_CUBE_BATCH) {
-    const int nl = std::min<int>(nlines - first, CMI_SKY_CUBE_BATCH);
-    SkyCubeRecordArgs r;
-    r.model = e->model;
-    r.cells = e->cells;
-    r.ncell = e->ncell;
-    r.nlines = nl;
-    for (int l = 0; l < CMI_SKY_CUBE_BATCH; ++l) {
-      r.lines[l] = l < nl ? lines[first + l] : 0;
-      r.weight[l] = l < nl ? cmi_emission_atomic_weight[lines[first + l]] : 1.;
-    }
-    r.dust_cross_section = dust_cross_section;
-    r.sigma_turb = sigma_turb;
-    for (int a = 0; a < 3; ++a)
-      r.v_obs[a] = v_obs[a];
-    r.velocity = e->cell_velocities;
-    r.records = b.records;
-    sky_cube_record_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
-                             e->stream>>>(r);
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(sky_cube_march(e, origin, nrays, directions, nl, nb, axis, b,
-                           out + (size_t)first * nchan * (size_t)nrays));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_field_sky_cube(cmi_gpu_engine *e, int32_t nfields,
-                                  const double *fields,
-                                  const double *extinction,
-                                  const double *velocity, const double *widths,
-                                  const double *origin,
-                                  const double *observer_velocity,
-                                  int64_t nrays, const double *directions,
-                                  int32_t nchan, double vmin, double vmax,
-                                  double *out) {
-  static const char *what = "render_field_sky_cube";
-  if (!e || !fields || !widths || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  if (nfields < 1 || nfields > 1024)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 fields (%d asked for)",
-                what, (int)nfields);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  LineCubeAxis axis;
-  double v_obs[3];
-  CMI_TRY(sky_cube_check(what, nfields, nrays, nchan, vmin, vmax,
-                         observer_velocity, axis, v_obs));
-  const size_t ncell = (size_t)e->ncell;
-  for (size_t i = 0; i < ncell * (size_t)nfields; ++i)
-    if (!(widths[i] >= 0.) || !std::isfinite(widths[i]))
-      return fail(CMI_GPU_EINVAL, "%s: the width of field %lld in cell %lld "
-                  "is negative or not finite", what, (long long)(i / ncell),
-                  (long long)(i % ncell));
-  HIP_TRY(hipSetDevice(e->device));
-  SkyCubeBuffers b;
-  if (velocity) {
-    HIP_TRY(hipMalloc(&b.velocity, sizeof(double) * 3 * ncell));
-    HIP_TRY(hipMemcpy(b.velocity, velocity, sizeof(double) * 3 * ncell,
-                      hipMemcpyHostToDevice));
-    CMI_TRY(line_cube_check_velocities(e, what, b.velocity,
-                                       3 * (int64_t)ncell));
-  }
-  const int nb = std::min<int>(nfields, CMI_SKY_CUBE_BATCH);
-  HIP_TRY(hipMalloc(&b.records, sizeof(double) * ncell * (4 + 2 * nb)));
-  HIP_TRY(hipMalloc(&b.fields, sizeof(double) * ncell * nb));
-  HIP_TRY(hipMalloc(&b.widths, sizeof(double) * ncell * nb));
-  if (extinction) {
-    HIP_TRY(hipMalloc(&b.extinction, sizeof(double) * ncell));
-    HIP_TRY(hipMemcpy(b.extinction, extinction, sizeof(double) * ncell,
-                      hipMemcpyHostToDevice));
-  }
-  for (int32_t first = 0; first < nfields; first += CMI_SKY_CUBE_BATCH) {
-    const int nl = std::min<int>(nfields - first, CMI_SKY_CUBE_BATCH);
-    HIP_TRY(hipMemcpy(b.fields, fields + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b.widths, widths + (size_t)first * ncell,
-                      sizeof(double) * ncell * nl, hipMemcpyHostToDevice));
-    field_sky_cube_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
-                                   e->stream>>>(
-        b.fields, b.widths, b.extinction, b.velocity, v_obs[0], v_obs[1],
-        v_obs[2], e->ncell, nl, b.records);
-    HIP_TRY(hipGetLastError());
-    CMI_TRY(sky_cube_march(e, origin, nrays, directions, nl, nb, axis, b,
-                           out + (size_t)first * nchan * (size_t)nrays));
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_line_sky_map_cube(cmi_gpu_engine *e, int32_t nlines,
-                                     const int32_t *lines,
-                                     const double *origin, const double *frame,
-                                     double lon_min, double lon_max,
-                                     double lat_min, double lat_max,
-                                     int32_t nlon, int32_t nlat,
-                                     double dust_cross_section,
-                                     const double *observer_velocity,
-                                     int32_t nchan, double vmin, double vmax,
-                                     double sigma_turb, double *cubes) {
-  static const char *what = "render_line_sky_map_cube";
-  if (!e || !lines || !cubes || nlines < 1)
-    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
-  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                        nlat));
-  const size_t npixel = (size_t)nlon * nlat;
-  if (nchan >= 1 && ((int64_t)nlines * nchan > (1ll << 28) ||
-                     (int64_t)nlines * nchan * (int64_t)npixel > (1ll << 28)))
-    return fail(CMI_GPU_EINVAL, "%s: %d x %d channels of %d x %d pixels: a "
-                "cube has at most 2^28 values", what, (int)nlines, (int)nchan,
-                (int)nlon, (int)nlat);
-  /* the map call's ray order: 8 x 8 tiles; pixel[k] is the pixel of ray k */
-  const size_t nplane = (size_t)nlines * (size_t)std::max<int32_t>(nchan, 1);
-  std::vector<int64_t> pixel;
-  std::vector<double> directions, rays;
-  try {
-    pixel.reserve(npixel);
-    directions.resize(3 * npixel);
-    rays.resize(nplane * npixel);
-  } catch (const std::bad_alloc &) {
-    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
-  }
-  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
-    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
-      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
-        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
-          sky_map_direction(frame, lon_min, lon_max, lat_min, lat_max, nlon,
-                            nlat, i, j, directions.data() + 3 * pixel.size());
-          pixel.push_back((int64_t)i * nlat + j);
-        }
-  CMI_TRY(cmi_gpu_render_line_sky_cube(
-      e, nlines, lines, origin, observer_velocity, (int64_t)npixel,
-      directions.data(), dust_cross_section, nchan, vmin, vmax, sigma_turb,
-      rays.data()));
-  for (size_t p = 0; p < nplane; ++p)
-    for (size_t k = 0; k < npixel; ++k)
-      cubes[p * npixel + (size_t)pixel[k]] = rays[p * npixel + k];
-  return CMI_GPU_OK;
-}
-
-/* ------------------------------------------------- continuum images -- */
-extern "C++" {
-namespace {
-/* device buffers of one continuum call, freed however it ends */
-struct ContinuumBuffers {
-  double *records = nullptr, *samples = nullptr, *image = nullptr,
-         *kappa = nullptr, *source = nullptr, *directions = nullptr,
-         *out = nullptr;
-  unsigned int *ninvalid = nullptr;
-  ~ContinuumBuffers() {
-    (void)hipFree(records);
-    (void)hipFree(samples);
-    (void)hipFree(image);
-    (void)hipFree(kappa);
-    (void)hipFree(source);
-    (void)hipFree(directions);
-    (void)hipFree(out);
-    (void)hipFree(ninvalid);
-  }
-};
-
-/* where the channels of a continuum call come from: the free-free
- * coefficients of the cells at freq[nf], or the caller's kappa[nf][ncell] and
- * source[nf][ncell] (host) */
-struct ContinuumInput {
-  const double *freq = nullptr;
-  const double *kappa = nullptr, *source = nullptr;
-};
-
-/* f(std::integral_constant<int, FB>) for the channel block of the engine */
-template <class F> void continuum_for_block(int fb, F &&f) {
-  switch (fb) {
-  case 4: f(std::integral_constant<int, 4>()); break;
-  case 16: f(std::integral_constant<int, 16>()); break;
-  default: f(std::integral_constant<int, 8>()); break;
-  }
-}
-
-/* what every continuum call asks of its channels before a launch; nvalue is
- * the number of pixels or rays of one channel */
-int continuum_check(const cmi_gpu_engine *e, const char *what, int32_t nf,
-                    int64_t nvalue, const ContinuumInput &in,
-                    const double *background) {
-  if (nf < 1)
-    return fail(CMI_GPU_EINVAL, "%s: at least one channel (%d asked for)",
-                what, (int)nf);
-  if ((int64_t)nf > (1ll << 28) || (int64_t)nf * nvalue > (1ll << 28))
-    return fail(CMI_GPU_EINVAL, "%s: %d channels of %lld values: a call "
-                "renders at most 2^28 values", what, (int)nf,
-                (long long)nvalue);
-  if (in.freq) {
-    for (int32_t f = 0; f < nf; ++f)
-      if (!std::isfinite(in.freq[f]) || !(in.freq[f] > 0.))
-        return fail(CMI_GPU_EINVAL, "%s: frequency %d is not finite and "
-                    "positive (%.17g)", what, (int)f, in.freq[f]);
-    if (!e->have_cells)
-      return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
-  }
-  if (background)
-    for (int32_t f = 0; f < nf; ++f)
-      if (!std::isfinite(background[f]))
-        return fail(CMI_GPU_EINVAL, "%s: the background of channel %d is not "
-                    "finite", what, (int)f);
-  return CMI_GPU_OK;
-}
-
-/* the channels [c0, c0 + nc) of the caller's fields into b.kappa and b.source
- * (device, [nc][ncell]) */
-int continuum_upload(cmi_gpu_engine *e, const ContinuumInput &in, int32_t c0,
-                     int32_t nc, ContinuumBuffers &b) {
-  const size_t ncell = (size_t)e->ncell;
-  HIP_TRY(hipMemcpy(b.kappa, in.kappa + (size_t)c0 * ncell,
-                    sizeof(double) * ncell * nc, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b.source, in.source + (size_t)c0 * ncell,
-                    sizeof(double) * ncell * nc, hipMemcpyHostToDevice));
-  return CMI_GPU_OK;
-}
-
-/* allocates the records (and the staging of the caller's fields) and refuses
- * fields with a value out of range: every block is uploaded and counted
- * before anything is marched. With one block it stays uploaded. */
-int continuum_begin(cmi_gpu_engine *e, const char *what,
-                    const ContinuumInput &in, int32_t nf, int fb,
-                    ContinuumBuffers &b) {
-  const size_t ncell = (size_t)e->ncell;
-  HIP_TRY(hipMalloc(&b.records, sizeof(double) * 2 * ncell * fb));
-  if (in.freq)
-    return CMI_GPU_OK;
-  const int nb = std::min<int>(nf, fb);
-  HIP_TRY(hipMalloc(&b.kappa, sizeof(double) * ncell * nb));
-  HIP_TRY(hipMalloc(&b.source, sizeof(double) * ncell * nb));
-  HIP_TRY(hipMalloc(&b.ninvalid, 2 * sizeof(unsigned int)));
-  HIP_TRY(hipMemsetAsync(b.ninvalid, 0, 2 * sizeof(unsigned int), e->stream));
-  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
-    const int32_t nc = std::min<int32_t>(fb, nf - c0);
-    CMI_TRY(continuum_upload(e, in, c0, nc, b));
-    const int64_t n = (int64_t)ncell * nc;
-    continuum_field_check_kernel<<<grid_blocks(e, n, 8), 256, 0, e->stream>>>(
-        b.kappa, b.source, n, b.ninvalid);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  unsigned int bad[2] = {0, 0};
-  HIP_TRY(hipMemcpy(bad, b.ninvalid, sizeof bad, hipMemcpyDeviceToHost));
-  if (bad[0])
-    return fail(CMI_GPU_EINVAL, "%s: %u absorption coefficient(s) are "
-                "negative or not finite", what, bad[0]);
-  if (bad[1])
-    return fail(CMI_GPU_EINVAL, "%s: %u source function value(s) are not "
-                "finite", what, bad[1]);
-  return CMI_GPU_OK;
-}
-
-/* the records of the channels [c0, c0 + nc) into b.records */
-int continuum_records(cmi_gpu_engine *e, const ContinuumInput &in, int32_t nf,
-                      int32_t c0, int32_t nc, int fb, ContinuumBuffers &b) {
-  if (in.freq) {
-    FreeFreeRecordArgs r;
-    r.cells = e->cells;
-    r.ncell = e->ncell;
-    r.helium_abundance = e->model.abundance[0];
-    r.fb = fb;
-    r.nfreq = nc;
-    for (int f = 0; f < CMI_CONTINUUM_MAX_FB; ++f)
-      r.freq[f] = f < nc ? in.freq[c0 + f] : 1.;
-    r.records = b.records;
-    free_free_record_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0,
-                              e->stream>>>(r);
-  } else {
-    /* (a single block is still there from the check) */
-    if (nf > fb)
-      CMI_TRY(continuum_upload(e, in, c0, nc, b));
-    field_continuum_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
-                                    e->stream>>>(b.kappa, b.source, e->ncell,
-                                                 nc, fb, b.records);
-  }
-  HIP_TRY(hipGetLastError());
-  return CMI_GPU_OK;
-}
-
-/* images[nf][nx * ny] (host) of the parallel camera: per block of FB channels
- * the records, then per chunk of pixel rows one march launch */
-int continuum_images(cmi_gpu_engine *e, const char *what,
-                     const ContinuumInput &in, int32_t nf,
-                     const double *background, const LineViewDev &v,
-                     double *images) {
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const int fb = e->tune.continuum_channel_block;
-  HIP_TRY(hipSetDevice(e->device));
-  ContinuumBuffers b;
-  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
-  const int64_t npixel = (int64_t)v.nx * v.ny;
-  const int64_t NY = (int64_t)v.ny * v.s;
-  const int64_t launch = e->tune.continuum_launch_rays
-                             ? e->tune.continuum_launch_rays
-                             : CMI_LINE_IMAGE_LAUNCH_SAMPLES / fb;
-  /* pixel rows per launch: the sample buffer holds FB channels of them */
-  const int64_t rows = std::max<int64_t>(
-      1, std::min<int64_t>(v.nx, launch / (NY * v.s)));
-  const int64_t chunk_samples = rows * v.s * NY;
-  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)npixel *
-                                  std::min<int>(nf, fb)));
-  if (v.s > 1)
-    HIP_TRY(hipMalloc(&b.samples,
-                      sizeof(double) * (size_t)chunk_samples * fb));
-  const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
-    const int32_t nc = std::min<int32_t>(fb, nf - c0);
-    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
-    for (int64_t ix0 = 0; ix0 < v.nx; ix0 += rows) {
-      const int64_t ix1 = std::min<int64_t>(v.nx, ix0 + rows);
-      ContinuumMarchArgs a;
-      a.grid = e->grid;
-      a.view = v;
-      a.records = b.records;
-      a.sx0 = (int32_t)(ix0 * v.s);
-      a.sx1 = (int32_t)(ix1 * v.s);
-      a.nc = nc;
-      a.pad = 0;
-      for (int i = 0; i < CMI_CONTINUUM_MAX_FB; ++i)
-        a.background[i] = (background && i < nc) ? background[c0 + i] : 0.;
-      if (v.s > 1) {
-        a.out = b.samples;
-        a.channel_stride = chunk_samples;
-      } else {
-        a.out = b.image + ix0 * v.ny;
-        a.channel_stride = npixel;
-      }
-      const int64_t tiles_x = (a.sx1 - a.sx0 + 2 * TX - 1) / (2 * TX);
-      /* (with the tuning key timing the march launches are timed like the
-       * transport launches: cmi_gpu_get_kernel_timing) */
-      EventPair ev;
-      CMI_TRY(timer_begin(e, ev));
-      continuum_for_block(fb, [&](auto width) {
-        continuum_march_kernel<decltype(width)::value>
-            <<<(unsigned)(tiles_x * tiles_y), 256, 0, e->stream>>>(a);
-      });
-      HIP_TRY(hipGetLastError());
-      CMI_TRY(timer_end(e, e->kernel_events, ev,
-                        (uint64_t)((a.sx1 - a.sx0) * NY)));
-      if (v.s > 1) {
-        /* the images' reduction, channels in the place of lines */
-        const int64_t work = (ix1 - ix0) * v.ny * nc;
-        line_image_reduce_kernel<<<(unsigned)((work + 255) / 256), 256, 0,
-                                   e->stream>>>(
-            b.samples, chunk_samples, nc, (int32_t)ix0, (int32_t)ix1, v.ny,
-            v.s, npixel, b.image);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(images + (size_t)c0 * npixel, b.image,
-                      sizeof(double) * (size_t)npixel * nc,
-                      hipMemcpyDeviceToHost));
-  }
-  return CMI_GPU_OK;
-}
-
-/* out[nf][nrays] (host) of the rays from a point: per block of FB channels
- * the records, then per chunk of rays one march launch, directions up,
- * results down */
-int continuum_sky(cmi_gpu_engine *e, const char *what, const ContinuumInput &in,
-                  int32_t nf, const double *background, const double *origin,
-                  int64_t nrays, const double *directions, double *out) {
-  const int fb = e->tune.continuum_channel_block;
-  HIP_TRY(hipSetDevice(e->device));
-  ContinuumBuffers b;
-  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
-  const int64_t launch = e->tune.continuum_launch_rays
-                             ? e->tune.continuum_launch_rays
-                             : CMI_SKY_LAUNCH_RAYS;
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nrays, launch));
-  HIP_TRY(hipMalloc(&b.directions, sizeof(double) * 3 * (size_t)chunk));
-  HIP_TRY(hipMalloc(&b.out, sizeof(double) * (size_t)chunk * fb));
-  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
-    const int32_t nc = std::min<int32_t>(fb, nf - c0);
-    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
-    for (int64_t r0 = 0; r0 < nrays; r0 += chunk) {
-      const int64_t n = std::min<int64_t>(chunk, nrays - r0);
-      HIP_TRY(hipMemcpy(b.directions, directions + 3 * r0,
-                        sizeof(double) * 3 * (size_t)n,
-                        hipMemcpyHostToDevice));
-      ContinuumSkyMarchArgs a;
-      a.grid = e->grid;
-      for (int k = 0; k < 3; ++k)
-        a.origin[k] = origin[k];
-      a.directions = b.directions;
-      a.records = b.records;
-      a.nrays = n;
-      a.nc = nc;
-      a.pad = 0;
-      a.channel_stride = chunk;
-      a.out = b.out;
-      for (int i = 0; i < CMI_CONTINUUM_MAX_FB; ++i)
-        a.background[i] = (background && i < nc) ? background[c0 + i] : 0.;
-      EventPair ev;
-      CMI_TRY(timer_begin(e, ev));
-      continuum_for_block(fb, [&](auto width) {
-        continuum_sky_march_kernel<decltype(width)::value>
-            <<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(a);
-      });
-      HIP_TRY(hipGetLastError());
-      CMI_TRY(timer_end(e, e->kernel_events, ev, (uint64_t)n));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-      for (int32_t i = 0; i < nc; ++i)
-        HIP_TRY(hipMemcpy(out + (size_t)(c0 + i) * nrays + r0,
-                          b.out + (size_t)i * chunk,
-                          sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-    }
-  }
-  return CMI_GPU_OK;
-}
-} // namespace
-} // extern "C++"
-
-int cmi_gpu_free_free_coefficients(cmi_gpu_engine *e, int32_t nf,
-                                   const double *freq, double *kappa_out,
-                                   double *source_out) {
-  static const char *what = "free_free_coefficients";
-  if (!e || !freq || !kappa_out || !source_out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  ContinuumInput in;
-  in.freq = freq;
-  CMI_TRY(continuum_check(e, what, nf, 1, in, nullptr));
-  HIP_TRY(hipSetDevice(e->device));
-  const int fb = e->tune.continuum_channel_block;
-  const size_t ncell = (size_t)e->ncell;
-  ContinuumBuffers b;
-  CMI_TRY(continuum_begin(e, what, in, nf, fb, b));
-  std::vector<double> host;
-  try {
-    host.resize(2 * ncell * fb);
-  } catch (const std::bad_alloc &) {
-    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
-  }
-  for (int32_t c0 = 0; c0 < nf; c0 += fb) {
-    const int32_t nc = std::min<int32_t>(fb, nf - c0);
-    CMI_TRY(continuum_records(e, in, nf, c0, nc, fb, b));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(host.data(), b.records, sizeof(double) * 2 * ncell * fb,
-                      hipMemcpyDeviceToHost));
-    for (int32_t i = 0; i < nc; ++i)
-      for (size_t c = 0; c < ncell; ++c) {
-        kappa_out[(size_t)(c0 + i) * ncell + c] = host[2 * (c * fb + i)];
-        source_out[(size_t)(c0 + i) * ncell + c] = host[2 * (c * fb + i) + 1];
-      }
-  }
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_render_continuum_images(cmi_gpu_engine *e, int32_t nf,
-                                    const double *freq,
-                                    const double *background, double theta,
-                                    double phi, int32_t nx, int32_t ny,
-                                    const double *anchor, const double *sides,
-                                    int32_t supersample, double *out) {
-  static const char *what = "render_continuum_images";
-  if (!e || !freq || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  ContinuumInput in;
-  in.freq = freq;
-  CMI_TRY(continuum_check(e, what, nf, (int64_t)nx * ny, in, background));
-  return continuum_images(e, what, in, nf, background, v, out);
-}
-
-int cmi_gpu_render_field_continuum_images(
-    cmi_gpu_engine *e, int32_t nf, const double *kappa, const double *source,
-    const double *background, double theta, double phi, int32_t nx,
-    int32_t ny, const double *anchor, const double *sides,
-    int32_t supersample, double *out) {
-  static const char *what = "render_field_continuum_images";
-  if (!e || !kappa || !source || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  LineViewDev v;
-  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
-                              supersample, v));
-  ContinuumInput in;
-  in.kappa = kappa;
-  in.source = source;
-  CMI_TRY(continuum_check(e, what, nf, (int64_t)nx * ny, in, background));
-  return continuum_images(e, what, in, nf, background, v, out);
-}
-
-int cmi_gpu_render_continuum_sky(cmi_gpu_engine *e, int32_t nf,
-                                 const double *freq, const double *background,
-                                 const double *origin, int64_t nrays,
-                                 const double *directions, double *out) {
-  static const char *what = "render_continuum_sky";
-  if (!e || !freq || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  ContinuumInput in;
-  in.freq = freq;
-  CMI_TRY(continuum_check(e, what, nf, nrays, in, background));
-  return continuum_sky(e, what, in, nf, background, origin, nrays, directions,
-                       out);
-}
-
-int cmi_gpu_render_field_continuum_sky(cmi_gpu_engine *e, int32_t nf,
-                                       const double *kappa,
-                                       const double *source,
-                                       const double *background,
-                                       const double *origin, int64_t nrays,
-                                       const double *directions, double *out) {
-  static const char *what = "render_field_continuum_sky";
-  if (!e || !kappa || !source || !out)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
-  ContinuumInput in;
-  in.kappa = kappa;
-  in.source = source;
-  CMI_TRY(continuum_check(e, what, nf, nrays, in, background));
-  return continuum_sky(e, what, in, nf, background, origin, nrays, directions,
-                       out);
-}
-
-int cmi_gpu_render_continuum_sky_map(cmi_gpu_engine *e, int32_t nf,
-                                     const double *freq,
-                                     const double *background,
-                                     const double *origin, int32_t nlon,
-                                     int32_t nlat, const double *lon_range,
-                                     const double *lat_range,
-                                     const double *frame, double *out) {
-  static const char *what = "render_continuum_sky_map";
-  if (!e || !freq || !out || !lon_range || !lat_range)
-    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
-  CMI_TRY(sky_map_check(what, frame, lon_range[0], lon_range[1], lat_range[0],
-                        lat_range[1], nlon, nlat));
-  const size_t npixel = (size_t)nlon * nlat;
-  ContinuumInput in;
-  in.freq = freq;
-  CMI_TRY(continuum_check(e, what, nf, (int64_t)npixel, in, background));
-  /* the map call's ray order: 8 x 8 tiles; pixel[k] is the pixel of ray k */
-  std::vector<int64_t> pixel;
-  std::vector<double> directions, rays;
-  try {
-    pixel.reserve(npixel);
-    directions.resize(3 * npixel);
-    rays.resize((size_t)nf * npixel);
-  } catch (const std::bad_alloc &) {
-    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
-  }
-  for (int32_t i0 = 0; i0 < nlon; i0 += 8)
-    for (int32_t j0 = 0; j0 < nlat; j0 += 8)
-      for (int32_t i = i0; i < std::min(nlon, i0 + 8); ++i)
-        for (int32_t j = j0; j < std::min(nlat, j0 + 8); ++j) {
-          sky_map_direction(frame, lon_range[0], lon_range[1], lat_range[0],
-                            lat_range[1], nlon, nlat, i, j,
-                            directions.data() + 3 * pixel.size());
-          pixel.push_back((int64_t)i * nlat + j);
-        }
-  CMI_TRY(sky_check(e, what, origin, (int64_t)npixel, 1ll << 28,
-                    directions.data()));
-  CMI_TRY(continuum_sky(e, what, in, nf, background, origin, (int64_t)npixel,
-                        directions.data(), rays.data()));
-  for (size_t p = 0; p < (size_t)nf; ++p)
-    for (size_t k = 0; k < npixel; ++k)
-      out[p * npixel + (size_t)pixel[k]] = rays[p * npixel + k];
-  return CMI_GPU_OK;
-}
-
-int cmi_gpu_continuum_probe(cmi_gpu_engine *e, int32_t nf, const double *kappa,
-                            const double *source, const double *background,
-                            int32_t point, const double *view, int64_t n,
-                            const double *rays, int32_t max_cells,
-                            double *out) {
-  static const char *what = "continuum_probe";
-  if (!e || !kappa || !source || !view || !out || max_cells < 0 ||
-      (point != 0 && point != 1))
-    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
-  if (nf < 1 || nf > 1024)
-    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 channels (%d asked "
-                "for)", what, (int)nf);
-  LineViewDev v;
-  double origin[3] = {0., 0., 0.};
-  if (point) {
-    CMI_TRY(sky_check(e, what, view, n, 1ll << 20, rays));
-    for (int a = 0; a < 3; ++a)
-      origin[a] = view[a];
-    /* (not read by the kernel; set so that it is passed initialised) */
-    std::memset(&v, 0, sizeof v);
-  } else {
-    if (n <= 0 || n > (1ll << 20) || !rays)
-      return fail(CMI_GPU_EINVAL, "%s: between 1 and 2^20 rays (%lld asked "
-                  "for)", what, (long long)n);
-    CMI_TRY(line_image_view(e, what, view[0], view[1], v));
-    for (int64_t k = 0; k < 2 * n; ++k)
-      if (!std::isfinite(rays[k]))
-        return fail(CMI_GPU_EINVAL, "%s: image coordinate %lld of ray %lld is "
-                    "not finite", what, (long long)(k % 2),
-                    (long long)(k / 2));
-  }
-  ContinuumInput in;
-  in.kappa = kappa;
-  in.source = source;
-  CMI_TRY(continuum_check(e, what, nf, 1, in, background));
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t ncell = (size_t)e->ncell;
-  const size_t width = 3 + (2 + (size_t)nf) * (size_t)max_cells + (size_t)nf;
-  const size_t nray_values = (point ? 3 : 2) * (size_t)n;
-  ContinuumBuffers b;
-  double *dbg = nullptr;
-  HIP_TRY(hipMalloc(&b.kappa, sizeof(double) * ncell * nf));
-  HIP_TRY(hipMalloc(&b.source, sizeof(double) * ncell * nf));
-  HIP_TRY(hipMalloc(&b.ninvalid, 2 * sizeof(unsigned int)));
-  HIP_TRY(hipMalloc(&b.directions, sizeof(double) * nray_values));
-  HIP_TRY(hipMalloc(&b.out, sizeof(double) * width * (size_t)n));
-  HIP_TRY(hipMalloc(&b.image, sizeof(double) * (size_t)nf));
-  dbg = b.image; /* the background on the device */
-  HIP_TRY(hipMemsetAsync(b.ninvalid, 0, 2 * sizeof(unsigned int), e->stream));
-  CMI_TRY(continuum_upload(e, in, 0, nf, b));
-  continuum_field_check_kernel<<<grid_blocks(e, (int64_t)ncell * nf, 8), 256,
-                                 0, e->stream>>>(b.kappa, b.source,
-                                                 (int64_t)ncell * nf,
-                                                 b.ninvalid);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  unsigned int bad[2] = {0, 0};
-  HIP_TRY(hipMemcpy(bad, b.ninvalid, sizeof bad, hipMemcpyDeviceToHost));
-  if (bad[0] || bad[1])
-    return fail(CMI_GPU_EINVAL, "%s: %u absorption coefficient(s) are "
-                "negative or not finite, %u source function value(s) are not "
-                "finite", what, bad[0], bad[1]);
-  std::vector<double> bg((size_t)nf, 0.);
-  if (background)
-    std::copy(background, background + nf, bg.begin());
-  HIP_TRY(hipMemcpy(dbg, bg.data(), sizeof(double) * (size_t)nf,
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(b.directions, rays, sizeof(double) * nray_values,
-                    hipMemcpyHostToDevice));
-  HIP_TRY(hipMemsetAsync(b.out, 0, sizeof(double) * width * (size_t)n,
-                         e->stream));
-  continuum_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
-      e->grid, v, point, origin[0], origin[1], origin[2], b.directions, n,
-      b.kappa, b.source, dbg, nf, e->ncell, max_cells, b.out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  HIP_TRY(hipMemcpy(out, b.out, sizeof(double) * width * (size_t)n,
-                    hipMemcpyDeviceToHost));
-  return CMI_GPU_OK;
-}
+/* the ray-traced renderers: line images and cubes, sky maps and cubes, the
+ * radio continuum */
+#include "render_driver.h"
 
 int cmi_gpu_check_sky_camera(const double *box_anchor, const double *box_sides,
                              const double *origin, const double *frame,

@@ -557,6 +557,18 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _p_or_none(a):
+    """_p(a), and the null pointer for None."""
+    return None if a is None else _p(a)
+
+
+def _line_indices(names):
+    """The indices in EMISSION_LINES of `names` as the int32 pointer the
+    library takes (it keeps its array alive)."""
+    idx = np.array([EMISSION_LINES.index(n) for n in names], dtype=np.int32)
+    return idx.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 class EngineGroup:
     """Several engines driven by this process (cmi_gpu_group_*): replicas
     (reduce_accumulators) or the blocks of a decomposed grid
@@ -769,7 +781,7 @@ class GpuEngine:
         if ionic_fractions is not None:
             x = _f64(ionic_fractions).reshape(NION, self.n)
         self._check(self._lib.cmi_gpu_upload_cells(
-            self._h, _p(n), _p(t), _p(x) if x is not None else None))
+            self._h, _p(n), _p(t), _p_or_none(x)))
 
     def upload_field(self, field, values):
         v = _f64(values).ravel()
@@ -901,13 +913,12 @@ class GpuEngine:
         first_cell + ncell): {line name: array over those cells}. `lines` are
         names from EMISSION_LINES (all of them by default)."""
         names = list(EMISSION_LINES if lines is None else lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         if ncell is None:
             ncell = self.n - first_cell
         out = np.empty((len(names), ncell))
         self._check(self._lib.cmi_gpu_compute_emissivities(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             first_cell, ncell, out.ctypes.data_as(C.POINTER(C.c_double))))
         return dict(zip(names, out))
 
@@ -1206,7 +1217,7 @@ class GpuEngine:
         out = np.zeros((n, width))
         self._check(self._lib.cmi_gpu_dust_probe(
             self._h, kind, seed, first_packet, n,
-            _p(inp) if inp is not None else None, _p(out), max_events))
+            _p_or_none(inp), _p(out), max_events))
         return out
 
     # emission-line images ----------------------------------------------------
@@ -1217,13 +1228,12 @@ class GpuEngine:
         W m^-2 sr^-1, dust of `dust_cross_section` m^2 per hydrogen nucleus
         along the way (include/cmi_gpu.h, cmi_gpu_render_line_images)."""
         names = list(EMISSION_LINES if lines is None else lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         a = _f64(anchor).reshape(2)
         s = _f64(sides).reshape(2)
         out = np.zeros((len(names), max(int(nx), 0), max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_line_images(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
             dust_cross_section, _p(out)))
         return dict(zip(names, out))
@@ -1284,7 +1294,7 @@ class GpuEngine:
         out = np.zeros((len(f), max(int(nx), 0), max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_field_images(
             self._h, len(f), _p(f), theta, phi, int(nx), int(ny), _p(a),
-            _p(s), int(supersample), _p(k) if k is not None else None,
+            _p(s), int(supersample), _p_or_none(k),
             _p(out)))
         return out
 
@@ -1318,14 +1328,13 @@ class GpuEngine:
         `sigma_turb` (include/cmi_gpu.h, cmi_gpu_render_line_cube). Only
         names of LINE_ATOMIC_WEIGHTS have a cube."""
         names = list(lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         a = _f64(anchor).reshape(2)
         s = _f64(sides).reshape(2)
         out = np.zeros((len(names), max(int(nchan), 0), max(int(nx), 0),
                         max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_line_cube(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
             dust_cross_section, int(nchan), vmin, vmax, sigma_turb, _p(out)))
         return dict(zip(names, out))
@@ -1346,8 +1355,8 @@ class GpuEngine:
         out = np.zeros((len(f), max(int(nchan), 0), max(int(nx), 0),
                         max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_field_cube(
-            self._h, len(f), _p(f), _p(k) if k is not None else None,
-            _p(v) if v is not None else None, _p(w), theta, phi, int(nx),
+            self._h, len(f), _p(f), _p_or_none(k),
+            _p_or_none(v), _p(w), theta, phi, int(nx),
             int(ny), _p(a), _p(s), int(supersample), int(nchan), vmin, vmax,
             _p(out)))
         return out
@@ -1361,13 +1370,12 @@ class GpuEngine:
         `dust_cross_section` m^2 per hydrogen nucleus along the way
         (include/cmi_gpu.h, cmi_gpu_render_line_sky)."""
         names = list(EMISSION_LINES if lines is None else lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         o = _f64(origin).reshape(3)
         d = _f64(directions).reshape(-1, 3)
         out = np.zeros((len(names), len(d)))
         self._check(self._lib.cmi_gpu_render_line_sky(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             _p(o), len(d), _p(d), dust_cross_section, _p(out)))
         return dict(zip(names, out))
 
@@ -1381,7 +1389,7 @@ class GpuEngine:
         out = np.zeros((len(f), len(d)))
         self._check(self._lib.cmi_gpu_render_field_sky(
             self._h, len(f), _p(f), _p(o), len(d), _p(d),
-            _p(k) if k is not None else None, _p(out)))
+            _p_or_none(k), _p(out)))
         return out
 
     def sky_probe(self, origin, directions, max_cells):
@@ -1401,13 +1409,12 @@ class GpuEngine:
         """Equirectangular maps of emission lines around `origin`: {name:
         (nlon, nlat) array}, the pixels of sky_map_directions."""
         names = list(EMISSION_LINES if lines is None else lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         o = _f64(origin).reshape(3)
         f = _f64(frame).reshape(9)
         out = np.zeros((len(names), max(int(nlon), 0), max(int(nlat), 0)))
         self._check(self._lib.cmi_gpu_render_line_sky_map(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
             lat_range[1], int(nlon), int(nlat), dust_cross_section, _p(out)))
         return dict(zip(names, out))
@@ -1443,7 +1450,7 @@ class GpuEngine:
         s = _f64(sides).reshape(2)
         out = np.zeros((len(nu), max(int(nx), 0), max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_continuum_images(
-            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            self._h, len(nu), _p(nu), _p_or_none(bg),
             theta, phi, int(nx), int(ny), _p(a), _p(s), int(supersample),
             _p(out)))
         return out
@@ -1462,7 +1469,7 @@ class GpuEngine:
         out = np.zeros((len(k), max(int(nx), 0), max(int(ny), 0)))
         self._check(self._lib.cmi_gpu_render_field_continuum_images(
             self._h, len(k), _p(k), _p(S),
-            _p(bg) if bg is not None else None, theta, phi, int(nx), int(ny),
+            _p_or_none(bg), theta, phi, int(nx), int(ny),
             _p(a), _p(s), int(supersample), _p(out)))
         return out
 
@@ -1475,7 +1482,7 @@ class GpuEngine:
         d = _f64(directions).reshape(-1, 3)
         out = np.zeros((len(nu), len(d)))
         self._check(self._lib.cmi_gpu_render_continuum_sky(
-            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            self._h, len(nu), _p(nu), _p_or_none(bg),
             _p(o), len(d), _p(d), _p(out)))
         return out
 
@@ -1491,7 +1498,7 @@ class GpuEngine:
         out = np.zeros((len(k), len(d)))
         self._check(self._lib.cmi_gpu_render_field_continuum_sky(
             self._h, len(k), _p(k), _p(S),
-            _p(bg) if bg is not None else None, _p(o), len(d), _p(d),
+            _p_or_none(bg), _p(o), len(d), _p(d),
             _p(out)))
         return out
 
@@ -1509,7 +1516,7 @@ class GpuEngine:
         lat = _f64(lat_range).reshape(2)
         out = np.zeros((len(nu), max(int(nlon), 0), max(int(nlat), 0)))
         self._check(self._lib.cmi_gpu_render_continuum_sky_map(
-            self._h, len(nu), _p(nu), _p(bg) if bg is not None else None,
+            self._h, len(nu), _p(nu), _p_or_none(bg),
             _p(o), int(nlon), int(nlat), _p(lon), _p(lat), _p(f), _p(out)))
         return out
 
@@ -1529,7 +1536,7 @@ class GpuEngine:
         r = _f64(rays).reshape(-1, 3 if point else 2)
         out = np.zeros((len(r), 3 + (2 + nf) * max_cells + nf))
         self._check(self._lib.cmi_gpu_continuum_probe(
-            self._h, nf, _p(k), _p(S), _p(bg) if bg is not None else None,
+            self._h, nf, _p(k), _p(S), _p_or_none(bg),
             int(point), _p(view), len(r), _p(r), int(max_cells), _p(out)))
         return out
 
@@ -1554,9 +1561,9 @@ class GpuEngine:
         d = _f64(directions).reshape(-1, 3)
         out = np.zeros((len(f), max(int(nchan), 0), len(d)))
         self._check(self._lib.cmi_gpu_render_field_sky_cube(
-            self._h, len(f), _p(f), _p(k) if k is not None else None,
-            _p(v) if v is not None else None, _p(w), _p(o),
-            _p(vo) if vo is not None else None, len(d), _p(d), int(nchan),
+            self._h, len(f), _p(f), _p_or_none(k),
+            _p_or_none(v), _p(w), _p(o),
+            _p_or_none(vo), len(d), _p(d), int(nchan),
             vmin, vmax, _p(out)))
         return out
 
@@ -1568,16 +1575,15 @@ class GpuEngine:
         widths from the cells' temperatures and `sigma_turb` as in
         render_line_cube. Only names of LINE_ATOMIC_WEIGHTS have a cube."""
         names = list(lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         vo = (None if observer_velocity is None
               else _f64(observer_velocity).reshape(3))
         o = _f64(origin).reshape(3)
         d = _f64(directions).reshape(-1, 3)
         out = np.zeros((len(names), max(int(nchan), 0), len(d)))
         self._check(self._lib.cmi_gpu_render_line_sky_cube(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
-            _p(o), _p(vo) if vo is not None else None, len(d), _p(d),
+            self._h, len(names), idx,
+            _p(o), _p_or_none(vo), len(d), _p(d),
             dust_cross_section, int(nchan), vmin, vmax, sigma_turb, _p(out)))
         return dict(zip(names, out))
 
@@ -1590,8 +1596,7 @@ class GpuEngine:
         nlat) array}, the longitude-latitude-velocity cube of an observer at
         `origin`. cube_moments and cube_channel_centres work on it."""
         names = list(lines)
-        idx = np.array([EMISSION_LINES.index(n) for n in names],
-                       dtype=np.int32)
+        idx = _line_indices(names)
         vo = (None if observer_velocity is None
               else _f64(observer_velocity).reshape(3))
         o = _f64(origin).reshape(3)
@@ -1599,10 +1604,10 @@ class GpuEngine:
         out = np.zeros((len(names), max(int(nchan), 0), max(int(nlon), 0),
                         max(int(nlat), 0)))
         self._check(self._lib.cmi_gpu_render_line_sky_map_cube(
-            self._h, len(names), idx.ctypes.data_as(C.POINTER(C.c_int32)),
+            self._h, len(names), idx,
             _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
             lat_range[1], int(nlon), int(nlat), dust_cross_section,
-            _p(vo) if vo is not None else None, int(nchan), vmin, vmax,
+            _p_or_none(vo), int(nchan), vmin, vmax,
             sigma_turb, _p(out)))
         return dict(zip(names, out))
 
@@ -1722,8 +1727,8 @@ class GpuEngine:
             _f64(observer_velocities).reshape(self.nviews, 3)
         self._check(self._lib.cmi_gpu_set_scattered_cube(
             self._h, int(nchan), vmin, vmax, sigma_turb,
-            _p(w) if w is not None else None,
-            _p(vo) if vo is not None else None))
+            _p_or_none(w),
+            _p_or_none(vo)))
         self.cube_channels = int(nchan)
 
     def download_cubes(self):

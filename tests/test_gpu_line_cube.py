@@ -131,6 +131,49 @@ def test_parity_with_the_restatement(eng, nchan):
     print("nchan", nchan, "worst ratio of difference to bound", worst)
 
 
+@pytest.mark.parametrize("s, nx", [(8, 2048 + 50), (1, 131072 + 50)])
+def test_more_pixel_rows_than_one_launch_takes(eng, s, nx):
+    """Case 2, the chunks of pixel rows: a launch takes 2^22 / CB sample rays,
+    with ny = 4 that is 2048 pixel rows at s = 8 and 131072 at s = 1, and a
+    second launch marches the last 50, for nchan = CB + 1 in two channel
+    blocks each - through the sample buffer and one reduction per field at
+    s = 8, straight into the cube at its row offset at s = 1. Two fields with
+    velocities, no extinction, the bound of Case 2, on the middle of the
+    oblique view's rectangle so that the last chunk's pixels are lit."""
+    ny, nchan = 4, CB + 1
+    rows = ((1 << 22) // CB) // (ny * s * s)
+    assert nx == rows + 50
+    fields, widths, vel, _ = random_cells(47)
+    vmin, vmax = -150., 150.   # every channel has emission in the last rows
+    edges = Q.edges(nchan, vmin, vmax)
+    theta, phi = 0.7, 0.3
+    anchor, sides = L.bounding_rectangle(BOX, theta, phi)
+    anchor, sides = anchor + 0.25 * sides, 0.5 * sides
+    n, _, _ = L.axes(theta, phi)
+    u = -((vel[0] * n[0] + vel[1] * n[1]) + vel[2] * n[2])
+    warm = widths > 0.
+    reach = np.broadcast_to(np.abs(u) + np.abs(edges).max(), widths.shape)
+    slope = (reach[warm] / widths[warm]).max()
+    steps = Q.longest_ray(BOX, theta, phi, nx, ny, anchor, sides, s)
+    want = Q.render(BOX, fields, widths, theta, phi, nx, ny, anchor, sides,
+                    nchan, vmin, vmax, s, velocity=vel)
+    total = L.render(BOX, fields, theta, phi, nx, ny, anchor, sides, s)
+    got = eng.render_field_cube(fields, widths, theta, phi, nx, ny, anchor,
+                                sides, nchan, vmin, vmax, s, velocity=vel)
+    assert got.shape == want.shape == (2, nchan, nx, ny)
+    assert not np.isnan(got).any()
+    assert (total > 0.).all()
+    # the last chunk, and in it the second channel block, are lit
+    assert (want[:, CB:, rows:] > 0.).any()
+    assert (got[:, :, rows:] > 0.).any() and (got[:, CB:, rows:] > 0.).any()
+    bound = EPS * (8. * steps * want +
+                   (U_DEV + U_CPU + 4. * slope) * total[:, None])
+    diff = np.abs(got - want)
+    print("s", s, "nx", nx, "steps", steps, "slope", slope,
+          "worst |gpu - cpu| / bound", (diff / bound).max())
+    assert (diff <= bound).all()
+
+
 def test_identity_2_and_the_sign_of_the_velocity(eng):
     """Case 3: theta = 0 (n = (0, 0, 1) exactly), velocities along n and
     edges in multiples of 2^-3: D = 40 added to every u and to the range

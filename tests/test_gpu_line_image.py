@@ -111,6 +111,34 @@ def test_field_images_match_the_restatement(nfields):
     eng.close()
 
 
+@pytest.mark.parametrize("s, nx", [(8, 16384 + 50), (1, (1 << 20) + 50)])
+def test_more_pixel_rows_than_one_launch_takes(s, nx):
+    """Case 2, the chunks of pixel rows: a launch takes 2^22 sample rays
+    (CMI_LINE_IMAGE_LAUNCH_SAMPLES), with ny = 4 that is 16384 pixel rows at
+    s = 8 and 2^20 at s = 1, and a second launch marches the last 50 - through
+    the sample buffer and the reduction at s = 8, straight into the image at
+    its row offset at s = 1. Two fields, no extinction, rtol 1e-13 as in Case
+    2, on the middle of the oblique view's rectangle so that every pixel is
+    lit, the last chunk's among them."""
+    ny = 4
+    rows = (1 << 22) // (ny * s * s)
+    assert nx == rows + 50
+    eng = plain_engine(BOX)
+    rng = np.random.default_rng(23 + s)
+    fields = 10. ** rng.uniform(-2., 1., (2, BOX.n))
+    theta, phi = 0.7, 0.3
+    anchor, sides = L.bounding_rectangle(BOX, theta, phi)
+    anchor, sides = anchor + 0.25 * sides, 0.5 * sides
+    want = L.render(BOX, fields, theta, phi, nx, ny, anchor, sides, s)
+    got = eng.render_field_images(fields, theta, phi, nx, ny, anchor, sides, s)
+    assert got.shape == want.shape == (2, nx, ny)
+    assert (want > 0.).all()
+    assert (got[:, rows:] > 0.).any()
+    print("s", s, "nx", nx, "equal", np.array_equal(got, want))
+    assert np.allclose(got, want, rtol=1e-13, atol=0.)
+    eng.close()
+
+
 LEX_LINES = ["HAlpha", "HBeta", "OIII_5007", "NII_6584", "OII_3727",
              "SII_6725", "NeIII_3869", "SIII_9405", "HeI_5876", "CII_158mu",
              "WFC2_F555W"]

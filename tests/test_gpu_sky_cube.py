@@ -79,6 +79,25 @@ def test_identity_1_one_wide_channel_is_the_sky(eng, nfields):
     assert (sky[0] == 0.).sum() > 400 and (sky[0] > 0.).sum() > 400
 
 
+def test_more_rays_than_one_launch_takes(eng):
+    """Case 1 across the chunks of rays: 2^22 + 1000 rays (CMI_SKY_LAUNCH_RAYS
+    is 2^22) are two launches, and the planes of each come down one by one
+    into their places among the call's rays. Two fields, nchan = 1 over a
+    range that covers every cell: render_field_sky on the same rays, bit for
+    bit, every ray in its place."""
+    fields, widths, vel, _ = random_cells(53)
+    reach = np.abs(vel).sum(axis=0).max() + 6. * widths.max()
+    n = (1 << 22) + 1000
+    origin = probe_origins(BOX)["inside"]
+    d = S.random_directions(np.random.default_rng(7), n)
+    sky = eng.render_field_sky(fields, origin, d)
+    cube = eng.render_field_sky_cube(fields, widths, origin, d, 1, -reach,
+                                     reach, velocity=vel)
+    assert cube.shape == (2, 1, n) and sky.shape == (2, n)
+    assert (sky[:, 1 << 22:] > 0.).any() and not np.array_equal(sky[0], sky[1])
+    assert np.array_equal(cube[:, 0], sky)
+
+
 @pytest.mark.parametrize("nchan", sorted({1, 5, CB, CB + 1, 2 * CB + 3}))
 def test_parity_with_the_restatement(eng, nchan):
     """Case 2: per ray r of n_r steps and per channel c
