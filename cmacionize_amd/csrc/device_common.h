@@ -38,6 +38,11 @@ enum { TYPE_PRIMARY = 0, TYPE_DIFFUSE_HI, TYPE_DIFFUSE_HeI, TYPE_ABSORBED };
 #define CMI_ELECTRON_MASS 9.10938356e-31
 /* the atomic mass unit of the same CODATA set (the reference has none) */
 #define CMI_ATOMIC_MASS_UNIT 1.660539040e-27
+/* C_HI = 3 h c^3 A_10 / (32 pi k_B nu_10^2) in K m^3 s^-1 from the constants
+ * above, nu_10 = 1420405751.768 Hz and A_10 = 2.8843e-15 s^-1, evaluated with
+ * 50 digits and rounded once: the integrated 21-cm opacity of a cell is C_HI
+ * n_HI / T_s, and 1 K km s^-1 of thin emission is 1.8127e18 atoms cm^-2 */
+#define CMI_HI_COLUMN_CONSTANT 5.516606267115072e-20
 
 #define CMI_MAX_SOURCES_INLINE 8
 

@@ -15,6 +15,7 @@
 #include "sky_cube_kernels.h"
 #include "dust_cube_kernels.h"
 #include "continuum_kernels.h"
+#include "absorbing_cube_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -250,6 +251,10 @@ struct cmi_gpu_engine {
      * per launch (0: the images' and the sky maps' own bounds) */
     int continuum_channel_block = CMI_CONTINUUM_FB;
     int64_t continuum_launch_rays = 0;
+    int absorbing_cube_channel_block = CMI_ABSORBING_CB;
+    int absorbing_cube_expm1_call = CMI_ABSORBING_EXPM1_CALL;
+    int absorbing_cube_window_skip = 1;
+    int64_t absorbing_cube_launch_rays = 0;
   } tune;
 
   /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
@@ -1755,6 +1760,17 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.continuum_channel_block = (int)value;
   } else if (k == "continuum_launch_rays")
     e->tune.continuum_launch_rays = value < 0 ? 0 : value;
+  else if (k == "absorbing_cube_channel_block") {
+    if (value != 4 && value != 8)
+      return fail(CMI_GPU_EINVAL, "set_tuning: absorbing_cube_channel_block "
+                  "is 4 or 8 (%lld asked for)", (long long)value);
+    e->tune.absorbing_cube_channel_block = (int)value;
+  } else if (k == "absorbing_cube_expm1_call")
+    e->tune.absorbing_cube_expm1_call = value != 0;
+  else if (k == "absorbing_cube_window_skip")
+    e->tune.absorbing_cube_window_skip = value != 0;
+  else if (k == "absorbing_cube_launch_rays")
+    e->tune.absorbing_cube_launch_rays = value < 0 ? 0 : value;
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
   return CMI_GPU_OK;

@@ -1,7 +1,7 @@
 /*
  * render_driver.h - the host side of the ray-traced renderers (included from
- * engine.hip): line images, line cubes, sky maps, sky cubes and the radio
- * continuum. A render call is
+ * engine.hip): line images, line cubes, sky maps, sky cubes, the radio
+ * continuum and the absorbing line cubes. A render call is
  *   - an arena that owns its device memory,
  *   - a source of per-cell records (the engine's cells or the caller's host
  *     fields), marched a batch at a time,
@@ -11,9 +11,10 @@
  *
  * The template kernels are first named here in the order line_image_march,
  * line_record, field_record, line_cube_march, sky_march, sky_cube_march,
- * continuum_march, continuum_sky_march, always from a function that is no
- * template itself: that order is the order of the kernels in the code object
- * (DESIGN_LOG.md 10 and 15).
+ * continuum_march, continuum_sky_march, hi_record, hi_record_check,
+ * field_absorbing_record, absorbing_cube_march, absorbing_sky_march, always
+ * from a function that is no template itself: that order is the order of the
+ * kernels in the code object (DESIGN_LOG.md 10 and 15).
  */
 #ifndef CMI_RENDER_DRIVER_H
 #define CMI_RENDER_DRIVER_H
@@ -263,20 +264,28 @@ int sky_cube_check(const char *what, int32_t nplanes, int64_t nrays,
   return CMI_GPU_OK;
 }
 
-/* refuses a device array of n velocities of which one is not finite */
-int line_cube_check_velocities(cmi_gpu_engine *e, const char *what,
-                               const double *velocity, int64_t n) {
+/* bad = how many of the n values of a device array are not finite */
+int count_not_finite(cmi_gpu_engine *e, const double *values, int64_t n,
+                     unsigned int &bad) {
   RenderArena arena;
   unsigned int *ninvalid = nullptr;
   CMI_TRY(arena.alloc(ninvalid, 1));
-  unsigned int bad = 0;
+  bad = 0;
   HIP_TRY(hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream));
   cell_velocity_check_kernel<<<grid_blocks(e, n, 8), 256, 0, e->stream>>>(
-      velocity, n, ninvalid);
+      values, n, ninvalid);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
                          e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+/* refuses a device array of n velocities of which one is not finite */
+int line_cube_check_velocities(cmi_gpu_engine *e, const char *what,
+                               const double *velocity, int64_t n) {
+  unsigned int bad = 0;
+  CMI_TRY(count_not_finite(e, velocity, n, bad));
   if (bad)
     return fail(CMI_GPU_EINVAL, "%s: %u velocity component(s) are not finite",
                 what, bad);
@@ -1083,6 +1092,339 @@ int continuum_sky(cmi_gpu_engine *e, const char *what, ContinuumInput &in,
     });
   });
 }
+
+/* --------------------------------------------- absorbing line cubes -- */
+
+/* f(integral_constant<int, CB>, bool_constant<CALL>) for the channel block
+ * and the expm1 form of the engine */
+template <class F> void absorbing_for_variant(int cb, bool call, F &&f) {
+  if (cb == 4) {
+    if (call)
+      f(std::integral_constant<int, 4>(), std::true_type());
+    else
+      f(std::integral_constant<int, 4>(), std::false_type());
+  } else {
+    if (call)
+      f(std::integral_constant<int, 8>(), std::true_type());
+    else
+      f(std::integral_constant<int, 8>(), std::false_type());
+  }
+}
+
+/* Where the records of an absorbing cube come from: the 21-cm line of the
+ * cells as they are (hi set), or the caller's host fields a, sl, b[ncell]
+ * with optional velocity[3][ncell] and {kc, sc}[ncell]. One record per cell
+ * and call: begin() checks, uploads and writes them. */
+struct AbsorbingInput {
+  bool point = false; /* the layout: rays from a point */
+  bool hi = false;
+  double sigma_turb = 0.;
+  int32_t spin_mode = CMI_HI_SPIN_KINETIC;
+  const double *spin = nullptr; /* [1] or [ncell] (host) */
+  bool free_free = true;
+  const double *a = nullptr, *sl = nullptr, *b = nullptr, *velocity = nullptr,
+               *kc = nullptr, *sc = nullptr;
+  /* the direction to the observer, or the observer's velocity */
+  double frame[3] = {0., 0., 0.};
+  double dv = 1.;
+  /* the background: [nchan] (host) or null, then one value for all */
+  const double *background = nullptr;
+  double background_all = 0.;
+  double *records = nullptr; /* device */
+
+  int doubles() const { return point ? 8 : 6; }
+  int begin(cmi_gpu_engine *e, const char *what, RenderArena &arena);
+  /* the background of the channels [c0, c0 + nc) as a march launch takes it */
+  void background_of(int32_t c0, int nc, double *out) const {
+    for (int i = 0; i < CMI_ABSORBING_MAX_CB; ++i)
+      out[i] = i < nc ? (background ? background[c0 + i] : background_all) : 0.;
+  }
+};
+
+/* what the H I calls ask of their arguments before anything is uploaded */
+int hi_check(const cmi_gpu_engine *e, const char *what, double sigma_turb,
+             int32_t spin_mode, const double *spin_temperature,
+             double background_temperature) {
+  CMI_TRY(check_sigma_turb(what, sigma_turb));
+  if (spin_mode != CMI_HI_SPIN_KINETIC && spin_mode != CMI_HI_SPIN_FIXED &&
+      spin_mode != CMI_HI_SPIN_CELLS)
+    return fail(CMI_GPU_EINVAL, "%s: no spin temperature mode %d", what,
+                (int)spin_mode);
+  if (spin_mode != CMI_HI_SPIN_KINETIC && !spin_temperature)
+    return fail(CMI_GPU_EINVAL, "%s: this spin temperature mode needs a spin "
+                "temperature", what);
+  if (spin_mode == CMI_HI_SPIN_FIXED &&
+      (!(spin_temperature[0] > 0.) || !std::isfinite(spin_temperature[0])))
+    return fail(CMI_GPU_EINVAL, "%s: the spin temperature must be positive "
+                "and finite (%.17g)", what, spin_temperature[0]);
+  if (!(background_temperature >= 0.) || !std::isfinite(background_temperature))
+    return fail(CMI_GPU_EINVAL, "%s: the background temperature must be >= 0 "
+                "and finite", what);
+  /* (the render calls have refused a block with their view or rays; the
+   * coefficients are what they march, so they are refused alike) */
+  if (e->grid.decomposed)
+    return fail(CMI_GPU_ESTATE, "%s: not available on a block of a decomposed "
+                "grid", what);
+  return check_have_cells(e, what);
+}
+
+/* B_nu10(T) on the host in the contract's form; 0 for T == 0 */
+double hi_background(double T) {
+  if (!(T > 0.))
+    return 0.;
+  const double nu = CMI_HI_FREQUENCY;
+  const double x = (CMI_PLANCK * nu) / (CMI_BOLTZMANN * T);
+  return (2. * CMI_PLANCK * nu * nu * nu / (CMI_LIGHTSPEED * CMI_LIGHTSPEED)) /
+         std::expm1(x);
+}
+
+/* the caller's background[nchan], or null */
+int absorbing_check_background(const char *what, const double *background,
+                               int32_t nchan) {
+  if (background)
+    for (int32_t c = 0; c < nchan; ++c)
+      if (!std::isfinite(background[c]))
+        return fail(CMI_GPU_EINVAL, "%s: the background of channel %d is not "
+                    "finite", what, (int)c);
+  return CMI_GPU_OK;
+}
+
+int AbsorbingInput::begin(cmi_gpu_engine *e, const char *what,
+                          RenderArena &arena) {
+  const size_t ncell = (size_t)e->ncell;
+  if (hi) {
+    HiRecordArgs r;
+    r.cells = e->cells;
+    r.ncell = e->ncell;
+    r.helium_abundance = e->model.abundance[0];
+    r.weight = cmi_emission_atomic_weight[0];
+    r.sigma_turb = sigma_turb;
+    r.dv = dv;
+    r.spin_fixed = spin_mode == CMI_HI_SPIN_FIXED ? spin[0] : 0.;
+    r.spin_cells = nullptr;
+    if (spin_mode == CMI_HI_SPIN_CELLS) {
+      double *dspin = nullptr;
+      unsigned int bad = 0;
+      CMI_TRY(arena.upload(dspin, spin, ncell));
+      CMI_TRY(count_not_finite(e, dspin, (int64_t)ncell, bad));
+      if (bad)
+        return fail(CMI_GPU_EINVAL, "%s: %u spin temperature(s) are not "
+                    "finite", what, bad);
+      r.spin_cells = dspin;
+    }
+    r.spin_mode = spin_mode;
+    r.free_free = free_free ? 1 : 0;
+    for (int k = 0; k < 3; ++k)
+      r.frame[k] = frame[k];
+    r.velocity = e->cell_velocities;
+    CMI_TRY(arena.alloc(records, ncell * doubles()));
+    r.records = records;
+    const int blocks = grid_blocks(e, e->ncell, 8);
+    if (point)
+      hi_record_kernel<true><<<blocks, 256, 0, e->stream>>>(r);
+    else
+      hi_record_kernel<false><<<blocks, 256, 0, e->stream>>>(r);
+    HIP_TRY(hipGetLastError());
+    /* finite cells can still overflow (a spin temperature of 1e-322 K gives
+     * a = inf, and inf * 0 is NaN): the records are held to what the
+     * caller's fields are held to */
+    unsigned int *ninvalid = nullptr;
+    unsigned int bad = 0;
+    CMI_TRY(arena.alloc(ninvalid, 1));
+    HIP_TRY(hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream));
+    if (point)
+      hi_record_check_kernel<true><<<blocks, 256, 0, e->stream>>>(
+          records, e->ncell, ninvalid);
+    else
+      hi_record_check_kernel<false><<<blocks, 256, 0, e->stream>>>(
+          records, e->ncell, ninvalid);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                           e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (bad)
+      return fail(CMI_GPU_EINVAL, "%s: %u cell(s) have a 21-cm coefficient "
+                  "that is not finite (a / dv, b, sl, kc, sc or sl - sc; a "
+                  "spin temperature too close to 0 does that)", what, bad);
+    return CMI_GPU_OK;
+  }
+  FieldAbsorbingRecordArgs r;
+  double *da = nullptr, *dsl = nullptr, *db = nullptr, *dkc = nullptr,
+         *dsc = nullptr, *dvelocity = nullptr;
+  unsigned int *ninvalid = nullptr;
+  if (velocity) {
+    CMI_TRY(arena.upload(dvelocity, velocity, 3 * ncell));
+    CMI_TRY(line_cube_check_velocities(e, what, dvelocity, 3 * (int64_t)ncell));
+  }
+  CMI_TRY(arena.upload(da, a, ncell));
+  CMI_TRY(arena.upload(dsl, sl, ncell));
+  CMI_TRY(arena.upload(db, b, ncell));
+  if (kc) {
+    CMI_TRY(arena.upload(dkc, kc, ncell));
+    CMI_TRY(arena.upload(dsc, sc, ncell));
+  }
+  r.a = da;
+  r.sl = dsl;
+  r.b = db;
+  r.kc = dkc;
+  r.sc = dsc;
+  r.velocity = dvelocity;
+  r.ncell = e->ncell;
+  r.dv = dv;
+  for (int k = 0; k < 3; ++k)
+    r.frame[k] = frame[k];
+  r.records = nullptr;
+  CMI_TRY(arena.alloc(ninvalid, 5));
+  HIP_TRY(hipMemsetAsync(ninvalid, 0, 5 * sizeof(unsigned int), e->stream));
+  absorbing_field_check_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0,
+                                 e->stream>>>(r, ninvalid);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  unsigned int bad[5] = {0, 0, 0, 0, 0};
+  HIP_TRY(hipMemcpy(bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost));
+  if (bad[0])
+    return fail(CMI_GPU_EINVAL, "%s: %u integrated line opacities are "
+                "negative, not finite or not finite once divided by the "
+                "channel width", what, bad[0]);
+  if (bad[1])
+    return fail(CMI_GPU_EINVAL, "%s: %u width(s) are negative or not finite",
+                what, bad[1]);
+  if (bad[2])
+    return fail(CMI_GPU_EINVAL, "%s: %u continuum absorption coefficient(s) "
+                "are negative or not finite", what, bad[2]);
+  if (bad[3])
+    return fail(CMI_GPU_EINVAL, "%s: %u line source function value(s) are not "
+                "finite", what, bad[3]);
+  if (bad[4])
+    return fail(CMI_GPU_EINVAL, "%s: %u continuum source function value(s) "
+                "are not finite, or not a finite distance from the line's",
+                what, bad[4]);
+  CMI_TRY(arena.alloc(records, ncell * doubles()));
+  r.records = records;
+  const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
+  if (point)
+    field_absorbing_record_kernel<true><<<blocks, 256, 0, e->stream>>>(r);
+  else
+    field_absorbing_record_kernel<false><<<blocks, 256, 0, e->stream>>>(r);
+  HIP_TRY(hipGetLastError());
+  return CMI_GPU_OK;
+}
+
+/* what the general calls ask of their pointers */
+int absorbing_check_fields(const char *what, const AbsorbingInput &in) {
+  if (!in.a || !in.sl || !in.b)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if ((in.kc == nullptr) != (in.sc == nullptr))
+    return fail(CMI_GPU_EINVAL, "%s: the continuum opacity and source "
+                "function come together or not at all", what);
+  return CMI_GPU_OK;
+}
+
+/* cube[nchan][nx * ny] (host) of the parallel camera: the records, then per
+ * chunk of pixel rows and block of CB channels one march launch */
+int absorbing_cube(cmi_gpu_engine *e, const char *what, AbsorbingInput &in,
+                   const LineCubeAxis &axis, const LineViewDev &v,
+                   double *cube) {
+  HIP_TRY(hipSetDevice(e->device));
+  RenderArena arena;
+  ParallelCamera cam;
+  in.point = false;
+  in.dv = axis.dv;
+  CMI_TRY(in.begin(e, what, arena));
+  const int cb = e->tune.absorbing_cube_channel_block;
+  const bool call = e->tune.absorbing_cube_expm1_call != 0;
+  /* (the sample buffer holds CB channels of a chunk's rows) */
+  CMI_TRY(cam.begin(e, v,
+                    e->tune.absorbing_cube_launch_rays
+                        ? e->tune.absorbing_cube_launch_rays
+                        : CMI_LINE_IMAGE_LAUNCH_SAMPLES / cb,
+                    cb, (size_t)axis.nchan, arena));
+  CMI_TRY(cam.march([&]() -> int {
+    for (int32_t c0 = 0; c0 < axis.nchan; c0 += cb) {
+      AbsorbingMarchArgs a;
+      a.grid = e->grid;
+      a.view = v;
+      a.records = in.records;
+      a.sx0 = cam.sx0();
+      a.sx1 = cam.sx1();
+      a.c0 = c0;
+      a.nc = std::min<int32_t>(cb, axis.nchan - c0);
+      a.full = e->tune.absorbing_cube_window_skip ? 0 : 1;
+      a.pad = 0;
+      a.vmin = axis.vmin;
+      a.dv = axis.dv;
+      a.channel_stride = cam.plane_stride();
+      a.out = cam.out(c0);
+      in.background_of(c0, a.nc, a.background);
+      EventPair ev;
+      CMI_TRY(timer_begin(e, ev));
+      absorbing_for_variant(cb, call, [&](auto width, auto as_call) {
+        absorbing_cube_march_kernel<decltype(width)::value,
+                                    decltype(as_call)::value>
+            <<<cam.tiles(), 256, 0, e->stream>>>(a);
+      });
+      HIP_TRY(hipGetLastError());
+      CMI_TRY(timer_end(e, e->kernel_events, ev,
+                        (uint64_t)((a.sx1 - a.sx0) * cam.NY)));
+      CMI_TRY(cam.reduce(0, a.nc, c0));
+    }
+    return CMI_GPU_OK;
+  }));
+  return cam.download(cube, (size_t)axis.nchan);
+}
+
+/* out[nchan][nrays] (host) of the rays from a point: the records, then per
+ * chunk of rays and block of CB channels one march launch */
+int absorbing_sky_cube(cmi_gpu_engine *e, const char *what, AbsorbingInput &in,
+                       const LineCubeAxis &axis, const double *origin,
+                       int64_t nrays, const double *directions, double *out) {
+  HIP_TRY(hipSetDevice(e->device));
+  RenderArena arena;
+  PointCamera cam;
+  in.point = true;
+  in.dv = axis.dv;
+  CMI_TRY(in.begin(e, what, arena));
+  const int cb = e->tune.absorbing_cube_channel_block;
+  const bool call = e->tune.absorbing_cube_expm1_call != 0;
+  CMI_TRY(cam.begin(e, origin, nrays, directions,
+                    e->tune.absorbing_cube_launch_rays
+                        ? e->tune.absorbing_cube_launch_rays
+                        : std::min<int64_t>(CMI_SKY_LAUNCH_RAYS,
+                                            CMI_SKY_CUBE_LAUNCH_VALUES /
+                                                axis.nchan),
+                    (size_t)axis.nchan, arena));
+  cam.one_copy = true;
+  return cam.march((size_t)axis.nchan, out, [&](int64_t n) -> int {
+    for (int32_t c0 = 0; c0 < axis.nchan; c0 += cb) {
+      AbsorbingSkyMarchArgs a;
+      a.grid = e->grid;
+      for (int k = 0; k < 3; ++k)
+        a.origin[k] = origin[k];
+      a.directions = cam.directions;
+      a.records = in.records;
+      a.nrays = n;
+      a.c0 = c0;
+      a.nc = std::min<int32_t>(cb, axis.nchan - c0);
+      a.full = e->tune.absorbing_cube_window_skip ? 0 : 1;
+      a.pad = 0;
+      a.vmin = axis.vmin;
+      a.dv = axis.dv;
+      a.channel_stride = cam.chunk;
+      a.out = cam.out;
+      in.background_of(c0, a.nc, a.background);
+      EventPair ev;
+      CMI_TRY(timer_begin(e, ev));
+      absorbing_for_variant(cb, call, [&](auto width, auto as_call) {
+        absorbing_sky_march_kernel<decltype(width)::value,
+                                        decltype(as_call)::value>
+            <<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(a);
+      });
+      HIP_TRY(hipGetLastError());
+      CMI_TRY(timer_end(e, e->kernel_events, ev, (uint64_t)n));
+    }
+    return CMI_GPU_OK;
+  });
+}
 } // namespace
 } // extern "C++"
 
@@ -1646,6 +1988,255 @@ int cmi_gpu_continuum_probe(cmi_gpu_engine *e, int32_t nf, const double *kappa,
   continuum_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
       e->grid, v, point, origin[0], origin[1], origin[2], drays, n, in.dkappa,
       in.dsource, dbackground, nf, e->ncell, max_cells, drows);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, drows, sizeof(double) * nvalue,
+                    hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+}
+
+/* --------------------------------------------- absorbing line cubes -- */
+
+int cmi_gpu_hi_coefficients(cmi_gpu_engine *e, double sigma_turb,
+                            int32_t spin_mode, const double *spin_temperature,
+                            int32_t free_free, double *a, double *sl,
+                            double *b, double *kc, double *sc) {
+  static const char *what = "hi_coefficients";
+  if (!e || !a || !sl || !b || !kc || !sc)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(hi_check(e, what, sigma_turb, spin_mode, spin_temperature, 0.));
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t ncell = (size_t)e->ncell;
+  std::vector<double> host;
+  try {
+    host.resize(6 * ncell);
+  } catch (const std::bad_alloc &) {
+    return fail(CMI_GPU_ENOMEM, "%s: out of host memory", what);
+  }
+  RenderArena arena;
+  AbsorbingInput in;
+  in.hi = true;
+  in.sigma_turb = sigma_turb;
+  in.spin_mode = spin_mode;
+  in.spin = spin_temperature;
+  in.free_free = free_free != 0;
+  /* (a / 1 is a) */
+  in.dv = 1.;
+  CMI_TRY(in.begin(e, what, arena));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(host.data(), in.records, sizeof(double) * 6 * ncell,
+                    hipMemcpyDeviceToHost));
+  for (size_t c = 0; c < ncell; ++c) {
+    a[c] = host[6 * c];
+    b[c] = host[6 * c + 2];
+    sl[c] = host[6 * c + 3];
+    kc[c] = host[6 * c + 4];
+    sc[c] = host[6 * c + 5];
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_hi_cube(cmi_gpu_engine *e, double theta, double phi,
+                           int32_t nx, int32_t ny, const double *anchor,
+                           const double *sides, int32_t supersample,
+                           int32_t nchan, double vmin, double vmax,
+                           double sigma_turb, int32_t spin_mode,
+                           const double *spin_temperature, int32_t free_free,
+                           double background_temperature, double *cube) {
+  static const char *what = "render_hi_cube";
+  if (!e || !cube)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, 1, nx, ny, nchan, vmin, vmax, axis));
+  CMI_TRY(hi_check(e, what, sigma_turb, spin_mode, spin_temperature,
+                   background_temperature));
+  AbsorbingInput in;
+  in.hi = true;
+  in.sigma_turb = sigma_turb;
+  in.spin_mode = spin_mode;
+  in.spin = spin_temperature;
+  in.free_free = free_free != 0;
+  in.background_all = hi_background(background_temperature);
+  for (int k = 0; k < 3; ++k)
+    in.frame[k] = v.n[k];
+  return absorbing_cube(e, what, in, axis, v, cube);
+}
+
+int cmi_gpu_render_hi_sky_cube(cmi_gpu_engine *e, const double *origin,
+                               const double *observer_velocity, int64_t nrays,
+                               const double *directions, int32_t nchan,
+                               double vmin, double vmax, double sigma_turb,
+                               int32_t spin_mode,
+                               const double *spin_temperature,
+                               int32_t free_free,
+                               double background_temperature, double *out) {
+  static const char *what = "render_hi_sky_cube";
+  if (!e || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  LineCubeAxis axis;
+  AbsorbingInput in;
+  CMI_TRY(sky_cube_check(what, 1, nrays, nchan, vmin, vmax, observer_velocity,
+                         axis, in.frame));
+  CMI_TRY(hi_check(e, what, sigma_turb, spin_mode, spin_temperature,
+                   background_temperature));
+  in.hi = true;
+  in.sigma_turb = sigma_turb;
+  in.spin_mode = spin_mode;
+  in.spin = spin_temperature;
+  in.free_free = free_free != 0;
+  in.background_all = hi_background(background_temperature);
+  return absorbing_sky_cube(e, what, in, axis, origin, nrays, directions, out);
+}
+
+int cmi_gpu_render_hi_sky_map_cube(
+    cmi_gpu_engine *e, const double *origin, const double *frame,
+    double lon_min, double lon_max, double lat_min, double lat_max,
+    int32_t nlon, int32_t nlat, const double *observer_velocity,
+    int32_t nchan, double vmin, double vmax, double sigma_turb,
+    int32_t spin_mode, const double *spin_temperature, int32_t free_free,
+    double background_temperature, double *cube) {
+  static const char *what = "render_hi_sky_map_cube";
+  if (!e || !cube)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(sky_map_check(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                        nlat));
+  const int64_t npixel = (int64_t)nlon * nlat;
+  if (nchan >= 1 &&
+      (nchan > (1 << 28) || (int64_t)nchan * npixel > (1ll << 28)))
+    return fail(CMI_GPU_EINVAL, "%s: %d channels of %d x %d pixels: a cube has "
+                "at most 2^28 values", what, (int)nchan, (int)nlon, (int)nlat);
+  SkyMapRays map;
+  CMI_TRY(map.begin(what, frame, lon_min, lon_max, lat_min, lat_max, nlon,
+                    nlat, (size_t)std::max<int32_t>(nchan, 1)));
+  CMI_TRY(cmi_gpu_render_hi_sky_cube(
+      e, origin, observer_velocity, npixel, map.directions.data(), nchan, vmin,
+      vmax, sigma_turb, spin_mode, spin_temperature, free_free,
+      background_temperature, map.rays.data()));
+  map.scatter(cube);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_render_field_absorbing_cube(
+    cmi_gpu_engine *e, const double *a, const double *sl, const double *b,
+    const double *velocity, const double *kc, const double *sc,
+    const double *background, double theta, double phi, int32_t nx,
+    int32_t ny, const double *anchor, const double *sides,
+    int32_t supersample, int32_t nchan, double vmin, double vmax,
+    double *cube) {
+  static const char *what = "render_field_absorbing_cube";
+  if (!e || !cube)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  AbsorbingInput in;
+  in.a = a;
+  in.sl = sl;
+  in.b = b;
+  in.velocity = velocity;
+  in.kc = kc;
+  in.sc = sc;
+  in.background = background;
+  CMI_TRY(absorbing_check_fields(what, in));
+  LineViewDev v;
+  CMI_TRY(line_image_geometry(e, what, theta, phi, nx, ny, anchor, sides,
+                              supersample, v));
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, 1, nx, ny, nchan, vmin, vmax, axis));
+  CMI_TRY(absorbing_check_background(what, background, nchan));
+  for (int k = 0; k < 3; ++k)
+    in.frame[k] = v.n[k];
+  return absorbing_cube(e, what, in, axis, v, cube);
+}
+
+int cmi_gpu_render_field_absorbing_sky_cube(
+    cmi_gpu_engine *e, const double *a, const double *sl, const double *b,
+    const double *velocity, const double *kc, const double *sc,
+    const double *background, const double *origin,
+    const double *observer_velocity, int64_t nrays, const double *directions,
+    int32_t nchan, double vmin, double vmax, double *out) {
+  static const char *what = "render_field_absorbing_sky_cube";
+  if (!e || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  AbsorbingInput in;
+  in.a = a;
+  in.sl = sl;
+  in.b = b;
+  in.velocity = velocity;
+  in.kc = kc;
+  in.sc = sc;
+  in.background = background;
+  CMI_TRY(absorbing_check_fields(what, in));
+  CMI_TRY(sky_check(e, what, origin, nrays, 1ll << 28, directions));
+  LineCubeAxis axis;
+  CMI_TRY(sky_cube_check(what, 1, nrays, nchan, vmin, vmax, observer_velocity,
+                         axis, in.frame));
+  CMI_TRY(absorbing_check_background(what, background, nchan));
+  return absorbing_sky_cube(e, what, in, axis, origin, nrays, directions, out);
+}
+
+int cmi_gpu_absorbing_cube_probe(
+    cmi_gpu_engine *e, const double *a, const double *sl, const double *b,
+    const double *velocity, const double *kc, const double *sc,
+    const double *background, int32_t nchan, double vmin, double vmax,
+    int32_t point, const double *view, const double *observer_velocity,
+    int64_t n, const double *rays, int32_t max_cells, double *out) {
+  static const char *what = "absorbing_cube_probe";
+  if (!e || !view || !out || max_cells < 0 || (point != 0 && point != 1))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  if (nchan < 1 || nchan > 1024)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and 1024 channels (%d asked "
+                "for)", what, (int)nchan);
+  AbsorbingInput in;
+  in.a = a;
+  in.sl = sl;
+  in.b = b;
+  in.velocity = velocity;
+  in.kc = kc;
+  in.sc = sc;
+  in.point = point != 0;
+  CMI_TRY(absorbing_check_fields(what, in));
+  LineViewDev v;
+  LineCubeAxis axis;
+  double origin[3] = {0., 0., 0.};
+  if (point) {
+    CMI_TRY(sky_check(e, what, view, n, 1ll << 20, rays));
+    CMI_TRY(sky_cube_check(what, 1, n, nchan, vmin, vmax, observer_velocity,
+                           axis, in.frame));
+    for (int k = 0; k < 3; ++k)
+      origin[k] = view[k];
+    /* (not read by the kernel; set so that it is passed initialised) */
+    std::memset(&v, 0, sizeof v);
+  } else {
+    if (n <= 0 || n > (1ll << 20) || !rays)
+      return fail(CMI_GPU_EINVAL, "%s: between 1 and 2^20 rays (%lld asked "
+                  "for)", what, (long long)n);
+    CMI_TRY(line_image_view(e, what, view[0], view[1], v));
+    CMI_TRY(check_image_coordinates(what, n, rays));
+    CMI_TRY(line_cube_axis(what, 1, 1, 1, nchan, vmin, vmax, axis));
+    for (int k = 0; k < 3; ++k)
+      in.frame[k] = v.n[k];
+  }
+  CMI_TRY(absorbing_check_background(what, background, nchan));
+  HIP_TRY(hipSetDevice(e->device));
+  RenderArena arena;
+  in.dv = axis.dv;
+  CMI_TRY(in.begin(e, what, arena));
+  const size_t nvalue =
+      (3 + (2 + (size_t)nchan) * (size_t)max_cells + (size_t)nchan) *
+      (size_t)n;
+  double *drays = nullptr, *drows = nullptr, *dbackground = nullptr;
+  std::vector<double> bg((size_t)nchan, 0.);
+  if (background)
+    std::copy(background, background + nchan, bg.begin());
+  CMI_TRY(arena.alloc(drows, nvalue));
+  CMI_TRY(arena.upload(dbackground, bg.data(), (size_t)nchan));
+  CMI_TRY(arena.upload(drays, rays, (point ? 3 : 2) * (size_t)n));
+  HIP_TRY(hipMemsetAsync(drows, 0, sizeof(double) * nvalue, e->stream));
+  absorbing_cube_probe_kernel<<<(unsigned)((n + 63) / 64), 64, 0, e->stream>>>(
+      e->grid, v, point, origin[0], origin[1], origin[2], drays, n, in.records,
+      dbackground, nchan, axis.vmin, axis.dv, max_cells, drows);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   HIP_TRY(hipMemcpy(out, drows, sizeof(double) * nvalue,

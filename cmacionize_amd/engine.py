@@ -130,6 +130,11 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_field_continuum_images", "cmi_gpu_render_continuum_sky",
     "cmi_gpu_render_field_continuum_sky",
     "cmi_gpu_render_continuum_sky_map", "cmi_gpu_continuum_probe",
+    "cmi_gpu_hi_coefficients", "cmi_gpu_render_hi_cube",
+    "cmi_gpu_render_hi_sky_cube", "cmi_gpu_render_hi_sky_map_cube",
+    "cmi_gpu_render_field_absorbing_cube",
+    "cmi_gpu_render_field_absorbing_sky_cube",
+    "cmi_gpu_absorbing_cube_probe",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -242,6 +247,27 @@ def continuum_flux_density(I, pixel_solid_angle):
     I = np.asarray(I, dtype=np.float64)
     w = np.asarray(pixel_solid_angle, dtype=np.float64)
     return (I * w).reshape(I.shape[0], -1).sum(axis=1)
+
+
+# the 21-cm line of the absorbing line cubes (csrc/absorbing_cube_kernels.h,
+# csrc/device_common.h): the hyperfine frequency (Hz), its Einstein A (s^-1)
+# and C_HI = 3 h c^3 A_10 / (32 pi k_B nu_10^2) in K m^3 s^-1
+HI_FREQUENCY = 1420405751.768
+HI_EINSTEIN_A = 2.8843e-15
+HI_COLUMN_CONSTANT = 5.516606267115072e-20
+
+# how the spin temperature of the H I calls is given
+HI_SPIN_KINETIC, HI_SPIN_FIXED, HI_SPIN_CELLS = 0, 1, 2
+
+
+def hi_column_density(cube, dv):
+    """The H I column density (m^-2) of the optically thin limit from an H I
+    cube (nchan, ...) in W m^-2 Hz^-1 sr^-1 with channels of dv m s^-1: the
+    sum over the channels of the Rayleigh-Jeans brightness temperature times
+    dv, over HI_COLUMN_CONSTANT. 1e-4 of it is the column in cm^-2."""
+    T_b = brightness_temperature(np.asarray(cube, dtype=np.float64),
+                                 HI_FREQUENCY)
+    return T_b.sum(axis=0) * dv / HI_COLUMN_CONSTANT
 
 
 _lib = None
@@ -474,6 +500,27 @@ def load_library():
         L.cmi_gpu_continuum_probe.argtypes = [
             vp, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp, C.c_int64, _dp,
             C.c_int32, _dp]
+    # (likewise a build from before the absorbing line cubes)
+    if hasattr(L, "cmi_gpu_hi_coefficients"):
+        hi = [C.c_double, C.c_int32, _dp, C.c_int32]
+        axis = [C.c_int32, C.c_double, C.c_double]
+        L.cmi_gpu_hi_coefficients.argtypes = [vp] + hi + [_dp] * 5
+        L.cmi_gpu_render_hi_cube.argtypes = [
+            vp, C.c_double, C.c_double, C.c_int32, C.c_int32, _dp, _dp,
+            C.c_int32] + axis + hi + [C.c_double, _dp]
+        L.cmi_gpu_render_hi_sky_cube.argtypes = [
+            vp, _dp, _dp, C.c_int64, _dp] + axis + hi + [C.c_double, _dp]
+        L.cmi_gpu_render_hi_sky_map_cube.argtypes = [
+            vp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_double,
+            C.c_int32, C.c_int32, _dp] + axis + hi + [C.c_double, _dp]
+        L.cmi_gpu_render_field_absorbing_cube.argtypes = [
+            vp] + [_dp] * 7 + [C.c_double, C.c_double, C.c_int32, C.c_int32,
+                               _dp, _dp, C.c_int32] + axis + [_dp]
+        L.cmi_gpu_render_field_absorbing_sky_cube.argtypes = [
+            vp] + [_dp] * 7 + [_dp, _dp, C.c_int64, _dp] + axis + [_dp]
+        L.cmi_gpu_absorbing_cube_probe.argtypes = [
+            vp] + [_dp] * 7 + axis + [C.c_int32, _dp, _dp, C.c_int64, _dp,
+                                      C.c_int32, _dp]
     _lib = L
     return L
 
@@ -1538,6 +1585,167 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_continuum_probe(
             self._h, nf, _p(k), _p(S), _p_or_none(bg),
             int(point), _p(view), len(r), _p(r), int(max_cells), _p(out)))
+        return out
+
+    # absorbing line cubes ---------------------------------------------------
+    def _spin(self, spin_temperature):
+        """(mode, array or None) of a spin temperature: None (the kinetic
+        temperature), one value or one per cell"""
+        if spin_temperature is None:
+            return HI_SPIN_KINETIC, None
+        t = _f64(spin_temperature)
+        if t.ndim == 0 or t.size == 1 and self.n != 1:
+            return HI_SPIN_FIXED, t.reshape(1)
+        return HI_SPIN_CELLS, t.reshape(self.n)
+
+    def _absorbing_fields(self, a, sl, b, velocity, kc, sc):
+        return [_f64(a).reshape(self.n), _f64(sl).reshape(self.n),
+                _f64(b).reshape(self.n),
+                None if velocity is None else _f64(velocity).reshape(3,
+                                                                     self.n),
+                None if kc is None else _f64(kc).reshape(self.n),
+                None if sc is None else _f64(sc).reshape(self.n)]
+
+    def hi_coefficients(self, sigma_turb=0., spin_temperature=None,
+                        free_free=True):
+        """What the H I calls march, per cell in the engine's cell order: the
+        dict {a, sl, b, kc, sc} of the integrated 21-cm opacity (m^-1 m s^-1),
+        the line source function B_nu(T_s), the Gaussian width (m s^-1) and
+        the free-free absorption coefficient and source function at the line
+        (include/cmi_gpu.h, "absorbing line cubes")."""
+        mode, ts = self._spin(spin_temperature)
+        out = [np.zeros(self.n) for _ in range(5)]
+        self._check(self._lib.cmi_gpu_hi_coefficients(
+            self._h, sigma_turb, mode, _p_or_none(ts), int(bool(free_free)),
+            *[_p(o) for o in out]))
+        return dict(zip(("a", "sl", "b", "kc", "sc"), out))
+
+    def render_hi_cube(self, theta, phi, nx, ny, anchor, sides, nchan, vmin,
+                       vmax, supersample=1, sigma_turb=0.,
+                       spin_temperature=None, free_free=True,
+                       background_temperature=0.):
+        """The 21-cm cube of the neutral gas for the view (theta, phi):
+        (nchan, nx, ny), the specific intensity in W m^-2 Hz^-1 sr^-1 of
+        `nchan` channels of equal width over [vmin, vmax) m s^-1, with the
+        line's own absorption, the free-free continuum of the ionized gas
+        (`free_free`) and a background of `background_temperature` K behind
+        the box. `spin_temperature`: None (the cells' kinetic temperature),
+        one value or one per cell (K). Velocities from set_cell_velocities;
+        the view arguments are those of render_line_images."""
+        mode, ts = self._spin(spin_temperature)
+        a = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((max(int(nchan), 0), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_hi_cube(
+            self._h, theta, phi, int(nx), int(ny), _p(a), _p(s),
+            int(supersample), int(nchan), vmin, vmax, sigma_turb, mode,
+            _p_or_none(ts), int(bool(free_free)), background_temperature,
+            _p(out)))
+        return out
+
+    def render_hi_sky_cube(self, origin, directions, nchan, vmin, vmax,
+                           sigma_turb=0., spin_temperature=None,
+                           free_free=True, background_temperature=0.,
+                           observer_velocity=None):
+        """The 21-cm spectrum along each of the unit vectors
+        directions[nrays][3] from `origin` (m): (nchan, nrays). A cell seen
+        along d by an observer of `observer_velocity` (m s^-1; None: at rest)
+        has the radial velocity (v - v_obs) . d."""
+        mode, ts = self._spin(spin_temperature)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((max(int(nchan), 0), len(d)))
+        self._check(self._lib.cmi_gpu_render_hi_sky_cube(
+            self._h, _p(o), _p_or_none(vo), len(d), _p(d), int(nchan), vmin,
+            vmax, sigma_turb, mode, _p_or_none(ts), int(bool(free_free)),
+            background_temperature, _p(out)))
+        return out
+
+    def render_hi_sky_map_cube(self, origin, nlon, nlat, nchan, vmin, vmax,
+                               lon_range=FULL_SKY_LONGITUDE,
+                               lat_range=FULL_SKY_LATITUDE,
+                               frame=IDENTITY_FRAME, sigma_turb=0.,
+                               spin_temperature=None, free_free=True,
+                               background_temperature=0.,
+                               observer_velocity=None):
+        """The longitude-latitude-velocity cube of the 21-cm line around
+        `origin`: (nchan, nlon, nlat), the pixels of sky_map_directions."""
+        mode, ts = self._spin(spin_temperature)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        f = _f64(frame).reshape(9)
+        out = np.zeros((max(int(nchan), 0), max(int(nlon), 0),
+                        max(int(nlat), 0)))
+        self._check(self._lib.cmi_gpu_render_hi_sky_map_cube(
+            self._h, _p(o), _p(f), lon_range[0], lon_range[1], lat_range[0],
+            lat_range[1], int(nlon), int(nlat), _p_or_none(vo), int(nchan),
+            vmin, vmax, sigma_turb, mode, _p_or_none(ts),
+            int(bool(free_free)), background_temperature, _p(out)))
+        return out
+
+    def render_field_absorbing_cube(self, a, sl, b, theta, phi, nx, ny, anchor,
+                                    sides, nchan, vmin, vmax, supersample=1,
+                                    velocity=None, kc=None, sc=None,
+                                    background=None):
+        """The cube of any absorbing line: a[ncell] the line opacity
+        integrated over velocity (m^-1 m s^-1), sl[ncell] its source function,
+        b[ncell] the Gaussian widths (m s^-1), optional velocity[3][ncell],
+        an optional continuum kc[ncell] (m^-1) and sc[ncell] in the same cells
+        and `background` (a scalar or [nchan]); (nchan, nx, ny)."""
+        f = self._absorbing_fields(a, sl, b, velocity, kc, sc)
+        bg = self._background(background, max(int(nchan), 0))
+        an = _f64(anchor).reshape(2)
+        s = _f64(sides).reshape(2)
+        out = np.zeros((max(int(nchan), 0), max(int(nx), 0), max(int(ny), 0)))
+        self._check(self._lib.cmi_gpu_render_field_absorbing_cube(
+            self._h, *[_p_or_none(x) for x in f], _p_or_none(bg), theta, phi,
+            int(nx), int(ny), _p(an), _p(s), int(supersample), int(nchan),
+            vmin, vmax, _p(out)))
+        return out
+
+    def render_field_absorbing_sky_cube(self, a, sl, b, origin, directions,
+                                        nchan, vmin, vmax, velocity=None,
+                                        kc=None, sc=None, background=None,
+                                        observer_velocity=None):
+        """The same along rays from a point; (nchan, nrays)."""
+        f = self._absorbing_fields(a, sl, b, velocity, kc, sc)
+        bg = self._background(background, max(int(nchan), 0))
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o = _f64(origin).reshape(3)
+        d = _f64(directions).reshape(-1, 3)
+        out = np.zeros((max(int(nchan), 0), len(d)))
+        self._check(self._lib.cmi_gpu_render_field_absorbing_sky_cube(
+            self._h, *[_p_or_none(x) for x in f], _p_or_none(bg), _p(o),
+            _p_or_none(vo), len(d), _p(d), int(nchan), vmin, vmax, _p(out)))
+        return out
+
+    def absorbing_cube_probe(self, a, sl, b, rays, max_cells, nchan, vmin,
+                             vmax, theta=None, phi=None, origin=None,
+                             velocity=None, kc=None, sc=None, background=None,
+                             observer_velocity=None):
+        """The march of chosen rays through the caller's fields, cell by
+        cell: rows {t0, t1, steps, cells[max_cells], ds[max_cells],
+        I[nchan][max_cells], I_end[nchan]}. With theta and phi the rays are
+        image coordinates [n][2] of the parallel camera, with origin
+        directions [n][3]."""
+        f = self._absorbing_fields(a, sl, b, velocity, kc, sc)
+        nchan = int(nchan)
+        bg = self._background(background, max(nchan, 0))
+        point = origin is not None
+        view = _f64(origin).reshape(3) if point else _f64([theta, phi])
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        r = _f64(rays).reshape(-1, 3 if point else 2)
+        out = np.zeros((len(r), 3 + (2 + max(nchan, 0)) * max_cells +
+                        max(nchan, 0)))
+        self._check(self._lib.cmi_gpu_absorbing_cube_probe(
+            self._h, *[_p_or_none(x) for x in f], _p_or_none(bg), nchan, vmin,
+            vmax, int(point), _p(view), _p_or_none(vo), len(r), _p(r),
+            int(max_cells), _p(out)))
         return out
 
     # sky cubes --------------------------------------------------------------

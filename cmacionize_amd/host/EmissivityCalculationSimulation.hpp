@@ -127,6 +127,20 @@
  * observer k >= 1), raw doubles [f][ix][iy] in W m^-2 Hz^-1 sr^-1, and the
  * frequencies as <prefix>_continuum_frequencies.txt, one line "nu bg" per
  * frequency with 17 significant digits. Needs type BinaryArray.
+ * H I cubes (read only with "HI cube: true", in either block,
+ * which needs the block's "velocity channels", "velocity minimum" and
+ * "velocity maximum"; the turbulent dispersion, the velocity field and the
+ * observer velocities are the block's):
+ *   EmissionImages:HI spin temperature type      Kinetic (the cells'
+ *                    temperature) or Fixed
+ *   EmissionImages:HI spin temperature           required for Fixed, > 0
+ *   EmissionImages:HI free-free continuum        true: the ionized gas's
+ *                    free-free emission and absorption at 1420 MHz
+ *   EmissionImages:HI background temperature     0. K: B_nu(T_bg) behind the
+ *                    box in every channel
+ * The 21-cm line of the neutral gas with its own absorption is then written
+ * as <prefix>_HI_cube.dat (_HI_cube_view<k>.dat), raw doubles [channel][ix]
+ * [iy] in W m^-2 Hz^-1 sr^-1. Needs type BinaryArray.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -301,6 +315,49 @@ class EmissivityCalculationSimulation {
       }
     }
 
+    /* the 21-cm keys of a block (read only if the block has "HI cube: true",
+     * looked at like "scattering") */
+    bool hi_cube = false, hi_free_free = true;
+    int32_t hi_spin_mode = 0; /* 0: the kinetic temperature, 1: one value */
+    double hi_spin_temperature = 0., hi_background_temperature = 0.;
+
+    void read_hi(ParameterFile &params, const std::string &block,
+                 const std::string &type) {
+      if (!params.peek_bool(block + ":HI cube"))
+        return;
+      hi_cube = params.get_bool(block + ":HI cube", false);
+      if (type != "BinaryArray")
+        throw ParameterError(block + ":HI cube needs type BinaryArray: a cube "
+                             "is written as raw doubles");
+      if (!cubes)
+        throw ParameterError(block + ":HI cube needs velocity channels, "
+                             "velocity minimum and velocity maximum");
+      const std::string kind =
+          params.get_string(block + ":HI spin temperature type", "Kinetic");
+      if (kind == "Fixed") {
+        if (!params.has_value(block + ":HI spin temperature"))
+          throw ParameterError(block + ":HI spin temperature is required with "
+                               "HI spin temperature type Fixed");
+        hi_spin_mode = 1;
+        hi_spin_temperature = params.get_physical_value(
+            QUANTITY_TEMPERATURE, block + ":HI spin temperature", "0. K");
+        if (!(hi_spin_temperature > 0.) || !std::isfinite(hi_spin_temperature))
+          throw ParameterError(block + ":HI spin temperature must be positive");
+      } else if (kind != "Kinetic") {
+        throw ParameterError("Unknown " + block +
+                             ":HI spin temperature type \"" + kind +
+                             "\" (Kinetic or Fixed)");
+      }
+      hi_free_free =
+          params.get_bool(block + ":HI free-free continuum", true);
+      hi_background_temperature = params.get_physical_value(
+          QUANTITY_TEMPERATURE, block + ":HI background temperature", "0. K");
+      if (!(hi_background_temperature >= 0.) ||
+          !std::isfinite(hi_background_temperature))
+        throw ParameterError(block + ":HI background temperature must not be "
+                             "negative");
+    }
+
     /* <name>.txt: one line "nu bg" per frequency. Returns the file's name. */
     std::string write_continuum_frequencies(const std::string &name) const {
       const std::string filename = name + ".txt";
@@ -449,6 +506,7 @@ class EmissivityCalculationSimulation {
       read_views(params);
       read_cubes(params, "EmissionImages", type);
       read_continuum(params, "EmissionImages", type);
+      read_hi(params, "EmissionImages", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       /* (looked at like the switch above: a file without it, or with it
@@ -671,6 +729,7 @@ class EmissivityCalculationSimulation {
       if (cubes)
         read_observer_velocities(params);
       read_continuum(params, "EmissionSkyMaps", type);
+      read_hi(params, "EmissionSkyMaps", type);
       /* (a key that is read shows in the used-values: with the switch
        * absent or off none of these is, the switch included) */
       /* (looked at like the switch above: a file without it, or with it
@@ -1052,7 +1111,7 @@ public:
                 std::to_string(img.nx) + " x " + std::to_string(img.ny) +
                 " pixels: more than 2^28 values in one call");
           cube.resize(cube_lines.size() * (size_t)img.nchan * npixel);
-          if (!cube_lines.empty() && !velocities.empty())
+          if ((!cube_lines.empty() || img.hi_cube) && !velocities.empty())
             rc = cmi_gpu_set_cell_velocities(engine, velocities.data());
         }
         for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
@@ -1114,6 +1173,29 @@ public:
             written += " " + img.write_continuum_frequencies(
                                  img.folder + "/" + img.prefix +
                                  "_continuum_frequencies");
+        }
+        if (rc == CMI_GPU_OK && img.hi_cube) {
+          status("Rendering H I cubes...");
+          if ((double)img.nchan * (double)npixel > (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionImages: an H I cube of " + std::to_string(img.nchan) +
+                " channels of " + std::to_string(img.nx) + " x " +
+                std::to_string(img.ny) +
+                " pixels: more than 2^28 values in one call");
+          std::vector<double> hi((size_t)img.nchan * npixel);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_render_hi_cube(
+                engine, theta[v], phi[v], (int32_t)img.nx, (int32_t)img.ny,
+                anchors.data() + 2 * v, sides.data() + 2 * v,
+                (int32_t)img.supersample, (int32_t)img.nchan, img.vmin,
+                img.vmax, img.sigma_turb, img.hi_spin_mode,
+                &img.hi_spin_temperature, img.hi_free_free ? 1 : 0,
+                img.hi_background_temperature, hi.data());
+            if (rc == CMI_GPU_OK && write_output)
+              written += " " + write_cube(img.folder + "/" + img.prefix +
+                                              "_HI_cube" + view_tag(v),
+                                          hi.data(), img.nchan, img.nx, img.ny);
+          }
         }
         if (rc == CMI_GPU_OK && img.scattering) {
           status("Shooting the lines' packets through the dust...");
@@ -1221,7 +1303,7 @@ public:
                 " pixels: more than 2^28 values in one call");
           cube.resize(cube_lines.size() * (size_t)sky.nchan * npixel);
           /* (the block's own field, whatever EmissionImages: left) */
-          if (!cube_lines.empty())
+          if (!cube_lines.empty() || sky.hi_cube)
             rc = cmi_gpu_set_cell_velocities(
                 engine,
                 sky_velocities.empty() ? nullptr : sky_velocities.data());
@@ -1286,6 +1368,31 @@ public:
             written += " " + sky.write_continuum_frequencies(
                                  sky.folder + "/" + sky.prefix +
                                  "_continuum_frequencies");
+        }
+        if (rc == CMI_GPU_OK && sky.hi_cube) {
+          status("Rendering H I sky cubes...");
+          if ((double)sky.nchan * (double)npixel > (double)(1ll << 28))
+            throw ParameterError(
+                "EmissionSkyMaps: an H I cube of " +
+                std::to_string(sky.nchan) + " channels of " +
+                std::to_string(sky.nlon) + " x " + std::to_string(sky.nlat) +
+                " pixels: more than 2^28 values in one call");
+          std::vector<double> hi((size_t)sky.nchan * npixel);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_render_hi_sky_map_cube(
+                engine, sky.observers[v].position.data(),
+                sky.observers[v].frame, sky.lon[0], sky.lon[1], sky.lat[0],
+                sky.lat[1], (int32_t)sky.nlon, (int32_t)sky.nlat,
+                sky.observers[v].velocity.data(), (int32_t)sky.nchan, sky.vmin,
+                sky.vmax, sky.sigma_turb, sky.hi_spin_mode,
+                &sky.hi_spin_temperature, sky.hi_free_free ? 1 : 0,
+                sky.hi_background_temperature, hi.data());
+            if (rc == CMI_GPU_OK && write_output)
+              written += " " + write_cube(sky.folder + "/" + sky.prefix +
+                                              "_HI_cube" + view_tag(v),
+                                          hi.data(), sky.nchan, sky.nlon,
+                                          sky.nlat);
+          }
         }
         if (rc == CMI_GPU_OK && sky.scattering) {
           status("Shooting the lines' packets towards the observer...");

@@ -1713,6 +1713,178 @@ int cmi_gpu_continuum_probe(cmi_gpu_engine *engine, int32_t nf,
                             const double *view, int64_t n, const double *rays,
                             int32_t max_cells, double *out);
 
+/* ----------------------------------------------- absorbing line cubes -- */
+/* A spectral line whose opacity has the line profile, with an optional
+ * continuum in the same cells, and the 21-cm line of neutral hydrogen as its
+ * first client: the position-velocity cube of H I emission, H I
+ * self-absorption and H I absorption against the continuum of the H II region
+ * itself. The spectral line cubes and sky cubes above resolve emission in
+ * velocity but attenuate all channels with one grey exp(-k ds); the continuum
+ * images have an opacity per channel but no profile. No counterpart in the
+ * reference.
+ *
+ * Per cell (host arrays [ncell] in the engine's cell order for the general
+ * calls):
+ *   a         the line opacity integrated over velocity, m^-1 m s^-1; finite,
+ *             >= 0, and a / dv finite
+ *   sl        the line source function, W m^-2 Hz^-1 sr^-1; finite
+ *   b         the Gaussian width sqrt(2) sigma, m s^-1; finite, >= 0
+ *   velocity  [3][ncell], finite; NULL: at rest
+ *   kc, sc    a continuum absorption coefficient (m^-1, finite, >= 0) and
+ *             source function (finite, and sl - sc finite) that are constant
+ *             over the cube's band; both NULL: none
+ * and background[nchan] (finite; NULL: all zero).
+ *
+ * Channels: those of the cubes, nchan equal channels over [vmin, vmax), dv =
+ * (vmax - vmin) / nchan, e_c = vmin + c * dv, and the fraction of a cell's
+ * profile in channel c is f_c = 0.5 * (E((e_{c+1} - u) / b) - E((e_c - u) /
+ * b)) with the E of "spectral line cubes", b == 0 included. u is that
+ * section's for the parallel camera and (v - v_obs) . d of "sky cubes" for
+ * the rays from a point.
+ *
+ * Per cell with path ds and per channel, every operation one IEEE operation
+ * (-ffp-contract=off) in this order:
+ *   al = (a / dv) * f_c;  kappa = al + kc
+ *   kappa == 0: the channel is left as it is
+ *   w = al / kappa;  S = sc + w * (sl - sc);  em = expm1(-(kappa * ds))
+ *   parallel camera (far side to near side, I starts at bg_c):
+ *     I = I + em * (I - S)
+ *   rays from a point (observer outwards, T = 1 and I = 0 at the start):
+ *     I = I + T * (S * -em);  T = T + T * em
+ *     and I + T * bg_c behind the last cell, or for a ray that misses.
+ * The views, the sample grid and its average, the rays and their checks, the
+ * start cell and the step are those of "continuum images". Exact
+ * consequences: a == 0 gives kappa == kc and S == sc, so that every channel is
+ * cmi_gpu_render_field_continuum_images (_sky) of {kc, sc} with nf = 1, bit
+ * for bit; sl == sc == I stays I (parallel camera); and a channel's bits
+ * depend on (vmin, dv, c) and the cells only - not on nchan, on the block of
+ * channels a launch marches or on the chunking of rays. A cell in which every
+ * channel of a launch has f_c == 0 exactly (all of its edges at or beyond 6 b
+ * on one side of u) is marched with one expm1 for all of them, kappa = kc and
+ * S = sc + 0 * (sl - sc), and skipped when kc == 0 as well: those are the
+ * bits of the update above, not an approximation of it.
+ *
+ * The 21-cm line of the cells as they are (constants h, k_B, c, m_u of the
+ * engine): nu_10 = 1420405751.768 Hz, A_10 = 2.8843e-15 s^-1,
+ *   C_HI = 3 h c^3 A_10 / (32 pi k_B nu_10^2) = 5.516606267115072e-20 K m^3
+ *          s^-1 (1 K km s^-1 of thin emission is 1.8127e18 atoms cm^-2),
+ *   n_HI = n * x_H0,  a = C_HI * n_HI / T_s,
+ *   sl = (2 * h * nu_10^3 / (c * c)) / expm1((h * nu_10) / (k_B * T_s)),
+ *   b = sqrt(2 * (k_B * T / (A_H * m_u) + sigma_turb * sigma_turb)), A_H =
+ *       1.00794 (cmi_gpu_emission_line_atomic_weight of HAlpha),
+ * T the cell's kinetic temperature. The spin temperature T_s is T
+ * (spin_mode 0, spin_temperature ignored), the one value spin_temperature[0]
+ * > 0 (spin_mode 1) or spin_temperature[ncell] (spin_mode 2, finite). A cell
+ * with n_HI == 0, T <= 0 or T_s <= 0 has a = 0 exactly; sl = 0 for T_s <= 0
+ * and the thermal part of b is dropped for T <= 0. With free_free != 0 {kc,
+ * sc} are the free-free coefficients of "continuum images" at nu_10, from
+ * the same device function; otherwise 0. background_temperature >= 0 gives
+ * bg_c = B_nu10(T_bg) in every channel (0 for 0 K), formed on the host.
+ * Velocities are those of cmi_gpu_set_cell_velocities.
+ *
+ * Output: specific intensity averaged over the channel, W m^-2 Hz^-1 sr^-1,
+ * out[c * npixel + ix * ny + iy] or out[c * nrays + r]; nchan * npixel (nchan
+ * * nrays) <= 2^28.
+ *
+ * Errors, each with a message for cmi_gpu_last_error, before any march and
+ * with `out` untouched: CMI_GPU_EINVAL for everything the cube calls
+ * (cmi_gpu_render_field_cube, cmi_gpu_render_field_sky_cube) refuse for
+ * their view, rays, velocity axis and velocities and everything the continuum
+ * calls refuse; for an a, b or kc that is negative or not finite, an sl, sc
+ * or background that is not finite (the fields are counted on the device once
+ * uploaded); for kc without sc or the reverse; for a spin temperature or a
+ * background temperature out of range; for cells whose 21-cm coefficients do
+ * not come out finite (a / dv, b, sl, kc, sc or sl - sc: a spin temperature
+ * of 1e-322 K overflows a), counted on the device like the caller's fields,
+ * so that the H I calls are held to what the general calls are held to.
+ * CMI_GPU_ESTATE for the H I calls without cell data, and for every call of
+ * this section, cmi_gpu_hi_coefficients and the probe included, on a block
+ * of a decomposed grid. All calls are synchronous; a call that fails leaves
+ * the engine usable.
+ *
+ * Tuning (cmi_gpu_set_tuning): absorbing_cube_channel_block = 4 or 8 channels
+ * per march launch; absorbing_cube_expm1_call = 1: the march calls expm1 as a
+ * function, 0: it is inlined per channel; absorbing_cube_window_skip = 0: no
+ * shortcut for dark cells; absorbing_cube_launch_rays = sample rays or rays
+ * per march launch (0: the cubes' own bounds). None changes a bit of the
+ * result. */
+
+/* The 21-cm {a, sl, b, kc, sc} of the cells: host arrays [ncell] in the
+ * engine's cell order - what the H I calls below march. */
+int cmi_gpu_hi_coefficients(cmi_gpu_engine *engine, double sigma_turb,
+                            int32_t spin_mode, const double *spin_temperature,
+                            int32_t free_free, double *a, double *sl,
+                            double *b, double *kc, double *sc);
+
+/* The H I cube of the parallel camera; view arguments as in
+ * cmi_gpu_render_field_images. */
+int cmi_gpu_render_hi_cube(cmi_gpu_engine *engine, double theta, double phi,
+                           int32_t nx, int32_t ny, const double anchor[2],
+                           const double sides[2], int32_t supersample,
+                           int32_t nchan, double vmin, double vmax,
+                           double sigma_turb, int32_t spin_mode,
+                           const double *spin_temperature, int32_t free_free,
+                           double background_temperature,
+                           double *cube /* [nchan][nx][ny] */);
+
+/* H I spectra along rays from a point; origin, observer_velocity (NULL: at
+ * rest) and rays as in cmi_gpu_render_field_sky_cube. */
+int cmi_gpu_render_hi_sky_cube(cmi_gpu_engine *engine, const double origin[3],
+                               const double *observer_velocity, int64_t nrays,
+                               const double *directions, int32_t nchan,
+                               double vmin, double vmax, double sigma_turb,
+                               int32_t spin_mode,
+                               const double *spin_temperature,
+                               int32_t free_free,
+                               double background_temperature,
+                               double *out /* [nchan][nrays] */);
+
+/* The longitude-latitude-velocity cube of cmi_gpu_render_line_sky_map_cube in
+ * H I: cube[c * nlon * nlat + i * nlat + j]. Equals
+ * cmi_gpu_render_hi_sky_cube on the map's directions, bit for bit. */
+int cmi_gpu_render_hi_sky_map_cube(
+    cmi_gpu_engine *engine, const double origin[3], const double frame[9],
+    double lon_min, double lon_max, double lat_min, double lat_max,
+    int32_t nlon, int32_t nlat, const double *observer_velocity,
+    int32_t nchan, double vmin, double vmax, double sigma_turb,
+    int32_t spin_mode, const double *spin_temperature, int32_t free_free,
+    double background_temperature, double *cube);
+
+/* The general solver for the parallel camera. Needs only cmi_gpu_create. */
+int cmi_gpu_render_field_absorbing_cube(
+    cmi_gpu_engine *engine, const double *a, const double *sl,
+    const double *b, const double *velocity /* or NULL */,
+    const double *kc /* or NULL */, const double *sc /* or NULL */,
+    const double *background /* [nchan] or NULL */, double theta, double phi,
+    int32_t nx, int32_t ny, const double anchor[2], const double sides[2],
+    int32_t supersample, int32_t nchan, double vmin, double vmax,
+    double *cube /* [nchan][nx][ny] */);
+
+/* The general solver for rays from a point. */
+int cmi_gpu_render_field_absorbing_sky_cube(
+    cmi_gpu_engine *engine, const double *a, const double *sl,
+    const double *b, const double *velocity, const double *kc,
+    const double *sc, const double *background, const double origin[3],
+    const double *observer_velocity, int64_t nrays, const double *directions,
+    int32_t nchan, double vmin, double vmax, double *out /* [nchan][nrays] */);
+
+/* Test hook: the march of n <= 2^20 chosen rays through the caller's fields
+ * (nchan <= 1024), cell by cell, in the style of cmi_gpu_continuum_probe:
+ * point == 0, view = {theta, phi}, rays[n][2]; point == 1, view = the
+ * origin[3], rays[n][3], observer_velocity as above. Row k of `out` has 3 +
+ * (2 + nchan) * max_cells + nchan doubles: {t0, t1, steps, cells[max_cells],
+ * ds[max_cells], I[nchan][max_cells], I_end[nchan]}; I[c][i] is I_c after
+ * step i (for point == 1 before the background is added) and I_end[c] what
+ * the render call returns. The probe runs the update above in every cell,
+ * without the shortcut for dark cells. */
+int cmi_gpu_absorbing_cube_probe(
+    cmi_gpu_engine *engine, const double *a, const double *sl,
+    const double *b, const double *velocity, const double *kc,
+    const double *sc, const double *background, int32_t nchan, double vmin,
+    double vmax, int32_t point, const double *view,
+    const double *observer_velocity, int64_t n, const double *rays,
+    int32_t max_cells, double *out);
+
 #ifdef __cplusplus
 }
 #endif
