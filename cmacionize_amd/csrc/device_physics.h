@@ -726,20 +726,24 @@ __device__ __forceinline__ void cmi_metal_fractions(const double (&ratio)[12],
  * normalised in place; x[14] out. */
 /* (`terms`: the temperature-only terms of this cell's T, evaluated here or
  * stored - MetalTermsEvaluated / MetalTermsStored) */
+/* The balance in two parts. The hydrogen / helium part: whether the cell has a
+ * balance at all (the gate: ionizing radiation and gas), x[0] and x[1] (h0,
+ * he0 - of the neutral gas and of the vacuum where the gate is shut), the
+ * heating terms normalised in place. */
 template <class Terms>
-__device__ inline void
-cmi_ionization_state_cell_from(const ModelDev &m, const Terms &terms,
-                               double jfac, double hfac, double ntot, double T,
-                               const double J[CMI_NION], double heating[2],
-                               double x[CMI_NION]) {
-  const double jH = jfac * J[ION_H_n];
-  const double jHe = jfac * J[ION_He_n];
+__device__ __forceinline__ bool cmi_ionization_state_cell_hydrogen_helium(
+    const ModelDev &m, const Terms &terms, double jfac, double hfac,
+    double ntot, double T, double J_H, double J_He, double heating[2],
+    double &h0, double &he0) {
+  const double jH = jfac * J_H;
+  const double jHe = jfac * J_He;
   heating[0] = hfac * heating[0];
   heating[1] = hfac * heating[1];
-  if (jH > 0. && ntot > 0.) {
+  const bool gate = jH > 0. && ntot > 0.;
+  if (gate) {
     const double alphaH = terms.alpha_H();
     const double AHe = m.abundance[0];
-    double h0, he0 = 0.;
+    he0 = 0.;
     if (AHe != 0.) {
       const double alphaHe = terms.alpha_He();
       cmi_ionization_states_hydrogen_helium(alphaH, alphaHe, jH, jHe, ntot,
@@ -747,38 +751,70 @@ cmi_ionization_state_cell_from(const ModelDev &m, const Terms &terms,
     } else {
       h0 = cmi_ionization_state_hydrogen(alphaH, jH, ntot);
     }
-    x[ION_H_n] = h0;
-    x[ION_He_n] = he0;
+  } else {
+    /* neutral gas: the tracked neutral stages are fully populated */
+    h0 = he0 = (ntot > 0.) ? 1. : 0.;
+  }
+  return gate;
+}
+
+/* The metals' part, x[2..13]: from the terms, the density, h0 and he0 as the
+ * first part left them, the helium abundance, the gate and the metals' own
+ * normalised mean intensities `jm` (by ion index). A hydrogen-only run's are
+ * zero (CmiNoMetalIntensities), so its x[2..13] can be made at any later time
+ * from n, T, the stored x[0] and x[1] and the gate (metal_fractions_kernel). */
+struct CmiNoMetalIntensities {
+  __device__ __forceinline__ double operator()(int) const { return 0.; }
+};
+template <class Terms, class Integrals>
+__device__ __forceinline__ void
+cmi_ionization_state_cell_metals(const Terms &terms, const Integrals &jm,
+                                 double ntot, double h0, double he0,
+                                 double AHe, bool gate, double x[CMI_NION]) {
+  if (gate) {
     const double nhp = ntot * (1. - h0);
     const double ne = ntot * (1. - h0 + AHe * (1. - he0));
     const double nh0 = ntot * h0;
     const double nhe0 = ntot * he0 * AHe;
-    /* normalised mean intensity of an ion, by ion index */
-    struct {
-      const double *J;
-      double jfac;
-      __device__ __forceinline__ double operator()(int ion) const {
-        double v = 0.; /* static indexing: J[] lives in registers */
-#pragma unroll
-        for (int i = ION_C_p1; i < CMI_NION; ++i)
-          v = (i == ion) ? J[i] : v;
-        return jfac * v;
-      }
-    } jm = {J, jfac};
     cmi_ionization_states_metals_from(terms, jm, ne, nh0, nhe0, nhp, x);
   } else {
 #pragma unroll
-    for (int i = 0; i < CMI_NION; ++i)
+    for (int i = ION_C_p1; i < CMI_NION; ++i)
       x[i] = 0.;
     if (ntot > 0.) {
-      /* neutral gas: the tracked neutral stages are fully populated */
-      x[ION_H_n] = 1.;
-      x[ION_He_n] = 1.;
       x[ION_N_n] = 1.;
       x[ION_O_n] = 1.;
       x[ION_Ne_n] = 1.;
     }
   }
+}
+
+template <class Terms>
+__device__ inline void
+cmi_ionization_state_cell_from(const ModelDev &m, const Terms &terms,
+                               double jfac, double hfac, double ntot, double T,
+                               const double J[CMI_NION], double heating[2],
+                               double x[CMI_NION]) {
+  double h0, he0;
+  const bool gate = cmi_ionization_state_cell_hydrogen_helium(
+      m, terms, jfac, hfac, ntot, T, J[ION_H_n], J[ION_He_n], heating, h0,
+      he0);
+  x[ION_H_n] = h0;
+  x[ION_He_n] = he0;
+  /* normalised mean intensity of an ion, by ion index */
+  struct {
+    const double *J;
+    double jfac;
+    __device__ __forceinline__ double operator()(int ion) const {
+      double v = 0.; /* static indexing: J[] lives in registers */
+#pragma unroll
+      for (int i = ION_C_p1; i < CMI_NION; ++i)
+        v = (i == ion) ? J[i] : v;
+      return jfac * v;
+    }
+  } jm = {J, jfac};
+  cmi_ionization_state_cell_metals(terms, jm, ntot, h0, he0,
+                                   m.abundance[0], gate, x);
 }
 
 __device__ inline void cmi_ionization_state_cell(const ModelDev &m, double jfac,

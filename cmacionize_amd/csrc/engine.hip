@@ -75,7 +75,9 @@ struct cmi_gpu_engine {
 
   GridDev grid;
   ModelDev model;
-  CellsDev cells;
+  /* the cells' arrays - through cells_settled() or cells_of_iteration() only:
+   * x[2..13] may be pending (metals_pending below) */
+  CellsDev cells_unsettled;
   int64_t ncell = 0;
 
   /* device allocations */
@@ -153,8 +155,20 @@ struct cmi_gpu_engine {
   /* SpectrumTrackers: counted while enabled (the exact marcher then) */
   TrackersDev trackers = {};
   bool trackers_enabled = false;
-  /* PAD transport kernels: n x_H inside a layer of ghost cells */
+  /* PAD transport kernels: n x_H inside a layer of ghost cells; whether it
+   * holds the records of the cells as they are (whatever writes
+   * CellsDev::opacity clears this - pad_records_stale - except the update
+   * that writes the padded records itself, hydrogen_update_kernel) */
   double *pad_H = nullptr;
+  bool pad_valid = false;
+  /* the hydrogen-only update's deferred half: the gates of the last whole-grid
+   * update, a bit per cell, and whether x[2..13] have still to be made from
+   * them (settle_metal_fractions). Once a pointer to a state field has been
+   * handed out (cmi_gpu_field_device_pointer) the engine cannot see every
+   * reader and writer any more: no deferral from then on. */
+  unsigned long long *metal_gate = nullptr;
+  bool metals_pending = false;
+  bool state_pointer_escaped = false;
   /* the temperature solve as a pipeline (temperature_pipeline.h) */
   char *temp_pipe_block = nullptr;
   uint32_t temp_pipe_capacity = 0;
@@ -212,6 +226,12 @@ struct cmi_gpu_engine {
      * temperature share its temperature-only terms (false: every lane
      * evaluates them for its own cell) */
     bool update_reuse = true;
+    /* ... x[2..13] of a whole-grid update made when somebody looks, not in
+     * every iteration (hydrogen_update_kernel / metal_fractions_kernel) */
+    bool defer_metals = true;
+    /* ... and that update writes the padded records of the next transport
+     * step itself (false: pad_record_kernel in every cmi_gpu_shoot) */
+    bool update_writes_pad = true;
     /* multi-ion runs: the cross sections of re-emitted flights in a kernel of
      * their own (flight_weights_kernel) instead of inside the interaction
      * kernels */
@@ -317,6 +337,18 @@ struct cmi_gpu_engine {
 };
 
 namespace {
+
+/* The cells' arrays for the iteration's own code - the transport, the
+ * hydrogen-only update, the records, the accumulator layout -, which neither
+ * reads x[2..13] nor changes what they are made from: nothing is settled. */
+inline CellsDev &cells_of_iteration(cmi_gpu_engine *e) {
+  return e->cells_unsettled;
+}
+inline const CellsDev &cells_of_iteration(const cmi_gpu_engine *e) {
+  return e->cells_unsettled;
+}
+
+int settle_metal_fractions(cmi_gpu_engine *e);
 
 /* A device buffer that only grows: make sure `ptr` holds `want` units, `bytes`
  * in all. The contents are not kept; launches still in flight may read the old
@@ -478,15 +510,18 @@ double *field_pointer(cmi_gpu_engine *e, int field) {
   if (field < CMI_GPU_FIELD_MEAN_INTENSITY)
     return e->state_block + (int64_t)field * e->ncell;
   const int f = field - CMI_GPU_FIELD_MEAN_INTENSITY;
-  if (e->cells.acc_cell_stride != 1) /* [ncell][16], rows in threshold order */
+  if (cells_of_iteration(e).acc_cell_stride != 1) /* [ncell][16], rows in
+                                                    * threshold order */
     return e->acc_block + cmi_acc_column(f);
-  return e->acc_block + (int64_t)f * e->cells.acc_field_stride;
+  return e->acc_block + (int64_t)f * cells_of_iteration(e).acc_field_stride;
 }
 
 /* element stride of a field: 1 for the state fields, the accumulator layout's
  * cell stride for the accumulator fields */
 int64_t field_stride(cmi_gpu_engine *e, int field) {
-  return field < CMI_GPU_FIELD_MEAN_INTENSITY ? 1 : e->cells.acc_cell_stride;
+  return field < CMI_GPU_FIELD_MEAN_INTENSITY
+             ? 1
+             : cells_of_iteration(e).acc_cell_stride;
 }
 
 /* lower the generated raw tables into the device layout, applying the unit
@@ -934,7 +969,7 @@ int grid_blocks(cmi_gpu_engine *e, int64_t work_items, int blocks_per_cu) {
   return (int)(want < cap ? want : cap);
 }
 
-void update_full_flag(cmi_gpu_engine *e) {
+int update_full_flag(cmi_gpu_engine *e) {
   /* the light transport kernel is exact iff no ion other than H0 can ever
    * have a non-zero cross section */
   bool full = e->model.xsec_verner != 0;
@@ -942,6 +977,10 @@ void update_full_flag(cmi_gpu_engine *e) {
     for (int i = 1; i < CMI_NION; ++i)
       if (e->model.xsec_fixed[i] != 0.)
         full = true;
+  /* (x[2..13] of a hydrogen-only update are made before the run stops being
+   * one) */
+  if (full != e->full_ions)
+    CMI_TRY(settle_metal_fractions(e));
   /* accumulator layout follows the transport kernel: [16][ncell] when only
    * hydrogen is accumulated (neighbouring cells share 64-B lines), [ncell][16]
    * when every step updates all 16 values of a cell. A switch zeroes the
@@ -957,18 +996,50 @@ void update_full_flag(cmi_gpu_engine *e) {
       e->acc_block_dirty = true;
   }
   e->full_ions = full;
+  CellsDev &cells = cells_of_iteration(e); /* (the layout's strides only) */
   if (full) {
-    e->cells.acc_field_stride = 1;
-    e->cells.acc_cell_stride = CMI_NACC;
+    cells.acc_field_stride = 1;
+    cells.acc_cell_stride = CMI_NACC;
   } else {
-    e->cells.acc_field_stride = e->ncell;
-    e->cells.acc_cell_stride = 1;
+    cells.acc_field_stride = e->ncell;
+    cells.acc_cell_stride = 1;
   }
+  return CMI_GPU_OK;
 }
 
+/* x[2..13] of the last deferred update, if they are still to be made */
+int settle_metal_fractions(cmi_gpu_engine *e) {
+  if (!e->metals_pending)
+    return CMI_GPU_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  MetalFractionsArgs a;
+  a.model = e->model;
+  a.cells = e->cells_unsettled;
+  a.count = e->ncell;
+  a.gate = e->metal_gate;
+  metal_fractions_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0,
+                           e->stream>>>(a, e->tune.update_reuse ? 1 : 0);
+  HIP_TRY(hipGetLastError());
+  e->metals_pending = false;
+  return CMI_GPU_OK;
+}
+
+/* The cells' arrays for everybody else - who reads x[2..13], or writes n, T,
+ * x[0], x[1] or the model's rates and abundances, which a pending x[2..13] is
+ * made from: settled first, which can fail. */
+int cells_settled(cmi_gpu_engine *e, CellsDev *&cells) {
+  CMI_TRY(settle_metal_fractions(e));
+  cells = &e->cells_unsettled;
+  return CMI_GPU_OK;
+}
+
+/* something other than hydrogen_update_kernel wrote transport records */
+inline void pad_records_stale(cmi_gpu_engine *e) { e->pad_valid = false; }
+
 int rebuild_opacity(cmi_gpu_engine *e) {
+  pad_records_stale(e);
   opacity_kernel<<<grid_blocks(e, e->ncell, 8), CMI_BLOCK, 0, e->stream>>>(
-      e->cells, e->ncell);
+      cells_of_iteration(e), e->ncell);
   HIP_TRY(hipGetLastError());
   return CMI_GPU_OK;
 }
@@ -1083,7 +1154,7 @@ int cmi_gpu_create(const cmi_gpu_config *config, cmi_gpu_engine **out) {
                       hipMemcpyHostToDevice));
   }
 
-  CellsDev &c = e->cells;
+  CellsDev &c = cells_of_iteration(e); /* (nothing pending yet) */
   c.number_density = e->state_block;
   c.temperature = e->state_block + e->ncell;
   for (int i = 0; i < CMI_NION; ++i)
@@ -1169,6 +1240,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->trackers.flux);
   (void)hipFree(e->temp_pipe_block);
   (void)hipFree(e->pad_H);
+  (void)hipFree(e->metal_gate);
   (void)hipFree(e->temp_pipe_counts);
   (void)hipFree(e->tables);
   (void)hipFree(e->spectra);
@@ -1432,8 +1504,7 @@ int cmi_gpu_set_cross_sections_table(cmi_gpu_engine *e, int32_t n,
   e->model.xsec_verner = 2;
   e->have_xsec = true;
   e->spectra_dirty = true;
-  update_full_flag(e);
-  return CMI_GPU_OK;
+  return update_full_flag(e);
 }
 
 int cmi_gpu_set_recombination_rates_table(cmi_gpu_engine *e, int32_t n,
@@ -1453,6 +1524,7 @@ int cmi_gpu_set_recombination_rates_table(cmi_gpu_engine *e, int32_t n,
                   "cmi_gpu_set_recombination_rates_table: rate %zu of ion %zu "
                   "is negative or not finite",
                   i % (size_t)n, i / (size_t)n);
+  CMI_TRY(settle_metal_fractions(e)); /* (made from the rates so far) */
   CMI_TRY(store_user_table(e, 3, e->model.recomb_table, n, CMI_NION,
                            temperature, alpha, interpolation));
   e->model.recomb_verner = 2;
@@ -1468,8 +1540,7 @@ int cmi_gpu_set_cross_sections_fixed(cmi_gpu_engine *e, const double *sigma) {
     e->model.xsec_fixed[i] = sigma[i];
   e->have_xsec = true;
   e->spectra_dirty = true;
-  update_full_flag(e);
-  return CMI_GPU_OK;
+  return update_full_flag(e);
 }
 
 int cmi_gpu_set_cross_sections_verner(cmi_gpu_engine *e) {
@@ -1478,14 +1549,14 @@ int cmi_gpu_set_cross_sections_verner(cmi_gpu_engine *e) {
   e->model.xsec_verner = 1;
   e->have_xsec = true;
   e->spectra_dirty = true;
-  update_full_flag(e);
-  return CMI_GPU_OK;
+  return update_full_flag(e);
 }
 
 int cmi_gpu_set_recombination_rates_fixed(cmi_gpu_engine *e,
                                           const double *alpha) {
   if (!e || !alpha)
     return fail(CMI_GPU_EINVAL, "fixed recombination rates: bad argument");
+  CMI_TRY(settle_metal_fractions(e)); /* (made from the rates so far) */
   e->model.recomb_verner = 0;
   for (int i = 0; i < CMI_NION; ++i)
     e->model.recomb_fixed[i] = alpha[i];
@@ -1496,6 +1567,7 @@ int cmi_gpu_set_recombination_rates_fixed(cmi_gpu_engine *e,
 int cmi_gpu_set_recombination_rates_verner(cmi_gpu_engine *e) {
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
+  CMI_TRY(settle_metal_fractions(e)); /* (made from the rates so far) */
   e->model.recomb_verner = 1;
   e->have_recomb = true;
   return CMI_GPU_OK;
@@ -1504,6 +1576,7 @@ int cmi_gpu_set_recombination_rates_verner(cmi_gpu_engine *e) {
 int cmi_gpu_set_abundances(cmi_gpu_engine *e, const double *abundances) {
   if (!e || !abundances)
     return fail(CMI_GPU_EINVAL, "abundances: bad argument");
+  CMI_TRY(settle_metal_fractions(e)); /* (made with the abundances so far) */
   for (int i = 0; i < 6; ++i)
     e->model.abundance[i] = abundances[i];
   return CMI_GPU_OK;
@@ -1547,16 +1620,18 @@ int cmi_gpu_upload_cells(cmi_gpu_engine *e, const double *number_density,
     return fail(CMI_GPU_EINVAL, "upload_cells: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   ++e->cells_epoch;
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
   const size_t bytes = (size_t)e->ncell * sizeof(double);
-  HIP_TRY(hipMemcpyAsync(e->cells.number_density, number_density, bytes,
+  HIP_TRY(hipMemcpyAsync(cells->number_density, number_density, bytes,
                          hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipMemcpyAsync(e->cells.temperature, temperature, bytes,
+  HIP_TRY(hipMemcpyAsync(cells->temperature, temperature, bytes,
                          hipMemcpyHostToDevice, e->stream));
   if (ionic_fractions) {
-    HIP_TRY(hipMemcpyAsync(e->cells.x[0], ionic_fractions, CMI_NION * bytes,
+    HIP_TRY(hipMemcpyAsync(cells->x[0], ionic_fractions, CMI_NION * bytes,
                            hipMemcpyHostToDevice, e->stream));
   } else {
-    HIP_TRY(hipMemsetAsync(e->cells.x[0], 0, CMI_NION * bytes, e->stream));
+    HIP_TRY(hipMemsetAsync(cells->x[0], 0, CMI_NION * bytes, e->stream));
   }
   CMI_TRY(rebuild_opacity(e));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1572,8 +1647,11 @@ int cmi_gpu_upload_field(cmi_gpu_engine *e, int32_t field,
   if (!dst)
     return fail(CMI_GPU_EINVAL, "upload_field: unknown field %d", field);
   HIP_TRY(hipSetDevice(e->device));
-  if (field < CMI_GPU_FIELD_MEAN_INTENSITY)
+  if (field < CMI_GPU_FIELD_MEAN_INTENSITY) {
     ++e->cells_epoch; /* a field of the cells' state */
+    /* (pending x[2..13] are those of the state before this upload) */
+    CMI_TRY(settle_metal_fractions(e));
+  }
   const int64_t stride = field_stride(e, field);
   if (stride == 1) {
     HIP_TRY(hipMemcpyAsync(dst, values, (size_t)e->ncell * sizeof(double),
@@ -1612,6 +1690,9 @@ int cmi_gpu_download_field(cmi_gpu_engine *e, int32_t field, double *values) {
   if (!src)
     return fail(CMI_GPU_EINVAL, "download_field: unknown field %d", field);
   HIP_TRY(hipSetDevice(e->device));
+  if (field >= CMI_GPU_FIELD_IONIC_FRACTION + ION_C_p1 &&
+      field < CMI_GPU_FIELD_MEAN_INTENSITY)
+    CMI_TRY(settle_metal_fractions(e));
   const int64_t stride = field_stride(e, field);
   if (stride == 1) {
     HIP_TRY(hipMemcpyAsync(values, src, (size_t)e->ncell * sizeof(double),
@@ -1639,16 +1720,39 @@ int cmi_gpu_accumulator_layout(cmi_gpu_engine *e, int64_t *field_stride_out,
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
   if (field_stride_out)
-    *field_stride_out = e->cells.acc_field_stride;
+    *field_stride_out = cells_of_iteration(e).acc_field_stride;
   if (cell_stride_out)
-    *cell_stride_out = e->cells.acc_cell_stride;
+    *cell_stride_out = cells_of_iteration(e).acc_cell_stride;
   return CMI_GPU_OK;
 }
 
 void *cmi_gpu_field_device_pointer(cmi_gpu_engine *e, int32_t field) {
   if (!e)
     return nullptr;
+  /* a state field in the hands of code the engine cannot see - which may read
+   * x[2..13], or write what they are made from, at any time from now on:
+   * they are made now and with every update of this engine's from here on */
+  if (field >= 0 && field < CMI_GPU_FIELD_MEAN_INTENSITY) {
+    if (settle_metal_fractions(e) != CMI_GPU_OK)
+      return nullptr;
+    e->state_pointer_escaped = true;
+  }
   return field_pointer(e, field);
+}
+
+int cmi_gpu_get_update_state(cmi_gpu_engine *e, int32_t *metals_pending,
+                             int32_t *pad_records_valid,
+                             int32_t *deferral_allowed) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (metals_pending)
+    *metals_pending = e->metals_pending ? 1 : 0;
+  if (pad_records_valid)
+    *pad_records_valid = e->pad_valid ? 1 : 0;
+  if (deferral_allowed)
+    *deferral_allowed =
+        (e->tune.defer_metals && !e->state_pointer_escaped) ? 1 : 0;
+  return CMI_GPU_OK;
 }
 
 int cmi_gpu_reset_grid(cmi_gpu_engine *e) {
@@ -1747,6 +1851,10 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.tile_counting_sort = value != 0;
   else if (k == "update_reuse")
     e->tune.update_reuse = value != 0;
+  else if (k == "defer_metals")
+    e->tune.defer_metals = value != 0;
+  else if (k == "update_writes_pad")
+    e->tune.update_writes_pad = value != 0;
   else if (k == "span_claim")
     e->tune.span_claim = value != 0;
   else if (k == "emit_before_flush")
@@ -2067,11 +2175,23 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
   const bool solve_temperature =
       e->tparams.do_temperature_calculation &&
       loop > (uint32_t)e->tparams.minimum_number_of_iterations;
+  /* the hydrogen-only update of the whole grid leaves x[2..13] to whoever
+   * looks at them first; it replaces whatever an earlier one left pending.
+   * Every other update makes the pending ones first: it writes only its own
+   * cells, or a temperature they are made from */
+  const bool whole = first_cell == 0 && ncell == e->ncell;
+  const bool defer = whole && !solve_temperature && !e->full_ions &&
+                     e->tune.defer_metals && !e->state_pointer_escaped;
+  if (!defer)
+    CMI_TRY(settle_metal_fractions(e));
+  if (defer && !e->metal_gate)
+    HIP_TRY(hipMalloc(&e->metal_gate, sizeof(unsigned long long) *
+                                          (size_t)((e->ncell + 63) / 64)));
 
   UpdateArgs a;
   a.grid = e->grid;
   a.model = e->model;
-  a.cells = e->cells;
+  a.cells = cells_of_iteration(e);
   /* src/IonizationStateCalculator.cpp:519-522 and :136-137 */
   const double jfac = e->model.total_luminosity / totweight;
   const double hfac = jfac * CMI_PLANCK;
@@ -2085,6 +2205,26 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
   EventPair ev;
   CMI_TRY(timer_begin(e, ev));
   const int blocks = grid_blocks(e, ncell, 8);
+  if (defer) {
+    HydrogenUpdateArgs h;
+    h.u = a;
+    h.gate = e->metal_gate;
+    /* (the ghost layer is in place from the last pad_records) */
+    h.pad_H = (e->pad_valid && e->tune.update_writes_pad) ? e->pad_H : nullptr;
+    h.ny = (uint32_t)e->grid.ncell[1];
+    h.nz = (uint32_t)e->grid.ncell[2];
+    if (!h.pad_H)
+      pad_records_stale(e);
+    if (e->config.track_heating)
+      hydrogen_update_kernel<true><<<blocks, CMI_BLOCK, 0, e->stream>>>(h);
+    else
+      hydrogen_update_kernel<false><<<blocks, CMI_BLOCK, 0, e->stream>>>(h);
+    HIP_TRY(hipGetLastError());
+    e->metals_pending = true;
+    CMI_TRY(timer_end(e, e->update_events, ev, 0));
+    return CMI_GPU_OK;
+  }
+  pad_records_stale(e); /* (every kernel below writes transport records) */
   if (solve_temperature && e->tune.temperature_pipeline) {
     CMI_TRY(temperature_pipeline(e, a));
   } else if (solve_temperature)
@@ -2117,9 +2257,11 @@ int cmi_gpu_compute_emissivities(cmi_gpu_engine *e, int32_t nlines,
   if (!e->have_cells)
     return fail(CMI_GPU_ESTATE,
                 "compute_emissivities: cell data must be set first");
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
   EmissivityArgs a;
   a.model = e->model;
-  a.cells = e->cells;
+  a.cells = *cells;
   a.first = first_cell;
   a.count = ncell;
   a.nlines = nlines;
@@ -3112,9 +3254,11 @@ int cmi_gpu_set_cell_source_line(cmi_gpu_engine *e, int32_t line) {
   if (!e->have_cells)
     return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
   CMI_TRY(cell_source_begin(e));
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
   CellSourceLineArgs a;
   a.model = e->model;
-  a.cells = e->cells;
+  a.cells = *cells;
   a.ncell = e->ncell;
   a.line = line;
   a.weights = e->cell_source_cells;
@@ -3209,12 +3353,14 @@ static int dust_prepare(cmi_gpu_engine *e) {
                            e->stream));
   }
   const unsigned blocks = (unsigned)((e->ncell + 255) / 256);
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
   if (e->dust_per_hydrogen)
     dust_opacity_per_hydrogen_kernel<<<blocks, 256, 0, e->stream>>>(
-        e->cells.number_density, e->dust_kappa, e->ncell, e->dust_opacity);
+        cells->number_density, e->dust_kappa, e->ncell, e->dust_opacity);
   else
     dust_opacity_kernel<<<blocks, 256, 0, e->stream>>>(
-        e->cells.number_density, e->cells.x[0], e->dust_kappa, e->ncell,
+        cells->number_density, cells->x[0], e->dust_kappa, e->ncell,
         e->dust_opacity);
   HIP_TRY(hipGetLastError());
   return CMI_GPU_OK;
@@ -3769,6 +3915,8 @@ int cmi_gpu_set_scattered_cube(cmi_gpu_engine *e, int32_t nchan, double vmin,
   const size_t ncell = (size_t)e->ncell;
   /* everything new is built aside: a call that fails leaves the previous
    * state in place */
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
   double *s2 = nullptr, *vobs = nullptr, *cube = nullptr, *dwidths = nullptr;
   unsigned int *ninvalid = nullptr;
   unsigned int bad = 0;
@@ -3787,7 +3935,7 @@ int cmi_gpu_set_scattered_cube(cmi_gpu_engine *e, int32_t nchan, double vmin,
   if (err == hipSuccess && line) {
     dust_cube_line_variance_kernel<<<(unsigned)((ncell + 255) / 256), 256, 0,
                                      e->stream>>>(
-        e->cells.temperature, cmi_emission_atomic_weight[e->cell_source_line],
+        cells->temperature, cmi_emission_atomic_weight[e->cell_source_line],
         sigma_turb, e->ncell, s2);
     err = hipGetLastError();
   } else if (err == hipSuccess) {

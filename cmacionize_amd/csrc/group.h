@@ -389,8 +389,8 @@ int cmi_gpu_group_create(int32_t n, cmi_gpu_engine *const *engines,
       const cmi_gpu_engine *first = engines[c.member[0]];
       const GridDev &gf = first->grid;
       bool same = gf.decomposed == gi.decomposed &&
-                  first->cells.acc_cell_stride ==
-                      engines[i]->cells.acc_cell_stride &&
+                  cells_of_iteration(first).acc_cell_stride ==
+                      cells_of_iteration(engines[i]).acc_cell_stride &&
                   first->config.track_heating ==
                       engines[i]->config.track_heating;
       for (int a = 0; a < 3; ++a)
@@ -491,7 +491,7 @@ int cmi_gpu_group_destroy(cmi_gpu_group *g) {
  * written: {pointer, doubles} pieces */
 static int active_accumulators(cmi_gpu_engine *e, double *ptr[2],
                                int64_t count[2]) {
-  if (e->cells.acc_cell_stride != 1) { /* [ncell][16]: everything */
+  if (cells_of_iteration(e).acc_cell_stride != 1) { /* [ncell][16]: everything */
     ptr[0] = e->acc_block;
     count[0] = (int64_t)CMI_NACC * e->ncell;
     return 1;
@@ -613,6 +613,12 @@ static int update_class(cmi_gpu_group *g, GroupClass &c, uint32_t loop,
   std::vector<int64_t> first(n + 1, 0);
   for (int r = 0; r < n; ++r)
     first[r + 1] = first[r] + ncell / n + (r < ncell % n ? 1 : 0);
+  /* (the gathers below write the members' state and records behind their
+   * engines' backs - an empty slab's engine included) */
+  for (int r = 0; r < n; ++r) {
+    CMI_TRY(settle_metal_fractions(g->engine[c.member[r]]));
+    pad_records_stale(g->engine[c.member[r]]);
+  }
   {
     const int rc = group_in_parallel(n, [&](int r) -> int {
       cmi_gpu_engine *e = g->engine[c.member[r]];

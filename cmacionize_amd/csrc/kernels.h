@@ -3435,6 +3435,155 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_IONIZATION_WAVES)
   }
 }
 
+/* The hydrogen-only update of the whole grid without a temperature solve, in
+ * two kernels. No kernel of such a run reads x[2..13] (the transport, the
+ * re-emission and opacity_kernel read x[0] and x[1]), and they are a function
+ * of n, T, x[0], x[1] and the gate of the balance alone
+ * (cmi_ionization_state_cell_metals): the kernel of every iteration leaves
+ * them out and keeps the gates, a bit per cell; whoever looks at them first
+ * has metal_fractions_kernel make them (engine.hip: settle_metal_fractions).
+ * The same two helpers as ionization_update_cell, on the same values: what the
+ * pair writes equals what the kernels above write, bit for bit. */
+struct HydrogenUpdateArgs {
+  UpdateArgs u; /* first == 0, count == the grid's cells */
+  /* bit l of word r: the gate of cell 64 r + l; (count + 63) / 64 words */
+  unsigned long long *gate;
+  /* the padded records (ShootArgs::pad_H) where they are valid but for this
+   * update - the cells' records are then written here as pad_record_kernel
+   * would, the ghost layer stays -, or null */
+  double *pad_H;
+  uint32_t ny, nz;
+};
+
+/* every iteration: a wave per row of 64 cells, row after row (grid-stride);
+ * x[0], x[1], the heating terms, the transport record, the padded record and
+ * the row's gates out */
+#ifndef CMI_HYDROGEN_UPDATE_WAVES
+#define CMI_HYDROGEN_UPDATE_WAVES 4
+#endif
+template <bool HEATING>
+__global__ void __launch_bounds__(CMI_BLOCK, CMI_HYDROGEN_UPDATE_WAVES)
+    hydrogen_update_kernel(const HydrogenUpdateArgs h) {
+  constexpr int WAVES = CMI_BLOCK / 64;
+  const UpdateArgs &a = h.u;
+  const int64_t rows = (a.count + 63) >> 6;
+  const int64_t nwaves = (int64_t)gridDim.x * WAVES;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (int64_t row = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+       row < rows; row += nwaves) {
+    const int64_t c = (row << 6) + (int64_t)lane;
+    bool gate = false;
+    if (c < a.count) { /* (lanes past the end of the last row: no gate) */
+      const double ntot = a.cells.number_density[c];
+      const double T = a.cells.temperature[c];
+      const double J_H = (*acc_at(a.cells, 0, c));
+      double heating[2];
+      heating[0] = HEATING ? (*acc_at(a.cells, CMI_NION, c)) : 0.;
+      heating[1] = HEATING ? (*acc_at(a.cells, CMI_NION + 1, c)) : 0.;
+      const MetalTermsEvaluated terms = {a.model, T, T * 1.e-4};
+      double h0, he0;
+      gate = cmi_ionization_state_cell_hydrogen_helium(
+          a.model, terms, a.jfac, a.hfac, ntot, T, J_H, 0., heating, h0, he0);
+      a.cells.x[ION_H_n][c] = h0;
+      a.cells.x[ION_He_n][c] = he0;
+      if (HEATING) {
+        (*acc_at(a.cells, CMI_NION, c)) = heating[0];
+        (*acc_at(a.cells, CMI_NION + 1, c)) = heating[1];
+      }
+      const double2 k = (ntot > 0.) ? make_double2(ntot * h0, ntot * he0)
+                                    : make_double2(-1., 0.);
+      a.cells.opacity[c] = k;
+      if (h.pad_H) {
+        /* (fewer than 2^31 cells per engine, fewer than 2^29 padded ones) */
+        constexpr uint32_t L = CMI_PAD_LAYERS;
+        const uint32_t cc = (uint32_t)c;
+        const uint32_t xy = cc / h.nz, pz = cc - xy * h.nz;
+        const uint32_t px = xy / h.ny, py = xy - px * h.ny;
+        const uint32_t padded =
+            ((px + L) * (h.ny + 2 * L) + (py + L)) * (h.nz + 2 * L) + pz + L;
+        h.pad_H[padded] = (k.x >= 0.) ? k.x : CMI_PAD_VACUUM;
+      }
+    }
+    const unsigned long long word = wave_ballot(gate);
+    if (lane == 0)
+      h.gate[row] = word;
+  }
+}
+
+/* when somebody looks: x[2..13] of every cell from n, T, x[0], x[1] and the
+ * gates - on the walk of ionization_kernel(a, reuse), with its terms of one
+ * temperature per wave in LDS */
+struct MetalFractionsArgs {
+  ModelDev model;
+  CellsDev cells;
+  int64_t count;
+  const unsigned long long *gate;
+};
+
+__global__ void __launch_bounds__(CMI_BLOCK)
+    metal_fractions_kernel(const MetalFractionsArgs a, const int reuse) {
+  constexpr int WAVES = CMI_BLOCK / 64;
+  __shared__ MetalTerms s_terms[WAVES];
+  const int wave_in_block =
+      __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  MetalTerms &stored = s_terms[wave_in_block];
+  const int64_t rows = (a.count + 63) >> 6;
+  const int64_t chunks =
+      (rows + CMI_UPDATE_CHUNK_ROWS - 1) / CMI_UPDATE_CHUNK_ROWS;
+  const int64_t nwaves = (int64_t)gridDim.x * WAVES;
+  const uint32_t lane = threadIdx.x & 63u;
+  const double AHe = a.model.abundance[0];
+  unsigned long long stored_for = 0;
+  bool have = false;
+  for (int64_t chunk = (int64_t)blockIdx.x * WAVES + wave_in_block;
+       chunk < chunks; chunk += nwaves) {
+    for (int64_t row = chunk * CMI_UPDATE_CHUNK_ROWS;
+         row < (chunk + 1) * CMI_UPDATE_CHUNK_ROWS && row < rows; ++row) {
+      const int64_t c = (row << 6) + (int64_t)lane;
+      const unsigned long long gates = a.gate[row]; /* (wave-uniform) */
+      if (c >= a.count)
+        continue;
+      const double ntot = a.cells.number_density[c];
+      const double T = a.cells.temperature[c];
+      const double h0 = a.cells.x[ION_H_n][c];
+      const double he0 = a.cells.x[ION_He_n][c];
+      const bool gate = ((gates >> lane) & 1ull) != 0ull;
+      const unsigned long long bits =
+          (unsigned long long)__double_as_longlong(T);
+      const unsigned long long first =
+          ((unsigned long long)__builtin_amdgcn_readfirstlane(
+               (uint32_t)(bits >> 32))
+           << 32) |
+          __builtin_amdgcn_readfirstlane((uint32_t)bits);
+      bool use_stored = false;
+      if (reuse != 0 && wave_ballot(bits != first) == 0ull) {
+        if (!(have && stored_for == first) && gates != 0ull) {
+          cmi_metal_terms(a.model, T, stored);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          stored_for = first;
+          have = true;
+        }
+        use_stored = have && stored_for == first;
+      }
+      double x[CMI_NION];
+      if (use_stored) {
+        const MetalTermsStored terms = {&stored};
+        cmi_ionization_state_cell_metals(terms, CmiNoMetalIntensities(), ntot,
+                                         h0, he0, AHe, gate, x);
+      } else {
+        const MetalTermsEvaluated terms = {a.model, T, T * 1.e-4};
+        cmi_ionization_state_cell_metals(terms, CmiNoMetalIntensities(), ntot,
+                                         h0, he0, AHe, gate, x);
+      }
+#pragma unroll
+      for (int i = ION_C_p1; i < CMI_NION; ++i)
+        a.cells.x[i][c] = x[i];
+    }
+  }
+}
+
 /* EmissivityCalculator::calculate_emissivities over the grid
  * (src/EmissivityCalculator.cpp:439-470): one cell per lane, the selected
  * lines written as out[k][cell - first]. Post-processing of the final grid. */

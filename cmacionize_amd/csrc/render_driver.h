@@ -531,11 +531,12 @@ int RecordSource::begin(cmi_gpu_engine *e, const char *what,
 /* the arguments of the two cube record kernels, which differ in the name of
  * the frame vector */
 template <class Args>
-void fill_cube_record_args(const cmi_gpu_engine *e, const RecordSource &s,
-                           int32_t first, int nl, Args &r, double *frame) {
+void fill_cube_record_args(const cmi_gpu_engine *e, const CellsDev &cells,
+                           const RecordSource &s, int32_t first, int nl,
+                           Args &r, double *frame) {
   constexpr int BATCH = sizeof r.lines / sizeof r.lines[0];
   r.model = e->model;
-  r.cells = e->cells;
+  r.cells = cells;
   r.ncell = e->ncell;
   r.nlines = nl;
   for (int l = 0; l < BATCH; ++l) {
@@ -553,10 +554,12 @@ void fill_cube_record_args(const cmi_gpu_engine *e, const RecordSource &s,
 int RecordSource::records_of(cmi_gpu_engine *e, int32_t first, int nl) {
   if (lines) {
     const int blocks = grid_blocks(e, e->ncell, 8);
+    CellsDev *cells;
+    CMI_TRY(cells_settled(e, cells));
     if (layout == RECORDS_PLAIN) {
       LineRecordArgs r;
       r.model = e->model;
-      r.cells = e->cells;
+      r.cells = *cells;
       r.ncell = e->ncell;
       r.nlines = nl;
       for (int l = 0; l < CMI_LINE_IMAGE_BATCH; ++l)
@@ -569,11 +572,11 @@ int RecordSource::records_of(cmi_gpu_engine *e, int32_t first, int nl) {
       });
     } else if (layout == RECORDS_CUBE) {
       LineCubeRecordArgs r;
-      fill_cube_record_args(e, *this, first, nl, r, r.n);
+      fill_cube_record_args(e, *cells, *this, first, nl, r, r.n);
       line_cube_record_kernel<<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
     } else {
       SkyCubeRecordArgs r;
-      fill_cube_record_args(e, *this, first, nl, r, r.v_obs);
+      fill_cube_record_args(e, *cells, *this, first, nl, r, r.v_obs);
       sky_cube_record_kernel<<<blocks, CMI_BLOCK, 0, e->stream>>>(r);
     }
   } else {
@@ -975,8 +978,10 @@ int ContinuumInput::begin(cmi_gpu_engine *e, const char *what, int32_t nf,
 /* the records of the channels [c0, c0 + nc) onto the stream */
 int ContinuumInput::records_of(cmi_gpu_engine *e, int32_t c0, int nc) {
   if (freq) {
+    CellsDev *cells;
+    CMI_TRY(cells_settled(e, cells));
     FreeFreeRecordArgs r;
-    r.cells = e->cells;
+    r.cells = *cells;
     r.ncell = e->ncell;
     r.helium_abundance = e->model.abundance[0];
     r.fb = fb;
@@ -1193,8 +1198,10 @@ int AbsorbingInput::begin(cmi_gpu_engine *e, const char *what,
                           RenderArena &arena) {
   const size_t ncell = (size_t)e->ncell;
   if (hi) {
+    CellsDev *cells;
+    CMI_TRY(cells_settled(e, cells));
     HiRecordArgs r;
-    r.cells = e->cells;
+    r.cells = *cells;
     r.ncell = e->ncell;
     r.helium_abundance = e->model.abundance[0];
     r.weight = cmi_emission_atomic_weight[0];

@@ -532,7 +532,7 @@ static ShootArgs shoot_args(const cmi_gpu_engine *e, const LaunchPlan &p,
   ShootArgs a;
   a.grid = e->grid;
   a.model = e->model;
-  a.cells = e->cells;
+  a.cells = cells_of_iteration(e);
   a.counters = e->counters;
   a.first_packet = first_packet;
   a.batch_offset = done;
@@ -575,15 +575,21 @@ static ShootArgs shoot_args(const cmi_gpu_engine *e, const LaunchPlan &p,
   return a;
 }
 
-/* the padded records of this call's cell state (0.1 ms at 256^3) */
+/* the padded records of this call's cell state (0.1 ms at 256^3), unless
+ * they are in place: the hydrogen-only update writes them with the records
+ * (hydrogen_update_kernel), everything else that writes a record says so
+ * (pad_records_stale) */
 static int pad_records(cmi_gpu_engine *e, const LaunchPlan &p) {
+  if (e->pad_valid)
+    return CMI_GPU_OK;
   const GridDev &g = e->grid;
   if (!e->pad_H)
     HIP_TRY(hipMalloc(&e->pad_H, sizeof(double) * (size_t)p.padded_cells));
   pad_record_kernel<<<grid_blocks(e, p.padded_cells, 8), CMI_BLOCK, 0,
-                      e->stream>>>(e->cells.opacity, e->pad_H, g.ncell[0],
-                                   g.ncell[1], g.ncell[2]);
+                      e->stream>>>(cells_of_iteration(e).opacity, e->pad_H,
+                                   g.ncell[0], g.ncell[1], g.ncell[2]);
   HIP_TRY(hipGetLastError());
+  e->pad_valid = true;
   return CMI_GPU_OK;
 }
 
@@ -743,7 +749,7 @@ static InteractArgs interact_args(const cmi_gpu_engine *e, const ShootArgs &a) {
   InteractArgs ia;
   memset(&ia, 0, sizeof ia);
   ia.model = e->model;
-  ia.cells = e->cells;
+  ia.cells = cells_of_iteration(e);
   ia.counters = e->counters;
   ia.first_packet = a.first_packet;
   ia.seed = a.seed;
@@ -969,7 +975,7 @@ static int tile_round_launch(cmi_gpu_engine *e, const LaunchPlan &p,
   TileArgs ta;
   ta.grid = e->grid;
   ta.model = e->model;
-  ta.cells = e->cells;
+  ta.cells = cells_of_iteration(e);
   ta.counters = e->counters;
   ta.tiles = t.tg;
   ta.refill_threshold = e->tune.tile_refill_threshold;

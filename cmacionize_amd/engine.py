@@ -134,7 +134,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_hi_sky_cube", "cmi_gpu_render_hi_sky_map_cube",
     "cmi_gpu_render_field_absorbing_cube",
     "cmi_gpu_render_field_absorbing_sky_cube",
-    "cmi_gpu_absorbing_cube_probe",
+    "cmi_gpu_absorbing_cube_probe", "cmi_gpu_get_update_state",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -330,6 +330,8 @@ def load_library():
     L.cmi_gpu_download_field.argtypes = [vp, C.c_int32, _dp]
     L.cmi_gpu_field_device_pointer.restype = C.c_void_p
     L.cmi_gpu_field_device_pointer.argtypes = [vp, C.c_int32]
+    if hasattr(L, "cmi_gpu_get_update_state"):  # (as for the stamps below)
+        L.cmi_gpu_get_update_state.argtypes = [vp] + 3 * [C.POINTER(C.c_int32)]
     L.cmi_gpu_reset_grid.argtypes = [vp]
     L.cmi_gpu_shoot.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64,
                                 C.c_uint64]
@@ -848,6 +850,14 @@ class GpuEngine:
 
     def field_device_pointer(self, field):
         return self._lib.cmi_gpu_field_device_pointer(self._h, field)
+
+    def update_state(self):
+        """(x[2..13] of the last update still to be made, padded records
+        valid, a whole-grid update may defer x[2..13]) as booleans."""
+        v = [C.c_int32() for _ in range(3)]
+        self._check(self._lib.cmi_gpu_get_update_state(
+            self._h, *[C.byref(x) for x in v]))
+        return tuple(bool(x.value) for x in v)
 
     # iteration body -----------------------------------------------------------
     def field_tensor(self, field):

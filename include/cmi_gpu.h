@@ -295,7 +295,17 @@ int cmi_gpu_download_field(cmi_gpu_engine *engine, int32_t field,
  * helium heating term, J of S++ O+ Ne+ S+++ N++ C++ - so that a photon below
  * 24.59 eV touches one 64-B line of the row, not two (field_stride 1 tells
  * the layout, not the field's offset: ask this function per field). */
+/* (A pointer to a state field - n, T, a fraction - lets the caller read and
+ * write the cells behind the engine's back: from this call on the engine
+ * makes every ionic fraction in every update, tuning "defer_metals" or not.) */
 void *cmi_gpu_field_device_pointer(cmi_gpu_engine *engine, int32_t field);
+/* How the hydrogen-only update stands (any pointer may be NULL): whether
+ * x[2..13] of the last update are still to be made, whether the padded
+ * records of the transport are those of the cells as they are, whether a
+ * whole-grid update of this engine may defer x[2..13] at all. */
+int cmi_gpu_get_update_state(cmi_gpu_engine *engine, int32_t *metals_pending,
+                             int32_t *pad_records_valid,
+                             int32_t *deferral_allowed);
 int cmi_gpu_accumulator_layout(cmi_gpu_engine *engine, int64_t *field_stride,
                                int64_t *cell_stride);
 
@@ -628,6 +638,15 @@ int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
  *                           those of one temperature and every row of 64
  *                           cells that all have it, bit for bit, reads them
  *                           (same results) - 0: every cell evaluates them
+ *   "defer_metals" (1)      hydrogen-only update of the whole grid without a
+ *                           temperature solve: x[2..13], which no kernel of
+ *                           such a run reads, are made when somebody looks
+ *                           (a download, the emissivities, a renderer, ...),
+ *                           not in every iteration (same results, bit for
+ *                           bit) - 0: by every update
+ *   "update_writes_pad" (1) ... and that update writes the padded records
+ *                           of the next transport step itself - 0: a pass of
+ *                           its own in every cmi_gpu_shoot
  *   "timing" (0)            record HIP events around every launch for
  *                           cmi_gpu_get_timing / _kernel_timing /
  *                           _launch_times (off: a run creates no events)
