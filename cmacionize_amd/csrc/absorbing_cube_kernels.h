@@ -284,54 +284,33 @@ struct AbsorbingMarchArgs {
 template <int CB, bool CALL>
 __global__ void __launch_bounds__(256)
     absorbing_cube_march_kernel(const AbsorbingMarchArgs a) {
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const LineViewDev &v = a.view;
-  const int32_t NY = v.ny * v.s;
-  const int32_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  const int32_t by = blockIdx.x % tiles_y, bx = blockIdx.x / tiles_y;
-  const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int32_t sx = a.sx0 + (2 * bx + (wave >> 1)) * TX + lane / TY;
-  const int32_t sy = (2 * by + (wave & 1)) * TY + lane % TY;
-  if (sx >= a.sx1 || sy >= NY)
+  int32_t sx, sy;
+  double x, y;
+  if (!tile_sample(a.view, a.sx0, a.sx1, sx, sy, x, y))
     return;
-  const int32_t ix = sx / v.s, iy = sy / v.s;
-  const double fa = ((sx - ix * v.s) + 0.5) / v.s;
-  const double fb = ((sy - iy * v.s) + 0.5) / v.s;
-  const double x = v.img_anchor[0] + v.img_sides[0] * ((ix + fa) / v.nx);
-  const double y = v.img_anchor[1] + v.img_sides[1] * ((iy + fb) / v.ny);
 
-  /* the block's edges; those past the last channel of a partial block repeat
-   * its upper edge (their channels hold f == 0 and are not stored) */
   double edge[CB + 1];
-#pragma unroll
-  for (int i = 0; i <= CB; ++i)
-    edge[i] = a.vmin + (double)(a.c0 + (i < a.nc ? i : a.nc)) * a.dv;
+  channel_block_edges<CB>(a.vmin, a.dv, a.c0, a.nc, edge);
 
   double I[CB];
 #pragma unroll
   for (int i = 0; i < CB; ++i)
     I[i] = a.background[i];
   double unused = 1.;
-  double pos[3], t_in, t_out;
-  int32_t index[3];
-  if (line_image_ray(a.grid, v, x, y, pos, index, t_in, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
+  GridRay ray;
+  if (ray.start(a.grid, a.view, x, y)) {
+    while (ray.inside(a.grid)) {
       const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records) + cell * 3;
+          reinterpret_cast<const double2 *>(a.records) + ray.cell(a.grid) * 3;
       const double2 au = rec[0];
       const double2 bs = rec[1];
       const double2 ks = rec[2];
-      const double ds = line_image_step(a.grid, v, pos, index);
+      const double ds = ray.step(a.grid);
       const double adv = au.x, u = au.y, b = bs.x, sl = bs.y;
       const double kc = ks.x, sc = ks.y;
       const double z_lo = (edge[0] - u) / b;
       const double z_hi = (edge[CB] - u) / b;
-      /* every edge of the block at or below -6 (or NaN: b == 0 and u on the
-       * upper edge), or every edge at or above 6: f_c == 0 for the block */
-      const bool dark = !a.full && (!(z_hi > -6.) || (z_lo >= 6.));
+      const bool dark = !a.full && channel_block_dark(z_lo, z_hi);
       if (dark) {
         if (kc != 0.) {
           const double S = sc + 0. * (sl - sc);
@@ -352,7 +331,7 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
-  const int64_t at = (int64_t)(sx - a.sx0) * NY + sy;
+  const int64_t at = tile_sample_at(a.view, a.sx0, sx, sy);
 #pragma unroll
   for (int i = 0; i < CB; ++i)
     if (i < a.nc)
@@ -388,12 +367,8 @@ __global__ void __launch_bounds__(256)
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.nrays)
     return;
-  const SkyRay ray = sky_load_ray(a.directions, r);
-
   double edge[CB + 1];
-#pragma unroll
-  for (int i = 0; i <= CB; ++i)
-    edge[i] = a.vmin + (double)(a.c0 + (i < a.nc ? i : a.nc)) * a.dv;
+  channel_block_edges<CB>(a.vmin, a.dv, a.c0, a.nc, edge);
 
   double I[CB], T[CB];
 #pragma unroll
@@ -401,25 +376,21 @@ __global__ void __launch_bounds__(256)
     I[i] = 0.;
     T[i] = 1.;
   }
-  double pos[3], t_start, t_out;
-  int32_t index[3];
-  if (sky_ray_start(a.grid, a.origin, ray, pos, index, t_start, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
+  GridRay ray;
+  if (ray.start(a.grid, a.origin, a.directions, r)) {
+    while (ray.inside(a.grid)) {
       const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records) + cell * 4;
+          reinterpret_cast<const double2 *>(a.records) + ray.cell(a.grid) * 4;
       const double2 aw = rec[0];
       const double2 ww = rec[1];
       const double2 bs = rec[2];
       const double2 ks = rec[3];
-      const double ds = sky_step(a.grid, ray, pos, index);
+      const double ds = ray.step(a.grid);
       const double adv = aw.x, b = bs.x, sl = bs.y, kc = ks.x, sc = ks.y;
       const double u = (aw.y * ray.d[0] + ww.x * ray.d[1]) + ww.y * ray.d[2];
       const double z_lo = (edge[0] - u) / b;
       const double z_hi = (edge[CB] - u) / b;
-      const bool dark = !a.full && (!(z_hi > -6.) || (z_lo >= 6.));
+      const bool dark = !a.full && channel_block_dark(z_lo, z_hi);
       if (dark) {
         if (kc != 0.) {
           const double S = sc + 0. * (sl - sc);
@@ -447,6 +418,45 @@ __global__ void __launch_bounds__(256)
       out[i * a.channel_stride] = I[i] + T[i] * a.background[i];
 }
 
+/* row k of absorbing_cube_probe_kernel with the camera chosen */
+template <bool POINT>
+__device__ __forceinline__ void absorbing_probe_row(
+    const GridDev &g, const LineViewDev &v, const double origin[3],
+    const double *__restrict__ rays, int64_t k,
+    const double *__restrict__ records, const double *__restrict__ background,
+    int32_t nchan, double vmin, double dv, int32_t max_cells, double *o) {
+  double *I_steps = o + 3 + 2 * (int64_t)max_cells;
+  double *I_end = I_steps + (int64_t)nchan * max_cells;
+  for (int32_t c = 0; c < nchan; ++c) {
+    const double bg = background[c];
+    const double e_lo = vmin + (double)c * dv;
+    const double e_hi = vmin + (double)(c + 1) * dv;
+    GridRay ray;
+    const bool hit = POINT ? ray.start(g, origin, rays, k)
+                           : ray.start(g, v, rays[2 * k], rays[2 * k + 1]);
+    double I = POINT ? 0. : bg, T = 1.;
+    /* (the geometry is every channel's: each writes the same prefix) */
+    probe_row(g, ray, hit, max_cells, o, [&](int64_t cell, double ds, int i) {
+      const double2 *rec =
+          reinterpret_cast<const double2 *>(records) + cell * (POINT ? 4 : 3);
+      const double2 r0 = rec[0];
+      double u = r0.y;
+      if (POINT) {
+        const double2 ww = rec[1];
+        u = (r0.y * ray.d[0] + ww.x * ray.d[1]) + ww.y * ray.d[2];
+      }
+      const double2 bs = rec[POINT ? 2 : 1];
+      const double2 ks = rec[POINT ? 3 : 2];
+      const double f =
+          0.5 * (cube_E((e_hi - u) / bs.x) - cube_E((e_lo - u) / bs.x));
+      absorbing_channel<POINT, true>(r0.x, f, bs.y, ks.x, ks.y, ds, I, T);
+      if (i < max_cells)
+        I_steps[(int64_t)c * max_cells + i] = I;
+    });
+    I_end[c] = POINT ? I + T * bg : I;
+  }
+}
+
 /* cmi_gpu_absorbing_cube_probe: row k = {t0, t1, steps, cells[max_cells],
  * ds[max_cells], I[nchan][max_cells], I_end[nchan]} of ray k, in the style of
  * continuum_probe_kernel: one channel at a time with the full update in every
@@ -466,66 +476,13 @@ __global__ void __launch_bounds__(64)
   if (k >= n)
     return;
   double *o = out + k * (3 + (2 + (int64_t)nchan) * max_cells + nchan);
-  double *I_steps = o + 3 + 2 * (int64_t)max_cells;
-  double *I_end = I_steps + (int64_t)nchan * max_cells;
   const double origin[3] = {ox, oy, oz};
-  SkyRay ray;
   if (point)
-    ray = sky_load_ray(rays, k);
-  for (int32_t c = 0; c < nchan; ++c) {
-    const double bg = background[c];
-    const double e_lo = vmin + (double)c * dv;
-    const double e_hi = vmin + (double)(c + 1) * dv;
-    double pos[3], t0, t1;
-    int32_t index[3];
-    const bool hit =
-        point ? sky_ray_start(g, origin, ray, pos, index, t0, t1)
-              : line_image_ray(g, v, rays[2 * k], rays[2 * k + 1], pos, index,
-                               t0, t1);
-    double I = point ? 0. : bg, T = 1.;
-    int steps = 0;
-    if (hit) {
-      while (line_image_inside(g, index)) {
-        const int64_t cell =
-            ((int64_t)index[0] * g.ncell[1] + index[1]) * g.ncell[2] +
-            index[2];
-        const double2 *rec =
-            reinterpret_cast<const double2 *>(records) + cell * (point ? 4 : 3);
-        const double2 r0 = rec[0];
-        double u = r0.y, ds;
-        if (point) {
-          const double2 ww = rec[1];
-          u = (r0.y * ray.d[0] + ww.x * ray.d[1]) + ww.y * ray.d[2];
-          ds = sky_step(g, ray, pos, index);
-        } else {
-          ds = line_image_step(g, v, pos, index);
-        }
-        const double2 bs = rec[point ? 2 : 1];
-        const double2 ks = rec[point ? 3 : 2];
-        const double f =
-            0.5 * (cube_E((e_hi - u) / bs.x) - cube_E((e_lo - u) / bs.x));
-        if (point)
-          absorbing_channel<true, true>(r0.x, f, bs.y, ks.x, ks.y, ds, I, T);
-        else
-          absorbing_channel<false, true>(r0.x, f, bs.y, ks.x, ks.y, ds, I, T);
-        if (steps < max_cells) {
-          /* (the geometry is every channel's: written with the first) */
-          if (c == 0) {
-            o[3 + steps] = (double)cell;
-            o[3 + max_cells + steps] = ds;
-          }
-          I_steps[(int64_t)c * max_cells + steps] = I;
-        }
-        ++steps;
-      }
-    }
-    I_end[c] = point ? I + T * bg : I;
-    if (c == 0) {
-      o[0] = hit ? t0 : __builtin_nan("");
-      o[1] = hit ? t1 : __builtin_nan("");
-      o[2] = (double)steps;
-    }
-  }
+    absorbing_probe_row<true>(g, v, origin, rays, k, records, background,
+                              nchan, vmin, dv, max_cells, o);
+  else
+    absorbing_probe_row<false>(g, v, origin, rays, k, records, background,
+                               nchan, vmin, dv, max_cells, o);
 }
 
 #endif

@@ -6,8 +6,7 @@
  * among their channels and emit what the cell does not absorb itself; here a
  * channel f has kappa_f (m^-1) and S_f (W m^-2 Hz^-1 sr^-1) per cell and the
  * cell absorbs its own emission. The rays, the cells and the path lengths are
- * the images' and the sky maps' (line_image_ray, line_image_inside,
- * line_image_step; sky_load_ray, sky_ray_start, sky_step; all unchanged).
+ * the images' and the sky maps' (ray_walk.h).
  *
  * Records: FB pairs {kappa_f, S_f} per cell as double2, 16 FB bytes, for one
  * block of FB consecutive channels; the slots past the last channel of a
@@ -181,40 +180,25 @@ struct ContinuumMarchArgs {
 template <int FB>
 __global__ void __launch_bounds__(256)
     continuum_march_kernel(const ContinuumMarchArgs a) {
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const LineViewDev &v = a.view;
-  const int32_t NY = v.ny * v.s;
-  const int32_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  const int32_t by = blockIdx.x % tiles_y, bx = blockIdx.x / tiles_y;
-  const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int32_t sx = a.sx0 + (2 * bx + (wave >> 1)) * TX + lane / TY;
-  const int32_t sy = (2 * by + (wave & 1)) * TY + lane % TY;
-  if (sx >= a.sx1 || sy >= NY)
+  int32_t sx, sy;
+  double x, y;
+  if (!tile_sample(a.view, a.sx0, a.sx1, sx, sy, x, y))
     return;
-  const int32_t ix = sx / v.s, iy = sy / v.s;
-  const double fa = ((sx - ix * v.s) + 0.5) / v.s;
-  const double fb = ((sy - iy * v.s) + 0.5) / v.s;
-  const double x = v.img_anchor[0] + v.img_sides[0] * ((ix + fa) / v.nx);
-  const double y = v.img_anchor[1] + v.img_sides[1] * ((iy + fb) / v.ny);
 
   double I[FB];
 #pragma unroll
   for (int i = 0; i < FB; ++i)
     I[i] = a.background[i];
-  double pos[3], t_in, t_out;
-  int32_t index[3];
-  if (line_image_ray(a.grid, v, x, y, pos, index, t_in, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
+  GridRay ray;
+  if (ray.start(a.grid, a.view, x, y)) {
+    while (ray.inside(a.grid)) {
       const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records) + cell * FB;
+          reinterpret_cast<const double2 *>(a.records) + ray.cell(a.grid) * FB;
       double2 ks[FB];
 #pragma unroll
       for (int i = 0; i < FB; ++i)
         ks[i] = rec[i];
-      const double ds = line_image_step(a.grid, v, pos, index);
+      const double ds = ray.step(a.grid);
 #pragma unroll
       for (int i = 0; i < FB; ++i) {
         /* (the slots past a partial block hold {0, 0}: em == 0) */
@@ -223,7 +207,7 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
-  const int64_t at = (int64_t)(sx - a.sx0) * NY + sy;
+  const int64_t at = tile_sample_at(a.view, a.sx0, sx, sy);
 #pragma unroll
   for (int i = 0; i < FB; ++i)
     if (i < a.nc)
@@ -252,28 +236,22 @@ __global__ void __launch_bounds__(256)
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.nrays)
     return;
-  const SkyRay ray = sky_load_ray(a.directions, r);
-
   double I[FB], T[FB];
 #pragma unroll
   for (int i = 0; i < FB; ++i) {
     I[i] = 0.;
     T[i] = 1.;
   }
-  double pos[3], t_start, t_out;
-  int32_t index[3];
-  if (sky_ray_start(a.grid, a.origin, ray, pos, index, t_start, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
+  GridRay ray;
+  if (ray.start(a.grid, a.origin, a.directions, r)) {
+    while (ray.inside(a.grid)) {
       const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records) + cell * FB;
+          reinterpret_cast<const double2 *>(a.records) + ray.cell(a.grid) * FB;
       double2 ks[FB];
 #pragma unroll
       for (int i = 0; i < FB; ++i)
         ks[i] = rec[i];
-      const double ds = sky_step(a.grid, ray, pos, index);
+      const double ds = ray.step(a.grid);
 #pragma unroll
       for (int i = 0; i < FB; ++i) {
         const double em = expm1(-(ks[i].x * ds));
@@ -286,6 +264,40 @@ __global__ void __launch_bounds__(256)
   for (int i = 0; i < FB; ++i)
     if (i < a.nc)
       a.out[i * a.channel_stride + r] = I[i] + T[i] * a.background[i];
+}
+
+/* row k of continuum_probe_kernel with the camera chosen */
+template <bool POINT>
+__device__ __forceinline__ void continuum_probe_row(
+    const GridDev &g, const LineViewDev &v, const double origin[3],
+    const double *__restrict__ rays, int64_t k,
+    const double *__restrict__ kappa, const double *__restrict__ source,
+    const double *__restrict__ background, int32_t nf, int64_t ncell,
+    int32_t max_cells, double *o) {
+  double *I_steps = o + 3 + 2 * (int64_t)max_cells;
+  double *I_end = I_steps + (int64_t)nf * max_cells;
+  for (int32_t f = 0; f < nf; ++f) {
+    const double bg = background[f];
+    GridRay ray;
+    const bool hit = POINT ? ray.start(g, origin, rays, k)
+                           : ray.start(g, v, rays[2 * k], rays[2 * k + 1]);
+    double I = POINT ? 0. : bg, T = 1.;
+    /* (the geometry is every channel's: each writes the same prefix) */
+    probe_row(g, ray, hit, max_cells, o, [&](int64_t cell, double ds, int i) {
+      const double kf = kappa[(int64_t)f * ncell + cell];
+      const double sf = source[(int64_t)f * ncell + cell];
+      const double em = expm1(-(kf * ds));
+      if (POINT) {
+        I = I + T * (sf * -em);
+        T = T + T * em;
+      } else {
+        I = I + em * (I - sf);
+      }
+      if (i < max_cells)
+        I_steps[(int64_t)f * max_cells + i] = I;
+    });
+    I_end[f] = POINT ? I + T * bg : I;
+  }
 }
 
 /* cmi_gpu_continuum_probe: row k = {t0, t1, steps, cells[max_cells],
@@ -309,51 +321,13 @@ __global__ void __launch_bounds__(64)
   if (k >= n)
     return;
   double *o = out + k * (3 + (2 + (int64_t)nf) * max_cells + nf);
-  double *I_steps = o + 3 + 2 * (int64_t)max_cells;
-  double *I_end = I_steps + (int64_t)nf * max_cells;
   const double origin[3] = {ox, oy, oz};
-  SkyRay ray;
   if (point)
-    ray = sky_load_ray(rays, k);
-  for (int32_t f = 0; f < nf; ++f) {
-    const double bg = background[f];
-    double pos[3], t0, t1;
-    int32_t index[3];
-    const bool hit =
-        point ? sky_ray_start(g, origin, ray, pos, index, t0, t1)
-              : line_image_ray(g, v, rays[2 * k], rays[2 * k + 1], pos, index,
-                               t0, t1);
-    double I = point ? 0. : bg, T = 1.;
-    int steps = 0;
-    if (hit) {
-      while (line_image_inside(g, index)) {
-        const int64_t cell =
-            ((int64_t)index[0] * g.ncell[1] + index[1]) * g.ncell[2] +
-            index[2];
-        const double kf = kappa[(int64_t)f * ncell + cell];
-        const double sf = source[(int64_t)f * ncell + cell];
-        const double ds = point ? sky_step(g, ray, pos, index)
-                                : line_image_step(g, v, pos, index);
-        const double em = expm1(-(kf * ds));
-        if (point) {
-          I = I + T * (sf * -em);
-          T = T + T * em;
-        } else {
-          I = I + em * (I - sf);
-        }
-        if (steps < max_cells) {
-          o[3 + steps] = (double)cell;
-          o[3 + max_cells + steps] = ds;
-          I_steps[(int64_t)f * max_cells + steps] = I;
-        }
-        ++steps;
-      }
-    }
-    I_end[f] = point ? I + T * bg : I;
-    o[0] = hit ? t0 : __builtin_nan("");
-    o[1] = hit ? t1 : __builtin_nan("");
-    o[2] = (double)steps;
-  }
+    continuum_probe_row<true>(g, v, origin, rays, k, kappa, source, background,
+                              nf, ncell, max_cells, o);
+  else
+    continuum_probe_row<false>(g, v, origin, rays, k, kappa, source,
+                               background, nf, ncell, max_cells, o);
 }
 
 #endif

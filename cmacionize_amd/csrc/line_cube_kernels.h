@@ -2,9 +2,9 @@
  * line_cube_kernels.h - spectral line cubes: the emission-line images of
  * line_image_kernels.h resolved in radial velocity (include/cmi_gpu.h,
  * "spectral line cubes", has the contract). The ray geometry, the march order
- * and the cell and path-length arithmetic are the images' (line_image_ray,
- * line_image_step, unchanged); what is new is that a step's contribution is
- * spread over the velocity channels its Gaussian overlaps.
+ * and the cell and path-length arithmetic are the images' (ray_walk.h); what
+ * is new is that a step's contribution is spread over the velocity channels
+ * its Gaussian overlaps.
  *
  * Velocity axis: nchan channels of equal width over [vmin, vmax), edge
  *   e_c = vmin + c * dv,  dv = (vmax - vmin) / nchan,  c = 0 .. nchan
@@ -214,46 +214,27 @@ struct LineCubeMarchArgs {
 template <int CB>
 __global__ void __launch_bounds__(256)
     line_cube_march_kernel(const LineCubeMarchArgs a) {
-  constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-  const LineViewDev &v = a.view;
-  const int32_t NY = v.ny * v.s;
-  const int32_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-  const int32_t by = blockIdx.x % tiles_y, bx = blockIdx.x / tiles_y;
-  const int32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int32_t sx = a.sx0 + (2 * bx + (wave >> 1)) * TX + lane / TY;
-  const int32_t sy = (2 * by + (wave & 1)) * TY + lane % TY;
-  if (sx >= a.sx1 || sy >= NY)
+  int32_t sx, sy;
+  double x, y;
+  if (!tile_sample(a.view, a.sx0, a.sx1, sx, sy, x, y))
     return;
   const int32_t line = blockIdx.y;
-  const int32_t ix = sx / v.s, iy = sy / v.s;
-  const double fa = ((sx - ix * v.s) + 0.5) / v.s;
-  const double fb = ((sy - iy * v.s) + 0.5) / v.s;
-  const double x = v.img_anchor[0] + v.img_sides[0] * ((ix + fa) / v.nx);
-  const double y = v.img_anchor[1] + v.img_sides[1] * ((iy + fb) / v.ny);
 
-  /* the block's edges; those past the last channel of a partial block repeat
-   * its upper edge (their channels are empty and not stored) */
   double edge[CB + 1];
-#pragma unroll
-  for (int i = 0; i <= CB; ++i)
-    edge[i] = a.vmin + (double)(a.c0 + (i < a.nc ? i : a.nc)) * a.dv;
+  channel_block_edges<CB>(a.vmin, a.dv, a.c0, a.nc, edge);
 
   double I[CB];
 #pragma unroll
   for (int i = 0; i < CB; ++i)
     I[i] = 0.;
-  double pos[3], t_in, t_out;
-  int32_t index[3];
-  if (line_image_ray(a.grid, v, x, y, pos, index, t_in, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
-      const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records + cell * a.nd);
+  GridRay ray;
+  if (ray.start(a.grid, a.view, x, y)) {
+    while (ray.inside(a.grid)) {
+      const double2 *rec = reinterpret_cast<const double2 *>(
+          a.records + ray.cell(a.grid) * a.nd);
       const double2 ku = rec[0];
       const double2 sb = rec[1 + line];
-      const double ds = line_image_step(a.grid, v, pos, index);
+      const double ds = ray.step(a.grid);
       const double k = ku.x, u = ku.y, s = sb.x, b = sb.y;
       double att = 1., w;
       if (k == 0.) {
@@ -265,9 +246,7 @@ __global__ void __launch_bounds__(256)
       }
       const double z_lo = (edge[0] - u) / b;
       const double z_hi = (edge[CB] - u) / b;
-      /* every edge of the block at or below -6 (or NaN: b == 0 and u on the
-       * upper edge), or every edge at or above 6: f_c == 0 for the block */
-      const bool dark = !(z_hi > -6.) || (z_lo >= 6.);
+      const bool dark = channel_block_dark(z_lo, z_hi);
       if (dark) {
         if (k != 0.) {
 #pragma unroll
@@ -289,7 +268,7 @@ __global__ void __launch_bounds__(256)
       }
     }
   }
-  const int64_t at = (int64_t)(sx - a.sx0) * NY + sy;
+  const int64_t at = tile_sample_at(a.view, a.sx0, sx, sy);
   double *out = a.out + line * a.line_stride + at;
 #pragma unroll
   for (int i = 0; i < CB; ++i)

@@ -337,12 +337,7 @@ struct ParallelCamera {
    * distance between two planes there */
   int32_t sx0() const { return (int32_t)(ix0 * v.s); }
   int32_t sx1() const { return (int32_t)(ix1 * v.s); }
-  unsigned tiles() const {
-    constexpr int TX = CMI_LINE_IMAGE_TILE_X, TY = 64 / TX;
-    const int64_t tiles_y = (NY + 2 * TY - 1) / (2 * TY);
-    const int64_t tiles_x = (sx1() - sx0() + 2 * TX - 1) / (2 * TX);
-    return (unsigned)(tiles_x * tiles_y);
-  }
+  unsigned tiles() const { return tile_workgroups(sx1() - sx0(), NY); }
   double *out(int64_t p) const {
     return sampled() ? samples : image + p * npixel + ix0 * v.ny;
   }

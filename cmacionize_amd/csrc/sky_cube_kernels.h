@@ -2,8 +2,8 @@
  * sky_cube_kernels.h - sky cubes: the sky maps of sky_image_kernels.h
  * resolved in radial velocity (include/cmi_gpu.h, "sky cubes", has the
  * contract). The rays, the slab test, the start cell and the step are the sky
- * maps' (sky_load_ray, sky_ray_start, sky_step, unchanged); the velocity
- * axis, E and f_c are the spectral line cubes' (cube_E, unchanged). What is
+ * maps' (ray_walk.h); the velocity axis, E and f_c are the spectral line
+ * cubes' (channel_block_edges, cube_E). What is
  * new is the radial velocity: every ray has a direction of its own, so a
  * cell's u is not a property of the cell. The records carry the cell's
  * velocity relative to the observer, w = v - v_obs, and a lane forms
@@ -169,33 +169,23 @@ __global__ void __launch_bounds__(256)
   if (r >= a.nrays)
     return;
   const int32_t line = blockIdx.y;
-  const SkyRay ray = sky_load_ray(a.directions, r);
-
-  /* the block's edges; those past the last channel of a partial block repeat
-   * its upper edge (their channels are empty and not stored) */
   double edge[CB + 1];
-#pragma unroll
-  for (int i = 0; i <= CB; ++i)
-    edge[i] = a.vmin + (double)(a.c0 + (i < a.nc ? i : a.nc)) * a.dv;
+  channel_block_edges<CB>(a.vmin, a.dv, a.c0, a.nc, edge);
 
   double I[CB];
 #pragma unroll
   for (int i = 0; i < CB; ++i)
     I[i] = 0.;
   double T = 1.;
-  double pos[3], t_start, t_out;
-  int32_t index[3];
-  if (sky_ray_start(a.grid, a.origin, ray, pos, index, t_start, t_out)) {
-    while (line_image_inside(a.grid, index)) {
-      const int64_t cell =
-          ((int64_t)index[0] * a.grid.ncell[1] + index[1]) * a.grid.ncell[2] +
-          index[2];
-      const double2 *rec =
-          reinterpret_cast<const double2 *>(a.records + cell * a.nd);
+  GridRay ray;
+  if (ray.start(a.grid, a.origin, a.directions, r)) {
+    while (ray.inside(a.grid)) {
+      const double2 *rec = reinterpret_cast<const double2 *>(
+          a.records + ray.cell(a.grid) * a.nd);
       const double2 kw = rec[0];
       const double2 ww = rec[1];
       const double2 sb = rec[2 + line];
-      const double ds = sky_step(a.grid, ray, pos, index);
+      const double ds = ray.step(a.grid);
       const double k = kw.x, s = sb.x, b = sb.y;
       const double u = (kw.y * ray.d[0] + ww.x * ray.d[1]) + ww.y * ray.d[2];
       double att = 1., w;
@@ -208,9 +198,7 @@ __global__ void __launch_bounds__(256)
       }
       const double z_lo = (edge[0] - u) / b;
       const double z_hi = (edge[CB] - u) / b;
-      /* every edge of the block at or below -6 (or NaN: b == 0 and u on the
-       * upper edge), or every edge at or above 6: f_c == 0 for the block */
-      const bool dark = !(z_hi > -6.) || (z_lo >= 6.);
+      const bool dark = channel_block_dark(z_lo, z_hi);
       if (!dark) {
         double E_lo = cube_E(z_lo);
 #pragma unroll

@@ -100,6 +100,35 @@ def main():
         background=bg[:5]))
     put("continuum_probe_point", eng.continuum_probe(
         kappa[:5], source[:5], d[:500], 40, origin=origin, background=bg[:5]))
+    # the absorbing line cubes: the 21-cm client and the caller's fields
+    put("render_hi_cube", eng.render_hi_cube(
+        theta, phi, nx, ny, anchor, sides, nchan, vmin, vmax, s, 3.e3,
+        background_temperature=2.725))
+    put("render_hi_sky_cube", eng.render_hi_sky_cube(
+        origin, d, nchan, vmin, vmax, 3.e3, background_temperature=2.725,
+        observer_velocity=vo))
+    put("render_hi_sky_map_cube", eng.render_hi_sky_map_cube(
+        origin, 37, 21, nchan, vmin, vmax, sigma_turb=3.e3,
+        observer_velocity=vo))
+    hi = eng.hi_coefficients(3.e3)
+    put("hi_coefficients", hi)
+    put("render_field_absorbing_cube", eng.render_field_absorbing_cube(
+        hi["a"], hi["sl"], hi["b"], theta, phi, nx, ny, anchor, sides, nchan,
+        vmin, vmax, s, velocity=vel, kc=hi["kc"], sc=hi["sc"],
+        background=hi["sl"].mean()))
+    put("render_field_absorbing_sky_cube",
+        eng.render_field_absorbing_sky_cube(
+            hi["a"], hi["sl"], hi["b"], origin, d, nchan, vmin, vmax,
+            velocity=vel, kc=hi["kc"], sc=hi["sc"],
+            background=hi["sl"].mean(), observer_velocity=vo))
+    put("absorbing_cube_probe_parallel", eng.absorbing_cube_probe(
+        hi["a"], hi["sl"], hi["b"], xy, 40, 5, vmin, vmax, theta=theta,
+        phi=phi, velocity=vel, kc=hi["kc"], sc=hi["sc"],
+        background=hi["sl"].mean()))
+    put("absorbing_cube_probe_point", eng.absorbing_cube_probe(
+        hi["a"], hi["sl"], hi["b"], d[:500], 40, 5, vmin, vmax,
+        origin=origin, velocity=vel, kc=hi["kc"], sc=hi["sc"],
+        background=hi["sl"].mean(), observer_velocity=vo))
     # the chunk loops past one chunk, through the continuum's launch size
     eng.set_tuning(continuum_launch_rays=1000)
     put("render_continuum_images_chunked", eng.render_continuum_images(
