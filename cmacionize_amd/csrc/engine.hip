@@ -16,6 +16,7 @@
 #include "dust_cube_kernels.h"
 #include "continuum_kernels.h"
 #include "absorbing_cube_kernels.h"
+#include "lyman_alpha_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -325,6 +326,17 @@ struct cmi_gpu_engine {
   const char *dust_cube_stale = nullptr;
   /* the line of cmi_gpu_set_cell_source_line */
   int32_t cell_source_line = -1;
+  /* Lyman alpha (cmi_gpu_set_lyman_alpha; lya.nchan 0: off): the kernels'
+   * argument with the engine's buffers records [ncell], image [nviews]
+   * [npixel] and cube [nviews][npixel][nchan], the dust the records were built
+   * with, the views, the packet counter of the event loop, and why the mode
+   * is stale (null: it is not) */
+  LyaDev lya = {};
+  DustDev lya_dust = {};
+  int32_t lya_nviews = 0;
+  unsigned long long *lya_next = nullptr;
+  LyaCountersDev *lya_counters = nullptr;
+  const char *lya_stale = nullptr;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1281,6 +1293,11 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(const_cast<double *>(e->dust_cube.obs_velocity));
   (void)hipFree(e->dust_cube.cube);
   (void)hipFree(e->cell_source_blocks);
+  (void)hipFree(const_cast<LyaRecord *>(e->lya.records));
+  (void)hipFree(e->lya.image);
+  (void)hipFree(e->lya.cube);
+  (void)hipFree(e->lya_next);
+  (void)hipFree(e->lya_counters);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
   delete e;
@@ -2897,6 +2914,9 @@ int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *e, double g,
 static void dust_cube_mark_stale(cmi_gpu_engine *e, const char *why) {
   if (e->dust_cube.nchan)
     e->dust_cube_stale = why;
+  /* Lyman-alpha mode is built from the same things */
+  if (e->lya.nchan)
+    e->lya_stale = why;
 }
 
 /* the views' descriptors and counters go with a camera that is replaced */
@@ -4028,6 +4048,422 @@ int cmi_gpu_download_cube_view(cmi_gpu_engine *e, int32_t view, double *I,
                       hipMemcpyDeviceToHost);
   }
   (void)hipFree(ordered);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+/* ------------------------------------------------------- Lyman alpha -- */
+
+/* packets of the first lya_shoot_kernel launch of a call; the later ones are
+ * sized from its cell crossings per packet, as cmi_gpu_dust_shoot sizes its
+ * own, between these bounds */
+#define CMI_LYA_FIRST_LAUNCH (1ull << 14)
+#define CMI_LYA_MIN_LAUNCH (1ull << 14)
+#define CMI_LYA_MAX_LAUNCH (1ull << 20)
+#define CMI_LYA_STEPS_PER_LAUNCH (1ull << 33)
+/* workgroups per CU of the event loop (-DCMI_LYA_EVENT_LOOP; one packet per
+ * lane launches a lane per packet): 8 x 4 waves wait for the 2 per SIMD that
+ * the kernel's registers allow */
+#define CMI_LYA_BLOCKS_PER_CU 8u
+#define CMI_LYA_MAX_SCATTER 100000000u
+
+static void lya_free(cmi_gpu_engine *e) {
+  (void)hipFree(const_cast<LyaRecord *>(e->lya.records));
+  (void)hipFree(e->lya.image);
+  (void)hipFree(e->lya.cube);
+  e->lya = LyaDev{};
+  e->lya_nviews = 0;
+  e->lya_stale = nullptr;
+}
+
+int cmi_gpu_reset_lya(cmi_gpu_engine *e) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "reset_lya: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (e->lya.nchan) {
+    const size_t npix = (size_t)e->lya_nviews * (size_t)e->lya.npixel;
+    HIP_TRY(hipMemsetAsync(e->lya.image, 0, npix * sizeof(double), e->stream));
+    HIP_TRY(hipMemsetAsync(e->lya.cube, 0,
+                           npix * e->lya.nchan * sizeof(double), e->stream));
+  }
+  if (e->lya_counters)
+    HIP_TRY(hipMemsetAsync(e->lya_counters, 0, sizeof(LyaCountersDev),
+                           e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_lyman_alpha(cmi_gpu_engine *e, int32_t nchan, double vmin,
+                            double vmax, double sigma_turb, double x_crit,
+                            uint64_t max_scatter, const double *n_HI,
+                            const double *temperature) {
+  static const char *what = "set_lyman_alpha";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  HIP_TRY(hipSetDevice(e->device));
+  if (nchan == 0) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    lya_free(e);
+    return CMI_GPU_OK;
+  }
+  CMI_TRY(dust_check_grid(e));
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  if (!e->have_ccd)
+    return fail(CMI_GPU_ESTATE, "%s: a camera must be set first", what);
+  if (dust_point_camera(e))
+    return fail(CMI_GPU_ESTATE, "%s: the point (sky) cameras are not "
+                "supported; set_ccd_image or set_ccd_images", what);
+  if (e->dust_source != DUST_SOURCE_CELLS || !e->have_cell_source)
+    return fail(CMI_GPU_ESTATE, "%s: a cell source must be selected "
+                "(set_cell_source_field or set_cell_source_line)", what);
+  if (e->cell_source_from_cells && e->cell_source_epoch != e->cells_epoch)
+    return fail(CMI_GPU_ESTATE, "%s: the cells changed after the line source "
+                "was set; set_cell_source_line again", what);
+  if (e->have_dust_scattering && !e->dust_per_hydrogen)
+    return fail(CMI_GPU_ESTATE, "%s: the dust must be given per hydrogen "
+                "nucleus (set_dust_scattering_per_hydrogen)", what);
+  if (!(sigma_turb >= 0.) || !std::isfinite(sigma_turb))
+    return fail(CMI_GPU_EINVAL, "%s: the turbulent velocity dispersion must "
+                "be >= 0 and finite", what);
+  if (!(x_crit >= 0.) || !std::isfinite(x_crit))
+    return fail(CMI_GPU_EINVAL, "%s: the core-skipping frequency must be >= 0 "
+                "and finite", what);
+  if (max_scatter < 1 || max_scatter > CMI_LYA_MAX_SCATTER)
+    return fail(CMI_GPU_EINVAL, "%s: the cap on scatterings must be 1 to %u "
+                "(the packet stream's block counter has 32 bits)", what,
+                CMI_LYA_MAX_SCATTER);
+  const int32_t nviews = e->dust_nviews;
+  LineCubeAxis axis;
+  CMI_TRY(line_cube_axis(what, nviews, e->dust.res[0], e->dust.res[1], nchan,
+                         vmin, vmax, axis));
+  const size_t npixel = dust_image_pixels(e);
+  const size_t ncell = (size_t)e->ncell;
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
+  /* everything new is built aside: a call that fails leaves the previous
+   * state in place */
+  LyaRecord *records = nullptr;
+  double *image = nullptr, *cube = nullptr, *dn = nullptr, *dT = nullptr;
+  unsigned int *ninvalid = nullptr;
+  unsigned int bad = 0;
+  hipError_t err = hipMalloc(&records, sizeof(LyaRecord) * ncell);
+  if (err == hipSuccess)
+    err = hipMalloc(&image, sizeof(double) * (size_t)nviews * npixel);
+  if (err == hipSuccess)
+    err = hipMalloc(&cube, sizeof(double) * (size_t)nviews * npixel * nchan);
+  if (err == hipSuccess)
+    err = hipMalloc(&ninvalid, sizeof(unsigned int));
+  if (err == hipSuccess && n_HI) {
+    err = hipMalloc(&dn, sizeof(double) * ncell);
+    if (err == hipSuccess)
+      err = hipMemcpy(dn, n_HI, sizeof(double) * ncell, hipMemcpyHostToDevice);
+  }
+  if (err == hipSuccess && temperature) {
+    err = hipMalloc(&dT, sizeof(double) * ncell);
+    if (err == hipSuccess)
+      err = hipMemcpy(dT, temperature, sizeof(double) * ncell,
+                      hipMemcpyHostToDevice);
+  }
+  if (err == hipSuccess && !e->lya_next)
+    err = hipMalloc(&e->lya_next, sizeof(unsigned long long));
+  if (err == hipSuccess && !e->lya_counters)
+    err = hipMalloc(&e->lya_counters, sizeof(LyaCountersDev));
+  if (err == hipSuccess)
+    err = hipMemsetAsync(ninvalid, 0, sizeof(unsigned int), e->stream);
+  if (err == hipSuccess) {
+    LyaRecordArgs a;
+    a.number_density = cells->number_density;
+    a.x_H = cells->x[0];
+    a.n_HI = dn;
+    a.temperature = dT ? dT : cells->temperature;
+    a.velocity = e->cell_velocities;
+    a.sigma_turb = sigma_turb;
+    a.sigma_d = e->have_dust_scattering ? e->dust_kappa : 0.;
+    a.ncell = e->ncell;
+    a.out = records;
+    a.ninvalid = ninvalid;
+    lya_record_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0, e->stream>>>(a);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(&bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                         e->stream);
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  (void)hipFree(dn);
+  (void)hipFree(dT);
+  (void)hipFree(ninvalid);
+  int rc = CMI_GPU_OK;
+  if (err == hipErrorOutOfMemory) {
+    (void)hipGetLastError();
+    rc = fail(CMI_GPU_ENOMEM, "%s: %d cubes of %d channels of %zu pixels do "
+              "not fit into the device's memory", what, (int)nviews,
+              (int)nchan, npixel);
+  } else if (err != hipSuccess) {
+    rc = fail(CMI_GPU_EDEVICE, "%s: %s", what, hipGetErrorString(err));
+  } else if (bad) {
+    rc = fail(CMI_GPU_EINVAL, "%s: %u cell(s) have a Doppler width that is not "
+              "positive and finite (T and sigma_turb both 0?) or a density "
+              "that is negative or not finite", what, bad);
+  }
+  if (rc) {
+    (void)hipFree(records);
+    (void)hipFree(image);
+    (void)hipFree(cube);
+    return rc;
+  }
+  lya_free(e);
+  LyaDev &l = e->lya;
+  l.records = records;
+  l.x_crit = x_crit;
+  l.x_crit2 = x_crit * x_crit;
+  l.max_scatter = (uint32_t)max_scatter;
+  l.nchan = nchan;
+  l.vmin = axis.vmin;
+  l.dv = axis.dv;
+  l.npixel = (int64_t)npixel;
+  l.image = image;
+  l.cube = cube;
+  e->lya_nviews = nviews;
+  /* the phase function of the dust the records were built with; without dust
+   * no event is a dust event, and the constants are those of g = 0.5 */
+  e->lya_dust = e->dust;
+  if (!e->have_dust_scattering) {
+    DustDev &d = e->lya_dust;
+    d.hgg = 0.5;
+    d.g2 = 0.25;
+    d.omg2 = 0.75;
+    d.thgg = 1.;
+    d.omhgg = 0.5;
+    d.od2hgg = 1.;
+    d.opg2 = 1.25;
+    d.pl = 0.;
+    d.sc = 1.;
+    d.pc = 0.;
+    d.albedo = 0.;
+  }
+  return cmi_gpu_reset_lya(e);
+}
+
+/* what a Lyman-alpha launch or probe asks of the engine; the dust kernels'
+ * arguments with the camera as it is now (the mode is stale once it changed) */
+static int lya_prepare(cmi_gpu_engine *e, const char *what, DustDev &dust) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (!e->lya.nchan)
+    return fail(CMI_GPU_ESTATE, "%s: Lyman-alpha mode is not set "
+                "(set_lyman_alpha)", what);
+  if (e->lya_stale)
+    return fail(CMI_GPU_ESTATE, "%s: %s after Lyman-alpha mode was set; "
+                "set_lyman_alpha again", what, e->lya_stale);
+  if (e->cell_source_from_cells && e->cell_source_epoch != e->cells_epoch)
+    return fail(CMI_GPU_ESTATE, "%s: the cells changed after the line source "
+                "was set; set_cell_source_line again", what);
+  HIP_TRY(hipSetDevice(e->device));
+  dust = e->lya_dust;
+  return CMI_GPU_OK;
+}
+
+static DustCamera<DUST_CAMERA_PARALLEL_VIEWS> lya_views(cmi_gpu_engine *e) {
+  DustCamera<DUST_CAMERA_PARALLEL_VIEWS> cam;
+  cam.views = (const DustViewDev *)e->dust_views_dev;
+  cam.nviews = e->dust_nviews;
+  cam.images = e->dust_image;
+  cam.counters = e->dust_view_counters;
+  return cam;
+}
+
+int cmi_gpu_lya_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
+                      uint64_t n) {
+  DustDev dust;
+  CMI_TRY(lya_prepare(e, "lya_shoot", dust));
+  uint64_t size = CMI_LYA_FIRST_LAUNCH;
+  for (uint64_t done = 0; done < n;) {
+    const uint64_t chunk = std::min<uint64_t>(n - done, size);
+    const bool measure = done + chunk < n;
+    unsigned long long steps_before = 0, steps_after = 0;
+    if (measure)
+      HIP_TRY(hipMemcpyAsync(&steps_before, &e->lya_counters->nsteps,
+                             sizeof steps_before, hipMemcpyDeviceToHost,
+                             e->stream));
+    HIP_TRY(hipMemsetAsync(e->lya_next, 0, sizeof(unsigned long long),
+                           e->stream));
+    EventPair ev;
+    CMI_TRY(timer_begin(e, ev));
+#ifndef CMI_LYA_EVENT_LOOP
+    const unsigned blocks = (unsigned)((chunk + 255) / 256);
+#else
+    const unsigned blocks = (unsigned)std::min<uint64_t>(
+        (chunk + 255) / 256, (uint64_t)e->num_cu * CMI_LYA_BLOCKS_PER_CU);
+#endif
+    if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
+      lya_shoot_kernel<DUST_CAMERA_PARALLEL_VIEWS>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, dust, e->cell_source, lya_views(e), e->lya, seed,
+              first_packet + done, chunk, e->lya_next, e->lya_counters);
+    else
+      lya_shoot_kernel<DUST_CAMERA_PARALLEL><<<blocks, 256, 0, e->stream>>>(
+          e->grid, dust, e->cell_source, DustCamera<DUST_CAMERA_PARALLEL>(),
+          e->lya, seed, first_packet + done, chunk, e->lya_next,
+          e->lya_counters);
+    HIP_TRY(hipGetLastError());
+    CMI_TRY(timer_end(e, e->shoot_events, ev, chunk));
+    done += chunk;
+    if (measure) {
+      HIP_TRY(hipMemcpyAsync(&steps_after, &e->lya_counters->nsteps,
+                             sizeof steps_after, hipMemcpyDeviceToHost,
+                             e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      const double per_packet =
+          std::max(1., (double)(steps_after - steps_before) / (double)chunk);
+      size = (uint64_t)std::min<double>(
+          (double)CMI_LYA_MAX_LAUNCH,
+          std::max<double>((double)CMI_LYA_MIN_LAUNCH,
+                           (double)CMI_LYA_STEPS_PER_LAUNCH / per_packet));
+    }
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_get_lya_counters(cmi_gpu_engine *e, uint64_t *counters) {
+  if (!e || !counters)
+    return fail(CMI_GPU_EINVAL, "get_lya_counters: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  LyaCountersDev c = {};
+  if (e->lya_counters)
+    HIP_TRY(hipMemcpy(&c, e->lya_counters, sizeof c, hipMemcpyDeviceToHost));
+  counters[0] = c.nsteps;
+  counters[1] = c.nhydrogen;
+  counters[2] = c.ndust;
+  counters[3] = c.nrejections;
+  counters[4] = c.natomics;
+  counters[5] = c.ncapped;
+  counters[6] = c.npackets;
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_download_lya_view(cmi_gpu_engine *e, int32_t view, double *image,
+                              double *cube) {
+  static const char *what = "download_lya_view";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (!e->lya.nchan)
+    return fail(CMI_GPU_ESTATE, "%s: Lyman-alpha mode is not set "
+                "(set_lyman_alpha)", what);
+  if (e->lya_stale)
+    return fail(CMI_GPU_ESTATE, "%s: %s after Lyman-alpha mode was set", what,
+                e->lya_stale);
+  if (view < 0 || view >= e->lya_nviews)
+    return fail(CMI_GPU_EINVAL, "%s: view %d of %d", what, (int)view,
+                (int)e->lya_nviews);
+  uint64_t c[7];
+  CMI_TRY(cmi_gpu_get_lya_counters(e, c));
+  if (c[5])
+    return fail(CMI_GPU_ESTATE, "%s: %llu packet(s) reached the cap of %u "
+                "scatterings; the image is incomplete", what,
+                (unsigned long long)c[5], e->lya.max_scatter);
+  const LyaDev &l = e->lya;
+  const size_t npixel = (size_t)l.npixel;
+  const size_t nvalue = npixel * l.nchan;
+  if (image)
+    HIP_TRY(hipMemcpy(image, l.image + (size_t)view * npixel,
+                      npixel * sizeof(double), hipMemcpyDeviceToHost));
+  if (!cube)
+    return CMI_GPU_OK;
+  double *ordered = nullptr;
+  HIP_TRY(hipMalloc(&ordered, sizeof(double) * nvalue));
+  dust_cube_reorder_kernel<<<(unsigned)((nvalue + 255) / 256), 256, 0,
+                             e->stream>>>(l.cube + (size_t)view * nvalue,
+                                          l.npixel, l.nchan, ordered);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(cube, ordered, sizeof(double) * nvalue,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(ordered);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_lya_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
+                      uint64_t first_packet, int64_t n, const double *in,
+                      double *out, int32_t max_events) {
+  static const char *what = "lya_probe";
+  if (!e || n < 0 || !out || kind < 0 || kind > LYA_PROBE_TRACE ||
+      max_events < 0 || n > (1 << 24))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  static const int in_width[4] = {4, 7, 2, 0};
+  const int width =
+      kind == LYA_PROBE_TRACE
+          ? CMI_LYA_TRACE_HEADER + CMI_LYA_TRACE_ROW * max_events
+          : 2;
+  if (in_width[kind] && !in)
+    return fail(CMI_GPU_EINVAL, "%s: input rows missing", what);
+  DustDev dust;
+  CMI_TRY(lya_prepare(e, what, dust));
+  /* with several views a trace follows the selected one through the single
+   * camera's kernel (it writes to no image) */
+  if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
+    dust_put_view(dust, e->dust_views[e->dust_probe_view]);
+  if (n == 0)
+    return CMI_GPU_OK;
+  double *din = nullptr, *dout = nullptr;
+  const size_t in_bytes = (size_t)n * in_width[kind] * sizeof(double);
+  const size_t out_bytes = (size_t)n * width * sizeof(double);
+  HIP_TRY(hipMalloc(&dout, out_bytes));
+  hipError_t err = hipSuccess;
+  if (in_bytes) {
+    err = hipMalloc(&din, in_bytes);
+    if (err == hipSuccess)
+      err = hipMemcpy(din, in, in_bytes, hipMemcpyHostToDevice);
+  }
+  if (err == hipSuccess)
+    err = hipMemsetAsync(dout, 0, out_bytes, e->stream);
+  for (int64_t k = 0; err == hipSuccess && k < n; k += CMI_DUST_PROBE_LAUNCH) {
+    const int64_t m = std::min<int64_t>(n - k, CMI_DUST_PROBE_LAUNCH);
+    lya_probe_kernel<DUST_CAMERA_PARALLEL>
+        <<<(unsigned)((m + 63) / 64), 64, 0, e->stream>>>(
+            e->grid, dust, e->cell_source, DustCamera<DUST_CAMERA_PARALLEL>(),
+            e->lya, kind, seed, first_packet + k, m, width,
+            din ? din + k * in_width[kind] : nullptr, dout + k * width,
+            max_events);
+    err = hipGetLastError();
+    if (err == hipSuccess)
+      err = hipStreamSynchronize(e->stream);
+  }
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_lyman_alpha_emissivity(cmi_gpu_engine *e, double *out) {
+  static const char *what = "lyman_alpha_emissivity";
+  if (!e || !out)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (!e->have_cells)
+    return fail(CMI_GPU_ESTATE, "%s: cell data must be set first", what);
+  HIP_TRY(hipSetDevice(e->device));
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
+  double *dev = nullptr;
+  HIP_TRY(hipMalloc(&dev, sizeof(double) * (size_t)e->ncell));
+  lya_emissivity_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
+                          e->stream>>>(
+      cells->number_density, cells->temperature, cells->x[0], cells->x[1],
+      e->model.abundance[0], e->ncell, dev);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess)
+    err = hipMemcpy(out, dev, sizeof(double) * (size_t)e->ncell,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(dev);
   HIP_TRY(err);
   return CMI_GPU_OK;
 }

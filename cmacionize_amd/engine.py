@@ -36,6 +36,10 @@ DUST_PROBE_OPTICAL_DEPTH, DUST_PROBE_TRACE = 3, 4
 DUST_PROBE_CELL_SOURCE = 5
 DUST_PROBE_SKY_PEEL = 6
 DUST_PROBE_CUBE_TRACE = 7
+# cmi_gpu_lya_probe kinds, and the largest cap on a packet's scatterings
+LYA_PROBE_VOIGT, LYA_PROBE_OPTICAL_DEPTH = 0, 1
+LYA_PROBE_SAMPLER, LYA_PROBE_TRACE = 2, 3
+LYA_MAX_SCATTER = 100000000
 # CMI_GPU_MAX_VIEWS: the views of one run (set_ccd_images, set_sky_cameras)
 MAX_VIEWS = 64
 
@@ -135,6 +139,9 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_field_absorbing_cube",
     "cmi_gpu_render_field_absorbing_sky_cube",
     "cmi_gpu_absorbing_cube_probe", "cmi_gpu_get_update_state",
+    "cmi_gpu_set_lyman_alpha", "cmi_gpu_lya_shoot", "cmi_gpu_lya_probe",
+    "cmi_gpu_download_lya_view", "cmi_gpu_reset_lya",
+    "cmi_gpu_get_lya_counters", "cmi_gpu_lyman_alpha_emissivity",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -481,6 +488,19 @@ def load_library():
     L.cmi_gpu_set_scattered_cube.argtypes = [
         vp, C.c_int32, C.c_double, C.c_double, C.c_double, _dp, _dp]
     L.cmi_gpu_download_cube_view.argtypes = [vp, C.c_int32, _dp, _dp, _dp]
+    # (a build from before Lyman alpha, loaded through CMI_GPU_LIBRARY for a
+    # comparison, does not have it)
+    if hasattr(L, "cmi_gpu_set_lyman_alpha"):
+        L.cmi_gpu_set_lyman_alpha.argtypes = [
+            vp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double,
+            C.c_uint64, _dp, _dp]
+        L.cmi_gpu_lya_shoot.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64]
+        L.cmi_gpu_lya_probe.argtypes = [vp, C.c_int32, C.c_uint32, C.c_uint64,
+                                        C.c_int64, _dp, _dp, C.c_int32]
+        L.cmi_gpu_download_lya_view.argtypes = [vp, C.c_int32, _dp, _dp]
+        L.cmi_gpu_reset_lya.argtypes = [vp]
+        L.cmi_gpu_get_lya_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.cmi_gpu_lyman_alpha_emissivity.argtypes = [vp, _dp]
     # (a build from before the continuum images, loaded through
     # CMI_GPU_LIBRARY for a comparison, does not have them)
     if hasattr(L, "cmi_gpu_free_free_coefficients"):
@@ -698,6 +718,7 @@ class GpuEngine:
                            (sub_ncell if sub_ncell is not None else ncell))
         self.n = int(np.prod(self.ncell))
         self.cube_channels = 0  # set_scattered_cube's nchan; 0: off
+        self.lya_channels = 0  # set_lyman_alpha's nchan; 0: off
         # tests, bench and tools read device timings; the engine records them
         # only on request
         self.set_tuning(timing=1)
@@ -2061,6 +2082,119 @@ class GpuEngine:
         if several:
             return images, cubes
         return images[:, 0], cubes[:, 0]
+
+    # Lyman alpha -------------------------------------------------------------
+    def set_lyman_alpha(self, nchan, vmin, vmax, sigma_turb=0., x_crit=0.,
+                        max_scatter=LYA_MAX_SCATTER, n_HI=None,
+                        temperature=None):
+        """Lyman-alpha mode for the parallel camera(s), the cell source, the
+        dust and the velocities as currently set (include/cmi_gpu.h, "Lyman
+        alpha"): builds the per-cell records and zeroes image and cube.
+        `n_HI` and `temperature` (ncell,) replace n_H x_H and T of the cells;
+        `x_crit` is the core-skipping frequency. nchan = 0 switches it off."""
+        n = None if n_HI is None else _f64(n_HI).reshape(self.n)
+        t = None if temperature is None else _f64(temperature).reshape(self.n)
+        self._check(self._lib.cmi_gpu_set_lyman_alpha(
+            self._h, int(nchan), vmin, vmax, sigma_turb, x_crit,
+            int(max_scatter), _p_or_none(n), _p_or_none(t)))
+        self.lya_channels = int(nchan)
+
+    def lya_shoot(self, seed, first_packet, n):
+        self._check(self._lib.cmi_gpu_lya_shoot(self._h, seed, first_packet,
+                                                n))
+
+    def lya_probe(self, kind, seed=0, first_packet=0, n=None, rows=None,
+                  max_events=0):
+        """Device functions of the Lyman-alpha path, one row per packet
+        (include/cmi_gpu.h, cmi_gpu_lya_probe); returns the output rows."""
+        in_width = {LYA_PROBE_VOIGT: 4, LYA_PROBE_OPTICAL_DEPTH: 7,
+                    LYA_PROBE_SAMPLER: 2}.get(kind, 0)
+        inp = None
+        if in_width:
+            inp = _f64(rows).reshape(-1, in_width)
+            n = len(inp)
+        width = 6 + 12 * max_events if kind == LYA_PROBE_TRACE else 2
+        out = np.zeros((int(n), width))
+        self._check(self._lib.cmi_gpu_lya_probe(
+            self._h, kind, seed, first_packet, int(n), _p_or_none(inp),
+            _p(out), max_events))
+        return out
+
+    def download_lya(self):
+        """The images (nviews, nx, ny) and the cubes (nviews, nchan, nx, ny)
+        of a Lyman-alpha run, unnormalised"""
+        if not self.lya_channels:
+            # the engine's own refusal (the mode is not set)
+            self._check(self._lib.cmi_gpu_download_lya_view(
+                self._h, 0, None, None))
+        images = np.zeros((self.nviews,) + self.image_shape)
+        cubes = np.zeros((self.nviews, self.lya_channels) + self.image_shape)
+        for v in range(self.nviews):
+            self._check(self._lib.cmi_gpu_download_lya_view(
+                self._h, v, _p(images[v]), _p(cubes[v])))
+        return images, cubes
+
+    def reset_lya(self):
+        self._check(self._lib.cmi_gpu_reset_lya(self._h))
+
+    def get_lya_counters(self):
+        c = (C.c_uint64 * 7)()
+        self._check(self._lib.cmi_gpu_get_lya_counters(self._h, c))
+        return dict(zip(("nsteps", "nhydrogen", "ndust", "nrejections",
+                         "natomics", "ncapped", "npackets"),
+                        (int(v) for v in c)))
+
+    def lyman_alpha_emissivity(self):
+        """W m^-3 of Lyman alpha from recombinations per cell, from the cells
+        as they are (cmi_gpu_lyman_alpha_emissivity)"""
+        out = np.zeros(self.n)
+        self._check(self._lib.cmi_gpu_lyman_alpha_emissivity(self._h, _p(out)))
+        return out
+
+    def render_lyman_alpha_cube(self, theta, phi, nx, ny, anchor, sides,
+                                npackets, seed, nchan, vmin, vmax,
+                                sigma_turb=0., core_skip=0., dust=None,
+                                source=None, max_scatter=LYA_MAX_SCATTER):
+        """The Lyman-alpha image (nx, ny) and cube (nchan, nx, ny) of one
+        Monte Carlo run of `npackets` packets that scatter off the cells' H I
+        (and off dust: `dust` = (sigma per hydrogen nucleus, albedo, g, p_l),
+        None for none), both scaled by L_total / (npackets A_pixel): W m^-2
+        sr^-1, per channel for the cube, the unit of
+        render_scattered_line_cube. `source` is a luminosity density (ncell,)
+        in W m^-3; None takes lyman_alpha_emissivity(). `core_skip` is
+        x_crit. With sequences for theta and phi the views share one run:
+        (nviews, nx, ny) and (nviews, nchan, nx, ny). Replaces the engine's
+        CCD image, dust and dust source, and leaves the mode off."""
+        if dust is None:
+            self.set_dust_scattering_per_hydrogen(0.5, 0., 0., 0.)
+        else:
+            sigma, albedo, g, p_l = dust
+            self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
+        several = bool(np.ndim(theta) or np.ndim(phi))
+        nviews = len(_f64(theta).reshape(-1)) if several else 1
+        a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
+        s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
+        pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
+        if several:
+            self.set_ccd_images(theta, phi, nx, ny, a, s)
+        else:
+            self.set_ccd_image(theta, phi, nx, ny, a[0], s[0])
+        self.set_cell_source_field(self.lyman_alpha_emissivity()
+                                   if source is None else source)
+        try:
+            self.set_lyman_alpha(nchan, vmin, vmax, sigma_turb, core_skip,
+                                 max_scatter)
+            self.lya_shoot(seed, 0, int(npackets))
+            total = self.get_cell_source(tables=False)
+            scale = total / (int(npackets) * pixel_area)
+            images, cubes = self.download_lya()
+            images = images * scale[:, None, None]
+            cubes = cubes * scale[:, None, None, None]
+        finally:
+            self.set_lyman_alpha(0, 0., 1.)
+        if several:
+            return images, cubes
+        return images[0], cubes[0]
 
     def get_timing(self, reset=True):
         s = C.c_double()

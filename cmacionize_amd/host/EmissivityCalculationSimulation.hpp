@@ -141,6 +141,18 @@
  * The 21-cm line of the neutral gas with its own absorption is then written
  * as <prefix>_HI_cube.dat (_HI_cube_view<k>.dat), raw doubles [channel][ix]
  * [iy] in W m^-2 Hz^-1 sr^-1. Needs type BinaryArray.
+ * Lyman alpha (read only with "Lyman alpha: true" in
+ * EmissionImages, which needs type BinaryArray and the block's "velocity
+ * channels", "velocity minimum" and "velocity maximum"; EmissionSkyMaps
+ * refuses the key): packets from the cells' recombinations scatter off the
+ * snapshot's own H I and off the block's dust, with the block's "number of
+ * packets", "random seed", "turbulent velocity dispersion", velocity field,
+ * dust keys and views, and
+ *   EmissionImages:Lyman alpha core skipping          0. (x_crit)
+ *   EmissionImages:Lyman alpha maximum scatterings    100000000
+ * Written as <prefix>_LymanAlpha_image.dat and <prefix>_LymanAlpha_cube.dat
+ * (_view<k> appended for view k >= 1), raw doubles [ix][iy] and [channel][ix]
+ * [iy] in the unit of the scattered-light images and cubes.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -402,6 +414,12 @@ class EmissivityCalculationSimulation {
     /* "scattered cubes": every flagged single-ion line's scattered light
      * also per velocity channel */
     bool scattered_cubes = false;
+    /* "Lyman alpha": the Monte Carlo Lyman-alpha image and cube of the
+     * snapshot's own H I; it reads the packets, the seed and
+     * the dust keys of the scattered light */
+    bool lyman_alpha = false;
+    double lya_core_skip = 0.;
+    long long lya_max_scatter = 100000000;
     long long npackets = 1000000, seed = 42;
     double albedo = 0., asymmetry = 0.5, polarisation = 0.;
     /* several views: views[0] repeats the members above, views[k] is read
@@ -521,9 +539,31 @@ class EmissivityCalculationSimulation {
         scattered_cubes =
             params.get_bool("EmissionImages:scattered cubes", false);
       }
-      if (!params.peek_bool("EmissionImages:scattering"))
+      /* (looked at like the switches above) */
+      if (params.peek_bool("EmissionImages:Lyman alpha")) {
+        lyman_alpha = params.get_bool("EmissionImages:Lyman alpha", false);
+        if (type != "BinaryArray")
+          throw ParameterError("EmissionImages:Lyman alpha needs type "
+                               "BinaryArray: a cube is written as raw doubles");
+        if (!cubes)
+          throw ParameterError("EmissionImages:Lyman alpha needs velocity "
+                               "channels, velocity minimum and velocity "
+                               "maximum");
+        lya_core_skip =
+            params.get_double("EmissionImages:Lyman alpha core skipping", 0.);
+        if (!(lya_core_skip >= 0.) || !std::isfinite(lya_core_skip))
+          throw ParameterError("EmissionImages:Lyman alpha core skipping must "
+                               "not be negative");
+        lya_max_scatter = params.get_integer(
+            "EmissionImages:Lyman alpha maximum scatterings", 100000000);
+        if (lya_max_scatter < 1 || lya_max_scatter > 100000000)
+          throw ParameterError("EmissionImages:Lyman alpha maximum "
+                               "scatterings must be 1..100000000");
+      }
+      if (!lyman_alpha && !params.peek_bool("EmissionImages:scattering"))
         return;
-      scattering = params.get_bool("EmissionImages:scattering", false);
+      if (params.peek_bool("EmissionImages:scattering"))
+        scattering = params.get_bool("EmissionImages:scattering", false);
       npackets = params.get_integer("EmissionImages:number of packets",
                                     1000000);
       seed = params.get_integer("EmissionImages:random seed", 42);
@@ -744,6 +784,10 @@ class EmissivityCalculationSimulation {
         scattered_cubes =
             params.get_bool("EmissionSkyMaps:scattered cubes", false);
       }
+      if (params.peek_bool("EmissionSkyMaps:Lyman alpha"))
+        throw ParameterError("EmissionSkyMaps:Lyman alpha is not supported: "
+                             "the Lyman-alpha transfer serves the parallel "
+                             "cameras of EmissionImages only");
       if (!params.peek_bool("EmissionSkyMaps:scattering"))
         return;
       scattering = params.get_bool("EmissionSkyMaps:scattering", false);
@@ -1275,6 +1319,66 @@ public:
           if (rc == CMI_GPU_OK && img.scattered_cubes)
             rc = cmi_gpu_set_scattered_cube(engine, 0, 0., 1., 0., nullptr,
                                             nullptr);
+        }
+        if (rc == CMI_GPU_OK && img.lyman_alpha) {
+          status("Shooting the Lyman alpha packets through the H I...");
+          /* the source: the cells' recombinations; the scatterers: the
+           * cells' own H I at their temperatures, and the block's dust */
+          std::vector<double> source(size);
+          rc = cmi_gpu_lyman_alpha_emissivity(engine, source.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_dust_scattering_per_hydrogen(
+                engine, img.asymmetry, img.polarisation, img.albedo,
+                img.dust_cross_section);
+          if (rc == CMI_GPU_OK)
+            rc = nviews == 1
+                     ? cmi_gpu_set_ccd_image(engine, theta[0], phi[0],
+                                             (int32_t)img.nx, (int32_t)img.ny,
+                                             anchors.data(), sides.data())
+                     : cmi_gpu_set_ccd_images(
+                           engine, (int32_t)nviews, theta.data(), phi.data(),
+                           (int32_t)img.nx, (int32_t)img.ny, anchors.data(),
+                           sides.data());
+          if (rc == CMI_GPU_OK && !velocities.empty())
+            rc = cmi_gpu_set_cell_velocities(engine, velocities.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_cell_source_field(engine, source.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_lyman_alpha(
+                engine, (int32_t)img.nchan, img.vmin, img.vmax, img.sigma_turb,
+                img.lya_core_skip, (uint64_t)img.lya_max_scatter, nullptr,
+                nullptr);
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_lya_shoot(engine, (uint32_t)img.seed, 0,
+                                   (uint64_t)img.npackets);
+          double total = 0.;
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
+          const size_t nvalue = (size_t)img.nchan * npixel;
+          std::vector<double> lya_image(npixel), lya_cube(nvalue);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_download_lya_view(engine, (int32_t)v,
+                                           lya_image.data(), lya_cube.data());
+            const double pixel_area = sides[2 * v] * sides[2 * v + 1] /
+                                      ((double)img.nx * (double)img.ny);
+            const double scale = total / ((double)img.npackets * pixel_area);
+            for (double &value : lya_cube)
+              value *= scale;
+            if (rc == CMI_GPU_OK && write_output) {
+              written += " " + write_image(img.folder + "/" + img.prefix +
+                                               "_LymanAlpha_image" +
+                                               view_tag(v),
+                                           img.type, lya_image.data(), img.nx,
+                                           img.ny, scale);
+              written += " " + write_cube(img.folder + "/" + img.prefix +
+                                              "_LymanAlpha_cube" + view_tag(v),
+                                          lya_cube.data(), img.nchan, img.nx,
+                                          img.ny);
+            }
+          }
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_lyman_alpha(engine, 0, 0., 1., 0., 0., 1, nullptr,
+                                         nullptr);
         }
       }
       if (rc == CMI_GPU_OK && placed && do_sky) {

@@ -1580,6 +1580,156 @@ int cmi_gpu_set_scattered_cube(cmi_gpu_engine *engine, int32_t nchan,
 int cmi_gpu_download_cube_view(cmi_gpu_engine *engine, int32_t view, double *I,
                                double *Q, double *U);
 
+/* -------------------------------------------------------- Lyman alpha -- */
+/* Monte Carlo transfer of the Lyman-alpha line: packets from the cell source
+ * scatter resonantly off H I and off dust, are redistributed in frequency at
+ * every hydrogen scattering, and are peeled off towards the parallel cameras
+ * into an image and a velocity cube per view (Stokes I). No counterpart in
+ * the reference. tests/support/lyman_alpha_reference.c restates everything
+ * below in plain C, random number for random number.
+ *
+ * Constants: lambda_0 = 1215.67e-10 m, A_21 = 6.265e8 s^-1, h nu_0 = h c /
+ * lambda_0 with the engine's h and c; m_H = 1.00794 m_u, the mass "spectral
+ * line cubes" uses for H alpha's width. dot3(a, b) = (a_x b_x + a_y b_y) +
+ * a_z b_z, no contraction.
+ *
+ * Per cell, built into one 64-byte record {kappa_0, 1 / b, a, kappa_d, v_x,
+ * v_y, v_z, 0} when the mode is set:
+ *   b       = sqrt(2 * (k_B T / m_H + sigma_t * sigma_t))
+ *   a       = A_21 * lambda_0 / (4 * pi * b)
+ *   kappa_0 = n_HI * (3 lambda_0^3 A_21 / (8 pi sqrt(pi))) / b  (5.90e-14 cm^2
+ *             per atom at 1e4 K); n_HI = n_H x_H of the cells, or the caller's
+ *   kappa_d = n_H sigma_d, sigma_d the cross section per hydrogen nucleus of
+ *             cmi_gpu_set_dust_scattering_per_hydrogen; 0 if no dust is set
+ *   v       = the cell's velocity (cmi_gpu_set_cell_velocities), 0 if none.
+ *
+ * A packet carries its lab-frame shift as a velocity q (positive = blue). In
+ * a cell, flying along k: x = (q - dot3(v, k)) * (1 / b), kappa(x) = kappa_0
+ * H(a, x) + kappa_d, with z = (x^2 - 0.855) / (x^2 + 3.42) and
+ *   H(a, x) = sqrt(pi) * Q + E,
+ *   Q = 0 for z <= 0, else (1 + 21 / x^2) * a / (pi * (x^2 + 1)) * (z * (0.1117
+ *       + z * (4.421 + z * (-9.207 + 5.674 * z)))),
+ *   E = exp(-x^2) for x^2 < 64, else 0
+ * (within 2.2 % of the Voigt function for |x| <= 1000 between 10 K and 1e5 K).
+ *
+ * Random numbers of packet i (stream seed, iteration 0, packet i):
+ *   6   the cell source's draws (cell, position, direction), as dust_shoot's
+ *   4   the emitting atom: r_1 = sqrt(-ln R), f_1 = 2 pi R', r_2, f_2 likewise;
+ *       w_e = v + b * (r_1 cos f_1, r_1 sin f_1, r_2 cos f_2);  q = dot3(w_e, k)
+ *   1   the forced first optical depth -ln(1 - R (1 - exp(-tau_max))), tau_max
+ *       the depth to the box edge along k at q
+ *   then per event, at the position the walk stopped, in the cell floor((pos -
+ *   anchor) * inv_cellside) clamped into the grid:
+ *   1   the species: hydrogen if R < kappa_0 H / kappa of that cell
+ *   hydrogen:
+ *   3n  u_par from f(u) ~ exp(-u^2) / ((x - u)^2 + a^2) by the rejection method
+ *       of Zheng & Miralda-Escude (2002) for |x|, the sign restored afterwards:
+ *       e_0 = exp(-u_0^2), th_0 = atan((u_0 - |x|) / a), p = (th_0 + pi / 2) /
+ *       ((1 - e_0) th_0 + (1 + e_0) pi / 2); per attempt {R_1, R_2, R_3}: R_1 <=
+ *       p: th = -pi / 2 + R_2 (th_0 + pi / 2), u = a tan(th) + |x|, accepted if
+ *       R_3 <= exp(-u^2); else th = th_0 + R_2 (pi / 2 - th_0), accepted if R_3
+ *       <= exp(-u^2) / e_0. The separation point is that of Laursen et al.
+ *       (2009) up to their core-wing transition: u_0 = 0 for |x| < 0.2, max(0,
+ *       |x| - 0.01 a^(1/6) exp(1.2 |x|)) for |x| < x_cw = 1.59 - 0.60 log10 a -
+ *       0.03 log10^2 a, else min(4, max(0, |x| - 0.5)); it changes the
+ *       acceptance rate only (at least 0.046 for |x| <= 12, about 1.8 / |x|
+ *       far in the wing). After 1e6 rejections the last candidate is taken.
+ *   2   rho = sqrt(s - ln R) with s = x_crit^2 if |x| < x_crit, else 0; psi =
+ *       2 pi R'; u_1 = rho cos psi, u_2 = rho sin psi
+ *       w = v + b * ((u_par k + u_1 e_1) + u_2 e_2) per component, e_1 = (cos
+ *       theta cos phi, cos theta sin phi, -sin theta), e_2 = (-sin phi, cos
+ *       phi, 0) from the angles of k
+ *   2   the new isotropic direction k' {cos theta, phi}; q += dot3(w, k') -
+ *       dot3(w, k); Q = U = V = 0
+ *   dust: the albedo multiplies the weight; DustScattering's scatter draws k'
+ *       (1 or 2 uniforms) and changes the Stokes vector as in dust_shoot; the
+ *       grain has the cell's velocity: q += dot3(v, k') - dot3(v, k)
+ *   1   the next optical depth -ln R.
+ * A packet that has scattered max_scatter times is stopped and counted.
+ *
+ * Events (per view, direction d to the observer): q_d = dot3(w_e, d) for the
+ * direct light, q + (dot3(w, d) - dot3(w, k)) for a peel-off (w the atom's
+ * velocity, or the cell's for dust); tau the depth to the box edge along d at
+ * q_d; the addend ((W * P) * exp(-tau)) * I with W = 1 for the direct light
+ * and forced weight * albedos otherwise, P = 0.25 / pi for hydrogen and the
+ * direct light (isotropic) and DustScattering's scatter_towards for dust, I
+ * the packet's Stokes I (after scatter_towards for dust). It goes into the
+ * pixel of the event's position and into the channel c with e_c <= u <
+ * e_{c+1}, u = -q_d, e_c = vmin + c * dv (a delta in velocity; the lower edge
+ * inclusive, as for b == 0 in "spectral line cubes"). An event outside
+ * [vmin, vmax) goes into the image only.
+ *
+ * What follows: a cube that covers every u sums to the image; with n_HI = 0
+ * and no dust only the direct light remains, a thin Gaussian line of width b;
+ * adding V to every velocity shifts every u by -dot3(V, d).
+ *
+ * Not modelled: recoil, deuterium, fine structure, the dipole phase function
+ * and the line's own polarisation, collisional excitation, an adaptive core
+ * skipping. */
+
+/* Switches the mode on for the parallel camera(s) as currently set: builds
+ * the records from the cells (n_HI and temperature: [ncell] of the caller's,
+ * or NULL for n_H x_H and T of the cells), the dust as set and the velocities
+ * as set, allocates and zeroes image, cube and counters. x_crit >= 0 is the
+ * core-skipping frequency (0: none), max_scatter the cap (1 to 1e8: the
+ * stream's block counter has 32 bits). nchan = 0 switches the mode off and
+ * frees the buffers. CMI_GPU_ESTATE: a block of a decomposed grid; no cells,
+ * no camera, a point camera, no cell source or a stale one; dust that is not
+ * per hydrogen nucleus. CMI_GPU_EINVAL: a periodic box; nchan < 0, a range
+ * that is not finite with vmax > vmin, sigma_turb or x_crit negative or not
+ * finite, max_scatter 0 or above 1e8, a cell whose b is not positive and
+ * finite or whose density is negative or not finite, too many values.
+ * CMI_GPU_ENOMEM if the cubes do not fit. A call that fails leaves the
+ * previous state in place. The mode is stale, and shoot, probe and download
+ * fail with CMI_GPU_ESTATE until this call is made again, once a camera, the
+ * cell source or the velocities are set again. Synchronous. */
+int cmi_gpu_set_lyman_alpha(cmi_gpu_engine *engine, int32_t nchan, double vmin,
+                            double vmax, double sigma_turb, double x_crit,
+                            uint64_t max_scatter,
+                            const double *n_HI /* [ncell] or NULL */,
+                            const double *temperature /* [ncell] or NULL */);
+
+/* Packets [first_packet, first_packet + n) of the stream `seed`, added to the
+ * image, the cube and the counters; launched in chunks. Asynchronous. */
+int cmi_gpu_lya_shoot(cmi_gpu_engine *engine, uint32_t seed,
+                      uint64_t first_packet, uint64_t n);
+
+/* Device functions row by row, for parity tests; row k of kind
+ *  0 VOIGT: in {a, x, kappa_0, kappa_d}, out {H, kappa_0 * H + kappa_d};
+ *  1 OPTICAL_DEPTH: in {pos[3], dir[3], q}, out {tau to the box edge, steps};
+ *  2 SAMPLER: in {x, a}, out {u_par, rejections} from the stream of packet
+ *    first_packet + k;
+ *  3 TRACE: out {events, hydrogen scatterings, dust scatterings, steps, capped,
+ *    rejections, rows[max_events][12]} of packet first_packet + k for the
+ *    selected view (cmi_gpu_select_probe_view), a row per event being {pos[3],
+ *    k[3], q, addend, species (0 direct, 1 hydrogen, 2 dust), u, u_par, x}
+ *    with k and q the incoming ones.
+ * out is [n][2], or [n][6 + 12 * max_events] for TRACE. Synchronous. */
+int cmi_gpu_lya_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
+                      uint64_t first_packet, int64_t n, const double *in,
+                      double *out, int32_t max_events);
+
+/* View `view`, unnormalised: image host [nx][ny], cube host [nchan][nx][ny];
+ * either may be NULL. CMI_GPU_ESTATE if the mode is off or stale, or a packet
+ * reached the cap (the image is incomplete). Synchronous. */
+int cmi_gpu_download_lya_view(cmi_gpu_engine *engine, int32_t view,
+                              double *image, double *cube);
+
+/* Zeroes image, cube and counters. Synchronous. */
+int cmi_gpu_reset_lya(cmi_gpu_engine *engine);
+
+/* {cell crossings, scatterings off hydrogen, off dust, rejections of the atom
+ * sampler, atomics, capped packets, packets} since the last reset. */
+int cmi_gpu_get_lya_counters(cmi_gpu_engine *engine, uint64_t *counters /*[7]*/);
+
+/* The Lyman-alpha emissivity of the cells as they are, recombinations only, W
+ * m^-3 into out[ncell]: f_alpha(T) alpha_B(T) n_e n_p h nu_0, alpha_B =
+ * 2.753e-14 L^1.5 / (1 + (L / 2.74)^0.407)^2.242 cm^3 s^-1 with L = 315614 / T
+ * (Hui & Gnedin 1997), f_alpha = 0.686 - 0.106 log10(T_4) - 0.009 T_4^-0.44
+ * (Cantalupo et al. 2008), n_e = n_H ((1 - x_H0) + A_He (1 - x_He0)) as in
+ * cmi_gpu_free_free_coefficients, n_p = n_H (1 - x_H0); 0 where T <= 0. */
+int cmi_gpu_lyman_alpha_emissivity(cmi_gpu_engine *engine, double *out);
+
 /* --------------------------------------------------- continuum images -- */
 /* The formal solution of the transfer equation with an absorption coefficient
  * and a source function of their own in every channel, and thermal free-free
