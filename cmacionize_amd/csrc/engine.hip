@@ -337,6 +337,9 @@ struct cmi_gpu_engine {
   unsigned long long *lya_next = nullptr;
   LyaCountersDev *lya_counters = nullptr;
   const char *lya_stale = nullptr;
+  /* the radiation field of the mode (cmi_gpu_set_lya_field; null: off): rows
+   * [ncell][8], which live and die with the mode */
+  double *lya_field = nullptr;
 
   /* device timing (HIP events around launches) is opt-in: set_tuning
    * ("timing", 1). Events are recycled through a pool; without timing a run
@@ -1298,6 +1301,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->lya.cube);
   (void)hipFree(e->lya_next);
   (void)hipFree(e->lya_counters);
+  (void)hipFree(e->lya_field);
   if (e->own_stream)
     (void)hipStreamDestroy(e->stream);
   delete e;
@@ -4071,6 +4075,8 @@ static void lya_free(cmi_gpu_engine *e) {
   (void)hipFree(const_cast<LyaRecord *>(e->lya.records));
   (void)hipFree(e->lya.image);
   (void)hipFree(e->lya.cube);
+  (void)hipFree(e->lya_field);
+  e->lya_field = nullptr;
   e->lya = LyaDev{};
   e->lya_nviews = 0;
   e->lya_stale = nullptr;
@@ -4088,6 +4094,11 @@ int cmi_gpu_reset_lya(cmi_gpu_engine *e) {
   }
   if (e->lya_counters)
     HIP_TRY(hipMemsetAsync(e->lya_counters, 0, sizeof(LyaCountersDev),
+                           e->stream));
+  if (e->lya_field)
+    HIP_TRY(hipMemsetAsync(e->lya_field, 0,
+                           sizeof(double) * CMI_LYA_FIELD_ROW *
+                               (size_t)e->ncell,
                            e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return CMI_GPU_OK;
@@ -4297,7 +4308,21 @@ int cmi_gpu_lya_shoot(cmi_gpu_engine *e, uint32_t seed, uint64_t first_packet,
     const unsigned blocks = (unsigned)std::min<uint64_t>(
         (chunk + 255) / 256, (uint64_t)e->num_cu * CMI_LYA_BLOCKS_PER_CU);
 #endif
-    if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
+    /* the field's launches are instantiations of their own: without it the
+     * kernels are the ones they were */
+    const LyaFieldDev field = {e->lya_field, 1. - dust.albedo * dust.hgg};
+    if (e->lya_field && e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
+      lya_shoot_kernel<DUST_CAMERA_PARALLEL_VIEWS, LyaFieldDev>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, dust, e->cell_source, lya_views(e), e->lya, seed,
+              first_packet + done, chunk, e->lya_next, e->lya_counters, field);
+    else if (e->lya_field)
+      lya_shoot_kernel<DUST_CAMERA_PARALLEL, LyaFieldDev>
+          <<<blocks, 256, 0, e->stream>>>(
+              e->grid, dust, e->cell_source,
+              DustCamera<DUST_CAMERA_PARALLEL>(), e->lya, seed,
+              first_packet + done, chunk, e->lya_next, e->lya_counters, field);
+    else if (e->dust_camera == DUST_CAMERA_PARALLEL_VIEWS)
       lya_shoot_kernel<DUST_CAMERA_PARALLEL_VIEWS>
           <<<blocks, 256, 0, e->stream>>>(
               e->grid, dust, e->cell_source, lya_views(e), e->lya, seed,
@@ -4438,6 +4463,128 @@ int cmi_gpu_lya_probe(cmi_gpu_engine *e, int32_t kind, uint32_t seed,
     err = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
   (void)hipFree(din);
   (void)hipFree(dout);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_set_lya_field(cmi_gpu_engine *e, int32_t enable) {
+  static const char *what = "set_lya_field";
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (!e->lya.nchan)
+    return fail(CMI_GPU_ESTATE, "%s: Lyman-alpha mode is not set "
+                "(set_lyman_alpha)", what);
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t bytes = sizeof(double) * CMI_LYA_FIELD_ROW * (size_t)e->ncell;
+  if (!enable) {
+    (void)hipFree(e->lya_field);
+    e->lya_field = nullptr;
+    return CMI_GPU_OK;
+  }
+  if (!e->lya_field) {
+    /* hipMalloc's 256-byte alignment makes every row one 64-byte line */
+    double *rows = nullptr;
+    const hipError_t err = hipMalloc(&rows, bytes);
+    if (err == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      return fail(CMI_GPU_ENOMEM, "%s: %zu bytes of rows do not fit into the "
+                  "device's memory", what, bytes);
+    }
+    HIP_TRY(err);
+    e->lya_field = rows;
+  }
+  HIP_TRY(hipMemsetAsync(e->lya_field, 0, bytes, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+/* what a reader of the field asks: the mode on and not stale, the field on,
+ * no capped packet */
+static int lya_field_ready(cmi_gpu_engine *e, const char *what) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null engine", what);
+  if (!e->lya.nchan)
+    return fail(CMI_GPU_ESTATE, "%s: Lyman-alpha mode is not set "
+                "(set_lyman_alpha)", what);
+  if (!e->lya_field)
+    return fail(CMI_GPU_ESTATE, "%s: the radiation field is off "
+                "(set_lya_field)", what);
+  if (e->lya_stale)
+    return fail(CMI_GPU_ESTATE, "%s: %s after Lyman-alpha mode was set", what,
+                e->lya_stale);
+  uint64_t c[7];
+  CMI_TRY(cmi_gpu_get_lya_counters(e, c));
+  if (c[5])
+    return fail(CMI_GPU_ESTATE, "%s: %llu packet(s) reached the cap of %u "
+                "scatterings; the field is incomplete", what,
+                (unsigned long long)c[5], e->lya.max_scatter);
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_download_lya_field(cmi_gpu_engine *e, double *rows) {
+  static const char *what = "download_lya_field";
+  if (e && !rows)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(lya_field_ready(e, what));
+  HIP_TRY(hipMemcpy(rows, e->lya_field,
+                    sizeof(double) * CMI_LYA_FIELD_ROW * (size_t)e->ncell,
+                    hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_lya_spin_temperature(cmi_gpu_engine *e,
+                                 double luminosity_per_packet,
+                                 double background_temperature,
+                                 int32_t collisions, double *P_alpha,
+                                 double *T_s) {
+  static const char *what = "lya_spin_temperature";
+  if (!e || !T_s)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  if (!(luminosity_per_packet > 0.) || !std::isfinite(luminosity_per_packet))
+    return fail(CMI_GPU_EINVAL, "%s: the luminosity per packet must be "
+                "positive and finite (%.17g)", what, luminosity_per_packet);
+  if (!(background_temperature > 0.) || !std::isfinite(background_temperature))
+    return fail(CMI_GPU_EINVAL, "%s: the background temperature must be "
+                "positive and finite (%.17g)", what, background_temperature);
+  CMI_TRY(lya_field_ready(e, what));
+  if (e->lya.x_crit > 0.)
+    return fail(CMI_GPU_ESTATE, "%s: the mode was set with core skipping "
+                "(x_crit = %g): the skipped scatterings are missing from the "
+                "scattering rate", what, e->lya.x_crit);
+  CellsDev *cells;
+  CMI_TRY(cells_settled(e, cells));
+  const size_t ncell = (size_t)e->ncell;
+  double *out = nullptr;
+  HIP_TRY(hipMalloc(&out, sizeof(double) * 2 * ncell));
+  LyaCouplingArgs a;
+  a.rows = e->lya_field;
+  a.records = e->lya.records;
+  a.number_density = cells->number_density;
+  a.temperature = cells->temperature;
+  a.x_H0 = cells->x[0];
+  a.x_He0 = cells->x[1];
+  a.A_He = e->model.abundance[0];
+  a.scale = luminosity_per_packet;
+  a.background = background_temperature;
+  a.cell_volume =
+      e->grid.cellside[0] * e->grid.cellside[1] * e->grid.cellside[2];
+  a.collisions = collisions ? 1 : 0;
+  a.ncell = e->ncell;
+  a.P_alpha = out;
+  a.T_s = out + ncell;
+  lya_coupling_kernel<<<(unsigned)((ncell + 255) / 256), 256, 0, e->stream>>>(
+      a);
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess && P_alpha)
+    err = hipMemcpy(P_alpha, out, sizeof(double) * ncell,
+                    hipMemcpyDeviceToHost);
+  if (err == hipSuccess)
+    err = hipMemcpy(T_s, out + ncell, sizeof(double) * ncell,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(out);
   HIP_TRY(err);
   return CMI_GPU_OK;
 }

@@ -30,6 +30,15 @@
  * the channel fastest; dust_cube_reorder_kernel turns a view into the ABI's
  * [channel][pixel]). An event is a delta in velocity: one atomic into the
  * image and one into the cube per event and view.
+ *
+ * The radiation field (include/cmi_gpu.h, "Lyman alpha radiation field";
+ * DESIGN.md 4.18). With FIELD the walk also tallies, per cell, one 64-byte row
+ * {L, S_H, S_d, G_x, G_y, G_z, N_H, N_d}: the first flight as an expected
+ * value along the march that finds tau_max, every later walk by its track
+ * length, the events as collision estimators. A lane's adds of one crossing
+ * land in one cache line. FIELD is a compile-time switch of the shoot kernel
+ * and of the two marches; without it they are the code they were, and the
+ * peel-off marches and the probes never tally.
  */
 #ifndef CMI_LYMAN_ALPHA_KERNELS_H
 #define CMI_LYMAN_ALPHA_KERNELS_H
@@ -49,11 +58,12 @@
 #define CMI_LYA_MAX_ATTEMPTS 1000000u
 
 /* one cell: line-centre opacity, 1 / b, Voigt parameter, dust opacity, bulk
- * velocity; one half cache line */
+ * velocity, and the H I density the opacity was built from (the walk does not
+ * read it; lya_coupling_kernel does); one half cache line */
 struct alignas(64) LyaRecord {
   double kappa0, inv_b, a, kappa_d;
   double v[3];
-  double pad;
+  double n_HI;
 };
 
 /* what a Lyman-alpha launch reads beyond the dust kernels' arguments */
@@ -99,6 +109,56 @@ struct LyaState {
   bool alive;
 };
 
+/* the row of a cell of the radiation field */
+#define CMI_LYA_FIELD_ROW 8
+enum {
+  LYA_FIELD_L = 0,
+  LYA_FIELD_S_H = 1,
+  LYA_FIELD_S_D = 2,
+  LYA_FIELD_G = 3,
+  LYA_FIELD_N_H = 6,
+  LYA_FIELD_N_D = 7
+};
+
+/* what a launch with the field on reads beyond LyaDev: the kernel's last
+ * argument, absent without the field */
+struct LyaFieldDev {
+  double *rows;      /* [ncell][8], 64-byte aligned */
+  double momentum_d; /* 1 - albedo g: the share of its momentum that a packet
+                        leaves with the dust */
+};
+
+/* the tally of a walk: the rows, the dust's momentum share and the weight of
+ * the flight; nothing at all without the field */
+template <bool FIELD> struct LyaTally {};
+template <> struct LyaTally<true> {
+  double *rows;
+  double momentum_d;
+  double W;
+};
+
+/* E(t) = (1 - exp(-t)) / t, 1 at t = 0: the mean of exp(-t') over a crossing
+ * of depth t */
+__device__ __forceinline__ double lya_mean_transmission(double t) {
+  return (t > 0.) ? -expm1(-t) / t : 1.;
+}
+
+/* a flight of effective length len (weight included) along k through `cell`,
+ * where hydrogen's opacity is kH and the dust's kd */
+__device__ __forceinline__ void lya_tally_flight(const LyaTally<true> &t,
+                                                 int64_t cell, double len,
+                                                 double kH, double kd,
+                                                 const double k[3]) {
+  double *row = t.rows + CMI_LYA_FIELD_ROW * cell;
+  const double push = len * (kH + kd * t.momentum_d);
+  atomicAdd(row + LYA_FIELD_L, len);
+  atomicAdd(row + LYA_FIELD_S_H, len * kH);
+  atomicAdd(row + LYA_FIELD_S_D, len * kd);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    atomicAdd(row + LYA_FIELD_G + a, push * k[a]);
+}
+
 struct LyaRecordArgs {
   const double *number_density, *x_H; /* the engine's cells */
   const double *n_HI, *temperature;   /* the caller's, or null / the cells' */
@@ -137,7 +197,7 @@ __global__ void __launch_bounds__(256) lya_record_kernel(const LyaRecordArgs a) 
     r.kappa_d = n_H * a.sigma_d;
     for (int k = 0; k < 3; ++k)
       r.v[k] = a.velocity ? a.velocity[k * a.ncell + c] : 0.;
-    r.pad = 0.;
+    r.n_HI = n_HI;
     a.out[c] = r;
   }
   for (int off = 32; off > 0; off >>= 1)
@@ -182,22 +242,33 @@ __device__ __forceinline__ void lya_start(const GridDev &g, GridRay &r,
   }
 }
 
-/* the optical depth to the box edge of a packet of shift q */
+/* the optical depth to the box edge of a packet of shift q. With FIELD it is
+ * the first flight of a packet and tallies its expected value: a crossing of
+ * length ds that begins at the depth tau counts ds exp(-tau) E(ds kappa), the
+ * length that the light of weight t.W still in flight covers in it */
+template <bool FIELD>
 __device__ __noinline__ double lya_integrate(const GridDev &g,
                                              const LyaRecord *__restrict__ rec,
                                              const double pos[3],
                                              const double dir[3],
                                              const double inv_dir[3], double q,
-                                             unsigned long long &nsteps) {
+                                             unsigned long long &nsteps,
+                                             LyaTally<FIELD> t = {}) {
   GridRay r;
   lya_start(g, r, pos, dir, inv_dir);
   double tau = 0.;
   int n = 0;
   while (r.inside(g)) {
-    const LyaRecord c = rec[r.cell(g)];
+    const int64_t cell = r.cell(g);
+    const LyaRecord c = rec[cell];
     const double ds = r.step(g);
     double kH, x;
-    tau += ds * lya_opacity(c, q, dir, kH, x);
+    const double dtau = ds * lya_opacity(c, q, dir, kH, x);
+    if constexpr (FIELD)
+      lya_tally_flight(t, cell,
+                       t.W * ((ds * exp(-tau)) * lya_mean_transmission(dtau)),
+                       kH, c.kappa_d, dir);
+    tau += dtau;
     ++n;
   }
   nsteps += n;
@@ -205,30 +276,39 @@ __device__ __noinline__ double lya_integrate(const GridDev &g,
 }
 
 /* moves the photon until the optical depth is used up; false: it left the
- * box, or no step was taken (dust_interact's contract) */
+ * box, or no step was taken (dust_interact's contract). With FIELD every
+ * crossing tallies t.W times the length flown in it (the backed-off length in
+ * the last one) */
+template <bool FIELD>
 __device__ __noinline__ bool lya_interact(const GridDev &g,
                                           const LyaRecord *__restrict__ rec,
                                           DustPhoton &p, double q, double tau,
-                                          unsigned long long &nsteps) {
+                                          unsigned long long &nsteps,
+                                          LyaTally<FIELD> t = {}) {
   GridRay r;
   lya_start(g, r, p.pos, p.dir, p.inv_dir);
   int n = 0;
   while (r.inside(g) && tau > 0.) {
-    const LyaRecord c = rec[r.cell(g)];
+    const int64_t cell = r.cell(g);
+    const LyaRecord c = rec[cell];
     const double from[3] = {r.pos[0], r.pos[1], r.pos[2]};
     const int32_t in[3] = {r.index[0], r.index[1], r.index[2]};
     const double ds = r.step(g);
     double kH, x;
     const double tau_cell = ds * lya_opacity(c, q, p.dir, kH, x);
     tau -= tau_cell;
+    double flown = ds;
     if (tau < 0.) {
       const double back = ds * tau / tau_cell;
+      flown = ds + back;
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         r.pos[a] = from[a] + (r.pos[a] - from[a]) * (ds + back) / ds;
         r.index[a] = in[a];
       }
     }
+    if constexpr (FIELD)
+      lya_tally_flight(t, cell, t.W * flown, kH, c.kappa_d, p.dir);
     ++n;
   }
   nsteps += n;
@@ -338,8 +418,8 @@ __device__ __noinline__ void lya_peel(const GridDev &g, const DustDev &dv,
     factor = 0.25 / M_PI;
     q_d = (species == 0) ? wd : q + (wd - dust_dot3(w, p.dir));
   }
-  const double tau = lya_integrate(g, l.records, p.pos, dv.obs_dir,
-                                   dv.obs_inv_dir, q_d, c.nsteps);
+  const double tau = lya_integrate<false>(g, l.records, p.pos, dv.obs_dir,
+                                          dv.obs_inv_dir, q_d, c.nsteps);
   const double addend = ((W * factor) * exp(-tau)) * peel.stokes[0];
   const double u = -q_d;
   if (tr.rows) {
@@ -392,13 +472,15 @@ lya_peel_views(const GridDev &g, const DustDev &d,
 
 /* a new packet: the cell source's draws, the emitting atom (two Box-Muller
  * pairs, the second's sine unused), the direct light, the forced first
- * interaction and the walk to it */
-template <int CAMERA>
+ * interaction and the walk to it. The march for tau_max tallies the first
+ * flight with weight 1, the light that leaves unscattered included; the forced
+ * walk that follows tallies nothing */
+template <int CAMERA, bool FIELD>
 __device__ __forceinline__ void
 lya_begin(const GridDev &g, const DustDev &d, const CellSourceDev &src,
           const DustCamera<CAMERA> &cam, const LyaDev &l, uint32_t seed,
           uint64_t id, LyaState &s, DustDev &dv, LyaCountersDev &c,
-          LyaTrace &tr) {
+          LyaTrace &tr, LyaTally<FIELD> &t) {
   s.rng.init(seed, 0u, id);
   c.npackets += 1;
   const int64_t cell = dust_emit_cells(g, src, s.rng, s.p);
@@ -414,24 +496,32 @@ lya_begin(const GridDev &g, const DustDev &d, const CellSourceDev &src,
   s.albedo = 1.;
   s.nscatter = 0;
   lya_peel_views<CAMERA>(g, d, cam, l, s.p, 0, s.q, w, 1., 0., 0., dv, c, tr);
-  const double tau_max = lya_integrate(g, l.records, s.p.pos, s.p.dir,
-                                       s.p.inv_dir, s.q, c.nsteps);
+  if constexpr (FIELD)
+    t.W = 1.;
+  const double tau_max = lya_integrate<FIELD>(g, l.records, s.p.pos, s.p.dir,
+                                              s.p.inv_dir, s.q, c.nsteps, t);
   s.forced = 1. - exp(-tau_max);
   const double tau = -log(1. - s.rng.next() * s.forced);
-  s.alive = lya_interact(g, l.records, s.p, s.q, tau, c.nsteps);
+  s.alive = lya_interact<false>(g, l.records, s.p, s.q, tau, c.nsteps);
 }
 
-/* one event of a packet that is alive, and the walk to the next */
-template <int CAMERA>
+/* one event of a packet that is alive, and the walk to the next; the event's
+ * cell counts the incoming weight as a collision (for dust: before the
+ * albedo), the walk tallies the outgoing one */
+template <int CAMERA, bool FIELD>
 __device__ __forceinline__ void
 lya_event(const GridDev &g, const DustDev &d, const DustCamera<CAMERA> &cam,
           const LyaDev &l, LyaState &s, DustDev &dv, LyaCountersDev &c,
-          LyaTrace &tr) {
+          LyaTrace &tr, LyaTally<FIELD> &t) {
   const LyaRecord r = l.records[dust_cube_cell(g, s.p.pos)];
   const double k[3] = {s.p.dir[0], s.p.dir[1], s.p.dir[2]};
   double kH, x;
   const double kappa = lya_opacity(r, s.q, k, kH, x);
   if (s.rng.next() < kH / kappa) {
+    if constexpr (FIELD)
+      atomicAdd(t.rows + CMI_LYA_FIELD_ROW * dust_cube_cell(g, s.p.pos) +
+                    LYA_FIELD_N_H,
+                s.forced * s.albedo);
     const double b = 1. / r.inv_b;
     const double u_par = lya_sample_parallel(x, r.a, s.rng, c.nrejections);
     const double skip = (fabs(x) < l.x_crit) ? l.x_crit2 : 0.;
@@ -456,6 +546,10 @@ lya_event(const GridDev &g, const DustDev &d, const DustCamera<CAMERA> &cam,
     s.q += dust_dot3(w, s.p.dir) - dust_dot3(w, k);
     c.nhydrogen += 1;
   } else {
+    if constexpr (FIELD)
+      atomicAdd(t.rows + CMI_LYA_FIELD_ROW * dust_cube_cell(g, s.p.pos) +
+                    LYA_FIELD_N_D,
+                s.forced * s.albedo);
     s.albedo *= d.albedo;
     lya_peel_views<CAMERA>(g, d, cam, l, s.p, 2, s.q, r.v, s.forced * s.albedo,
                            0., x, dv, c, tr);
@@ -469,16 +563,28 @@ lya_event(const GridDev &g, const DustDev &d, const DustCamera<CAMERA> &cam,
     return;
   }
   const double tau = -log(s.rng.next());
-  s.alive = lya_interact(g, l.records, s.p, s.q, tau, c.nsteps);
+  if constexpr (FIELD)
+    t.W = s.forced * s.albedo;
+  s.alive = lya_interact<FIELD>(g, l.records, s.p, s.q, tau, c.nsteps, t);
 }
 
-/* packets [first, first + n); *next is 0 at the launch */
-template <int CAMERA>
+__device__ __forceinline__ LyaTally<false> lya_tally_of() { return {}; }
+__device__ __forceinline__ LyaTally<true> lya_tally_of(const LyaFieldDev &f) {
+  return {f.rows, f.momentum_d, 0.};
+}
+
+/* packets [first, first + n); *next is 0 at the launch. FIELD is empty, or
+ * LyaFieldDev for a launch that tallies the radiation field: the kernel
+ * without it has the arguments it always had */
+template <int CAMERA, typename... FIELD>
 __global__ void __launch_bounds__(256)
     lya_shoot_kernel(GridDev g, DustDev d, CellSourceDev src,
                      DustCamera<CAMERA> cam, LyaDev l, uint32_t seed,
                      uint64_t first, uint64_t n, unsigned long long *next,
-                     LyaCountersDev *counters) {
+                     LyaCountersDev *counters, FIELD... field) {
+  static_assert(sizeof...(FIELD) <= 1, "at most one field");
+  constexpr bool TALLY = sizeof...(FIELD) == 1;
+  LyaTally<TALLY> t = lya_tally_of(field...);
   LyaCountersDev c = {};
   LyaTrace tr = {nullptr, 0, 0};
   LyaState s;
@@ -489,9 +595,10 @@ __global__ void __launch_bounds__(256)
 #ifndef CMI_LYA_EVENT_LOOP
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) {
-    lya_begin<CAMERA>(g, d, src, cam, l, seed, first + k, s, dv, c, tr);
+    lya_begin<CAMERA, TALLY>(g, d, src, cam, l, seed, first + k, s, dv, c, tr,
+                             t);
     while (s.alive)
-      lya_event<CAMERA>(g, d, cam, l, s, dv, c, tr);
+      lya_event<CAMERA, TALLY>(g, d, cam, l, s, dv, c, tr, t);
   }
 #else
   for (;;) {
@@ -499,9 +606,10 @@ __global__ void __launch_bounds__(256)
       const unsigned long long k = atomicAdd(next, 1ull);
       if (k >= n)
         break;
-      lya_begin<CAMERA>(g, d, src, cam, l, seed, first + k, s, dv, c, tr);
+      lya_begin<CAMERA, TALLY>(g, d, src, cam, l, seed, first + k, s, dv, c,
+                               tr, t);
     } else {
-      lya_event<CAMERA>(g, d, cam, l, s, dv, c, tr);
+      lya_event<CAMERA, TALLY>(g, d, cam, l, s, dv, c, tr, t);
     }
   }
 #endif
@@ -546,7 +654,7 @@ __global__ void __launch_bounds__(64)
     const double *r = in + 7 * k;
     const double inv[3] = {1. / r[3], 1. / r[4], 1. / r[5]};
     unsigned long long nsteps = 0;
-    o[0] = lya_integrate(g, l.records, r, r + 3, inv, r[6], nsteps);
+    o[0] = lya_integrate<false>(g, l.records, r, r + 3, inv, r[6], nsteps);
     o[1] = (double)nsteps;
   } else if (kind == LYA_PROBE_SAMPLER) {
     /* in: {x, a}; out: {u_par, rejections} */
@@ -563,9 +671,11 @@ __global__ void __launch_bounds__(64)
     DustDev dv;
     if constexpr (CAMERA == DUST_CAMERA_PARALLEL_VIEWS)
       dv = d;
-    lya_begin<CAMERA>(g, d, src, cam, l, seed, first + k, s, dv, c, tr);
+    LyaTally<false> t;
+    lya_begin<CAMERA, false>(g, d, src, cam, l, seed, first + k, s, dv, c, tr,
+                             t);
     while (s.alive)
-      lya_event<CAMERA>(g, d, cam, l, s, dv, c, tr);
+      lya_event<CAMERA, false>(g, d, cam, l, s, dv, c, tr, t);
     o[0] = tr.n;
     o[1] = (double)c.nhydrogen;
     o[2] = (double)c.ndust;
@@ -601,6 +711,74 @@ __global__ void __launch_bounds__(256)
         (CMI_PLANCK * CMI_LIGHTSPEED / CMI_LYA_LAMBDA0);
   }
   out[c] = j;
+}
+
+/* Wouthuysen-Field coupling (include/cmi_gpu.h, cmi_gpu_lya_spin_temperature,
+ * has the formulas and their sources). The de-excitation rate coefficients in
+ * m^3 s^-1: H-H of Kuhlen, Madau & Montgomery (2006), e-H of Liszt (2001) held
+ * at its 1e4 K value above and at its 1 K value below */
+#define CMI_LYA_KAPPA_HH 3.1e-17
+__device__ __forceinline__ double lya_kappa_HH(double T) {
+  return CMI_LYA_KAPPA_HH * pow(T, 0.357) * exp(-32. / T);
+}
+__device__ __forceinline__ double lya_kappa_eH(double T) {
+  const double lT = log10(fmin(fmax(T, 1.), 1.e4));
+  return 1.e-6 * pow(10., -9.607 + 0.5 * lT * exp(-pow(lT, 4.5) / 1800.));
+}
+
+struct LyaCouplingArgs {
+  const double *rows; /* [ncell][8] */
+  const LyaRecord *records;
+  const double *number_density, *temperature, *x_H0, *x_He0; /* the cells */
+  double A_He;
+  double scale;       /* W per packet */
+  double background;  /* T_gamma, K */
+  double cell_volume; /* m^3 */
+  int32_t collisions;
+  int64_t ncell;
+  double *P_alpha; /* [ncell] or null */
+  double *T_s;     /* [ncell] */
+};
+
+/* the spin temperature of a cell from its scattering rate P, its kinetic
+ * temperature and its collision rate C_10; the colour temperature of the
+ * Lyman-alpha field is taken as T_k */
+__device__ __forceinline__ double lya_spin_temperature(double P, double C_10,
+                                                       double T_k,
+                                                       double T_gamma) {
+  if (!(T_k > 0.))
+    return T_gamma;
+  const double T_star = CMI_PLANCK * CMI_HI_FREQUENCY / CMI_BOLTZMANN;
+  const double x_a = 4. * P * T_star / (27. * CMI_HI_EINSTEIN_A * T_gamma);
+  const double x_c = (C_10 / CMI_HI_EINSTEIN_A) * (T_star / T_gamma);
+  const double x = x_a + x_c;
+  return (1. + x) / (1. / T_gamma + x / T_k);
+}
+
+/* one thread per cell: P_alpha = s S_H / (h nu_0 n_HI V), 0 where n_HI = 0,
+ * and T_s */
+__global__ void __launch_bounds__(256)
+    lya_coupling_kernel(const LyaCouplingArgs a) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= a.ncell)
+    return;
+  const double n_HI = a.records[c].n_HI;
+  const double S_H = a.rows[CMI_LYA_FIELD_ROW * c + LYA_FIELD_S_H];
+  const double P =
+      (n_HI > 0.) ? a.scale * S_H /
+                        ((CMI_PLANCK * CMI_LIGHTSPEED / CMI_LYA_LAMBDA0) *
+                         n_HI * a.cell_volume)
+                  : 0.;
+  const double T = a.temperature[c];
+  double C_10 = 0.;
+  if (a.collisions && T > 0.) {
+    const double n = a.number_density[c];
+    const double n_e = n * ((1. - a.x_H0[c]) + a.A_He * (1. - a.x_He0[c]));
+    C_10 = n_HI * lya_kappa_HH(T) + n_e * lya_kappa_eH(T);
+  }
+  if (a.P_alpha)
+    a.P_alpha[c] = P;
+  a.T_s[c] = lya_spin_temperature(P, C_10, T, a.background);
 }
 
 #endif

@@ -40,6 +40,9 @@ DUST_PROBE_CUBE_TRACE = 7
 LYA_PROBE_VOIGT, LYA_PROBE_OPTICAL_DEPTH = 0, 1
 LYA_PROBE_SAMPLER, LYA_PROBE_TRACE = 2, 3
 LYA_MAX_SCATTER = 100000000
+LYA_LAMBDA0 = 1215.67e-10  # m
+# the columns of a row of cmi_gpu_download_lya_field
+LYA_FIELD_COLUMNS = ("L", "S_H", "S_d", "G_x", "G_y", "G_z", "N_H", "N_d")
 # CMI_GPU_MAX_VIEWS: the views of one run (set_ccd_images, set_sky_cameras)
 MAX_VIEWS = 64
 
@@ -142,6 +145,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_set_lyman_alpha", "cmi_gpu_lya_shoot", "cmi_gpu_lya_probe",
     "cmi_gpu_download_lya_view", "cmi_gpu_reset_lya",
     "cmi_gpu_get_lya_counters", "cmi_gpu_lyman_alpha_emissivity",
+    "cmi_gpu_set_lya_field", "cmi_gpu_download_lya_field",
+    "cmi_gpu_lya_spin_temperature",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -501,6 +506,12 @@ def load_library():
         L.cmi_gpu_reset_lya.argtypes = [vp]
         L.cmi_gpu_get_lya_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.cmi_gpu_lyman_alpha_emissivity.argtypes = [vp, _dp]
+    # (nor does a build from before the Lyman-alpha radiation field have it)
+    if hasattr(L, "cmi_gpu_set_lya_field"):
+        L.cmi_gpu_set_lya_field.argtypes = [vp, C.c_int32]
+        L.cmi_gpu_download_lya_field.argtypes = [vp, _dp]
+        L.cmi_gpu_lya_spin_temperature.argtypes = [
+            vp, C.c_double, C.c_double, C.c_int32, _dp, _dp]
     # (a build from before the continuum images, loaded through
     # CMI_GPU_LIBRARY for a comparison, does not have them)
     if hasattr(L, "cmi_gpu_free_free_coefficients"):
@@ -719,6 +730,9 @@ class GpuEngine:
         self.n = int(np.prod(self.ncell))
         self.cube_channels = 0  # set_scattered_cube's nchan; 0: off
         self.lya_channels = 0  # set_lyman_alpha's nchan; 0: off
+        self.lya_x_crit = 0.
+        self.cell_volume = float(np.prod([float(sides[a]) / int(ncell[a])
+                                          for a in range(3)]))  # m^3
         # tests, bench and tools read device timings; the engine records them
         # only on request
         self.set_tuning(timing=1)
@@ -2098,6 +2112,7 @@ class GpuEngine:
             self._h, int(nchan), vmin, vmax, sigma_turb, x_crit,
             int(max_scatter), _p_or_none(n), _p_or_none(t)))
         self.lya_channels = int(nchan)
+        self.lya_x_crit = float(x_crit)
 
     def lya_shoot(self, seed, first_packet, n):
         self._check(self._lib.cmi_gpu_lya_shoot(self._h, seed, first_packet,
@@ -2144,6 +2159,64 @@ class GpuEngine:
                          "natomics", "ncapped", "npackets"),
                         (int(v) for v in c)))
 
+    def set_lya_field(self, enable=True):
+        """Switches the radiation field of the Lyman-alpha mode on (zeroed)
+        or off: the per-cell tallies of include/cmi_gpu.h, "Lyman alpha
+        radiation field". set_lyman_alpha, called anew, switches it off."""
+        self._check(self._lib.cmi_gpu_set_lya_field(self._h,
+                                                    int(bool(enable))))
+
+    def download_lya_field(self):
+        """The raw tallies of a Lyman-alpha run with the field on: a dict of
+        the eight arrays (ncell,) L, S_H, S_d, G_x, G_y, G_z, N_H, N_d"""
+        rows = np.zeros((self.n, 8))
+        self._check(self._lib.cmi_gpu_download_lya_field(self._h, _p(rows)))
+        return {name: np.ascontiguousarray(rows[:, k])
+                for k, name in enumerate(LYA_FIELD_COLUMNS)}
+
+    def _lya_scale(self, npackets, total_luminosity):
+        if total_luminosity is None:
+            total_luminosity = self.get_cell_source(tables=False)
+        return float(total_luminosity) / int(npackets)
+
+    def lya_radiation_field(self, npackets, total_luminosity=None):
+        """The field of a run of `npackets` packets in physical units, a
+        dict: `energy_density` (ncell,) in J m^-3, `scattering_rate` (ncell,)
+        per atom in s^-1 (0 where the records have no H I; None if the mode
+        skips the core, whose skipped scatterings it would leave out),
+        `force` (3, ncell) in N m^-3. `total_luminosity` (W): None takes the
+        cell source's."""
+        s = self._lya_scale(npackets, total_luminosity)
+        f = self.download_lya_field()
+        per_volume = s / (LIGHTSPEED * self.cell_volume)
+        rate = None
+        if not self.lya_x_crit > 0.:
+            rate = np.zeros(self.n)
+            self._check(self._lib.cmi_gpu_lya_spin_temperature(
+                self._h, s, 1., 0, _p(rate), _p(np.zeros(self.n))))
+        return {"energy_density": f["L"] * per_volume,
+                "scattering_rate": rate,
+                "force": np.stack([f["G_x"], f["G_y"], f["G_z"]]) *
+                per_volume}
+
+    def lya_spin_temperature(self, npackets, background_temperature,
+                             collisions=True, total_luminosity=None):
+        """(P_alpha, T_s), (ncell,) each: the Lyman-alpha scattering rate per
+        atom (s^-1) of a run of `npackets` packets and the 21-cm spin
+        temperature (K) it implies against a background of
+        `background_temperature` K, with (`collisions`) or without the
+        collisional coupling of the cells (include/cmi_gpu.h,
+        cmi_gpu_lya_spin_temperature). T_s goes as it is into
+        render_hi_cube(spin_temperature=T_s) and its sky variants. Refused if
+        the mode skips the core."""
+        s = self._lya_scale(npackets, total_luminosity)
+        P = np.zeros(self.n)
+        T_s = np.zeros(self.n)
+        self._check(self._lib.cmi_gpu_lya_spin_temperature(
+            self._h, s, background_temperature, int(bool(collisions)), _p(P),
+            _p(T_s)))
+        return P, T_s
+
     def lyman_alpha_emissivity(self):
         """W m^-3 of Lyman alpha from recombinations per cell, from the cells
         as they are (cmi_gpu_lyman_alpha_emissivity)"""
@@ -2154,7 +2227,8 @@ class GpuEngine:
     def render_lyman_alpha_cube(self, theta, phi, nx, ny, anchor, sides,
                                 npackets, seed, nchan, vmin, vmax,
                                 sigma_turb=0., core_skip=0., dust=None,
-                                source=None, max_scatter=LYA_MAX_SCATTER):
+                                source=None, max_scatter=LYA_MAX_SCATTER,
+                                field=False):
         """The Lyman-alpha image (nx, ny) and cube (nchan, nx, ny) of one
         Monte Carlo run of `npackets` packets that scatter off the cells' H I
         (and off dust: `dust` = (sigma per hydrogen nucleus, albedo, g, p_l),
@@ -2163,8 +2237,10 @@ class GpuEngine:
         render_scattered_line_cube. `source` is a luminosity density (ncell,)
         in W m^-3; None takes lyman_alpha_emissivity(). `core_skip` is
         x_crit. With sequences for theta and phi the views share one run:
-        (nviews, nx, ny) and (nviews, nchan, nx, ny). Replaces the engine's
-        CCD image, dust and dust source, and leaves the mode off."""
+        (nviews, nx, ny) and (nviews, nchan, nx, ny). With `field` the run
+        also tallies the radiation field, and the dict of
+        lya_radiation_field is returned as a third value. Replaces the
+        engine's CCD image, dust and dust source, and leaves the mode off."""
         if dust is None:
             self.set_dust_scattering_per_hydrogen(0.5, 0., 0., 0.)
         else:
@@ -2184,17 +2260,23 @@ class GpuEngine:
         try:
             self.set_lyman_alpha(nchan, vmin, vmax, sigma_turb, core_skip,
                                  max_scatter)
+            if field:
+                self.set_lya_field(True)
             self.lya_shoot(seed, 0, int(npackets))
             total = self.get_cell_source(tables=False)
             scale = total / (int(npackets) * pixel_area)
             images, cubes = self.download_lya()
             images = images * scale[:, None, None]
             cubes = cubes * scale[:, None, None, None]
+            if field:
+                field = self.lya_radiation_field(npackets, total)
         finally:
             self.set_lyman_alpha(0, 0., 1.)
-        if several:
-            return images, cubes
-        return images[0], cubes[0]
+        if not several:
+            images, cubes = images[0], cubes[0]
+        if field:
+            return images, cubes, field
+        return images, cubes
 
     def get_timing(self, reset=True):
         s = C.c_double()

@@ -153,6 +153,25 @@
  * Written as <prefix>_LymanAlpha_image.dat and <prefix>_LymanAlpha_cube.dat
  * (_view<k> appended for view k >= 1), raw doubles [ix][iy] and [channel][ix]
  * [iy] in the unit of the scattered-light images and cubes.
+ * Lyman-alpha radiation field (both keys are read only in
+ * EmissionImages and only with "Lyman alpha: true"):
+ *   EmissionImages:Lyman alpha radiation field   false: true writes the field
+ *                    the run leaves in the cells as <prefix>_LymanAlpha_field
+ *                    .dat, raw doubles [5][nx][ny][nz]: the energy density in
+ *                    J m^-3, the scattering rate per H I atom in s^-1, the
+ *                    force density x, y, z in N m^-3
+ *   EmissionImages:HI Lyman alpha coupling       false (read only if the block
+ *                    has "HI cube: true" as well; it implies the field): the
+ *                    Lyman-alpha run comes first, and the H I cube is rendered
+ *                    with the spin temperature that the run's scattering rate
+ *                    and the cells' collisions give against "HI background
+ *                    temperature" (Wouthuysen-Field coupling), written as
+ *                    <prefix>_HI_spin_temperature.dat, raw doubles [nx][ny]
+ *                    [nz] in K. Refused with "Lyman alpha core skipping" > 0
+ *                    (the skipped scatterings are missing from the rate), with
+ *                    "HI spin temperature type: Fixed" and with a background
+ *                    temperature of 0. The H I cube of EmissionSkyMaps is not
+ *                    coupled: it keeps its own spin temperature type.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -418,6 +437,10 @@ class EmissivityCalculationSimulation {
      * snapshot's own H I; it reads the packets, the seed and
      * the dust keys of the scattered light */
     bool lyman_alpha = false;
+    /* "Lyman alpha radiation field", "HI Lyman alpha coupling" (DESIGN.md
+     * 4.18): what the run leaves in the cells, and the H I cube with the spin
+     * temperature it gives */
+    bool lya_field = false, lya_coupling = false;
     double lya_core_skip = 0.;
     long long lya_max_scatter = 100000000;
     long long npackets = 1000000, seed = 42;
@@ -559,6 +582,29 @@ class EmissivityCalculationSimulation {
         if (lya_max_scatter < 1 || lya_max_scatter > 100000000)
           throw ParameterError("EmissionImages:Lyman alpha maximum "
                                "scatterings must be 1..100000000");
+        if (params.peek_bool("EmissionImages:Lyman alpha radiation field"))
+          lya_field = params.get_bool(
+              "EmissionImages:Lyman alpha radiation field", false);
+        if (hi_cube &&
+            params.peek_bool("EmissionImages:HI Lyman alpha coupling")) {
+          lya_coupling =
+              params.get_bool("EmissionImages:HI Lyman alpha coupling", false);
+          if (lya_core_skip > 0.)
+            throw ParameterError(
+                "EmissionImages:HI Lyman alpha coupling needs "
+                "EmissionImages:Lyman alpha core skipping 0: the skipped "
+                "scatterings are missing from the scattering rate");
+          if (hi_spin_mode != 0)
+            throw ParameterError(
+                "EmissionImages:HI Lyman alpha coupling computes the spin "
+                "temperature: EmissionImages:HI spin temperature type must "
+                "not be Fixed");
+          if (!(hi_background_temperature > 0.))
+            throw ParameterError(
+                "EmissionImages:HI Lyman alpha coupling needs a positive "
+                "EmissionImages:HI background temperature");
+          lya_field = true;
+        }
       }
       if (!lyman_alpha && !params.peek_bool("EmissionImages:scattering"))
         return;
@@ -1218,7 +1264,112 @@ public:
                                  img.folder + "/" + img.prefix +
                                  "_continuum_frequencies");
         }
-        if (rc == CMI_GPU_OK && img.hi_cube) {
+        /* with "HI Lyman alpha coupling" the Lyman-alpha run comes first and
+         * leaves the spin temperature of the cells here */
+        std::vector<double> coupled_spin;
+        const auto shoot_lyman_alpha = [&]() {
+          if (!(rc == CMI_GPU_OK && img.lyman_alpha))
+            return;
+          status("Shooting the Lyman alpha packets through the H I...");
+          /* the source: the cells' recombinations; the scatterers: the
+           * cells' own H I at their temperatures, and the block's dust */
+          std::vector<double> source(size);
+          rc = cmi_gpu_lyman_alpha_emissivity(engine, source.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_dust_scattering_per_hydrogen(
+                engine, img.asymmetry, img.polarisation, img.albedo,
+                img.dust_cross_section);
+          if (rc == CMI_GPU_OK)
+            rc = nviews == 1
+                     ? cmi_gpu_set_ccd_image(engine, theta[0], phi[0],
+                                             (int32_t)img.nx, (int32_t)img.ny,
+                                             anchors.data(), sides.data())
+                     : cmi_gpu_set_ccd_images(
+                           engine, (int32_t)nviews, theta.data(), phi.data(),
+                           (int32_t)img.nx, (int32_t)img.ny, anchors.data(),
+                           sides.data());
+          if (rc == CMI_GPU_OK && !velocities.empty())
+            rc = cmi_gpu_set_cell_velocities(engine, velocities.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_cell_source_field(engine, source.data());
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_lyman_alpha(
+                engine, (int32_t)img.nchan, img.vmin, img.vmax, img.sigma_turb,
+                img.lya_core_skip, (uint64_t)img.lya_max_scatter, nullptr,
+                nullptr);
+          if (rc == CMI_GPU_OK && img.lya_field)
+            rc = cmi_gpu_set_lya_field(engine, 1);
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_lya_shoot(engine, (uint32_t)img.seed, 0,
+                                   (uint64_t)img.npackets);
+          double total = 0.;
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
+          const size_t nvalue = (size_t)img.nchan * npixel;
+          std::vector<double> lya_image(npixel), lya_cube(nvalue);
+          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
+            rc = cmi_gpu_download_lya_view(engine, (int32_t)v,
+                                           lya_image.data(), lya_cube.data());
+            const double pixel_area = sides[2 * v] * sides[2 * v + 1] /
+                                      ((double)img.nx * (double)img.ny);
+            const double scale = total / ((double)img.npackets * pixel_area);
+            for (double &value : lya_cube)
+              value *= scale;
+            if (rc == CMI_GPU_OK && write_output) {
+              written += " " + write_image(img.folder + "/" + img.prefix +
+                                               "_LymanAlpha_image" +
+                                               view_tag(v),
+                                           img.type, lya_image.data(), img.nx,
+                                           img.ny, scale);
+              written += " " + write_cube(img.folder + "/" + img.prefix +
+                                              "_LymanAlpha_cube" + view_tag(v),
+                                          lya_cube.data(), img.nchan, img.nx,
+                                          img.ny);
+            }
+          }
+          if (rc == CMI_GPU_OK && img.lya_field) {
+            /* rows {L, S_H, S_d, G[3], N_H, N_d} -> [5][ncell] in physical
+             * units; the rate per atom is the engine's (it knows the records'
+             * n_HI), 0 if the core is skipped */
+            const double per_packet = total / (double)img.npackets;
+            const double volume = (box_sides[0] / ncell[0]) *
+                                  (box_sides[1] / ncell[1]) *
+                                  (box_sides[2] / ncell[2]);
+            const double per_volume = per_packet / (299792458. * volume);
+            std::vector<double> rows(8 * size), field(5 * size, 0.),
+                spin(size);
+            rc = cmi_gpu_download_lya_field(engine, rows.data());
+            if (rc == CMI_GPU_OK && !(img.lya_core_skip > 0.))
+              rc = cmi_gpu_lya_spin_temperature(
+                  engine, per_packet,
+                  img.lya_coupling ? img.hi_background_temperature : 1.,
+                  img.lya_coupling ? 1 : 0, field.data() + size, spin.data());
+            for (size_t c = 0; c < size; ++c) {
+              field[c] = rows[8 * c] * per_volume;
+              for (size_t a = 0; a < 3; ++a)
+                field[(2 + a) * size + c] = rows[8 * c + 3 + a] * per_volume;
+            }
+            if (img.lya_coupling)
+              coupled_spin = spin;
+            if (rc == CMI_GPU_OK && write_output) {
+              written += " " + write_cube(img.folder + "/" + img.prefix +
+                                              "_LymanAlpha_field",
+                                          field.data(), 5 * ncell[0], ncell[1],
+                                          ncell[2]);
+              if (img.lya_coupling)
+                written += " " + write_cube(img.folder + "/" + img.prefix +
+                                                "_HI_spin_temperature",
+                                            spin.data(), ncell[0], ncell[1],
+                                            ncell[2]);
+            }
+          }
+          if (rc == CMI_GPU_OK)
+            rc = cmi_gpu_set_lyman_alpha(engine, 0, 0., 1., 0., 0., 1, nullptr,
+                                         nullptr);
+        };
+        const auto render_hi_cubes = [&]() {
+          if (!(rc == CMI_GPU_OK && img.hi_cube))
+            return;
           status("Rendering H I cubes...");
           if ((double)img.nchan * (double)npixel > (double)(1ll << 28))
             throw ParameterError(
@@ -1232,15 +1383,21 @@ public:
                 engine, theta[v], phi[v], (int32_t)img.nx, (int32_t)img.ny,
                 anchors.data() + 2 * v, sides.data() + 2 * v,
                 (int32_t)img.supersample, (int32_t)img.nchan, img.vmin,
-                img.vmax, img.sigma_turb, img.hi_spin_mode,
-                &img.hi_spin_temperature, img.hi_free_free ? 1 : 0,
-                img.hi_background_temperature, hi.data());
+                img.vmax, img.sigma_turb,
+                img.lya_coupling ? 2 : img.hi_spin_mode,
+                img.lya_coupling ? coupled_spin.data()
+                                 : &img.hi_spin_temperature,
+                img.hi_free_free ? 1 : 0, img.hi_background_temperature,
+                hi.data());
             if (rc == CMI_GPU_OK && write_output)
               written += " " + write_cube(img.folder + "/" + img.prefix +
                                               "_HI_cube" + view_tag(v),
                                           hi.data(), img.nchan, img.nx, img.ny);
           }
-        }
+        };
+        if (img.lya_coupling)
+          shoot_lyman_alpha();
+        render_hi_cubes();
         if (rc == CMI_GPU_OK && img.scattering) {
           status("Shooting the lines' packets through the dust...");
           rc = cmi_gpu_set_dust_scattering_per_hydrogen(
@@ -1320,66 +1477,8 @@ public:
             rc = cmi_gpu_set_scattered_cube(engine, 0, 0., 1., 0., nullptr,
                                             nullptr);
         }
-        if (rc == CMI_GPU_OK && img.lyman_alpha) {
-          status("Shooting the Lyman alpha packets through the H I...");
-          /* the source: the cells' recombinations; the scatterers: the
-           * cells' own H I at their temperatures, and the block's dust */
-          std::vector<double> source(size);
-          rc = cmi_gpu_lyman_alpha_emissivity(engine, source.data());
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_dust_scattering_per_hydrogen(
-                engine, img.asymmetry, img.polarisation, img.albedo,
-                img.dust_cross_section);
-          if (rc == CMI_GPU_OK)
-            rc = nviews == 1
-                     ? cmi_gpu_set_ccd_image(engine, theta[0], phi[0],
-                                             (int32_t)img.nx, (int32_t)img.ny,
-                                             anchors.data(), sides.data())
-                     : cmi_gpu_set_ccd_images(
-                           engine, (int32_t)nviews, theta.data(), phi.data(),
-                           (int32_t)img.nx, (int32_t)img.ny, anchors.data(),
-                           sides.data());
-          if (rc == CMI_GPU_OK && !velocities.empty())
-            rc = cmi_gpu_set_cell_velocities(engine, velocities.data());
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_cell_source_field(engine, source.data());
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_lyman_alpha(
-                engine, (int32_t)img.nchan, img.vmin, img.vmax, img.sigma_turb,
-                img.lya_core_skip, (uint64_t)img.lya_max_scatter, nullptr,
-                nullptr);
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_lya_shoot(engine, (uint32_t)img.seed, 0,
-                                   (uint64_t)img.npackets);
-          double total = 0.;
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_get_cell_source(engine, &total, nullptr, nullptr);
-          const size_t nvalue = (size_t)img.nchan * npixel;
-          std::vector<double> lya_image(npixel), lya_cube(nvalue);
-          for (size_t v = 0; rc == CMI_GPU_OK && v < nviews; ++v) {
-            rc = cmi_gpu_download_lya_view(engine, (int32_t)v,
-                                           lya_image.data(), lya_cube.data());
-            const double pixel_area = sides[2 * v] * sides[2 * v + 1] /
-                                      ((double)img.nx * (double)img.ny);
-            const double scale = total / ((double)img.npackets * pixel_area);
-            for (double &value : lya_cube)
-              value *= scale;
-            if (rc == CMI_GPU_OK && write_output) {
-              written += " " + write_image(img.folder + "/" + img.prefix +
-                                               "_LymanAlpha_image" +
-                                               view_tag(v),
-                                           img.type, lya_image.data(), img.nx,
-                                           img.ny, scale);
-              written += " " + write_cube(img.folder + "/" + img.prefix +
-                                              "_LymanAlpha_cube" + view_tag(v),
-                                          lya_cube.data(), img.nchan, img.nx,
-                                          img.ny);
-            }
-          }
-          if (rc == CMI_GPU_OK)
-            rc = cmi_gpu_set_lyman_alpha(engine, 0, 0., 1., 0., 0., 1, nullptr,
-                                         nullptr);
-        }
+        if (!img.lya_coupling)
+          shoot_lyman_alpha();
       }
       if (rc == CMI_GPU_OK && placed && do_sky) {
         status("Rendering emission line sky maps...");

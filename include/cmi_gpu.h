@@ -1594,7 +1594,7 @@ int cmi_gpu_download_cube_view(cmi_gpu_engine *engine, int32_t view, double *I,
  * a_z b_z, no contraction.
  *
  * Per cell, built into one 64-byte record {kappa_0, 1 / b, a, kappa_d, v_x,
- * v_y, v_z, 0} when the mode is set:
+ * v_y, v_z, n_HI} when the mode is set:
  *   b       = sqrt(2 * (k_B T / m_H + sigma_t * sigma_t))
  *   a       = A_21 * lambda_0 / (4 * pi * b)
  *   kappa_0 = n_HI * (3 lambda_0^3 A_21 / (8 pi sqrt(pi))) / b  (5.90e-14 cm^2
@@ -1729,6 +1729,111 @@ int cmi_gpu_get_lya_counters(cmi_gpu_engine *engine, uint64_t *counters /*[7]*/)
  * (Cantalupo et al. 2008), n_e = n_H ((1 - x_H0) + A_He (1 - x_He0)) as in
  * cmi_gpu_free_free_coefficients, n_p = n_H (1 - x_H0); 0 where T <= 0. */
 int cmi_gpu_lyman_alpha_emissivity(cmi_gpu_engine *engine, double *out);
+
+/* ---------------------------------------- Lyman alpha radiation field -- */
+/* What a Lyman-alpha run leaves in the gas, cell by cell: the energy density
+ * of the line, the scattering rate per atom (which sets the 21-cm spin
+ * temperature where collisions do not: Wouthuysen-Field coupling), and the
+ * momentum it deposits (the Lyman-alpha radiation pressure). All are sums over
+ * the crossings and events of the walk of "Lyman alpha"; the walk, its random
+ * numbers, the image, the cube and the counters are the same with the field on
+ * or off. No counterpart in the reference.
+ * tests/support/lya_field_reference.c restates everything below in plain C.
+ *
+ * One row of eight doubles per cell, [ncell][8], 64 bytes and 64-byte aligned:
+ *   {L, S_H, S_d, G_x, G_y, G_z, N_H, N_d}.
+ * In a cell, for a packet of shift q flying along k: kappa_H = kappa_0 H(a, x),
+ * kappa_d as in the record, kappa_p = kappa_H + kappa_d * (1 - omega * g) with
+ * the albedo omega and the asymmetry g of the dust as set (the share 1 - omega g
+ * of its momentum that a packet leaves with the dust on average; all of it
+ * with hydrogen, whose re-emission is isotropic).
+ *
+ * The first flight - the march from the emission point along k at q that finds
+ * tau_max - is tallied as an expected value with weight 1: for the crossing of
+ * length ds that begins at the depth tau_in (the sum of ds kappa before it)
+ * and has dtau = ds * kappa,
+ *   l = (ds * exp(-tau_in)) * E(dtau),  E(t) = -expm1(-t) / t, E(0) = 1
+ * is the length that the light still in flight covers in the cell (kappa = 0
+ * gives l = ds exactly). L += l, S_H += l kappa_H, S_d += l kappa_d, G += (l
+ * kappa_p) k. The forced first walk that follows the same path adds nothing to
+ * these five. Why an expected value: the forced walk carries only the share 1 -
+ * exp(-tau_max) that interacts, on a path drawn from the truncated exponential;
+ * the light that leaves unscattered fills the cells too, and one deterministic
+ * sum over the crossings the march makes anyway counts both without a second
+ * march and without noise.
+ *
+ * Every later walk - after an event, with the weight W = forced weight *
+ * albedos as it stands after the event - is tallied by its track length: for
+ * each crossing, with ds the length actually flown in the cell (the backed-off
+ * length in the last one), L += W ds, S_H += W ds kappa_H, S_d += W ds kappa_d,
+ * G += (W ds kappa_p) k.
+ *
+ * Collision estimators: a hydrogen event adds the incoming weight W to N_H of
+ * the event's cell, a dust event the weight before the albedo is applied to
+ * N_d. In expectation N_H = S_H and N_d = S_d cell by cell, with or without
+ * core skipping: the check of the weights and of the first-flight estimator
+ * that every run carries.
+ *
+ * The peel-off marches tally nothing. A capped packet keeps what it tallied;
+ * the downloads then refuse, as for the image.
+ *
+ * Physical units, for a run of N packets from a source of L_total W, s =
+ * L_total / N and the cell volume V: the energy density s L / (c V) J m^-3; the
+ * scattering rate per atom P_alpha = s S_H / (h nu_0 n_HI V) s^-1; the force
+ * density s G / (c V) N m^-3. With core skipping (x_crit > 0) S_H and N_H
+ * leave out the skipped scatterings: P_alpha is then too small. L and G are as
+ * good as the skipping itself: unbiased while a skipped scattering does not
+ * move the packet, which holds in the core proper and not for an x_crit beyond
+ * it (the force on a static sphere of 10 K gas, a = 0.015,
+ * comes out halved with x_crit = 3). */
+
+/* Switches the radiation field of the Lyman-alpha mode on (enable != 0:
+ * allocates the rows if need be and zeroes them) or off (frees them). While it
+ * is on, cmi_gpu_lya_shoot launches the kernel instantiation that tallies.
+ * CMI_GPU_ESTATE if the Lyman-alpha mode is not set; CMI_GPU_ENOMEM if the rows
+ * do not fit. cmi_gpu_set_lyman_alpha, called anew, switches the field off;
+ * cmi_gpu_reset_lya zeroes the rows with the image. Synchronous. */
+int cmi_gpu_set_lya_field(cmi_gpu_engine *engine, int32_t enable);
+
+/* The raw tallies, rows host [ncell][8]. CMI_GPU_ESTATE if the mode or the
+ * field is off, if the mode is stale, or after a capped packet. Synchronous. */
+int cmi_gpu_download_lya_field(cmi_gpu_engine *engine,
+                               double *rows /* [ncell][8] */);
+
+/* The scattering rate per atom and the 21-cm spin temperature it implies,
+ * from the tallies, the records and the cells as they are at the call:
+ *   P_alpha = s S_H / (h nu_0 n_HI V), 0 where n_HI = 0; s =
+ *             luminosity_per_packet (W), n_HI that of the records
+ *   x_alpha = 4 P_alpha T_* / (27 A_10 T_gamma), T_* = h nu_10 / k_B = 0.0682 K
+ *             with nu_10 = 1420405751.768 Hz and A_10 = 2.8843e-15 s^-1 of "H I
+ *             21-cm cubes", T_gamma = background_temperature
+ *   x_c     = (C_10 / A_10) (T_* / T_gamma) with collisions != 0, else 0;
+ *             C_10 = n_HI kappa_HH(T) + n_e kappa_eH(T), T the cells'
+ *             temperature, n_e = n_H ((1 - x_H0) + A_He (1 - x_He0)) as in
+ *             cmi_gpu_free_free_coefficients;
+ *             kappa_HH = 3.1e-11 T^0.357 exp(-32 / T) cm^3 s^-1 (Kuhlen, Madau
+ *             & Montgomery 2006, ApJ 637, L1);
+ *             log10(kappa_eH / cm^3 s^-1) = -9.607 + 0.5 log10 T exp(-(log10
+ *             T)^4.5 / 1800) for 1 K <= T <= 1e4 K, held at its 1e4 K value
+ *             above and at its 1 K value below (Liszt 2001, A&A 371, 698)
+ *   T_s     = (1 + x) / (1 / T_gamma + x / T_k), x = x_alpha + x_c, which is
+ *             1 / T_s = (1 / T_gamma + x / T_k) / (1 + x): the colour
+ *             temperature of the Lyman-alpha field is taken as the kinetic
+ *             temperature T_k = T (true after the ~1e3 scatterings that bring
+ *             the spectrum near line centre into equilibrium with the gas;
+ *             Field 1959). A cell with T_k <= 0 gets T_s = T_gamma.
+ * P_alpha host [ncell] or NULL, T_s host [ncell], the argument
+ * spin_temperature of cmi_gpu_render_hi_cube and its sky variants with
+ * spin_mode 2. CMI_GPU_EINVAL for a scale or a background that is not positive
+ * and finite. CMI_GPU_ESTATE as for the download, and if the mode was set with
+ * x_crit > 0: the skipped core scatterings would make P_alpha too small, and
+ * it is not handed out silently. Synchronous. */
+int cmi_gpu_lya_spin_temperature(cmi_gpu_engine *engine,
+                                 double luminosity_per_packet,
+                                 double background_temperature,
+                                 int32_t collisions,
+                                 double *P_alpha /* [ncell] or NULL */,
+                                 double *T_s /* [ncell] */);
 
 /* --------------------------------------------------- continuum images -- */
 /* The formal solution of the transfer equation with an absorption coefficient

@@ -10,6 +10,12 @@ instructions and of scratch / buffer memory instructions (spill code and
 stack traffic).
 
     python tools/compare_device_asm.py parent/engine.s csrc/engine.s
+
+A function that only changed its name - a template parameter it gained, whose
+new instantiations are reported as new functions - is still the parent's if
+its instructions are: `--rename PARENT_SYMBOL=NEW_SYMBOL` (any number of
+them) renames the symbol in the parent's listing, in the calls to it too,
+before the comparison.
 """
 import re
 import sys
@@ -37,8 +43,30 @@ def functions(path):
     return out
 
 
+def renamed(funcs, pairs):
+    """`funcs` with the symbols of `pairs` renamed, longest first (a symbol
+    may be the beginning of another)"""
+    pairs = sorted(pairs, key=lambda p: -len(p[0]))
+
+    def sub(text):
+        for old, new in pairs:
+            text = re.sub(r"(?<![\w$])" + re.escape(old) + r"(?![\w$])", new,
+                          text)
+        return text
+    return {sub(k): [sub(s) for s in v] for k, v in funcs.items()}
+
+
 def main():
-    parent, new = functions(sys.argv[1]), functions(sys.argv[2])
+    args = sys.argv[1:]
+    pairs = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        pairs.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    parent, new = functions(args[0]), functions(args[1])
+    if pairs:
+        parent = renamed(parent, pairs)
+        print("renamed in the parent:", ["%s -> %s" % p for p in pairs])
     same = [k for k in parent if new.get(k) == parent[k]]
     print("%d of %d parent functions identical" % (len(same), len(parent)))
     print("differing:", [k for k in parent if k in new and new[k] != parent[k]])
