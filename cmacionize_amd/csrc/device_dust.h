@@ -615,14 +615,14 @@ __device__ __noinline__ void dust_scatter(const DustDev &d, PacketRng &rng,
   p.par[4] = cph;
 }
 
-/* DustScattering::scatter_towards, src/DustScattering.cpp:325-518: the
- * photon's Stokes vector after a scattering towards the observer (direction
- * d.obs_dir, angles d.view); the photon takes the observer's direction.
- * Returns the HG phase function per steradian. */
-__device__ __noinline__ double dust_scatter_towards(const DustDev &d,
-                                                    DustPhoton &p) {
-  const double mu = d.obs_dir[0] * p.dir[0] + d.obs_dir[1] * p.dir[1] +
-                    d.obs_dir[2] * p.dir[2];
+/* The Stokes update of DustScattering::scatter_towards,
+ * src/DustScattering.cpp:325-500, for an observer whose direction has the
+ * polar angle of sine view[0] and cosine view[1] and the azimuth view[2], at
+ * the cosine mu of the scattering angle: the body that
+ * dust_scatter_towards and dust_scatter_towards_point share. */
+__device__ __forceinline__ void dust_scatter_stokes(const DustDev &d,
+                                                    const double *view,
+                                                    double mu, DustPhoton &p) {
   if (fabs(mu) == 1.) {
     if (mu == -1.)
       p.stokes[2] = -p.stokes[2];
@@ -630,12 +630,12 @@ __device__ __noinline__ double dust_scatter_towards(const DustDev &d,
     const DustPhase m = dust_phase(d, mu, true);
     const double smu = sqrt(-(mu * mu - 1.));
     const double st0 = p.par[0], ct0 = p.par[1];
-    const double so = d.view[0], co = d.view[1];
+    const double so = view[0], co = view[1];
     double r1;
     if (st0 == 0.) {
       r1 = M_PI;
     } else {
-      const double y = sin(p.par[2] - d.view[2] - M_PI) * so / smu;
+      const double y = sin(p.par[2] - view[2] - M_PI) * so / smu;
       const double x = (co - ct0 * mu) / (st0 * smu);
       r1 = atan2(y, x) + M_PI;
     }
@@ -656,6 +656,17 @@ __device__ __noinline__ double dust_scatter_towards(const DustDev &d,
     dust_double_angle(c2, s2, cc2, ss2);
     dust_apply_phase(m, cc1, ss1, cc2, ss2, mirror, p.stokes);
   }
+}
+
+/* DustScattering::scatter_towards, src/DustScattering.cpp:325-518: the
+ * photon's Stokes vector after a scattering towards the observer (direction
+ * d.obs_dir, angles d.view); the photon takes the observer's direction.
+ * Returns the HG phase function per steradian. */
+__device__ __noinline__ double dust_scatter_towards(const DustDev &d,
+                                                    DustPhoton &p) {
+  const double mu = d.obs_dir[0] * p.dir[0] + d.obs_dir[1] * p.dir[1] +
+                    d.obs_dir[2] * p.dir[2];
+  dust_scatter_stokes(d, d.view, mu, p);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     p.dir[a] = d.obs_dir[a];
@@ -701,11 +712,8 @@ dust_integrate_to(const GridDev &g, const double2 *__restrict__ opacity,
 /* dust_scatter_towards for an observer in the direction k (a unit vector)
  * from the photon: the same operations with the observer's angles computed
  * from k (the header comment lists them); the photon takes k, 1 / k and
- * those angles. Returns the HG phase function per steradian.
- * This body is a copy of dust_scatter_towards' (which is left alone so that
- * its code stays the parallel camera's to the instruction): a change to
- * either must be made to both, and to scatter_towards and
- * scatter_towards_point of the CPU restatements. */
+ * those angles. Returns the HG phase function per steradian. (The CPU
+ * restatements have scatter_towards and scatter_towards_point.) */
 __device__ __noinline__ double
 dust_scatter_towards_point(const DustDev &d, DustPhoton &p,
                            const double k[3]) {
@@ -714,38 +722,7 @@ dust_scatter_towards_point(const DustDev &d, DustPhoton &p,
   const double pho = so == 0. ? 0. : atan2(k[1], k[0]);
   const double view[5] = {so, co, pho, sin(pho), cos(pho)};
   const double mu = k[0] * p.dir[0] + k[1] * p.dir[1] + k[2] * p.dir[2];
-  if (fabs(mu) == 1.) {
-    if (mu == -1.)
-      p.stokes[2] = -p.stokes[2];
-  } else {
-    const DustPhase m = dust_phase(d, mu, true);
-    const double smu = sqrt(-(mu * mu - 1.));
-    const double st0 = p.par[0], ct0 = p.par[1];
-    double r1;
-    if (st0 == 0.) {
-      r1 = M_PI;
-    } else {
-      const double y = sin(p.par[2] - pho - M_PI) * so / smu;
-      const double x = (co - ct0 * mu) / (st0 * smu);
-      r1 = atan2(y, x) + M_PI;
-    }
-    const bool mirror = r1 > M_PI;
-    const double a1 = mirror ? 2. * M_PI - r1 : r1;
-    const double c1 = cos(a1), s1 = sin(a1);
-    double s2, c2;
-    if (fabs(co) < 1.) {
-      s2 = s1 * st0 / so;
-      const double den = so * smu;
-      c2 = ct0 / den - co * mu / den;
-    } else {
-      s2 = 0.;
-      c2 = co >= 1. ? -1. : 1.;
-    }
-    double cc1, ss1, cc2, ss2;
-    dust_double_angle(c1, s1, cc1, ss1);
-    dust_double_angle(c2, s2, cc2, ss2);
-    dust_apply_phase(m, cc1, ss1, cc2, ss2, mirror, p.stokes);
-  }
+  dust_scatter_stokes(d, view, mu, p);
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     p.dir[a] = k[a];

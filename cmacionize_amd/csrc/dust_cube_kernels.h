@@ -157,20 +157,7 @@ dust_cube_put(const DustCubeDev &cube, double *image, int view,
               double weight, double u, double b, DustEvents &ev,
               unsigned long long &natomics) {
   if (TRACE) {
-    if (ev.n < ev.max_events) {
-      double *r = ev.rows + 10 * ev.n;
-      r[0] = pos[0];
-      r[1] = pos[1];
-      r[2] = pos[2];
-      r[3] = stokes[0];
-      r[4] = stokes[1];
-      r[5] = stokes[2];
-      r[6] = stokes[3];
-      r[7] = weight;
-      r[8] = u;
-      r[9] = b;
-    }
-    ++ev.n;
+    dust_trace_row(ev, pos, stokes, weight, u, b);
     return;
   }
   if (pixel < 0)

@@ -42,6 +42,29 @@ struct DustEvents {
   int n;
 };
 
+/* the next row of a trace: {x, y, z, I, Q, U, V, weight} and what the caller
+ * appends (`more`: the cube run's u and b); beyond max_events the event is
+ * counted and no row is written */
+template <class... MORE>
+__device__ __forceinline__ void
+dust_trace_row(DustEvents &ev, const double pos[3], const double stokes[4],
+               double weight, MORE... more) {
+  if (ev.n < ev.max_events) {
+    double *r = ev.rows + (int)(8 + sizeof...(MORE)) * ev.n;
+    r[0] = pos[0];
+    r[1] = pos[1];
+    r[2] = pos[2];
+    r[3] = stokes[0];
+    r[4] = stokes[1];
+    r[5] = stokes[2];
+    r[6] = stokes[3];
+    r[7] = weight;
+    [[maybe_unused]] int j = 8;
+    ((r[j++] = more), ...);
+  }
+  ++ev.n;
+}
+
 template <bool TRACE>
 __device__ __forceinline__ void dust_add(const DustDev &d, const double pos[3],
                                          double wi, double wq, double wu,
@@ -49,18 +72,7 @@ __device__ __forceinline__ void dust_add(const DustDev &d, const double pos[3],
                                          DustEvents &ev,
                                          unsigned long long &natomics) {
   if (TRACE) {
-    if (ev.n < ev.max_events) {
-      double *r = ev.rows + 8 * ev.n;
-      r[0] = pos[0];
-      r[1] = pos[1];
-      r[2] = pos[2];
-      r[3] = stokes[0];
-      r[4] = stokes[1];
-      r[5] = stokes[2];
-      r[6] = stokes[3];
-      r[7] = weight;
-    }
-    ++ev.n;
+    dust_trace_row(ev, pos, stokes, weight);
     return;
   }
   const int64_t pixel = dust_pixel(d, pos);
@@ -91,18 +103,7 @@ dust_sky_add(const SkyCameraDev &cam, const double pos[3], int64_t pixel,
              double wi, double wq, double wu, const double stokes[4],
              double weight, DustEvents &ev, DustCountersDev &c) {
   if (TRACE) {
-    if (ev.n < ev.max_events) {
-      double *r = ev.rows + 8 * ev.n;
-      r[0] = pos[0];
-      r[1] = pos[1];
-      r[2] = pos[2];
-      r[3] = stokes[0];
-      r[4] = stokes[1];
-      r[5] = stokes[2];
-      r[6] = stokes[3];
-      r[7] = weight;
-    }
-    ++ev.n;
+    dust_trace_row(ev, pos, stokes, weight);
     return;
   }
   if (pixel < 0) {

@@ -28,6 +28,9 @@ struct RenderArena {
   static constexpr int MAX_BUFFERS = 16;
   void *owned[MAX_BUFFERS];
   int nowned = 0;
+  /* an alloc failed for want of device memory: the callers that have a
+   * message of their own for that (CMI_GPU_ENOMEM) ask here */
+  bool out_of_memory = false;
   RenderArena() = default;
   RenderArena(const RenderArena &) = delete;
   RenderArena &operator=(const RenderArena &) = delete;
@@ -40,11 +43,19 @@ struct RenderArena {
       return fail(CMI_GPU_ESTATE, "a render call asked for more than %d "
                   "device buffers", MAX_BUFFERS);
     void *fresh = nullptr;
-    HIP_TRY(hipMalloc(&fresh, sizeof(T) * n));
+    const hipError_t err = hipMalloc(&fresh, sizeof(T) * n);
+    if (err == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      out_of_memory = true;
+    }
+    HIP_TRY(err);
     owned[nowned++] = fresh;
     p = static_cast<T *>(fresh);
     return CMI_GPU_OK;
   }
+  /* the caller has taken the buffers over (a setter that built its new state
+   * aside and adopts it): nothing is freed */
+  void release() { nowned = 0; }
   /* a device copy of the host array src[n] */
   int upload(double *&p, const double *src, size_t n) {
     CMI_TRY(alloc(p, n));

@@ -1346,34 +1346,90 @@ class GpuEngine:
         line, hence its noise: (nlines, nviews, 3, nx, ny)."""
         names = list(EMISSION_LINES if lines is None else lines)
         self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
-        if np.ndim(theta) or np.ndim(phi):
-            nviews = len(_f64(theta).reshape(-1))
-            a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
-            s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
-            pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
+        several, scaled = self._scattered_parallel_cameras(
+            theta, phi, nx, ny, anchor, sides, npackets)
+        images, _ = self._scattered_line_runs(names, npackets, seed, scaled)
+        return images if several else images[:, 0]
+
+    # what the four render_scattered_line_* calls share ----------------------
+    def _scattered_parallel_cameras(self, theta, phi, nx, ny, anchor, sides,
+                                    npackets):
+        """Sets the parallel camera, or the several with sequences for theta
+        and phi. Returns `several` and scaled(raw, total): the stack raw
+        (nviews, 3, ..., nx, ny) of a run of total luminosity `total` times
+        L_total / (npackets A_pixel) of its view."""
+        several = bool(np.ndim(theta) or np.ndim(phi))
+        nviews = len(_f64(theta).reshape(-1)) if several else 1
+        a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
+        s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
+        pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
+        if several:
             self.set_ccd_images(theta, phi, nx, ny, a, s)
-            out = np.zeros((len(names), nviews, 3, int(nx), int(ny)))
+        else:
+            self.set_ccd_image(theta, phi, nx, ny, a[0], s[0])
+
+        def scaled(raw, total):
+            scale = total / (int(npackets) * pixel_area)
+            return raw * scale.reshape((-1,) + (1,) * (raw.ndim - 1))
+        return several, scaled
+
+    def _scattered_point_cameras(self, origin, nlon, nlat, exclusion_radius,
+                                 lon_range, lat_range, frame_pole,
+                                 frame_zero_longitude, direct_light,
+                                 npackets):
+        """Sets the sky camera, or the several with origin of shape (nviews,
+        3): the frames, the cameras, the pixels' solid angles. Returns
+        `several`, the number of observers and scaled(raw, total): the stack
+        raw (nviews, 3, ..., nlon, nlat) times L_total / (npackets
+        omega_ij)."""
+        several = np.ndim(origin) == 2
+        o = _f64(origin).reshape(-1, 3)
+        nviews = len(o)
+        poles = np.broadcast_to(_f64(frame_pole), (nviews, 3))
+        zeros = np.broadcast_to(_f64(frame_zero_longitude), (nviews, 3))
+        frames = np.array([sky_frame(p, z) for p, z in zip(poles, zeros)])
+        if several:
+            self.set_sky_cameras(o, nlon, nlat, exclusion_radius, lon_range,
+                                 lat_range, frames, direct_light)
+        else:
+            self.set_sky_camera(o[0], nlon, nlat, exclusion_radius, lon_range,
+                                lat_range, frames[0], direct_light)
+        omega = np.array([
+            sky_map_directions(nlon, nlat, lon_range, lat_range, f)[1]
+            for f in frames])
+
+        def scaled(raw, total):
+            return raw * (total / int(npackets)) / omega.reshape(
+                (nviews,) + (1,) * (raw.ndim - 3) + (int(nlon), int(nlat)))
+        return several, nviews, scaled
+
+    def _scattered_line_runs(self, names, npackets, seed, scaled, cube=None):
+        """One run of npackets packets per line into the cameras as set: the
+        scaled images (nlines, nviews, 3, nx, ny) and, with cube = (nchan,
+        vmin, vmax, sigma_turb, observer_velocities), the scaled cubes
+        (nlines, nviews, 3, nchan, nx, ny) of cube mode, which is set anew
+        for every line and left off."""
+        shape = (len(names), self.nviews, 3)
+        images = np.zeros(shape + self.image_shape)
+        cubes = None if cube is None else \
+            np.zeros(shape + (int(cube[0]),) + self.image_shape)
+        try:
             for k, name in enumerate(names):
                 self.set_cell_source_line(name)
-                self.reset_image()
+                if cube is None:
+                    self.reset_image()
+                else:
+                    self.set_scattered_cube(*cube[:4],
+                                            observer_velocities=cube[4])
                 self.dust_shoot(seed, 0, int(npackets))
                 total = self.get_cell_source(tables=False)
-                out[k] = self.download_images() * \
-                    (total / (int(npackets) * pixel_area))[:, None, None, None]
-            return out
-        a = _f64(anchor).reshape(2)
-        s = _f64(sides).reshape(2)
-        pixel_area = s[0] * s[1] / (int(nx) * int(ny))
-        self.set_ccd_image(theta, phi, nx, ny, a, s)
-        out = np.zeros((len(names), 3, int(nx), int(ny)))
-        for k, name in enumerate(names):
-            self.set_cell_source_line(name)
-            self.reset_image()
-            self.dust_shoot(seed, 0, int(npackets))
-            total = self.get_cell_source(tables=False)
-            out[k] = self.download_image() * \
-                (total / (int(npackets) * pixel_area))
-        return out
+                images[k] = scaled(self.download_images(), total)
+                if cube is not None:
+                    cubes[k] = scaled(self.download_cubes(), total)
+        finally:
+            if cube is not None:
+                self.set_scattered_cube(0, 0., 1.)
+        return images, cubes
 
     def render_field_images(self, fields, theta, phi, nx, ny, anchor, sides,
                             supersample=1, extinction=None):
@@ -1932,39 +1988,11 @@ class GpuEngine:
         names = list(EMISSION_LINES if lines is None else lines)
         self.set_dust_scattering_per_hydrogen(g, p_l, albedo,
                                               dust_cross_section)
-        if np.ndim(origin) == 2:
-            o = _f64(origin).reshape(-1, 3)
-            nviews = len(o)
-            poles = np.broadcast_to(_f64(frame_pole), (nviews, 3))
-            zeros = np.broadcast_to(_f64(frame_zero_longitude), (nviews, 3))
-            frames = np.array([sky_frame(p, z) for p, z in zip(poles, zeros)])
-            self.set_sky_cameras(o, nlon, nlat, exclusion_radius, lon_range,
-                                 lat_range, frames, direct_light)
-            omega = np.array([
-                sky_map_directions(nlon, nlat, lon_range, lat_range, f)[1]
-                for f in frames]).reshape(nviews, 1, int(nlon), int(nlat))
-            out = np.zeros((len(names), nviews, 3, int(nlon), int(nlat)))
-            for k, name in enumerate(names):
-                self.set_cell_source_line(name)
-                self.reset_image()
-                self.dust_shoot(seed, 0, int(npackets))
-                total = self.get_cell_source(tables=False)
-                out[k] = self.download_images() * (total / int(npackets)) \
-                    / omega
-            return out
-        frame = sky_frame(frame_pole, frame_zero_longitude)
-        self.set_sky_camera(origin, nlon, nlat, exclusion_radius, lon_range,
-                            lat_range, frame, direct_light)
-        _, omega = sky_map_directions(nlon, nlat, lon_range, lat_range, frame)
-        omega = omega.reshape(int(nlon), int(nlat))
-        out = np.zeros((len(names), 3, int(nlon), int(nlat)))
-        for k, name in enumerate(names):
-            self.set_cell_source_line(name)
-            self.reset_image()
-            self.dust_shoot(seed, 0, int(npackets))
-            total = self.get_cell_source(tables=False)
-            out[k] = self.download_image() * (total / int(npackets)) / omega
-        return out
+        several, _, scaled = self._scattered_point_cameras(
+            origin, nlon, nlat, exclusion_radius, lon_range, lat_range,
+            frame_pole, frame_zero_longitude, direct_light, npackets)
+        images, _ = self._scattered_line_runs(names, npackets, seed, scaled)
+        return images if several else images[:, 0]
 
     # scattered-light line cubes ---------------------------------------------
     def set_scattered_cube(self, nchan, vmin, vmax, sigma_turb=0.,
@@ -2013,31 +2041,11 @@ class GpuEngine:
         CCD image, dust and dust source, and leaves cube mode off."""
         names = list(lines)
         self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
-        several = bool(np.ndim(theta) or np.ndim(phi))
-        nviews = len(_f64(theta).reshape(-1)) if several else 1
-        a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
-        s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
-        pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
-        if several:
-            self.set_ccd_images(theta, phi, nx, ny, a, s)
-        else:
-            self.set_ccd_image(theta, phi, nx, ny, a[0], s[0])
-        images = np.zeros((len(names), nviews, 3, int(nx), int(ny)))
-        cubes = np.zeros((len(names), nviews, 3, int(nchan), int(nx),
-                          int(ny)))
-        try:
-            for k, name in enumerate(names):
-                self.set_cell_source_line(name)
-                self.set_scattered_cube(nchan, vmin, vmax, sigma_turb)
-                self.dust_shoot(seed, 0, int(npackets))
-                total = self.get_cell_source(tables=False)
-                scale = total / (int(npackets) * pixel_area)
-                images[k] = self.download_images() * \
-                    scale[:, None, None, None]
-                cubes[k] = self.download_cubes() * \
-                    scale[:, None, None, None, None]
-        finally:
-            self.set_scattered_cube(0, 0., 1.)
+        several, scaled = self._scattered_parallel_cameras(
+            theta, phi, nx, ny, anchor, sides, npackets)
+        images, cubes = self._scattered_line_runs(
+            names, npackets, seed, scaled,
+            cube=(nchan, vmin, vmax, sigma_turb, None))
         if several:
             return images, cubes
         return images[:, 0], cubes[:, 0]
@@ -2060,39 +2068,14 @@ class GpuEngine:
         names = list(lines)
         self.set_dust_scattering_per_hydrogen(g, p_l, albedo,
                                               dust_cross_section)
-        several = np.ndim(origin) == 2
-        o = _f64(origin).reshape(-1, 3)
-        nviews = len(o)
-        poles = np.broadcast_to(_f64(frame_pole), (nviews, 3))
-        zeros = np.broadcast_to(_f64(frame_zero_longitude), (nviews, 3))
-        frames = np.array([sky_frame(p, z) for p, z in zip(poles, zeros)])
-        if several:
-            self.set_sky_cameras(o, nlon, nlat, exclusion_radius, lon_range,
-                                 lat_range, frames, direct_light)
-        else:
-            self.set_sky_camera(o[0], nlon, nlat, exclusion_radius, lon_range,
-                                lat_range, frames[0], direct_light)
+        several, nviews, scaled = self._scattered_point_cameras(
+            origin, nlon, nlat, exclusion_radius, lon_range, lat_range,
+            frame_pole, frame_zero_longitude, direct_light, npackets)
         vo = None if observer_velocity is None else \
             _f64(np.broadcast_to(_f64(observer_velocity), (nviews, 3)))
-        omega = np.array([
-            sky_map_directions(nlon, nlat, lon_range, lat_range, f)[1]
-            for f in frames]).reshape(nviews, 1, int(nlon), int(nlat))
-        images = np.zeros((len(names), nviews, 3, int(nlon), int(nlat)))
-        cubes = np.zeros((len(names), nviews, 3, int(nchan), int(nlon),
-                          int(nlat)))
-        try:
-            for k, name in enumerate(names):
-                self.set_cell_source_line(name)
-                self.set_scattered_cube(nchan, vmin, vmax, sigma_turb,
-                                        observer_velocities=vo)
-                self.dust_shoot(seed, 0, int(npackets))
-                total = self.get_cell_source(tables=False)
-                images[k] = self.download_images() * \
-                    (total / int(npackets)) / omega
-                cubes[k] = self.download_cubes() * \
-                    (total / int(npackets)) / omega[:, :, None]
-        finally:
-            self.set_scattered_cube(0, 0., 1.)
+        images, cubes = self._scattered_line_runs(
+            names, npackets, seed, scaled,
+            cube=(nchan, vmin, vmax, sigma_turb, vo))
         if several:
             return images, cubes
         return images[:, 0], cubes[:, 0]
@@ -2246,15 +2229,8 @@ class GpuEngine:
         else:
             sigma, albedo, g, p_l = dust
             self.set_dust_scattering_per_hydrogen(g, p_l, albedo, sigma)
-        several = bool(np.ndim(theta) or np.ndim(phi))
-        nviews = len(_f64(theta).reshape(-1)) if several else 1
-        a = _f64(np.broadcast_to(_f64(anchor), (nviews, 2)))
-        s = _f64(np.broadcast_to(_f64(sides), (nviews, 2)))
-        pixel_area = s[:, 0] * s[:, 1] / (int(nx) * int(ny))
-        if several:
-            self.set_ccd_images(theta, phi, nx, ny, a, s)
-        else:
-            self.set_ccd_image(theta, phi, nx, ny, a[0], s[0])
+        several, scaled = self._scattered_parallel_cameras(
+            theta, phi, nx, ny, anchor, sides, npackets)
         self.set_cell_source_field(self.lyman_alpha_emissivity()
                                    if source is None else source)
         try:
@@ -2264,10 +2240,9 @@ class GpuEngine:
                 self.set_lya_field(True)
             self.lya_shoot(seed, 0, int(npackets))
             total = self.get_cell_source(tables=False)
-            scale = total / (int(npackets) * pixel_area)
             images, cubes = self.download_lya()
-            images = images * scale[:, None, None]
-            cubes = cubes * scale[:, None, None, None]
+            images = scaled(images, total)
+            cubes = scaled(cubes, total)
             if field:
                 field = self.lya_radiation_field(npackets, total)
         finally:

@@ -882,7 +882,11 @@ int cmi_gpu_set_dust_scattering_per_hydrogen(cmi_gpu_engine *engine, double g,
 /* replaces: the CCDImage ctor (src/CCDImage.hpp:123-160): view angles theta,
  * phi (radians), resolution nx x ny, image anchor[2] and sides[2] (m). The
  * image is I, Q, U of nx x ny pixels, pixel (ix, iy) at ix * ny + iy
- * (src/CCDImage.hpp:242-270). A new call replaces and clears the image. */
+ * (src/CCDImage.hpp:242-270). A new call replaces and clears the image. The
+ * new image is allocated before anything of the engine changes: a call that
+ * fails - CMI_GPU_EINVAL, or CMI_GPU_ENOMEM if the image does not fit into
+ * the device's memory - leaves the camera selected before, and its image, as
+ * they were. */
 int cmi_gpu_set_ccd_image(cmi_gpu_engine *engine, double theta, double phi,
                           int32_t nx, int32_t ny, const double *anchor,
                           const double *sides);
@@ -1047,7 +1051,10 @@ int cmi_gpu_dust_probe(cmi_gpu_engine *engine, int32_t kind, uint32_t seed,
  * cmi_gpu_render_line_sky_map; nlon, nlat < 1 or nlon nlat > 2^28; an
  * exclusion radius that is negative or not finite, or 0 with the origin in
  * the closed box (the estimator's variance diverges at r -> 0 and an event
- * at r = 0 would add infinity). Synchronous. */
+ * at r = 0 would add infinity). CMI_GPU_ENOMEM if the map does not fit into
+ * the device's memory; like a refused call it leaves the camera selected
+ * before, and its image, as they were (the map is allocated before anything
+ * of the engine changes). Synchronous. */
 int cmi_gpu_set_sky_camera(cmi_gpu_engine *engine, const double origin[3],
                            const double frame[9], double lon_min,
                            double lon_max, double lat_min, double lat_max,

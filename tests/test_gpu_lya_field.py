@@ -189,6 +189,37 @@ def test_three_views_and_field_off(parity):
     assert np.allclose(off_cube, cube, rtol=1e-12, atol=1e-14 * image.max())
 
 
+@pytest.mark.parametrize("views", [None, VIEWS], ids=["one", "three"])
+def test_past_the_first_launch(views):
+    """The field's instantiations through the chunk loop of cmi_gpu_lya_shoot
+    past its first launch of 2^14 packets (N above stays below it): [0, n) in
+    one call against [0, 2^14) and [2^14, n) in two, on an 8^3 grid with
+    16 x 16 images. The counters are equal; rows, images and cubes differ by
+    the order of the atomics."""
+    first = 1 << 14
+    n = first + 100
+    scene, _ = Y.parity_scene(ncell=(8, 8, 8), nx=16, ny=16, tau0=30.)
+    eng = scene.engine(views)
+    eng.set_lya_field()
+    rows, image, cube, c = run(eng, SEED, 0, n)
+    eng.reset_lya()
+    eng.lya_shoot(SEED, 0, first)
+    eng.lya_shoot(SEED, first, n - first)
+    rows2 = rows_of(eng)
+    image2, cube2 = eng.download_lya()
+    c2 = eng.get_lya_counters()
+    eng.close()
+    assert c["npackets"] == n and c["ncapped"] == 0 and c["nhydrogen"] > n
+    assert c2 == c
+    assert rows[:, F.L_].sum() > 0.
+    assert excess(rows2, rows, order_of_the_atomics(rows)) <= 1.
+    for v in range(len(image)):
+        assert image[v].sum() > 0.
+        atol = 1e-14 * image[v].max()
+        assert np.allclose(image2[v], image[v], rtol=1e-12, atol=atol), v
+        assert np.allclose(cube2[v], cube[v], rtol=1e-12, atol=atol), v
+
+
 # ------------------------------------------------------------ identities --
 
 @pytest.mark.parametrize("x_crit", [0., 3.])

@@ -148,6 +148,21 @@ def test_atom_sampler_rows(small):
     assert np.array_equal(np.sign(gpu[keep, 0]) , np.sign(u))
 
 
+def test_probe_rows_past_one_launch(small):
+    """More rows than one launch of cmi_gpu_lya_probe takes (2^14): the rows
+    past it are the rows probed alone, with first_packet moved up by 2^14."""
+    scene, eng = small
+    rng = np.random.default_rng(6)
+    launch = 1 << 14
+    n = launch + 50
+    rows = np.c_[rng.normal(0., 2.5, n), 10. ** rng.uniform(-3.9, -1.8, n)]
+    gpu = eng.lya_probe(Y.SAMPLER, seed=SEED, first_packet=100, rows=rows)
+    alone = eng.lya_probe(Y.SAMPLER, seed=SEED, first_packet=100 + launch,
+                          rows=rows[launch:])
+    assert np.abs(gpu[launch:, 0]).min() > 0.
+    assert np.array_equal(gpu[launch:], alone)
+
+
 def test_traces(parity):
     """the first TRACE_EVENTS events of TRACE_PACKETS packets, row by row; no
     row is left out (test_lyman_alpha_host.py::test_parity_seeds_need_no_
@@ -334,6 +349,35 @@ def test_three_views_against_three_single_cameras():
         steps += c["nsteps"]
     # the walk is shared, the peel-off marches are per view
     assert counters["nsteps"] < steps
+
+
+def test_three_views_past_the_first_launch():
+    """The several-views instantiation through the chunk loop of
+    cmi_gpu_lya_shoot past its first launch of 2^14 packets (test_whole_run
+    crosses it with one view): [0, n) in one call against [0, 2^14) and
+    [2^14, n) in two, on an 8^3 grid with 16 x 16 images. The counters are
+    equal, images and cubes differ by the order of the atomics."""
+    views = [(1.1, 0.6), (0.3, 2.0), (np.pi / 2., 0.)]
+    first = 1 << 14
+    n = first + 100
+    scene, _ = Y.parity_scene(ncell=(8, 8, 8), nx=16, ny=16, tau0=30.)
+    eng = scene.engine(views)
+    eng.lya_shoot(SEED, 0, n)
+    images, cubes = eng.download_lya()
+    c = eng.get_lya_counters()
+    eng.reset_lya()
+    eng.lya_shoot(SEED, 0, first)
+    eng.lya_shoot(SEED, first, n - first)
+    images2, cubes2 = eng.download_lya()
+    c2 = eng.get_lya_counters()
+    eng.close()
+    assert c["npackets"] == n and c["ncapped"] == 0 and c["nhydrogen"] > n
+    assert c2 == c
+    for v in range(3):
+        assert images[v].sum() > 0.
+        atol = 1e-14 * images[v].max()
+        assert np.allclose(images2[v], images[v], rtol=1e-12, atol=atol), v
+        assert np.allclose(cubes2[v], cubes[v], rtol=1e-12, atol=atol), v
 
 
 # --------------------------------------------------------- identities --

@@ -497,6 +497,40 @@ def test_sky_cameras_serve_the_cell_source_only():
     g.close()
 
 
+def test_galaxy_with_views_past_the_first_launch():
+    """The galaxy's several-views instantiation through the chunk loop of
+    cmi_gpu_dust_shoot past its first launch of 2^14 packets (the scenes above
+    cross it with the cell source): [0, n) in one call against [0, 2^14) and
+    [2^14, n) in two. The counters are equal, the images differ by the order
+    of the atomics."""
+    from cmacionize_amd import GpuEngine
+    first = 1 << 14
+    n = first + 100
+    g = GpuEngine((8, 8, 8), (-1., -1., -1.), (2., 2., 2.), (0, 0, 0),
+                  device=0)
+    g.upload_cells(np.ones(512), np.zeros(512), None)
+    g.set_dust_scattering_per_hydrogen(0.4, 0.3, 0.5, 0.3)
+    g.set_continuous_source_spiral_galaxy(0.5, 0.1, 0.2)
+    g.set_ccd_images([0.7, 0.], [0.3, 0.], 16, 16, (-2., -2.), (4., 4.))
+
+    def result():
+        return (g.download_images(), g.get_dust_counters(),
+                [g.get_dust_view_counters(v) for v in range(2)])
+
+    g.dust_shoot(SEED, 0, n)
+    whole, c, views = result()
+    g.reset_image()
+    g.dust_shoot(SEED, 0, first)
+    g.dust_shoot(SEED, first, n - first)
+    parts, cp, viewsp = result()
+    g.close()
+    assert c["npackets"] == n and c["nscatter"] > 0
+    assert cp == c and viewsp == views
+    for v in range(2):
+        assert whole[v][0].sum() > 0.
+        assert _close(parts[v], whole[v]), v
+
+
 # ------------------------------------------------------ 6. end to end --
 
 def _line_engine(model):

@@ -171,6 +171,23 @@ def test_traces(scene):
     assert np.ptp(rows[:, 8]) > 5.0e3 and np.ptp(rows[:, 9]) > 2.0e3
 
 
+def test_traces_past_one_launch(scene):
+    """The cube instantiations of the probe kernel (they serve CUBE_TRACE
+    alone) with more rows than one launch of cmi_gpu_dust_probe takes (2^14):
+    the rows past it are the rows traced alone, with first_packet moved up by
+    2^14."""
+    from cmacionize_amd import engine as E
+    s = scene
+    s.cube(s.moving(9, *AXIS))
+    launch, cap = 1 << 14, 2
+    gpu = s.eng.dust_probe(E.DUST_PROBE_CUBE_TRACE, SEED, 3, launch + 50, None,
+                           cap)
+    alone = s.eng.dust_probe(E.DUST_PROBE_CUBE_TRACE, SEED, 3 + launch, 50,
+                             None, cap)
+    assert gpu[launch:, 0].min() >= 1.
+    assert np.array_equal(gpu[launch:], alone)
+
+
 def test_a_packet_alone_is_the_packet_among_others(scene):
     """the guard of DESIGN.md 4.6 for the new instantiations"""
     from cmacionize_amd import engine as E

@@ -126,6 +126,23 @@ def _peel_rows(model, cam, n):
     return rows, 2 + len(special)
 
 
+def test_probe_rows_past_one_launch(scene):
+    """The point camera's probe instantiation with more rows than one launch
+    of cmi_gpu_dust_probe takes (2^14): the rows past it are the rows probed
+    alone, with first_packet moved up by 2^14."""
+    from cmacionize_amd import engine as E
+    import test_gpu_dust as D
+    model, field, eng = scene
+    CAMERAS["inside"].apply(eng)
+    launch = 1 << 14
+    rows = D._rows(launch + 50, 5, True)
+    gpu = eng.dust_probe(E.DUST_PROBE_SCATTER, SEED, 7, len(rows), rows)
+    alone = eng.dust_probe(E.DUST_PROBE_SCATTER, SEED, 7 + launch, 50,
+                           rows[launch:])
+    assert np.abs(gpu[launch:, 8]).min() > 0.
+    assert np.array_equal(gpu[launch:], alone)
+
+
 @pytest.mark.parametrize("name", list(CAMERAS))
 def test_sky_peel_rows(scene, name):
     """7. One peel-off per row against the restatement."""
