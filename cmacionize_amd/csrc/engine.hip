@@ -17,6 +17,7 @@
 #include "continuum_kernels.h"
 #include "absorbing_cube_kernels.h"
 #include "lyman_alpha_kernels.h"
+#include "absorption_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -276,6 +277,12 @@ struct cmi_gpu_engine {
     int absorbing_cube_expm1_call = CMI_ABSORBING_EXPM1_CALL;
     int absorbing_cube_window_skip = 1;
     int64_t absorbing_cube_launch_rays = 0;
+    /* absorption spectra: slab rows per wave (1, 2 or 4; 0: by the number of
+     * channels, CMI_ABSORPTION_R at most), the upper edge's E
+     * from the neighbouring lane, the two exact skips */
+    int absorption_slab_rows = 0;
+    int absorption_edge_sharing = CMI_ABSORPTION_EDGE_SHARING;
+    int absorption_skips = 1;
   } tune;
 
   /* dusty radiative transfer (dust_kernels.h): the kernels' parameters, the
@@ -1900,6 +1907,16 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.absorbing_cube_window_skip = value != 0;
   else if (k == "absorbing_cube_launch_rays")
     e->tune.absorbing_cube_launch_rays = value < 0 ? 0 : value;
+  else if (k == "absorption_slab_rows") {
+    if (value != 0 && value != 1 && value != 2 && value != 4)
+      return fail(CMI_GPU_EINVAL, "set_tuning: absorption_slab_rows is 1, 2 "
+                  "or 4, or 0 for the default (%lld asked for)",
+                  (long long)value);
+    e->tune.absorption_slab_rows = (int)value;
+  } else if (k == "absorption_edge_sharing")
+    e->tune.absorption_edge_sharing = value != 0;
+  else if (k == "absorption_skips")
+    e->tune.absorption_skips = value != 0;
   else
     return fail(CMI_GPU_EINVAL, "set_tuning: unknown key '%s'", key);
   return CMI_GPU_OK;

@@ -206,13 +206,20 @@ __global__ void __launch_bounds__(256) lya_record_kernel(const LyaRecordArgs a) 
     atomicAdd(a.ninvalid, bad);
 }
 
-/* H(a, x) from x^2: the approximation of the contract (Tasitsiomi 2006) */
-__device__ __forceinline__ double lya_voigt(double a, double x2) {
+/* the wing term Q of H(a, x) = sqrt(pi) Q + exp(-x^2) from x^2 (Tasitsiomi
+ * 2006); the absorption spectra (absorption_kernels.h) use it too */
+__device__ __forceinline__ double lya_voigt_wing(double a, double x2) {
   const double z = (x2 - 0.855) / (x2 + 3.42);
   double Q = 0.;
   if (z > 0.)
     Q = (1. + 21. / x2) * a / (M_PI * (x2 + 1.)) *
         (z * (0.1117 + z * (4.421 + z * (-9.207 + 5.674 * z))));
+  return Q;
+}
+
+/* H(a, x) from x^2: the approximation of the contract (Tasitsiomi 2006) */
+__device__ __forceinline__ double lya_voigt(double a, double x2) {
+  const double Q = lya_voigt_wing(a, x2);
   const double core = (x2 < CMI_LYA_EXP_CUT) ? exp(-x2) : 0.;
   return sqrt(M_PI) * Q + core;
 }

@@ -2257,4 +2257,362 @@ int cmi_gpu_absorbing_cube_probe(
   return CMI_GPU_OK;
 }
 
+/* ---------------------------------------------- absorption spectra -- */
+
+extern "C++" {
+namespace {
+/* The lines of an absorption call: K constants S and g, and the densities and
+ * widths either of the caller (n, b: host [K][ncell]) or built from the cells
+ * (ions, weights, sigma_turb). begin() checks, uploads and writes the records
+ * {n, b}[K][ncell] and {w, 0}[ncell]. */
+struct AbsorptionInput {
+  int32_t nlines = 0;
+  const double *S = nullptr, *g = nullptr;
+  const double *n = nullptr, *b = nullptr, *velocity = nullptr;
+  const int32_t *ions = nullptr;
+  const double *weights = nullptr;
+  double sigma_turb = 0.;
+  bool from_cells = false;
+  double v_obs[3] = {0., 0., 0.};
+  double2 *records = nullptr;
+  double *velocity_records = nullptr, *dS = nullptr, *dg = nullptr;
+
+  int check(const cmi_gpu_engine *e, const char *what) const;
+  int begin(cmi_gpu_engine *e, const char *what, RenderArena &arena);
+};
+
+int AbsorptionInput::check(const cmi_gpu_engine *e, const char *what) const {
+  if (nlines < 1 || nlines > CMI_ABSORPTION_MAX_LINES)
+    return fail(CMI_GPU_EINVAL, "%s: between 1 and %d lines (%d asked for)",
+                what, CMI_ABSORPTION_MAX_LINES, (int)nlines);
+  if (!S || !g)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  for (int32_t l = 0; l < nlines; ++l) {
+    if (!(S[l] >= 0.) || !std::isfinite(S[l]))
+      return fail(CMI_GPU_EINVAL, "%s: the integrated cross section of line "
+                  "%d is negative or not finite", what, (int)l);
+    if (!(g[l] >= 0.) || !std::isfinite(g[l]))
+      return fail(CMI_GPU_EINVAL, "%s: the damping width of line %d is "
+                  "negative or not finite", what, (int)l);
+  }
+  if (from_cells) {
+    if (!ions || !weights)
+      return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+    for (int32_t l = 0; l < nlines; ++l) {
+      if (ions[l] < 0 || ions[l] >= CMI_NION)
+        return fail(CMI_GPU_EINVAL, "%s: no ion %d", what, (int)ions[l]);
+      if (!(weights[l] > 0.) || !std::isfinite(weights[l]))
+        return fail(CMI_GPU_EINVAL, "%s: the atomic weight of line %d must be "
+                    "positive and finite", what, (int)l);
+    }
+    CMI_TRY(check_sigma_turb(what, sigma_turb));
+    CMI_TRY(check_have_cells(e, what));
+  } else if (!n || !b) {
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  }
+  return CMI_GPU_OK;
+}
+
+int AbsorptionInput::begin(cmi_gpu_engine *e, const char *what,
+                           RenderArena &arena) {
+  const size_t ncell = (size_t)e->ncell;
+  const int64_t count = (int64_t)nlines * e->ncell;
+  const double *dvelocity = nullptr;
+  CMI_TRY(arena.upload(dS, S, (size_t)nlines));
+  CMI_TRY(arena.upload(dg, g, (size_t)nlines));
+  CMI_TRY(arena.alloc(records, (size_t)count));
+  if (from_cells) {
+    CellsDev *cells;
+    CMI_TRY(cells_settled(e, cells));
+    AbsorptionIonRecordArgs r;
+    r.cells = *cells;
+    r.ncell = e->ncell;
+    r.nlines = nlines;
+    for (int32_t l = 0; l < nlines; ++l) {
+      const int el = cmi_absorption_ion_element[ions[l]];
+      r.ion[l] = ions[l];
+      r.abundance[l] = el < 0 ? 1. : e->model.abundance[el];
+      r.weight[l] = weights[l];
+    }
+    r.sigma_turb = sigma_turb;
+    r.records = records;
+    absorption_ion_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256, 0,
+                                   e->stream>>>(r);
+    HIP_TRY(hipGetLastError());
+    dvelocity = e->cell_velocities;
+  } else {
+    double *dn = nullptr, *db = nullptr, *dvel = nullptr;
+    if (velocity) {
+      CMI_TRY(arena.upload(dvel, velocity, 3 * ncell));
+      CMI_TRY(line_cube_check_velocities(e, what, dvel, 3 * (int64_t)ncell));
+      dvelocity = dvel;
+    }
+    CMI_TRY(arena.upload(dn, n, (size_t)count));
+    CMI_TRY(arena.upload(db, b, (size_t)count));
+    field_absorption_record_kernel<<<(unsigned)((count + 255) / 256), 256, 0,
+                                     e->stream>>>(dn, db, count, records);
+    HIP_TRY(hipGetLastError());
+  }
+  unsigned int *ninvalid = nullptr;
+  unsigned int bad[3] = {0, 0, 0};
+  CMI_TRY(arena.alloc(ninvalid, 3));
+  HIP_TRY(hipMemsetAsync(ninvalid, 0, sizeof bad, e->stream));
+  absorption_record_check_kernel<<<grid_blocks(e, e->ncell, 8), 256, 0,
+                                   e->stream>>>(records, dg, e->ncell, nlines,
+                                                ninvalid);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(bad, ninvalid, sizeof bad, hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (bad[0])
+    return fail(CMI_GPU_EINVAL, "%s: %u absorber densities are negative or "
+                "not finite", what, bad[0]);
+  if (bad[1])
+    return fail(CMI_GPU_EINVAL, "%s: %u Doppler width(s) are negative or not "
+                "finite", what, bad[1]);
+  if (bad[2])
+    return fail(CMI_GPU_EINVAL, "%s: %u cell(s) of a damped line hold "
+                "absorbers of Doppler width 0 (a = g / b has no value)", what,
+                bad[2]);
+  CMI_TRY(arena.alloc(velocity_records, 4 * ncell));
+  absorption_velocity_record_kernel<<<(unsigned)((e->ncell + 255) / 256), 256,
+                                      0, e->stream>>>(
+      dvelocity, v_obs[0], v_obs[1], v_obs[2], e->ncell, velocity_records);
+  HIP_TRY(hipGetLastError());
+  return CMI_GPU_OK;
+}
+
+/* what an absorption call asks of the engine and of its sightlines */
+int absorption_check_rays(const cmi_gpu_engine *e, const char *what,
+                          int64_t nrays, int64_t max_rays,
+                          const double *origins, const double *directions,
+                          const double *lengths) {
+  if (!origins || !lengths)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  /* (the grid, the count and the directions as every sky call has them
+   * checked; the origin it looks at is the first ray's) */
+  CMI_TRY(sky_check(e, what, origins, nrays, max_rays, directions));
+  for (int64_t r = 0; r < nrays; ++r) {
+    for (int a = 0; a < 3; ++a)
+      if (!std::isfinite(origins[3 * r + a]))
+        return fail(CMI_GPU_EINVAL, "%s: component %d of the origin of ray "
+                    "%lld is not finite", what, a, (long long)r);
+    if (!(lengths[r] > 0.))
+      return fail(CMI_GPU_EINVAL, "%s: the length of ray %lld must be "
+                  "positive (+inf: to the edge of the box)", what,
+                  (long long)r);
+  }
+  return CMI_GPU_OK;
+}
+
+template <class F> void absorption_for_variant(int rows, bool share, F &&f) {
+  if (rows == 1) {
+    if (share)
+      f(std::integral_constant<int, 1>(), std::true_type());
+    else
+      f(std::integral_constant<int, 1>(), std::false_type());
+  } else if (rows == 2) {
+    if (share)
+      f(std::integral_constant<int, 2>(), std::true_type());
+    else
+      f(std::integral_constant<int, 2>(), std::false_type());
+  } else {
+    if (share)
+      f(std::integral_constant<int, 4>(), std::true_type());
+    else
+      f(std::integral_constant<int, 4>(), std::false_type());
+  }
+}
+
+/* tau[nrays][K][nchan] and N[nrays][K] (host): the records, one launch */
+int absorption_spectra(cmi_gpu_engine *e, const char *what,
+                       AbsorptionInput &in, const LineCubeAxis &axis,
+                       int64_t nrays, const double *origins,
+                       const double *directions, const double *lengths,
+                       double *tau, double *N) {
+  HIP_TRY(hipSetDevice(e->device));
+  RenderArena arena;
+  CMI_TRY(in.begin(e, what, arena));
+  int rows = e->tune.absorption_slab_rows;
+  if (!rows)
+    rows = axis.nchan <= 64 ? 1 : (axis.nchan <= 128 ? 2 : CMI_ABSORPTION_R);
+  const size_t nrl = (size_t)nrays * (size_t)in.nlines;
+  double *dorigins = nullptr, *ddirections = nullptr, *dlengths = nullptr,
+         *dtau = nullptr, *dN = nullptr;
+  CMI_TRY(arena.upload(dorigins, origins, 3 * (size_t)nrays));
+  CMI_TRY(arena.upload(ddirections, directions, 3 * (size_t)nrays));
+  CMI_TRY(arena.upload(dlengths, lengths, (size_t)nrays));
+  CMI_TRY(arena.alloc(dtau, nrl * (size_t)axis.nchan));
+  CMI_TRY(arena.alloc(dN, nrl));
+  AbsorptionMarchArgs a;
+  a.grid = e->grid;
+  a.origins = dorigins;
+  a.directions = ddirections;
+  a.lengths = dlengths;
+  a.velocity_records = in.velocity_records;
+  a.records = in.records;
+  a.S = in.dS;
+  a.g = in.dg;
+  a.ncell = e->ncell;
+  a.nlines = (uint32_t)in.nlines;
+  a.nslab = (uint32_t)((axis.nchan + 64 * rows - 1) / (64 * rows));
+  /* (nrays K nchan <= 2^28 has been checked) */
+  a.nitems = (uint32_t)(nrl * a.nslab);
+  a.nchan = axis.nchan;
+  a.full = e->tune.absorption_skips ? 0 : 1;
+  a.pad = 0;
+  a.vmin = axis.vmin;
+  a.dv = axis.dv;
+  a.tau = dtau;
+  a.N = dN;
+  EventPair ev;
+  CMI_TRY(timer_begin(e, ev));
+  absorption_for_variant(rows, e->tune.absorption_edge_sharing != 0,
+                         [&](auto r, auto share) {
+    absorption_march_kernel<decltype(r)::value, decltype(share)::value>
+        <<<(a.nitems + 3) / 4, 256, 0, e->stream>>>(a);
+  });
+  HIP_TRY(hipGetLastError());
+  CMI_TRY(timer_end(e, e->kernel_events, ev, (uint64_t)nrays));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(tau, dtau, sizeof(double) * nrl * (size_t)axis.nchan,
+                    hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(N, dN, sizeof(double) * nrl, hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+}
+
+/* the checks the two render calls share; *empty: zero rays, nothing to do */
+int absorption_render_check(cmi_gpu_engine *e, const char *what,
+                            const AbsorptionInput &in, int64_t nrays,
+                            const double *origins, const double *directions,
+                            const double *lengths,
+                            const double *observer_velocity, int32_t nchan,
+                            double vmin, double vmax, const double *tau,
+                            const double *N, LineCubeAxis &axis,
+                            double v_obs[3], bool &empty) {
+  empty = false;
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(in.check(e, what));
+  if (nrays == 0) {
+    CMI_TRY(sky_cube_check(what, in.nlines, 1, nchan, vmin, vmax,
+                           observer_velocity, axis, v_obs));
+    empty = true;
+    return CMI_GPU_OK;
+  }
+  if (!tau || !N)
+    return fail(CMI_GPU_EINVAL, "%s: null argument", what);
+  CMI_TRY(absorption_check_rays(e, what, nrays, 1ll << 24, origins, directions,
+                                lengths));
+  return sky_cube_check(what, in.nlines, nrays, nchan, vmin, vmax,
+                        observer_velocity, axis, v_obs);
+}
+} // namespace
+} // extern "C++"
+
+int cmi_gpu_render_field_absorption_spectra(
+    cmi_gpu_engine *e, int32_t nlines, const double *n, const double *b,
+    const double *S, const double *g, const double *velocity, int64_t nrays,
+    const double *origins, const double *directions, const double *lengths,
+    const double *observer_velocity, int32_t nchan, double vmin, double vmax,
+    double *tau, double *N) {
+  static const char *what = "render_field_absorption_spectra";
+  AbsorptionInput in;
+  in.nlines = nlines;
+  in.S = S;
+  in.g = g;
+  in.n = n;
+  in.b = b;
+  in.velocity = velocity;
+  LineCubeAxis axis;
+  bool empty;
+  CMI_TRY(absorption_render_check(e, what, in, nrays, origins, directions,
+                                  lengths, observer_velocity, nchan, vmin,
+                                  vmax, tau, N, axis, in.v_obs, empty));
+  if (empty)
+    return CMI_GPU_OK;
+  return absorption_spectra(e, what, in, axis, nrays, origins, directions,
+                            lengths, tau, N);
+}
+
+int cmi_gpu_render_absorption_spectra(
+    cmi_gpu_engine *e, int32_t nlines, const int32_t *ions,
+    const double *weights, const double *S, const double *g,
+    double sigma_turb, int64_t nrays, const double *origins,
+    const double *directions, const double *lengths,
+    const double *observer_velocity, int32_t nchan, double vmin, double vmax,
+    double *tau, double *N) {
+  static const char *what = "render_absorption_spectra";
+  AbsorptionInput in;
+  in.nlines = nlines;
+  in.S = S;
+  in.g = g;
+  in.ions = ions;
+  in.weights = weights;
+  in.sigma_turb = sigma_turb;
+  in.from_cells = true;
+  LineCubeAxis axis;
+  bool empty;
+  CMI_TRY(absorption_render_check(e, what, in, nrays, origins, directions,
+                                  lengths, observer_velocity, nchan, vmin,
+                                  vmax, tau, N, axis, in.v_obs, empty));
+  if (empty)
+    return CMI_GPU_OK;
+  return absorption_spectra(e, what, in, axis, nrays, origins, directions,
+                            lengths, tau, N);
+}
+
+int cmi_gpu_absorption_probe(cmi_gpu_engine *e, const double *n,
+                             const double *b, double S, double g,
+                             const double *velocity, const double *origin,
+                             const double *direction, double length,
+                             const double *observer_velocity, int32_t nchan,
+                             double vmin, double vmax, int32_t nprobe,
+                             const int32_t *channels, int32_t max_cells,
+                             double *out) {
+  static const char *what = "absorption_probe";
+  if (!e || !out || max_cells < 0 || nprobe < 0 ||
+      nprobe > CMI_ABSORPTION_PROBE_CHANNELS || (nprobe > 0 && !channels))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", what);
+  AbsorptionInput in;
+  in.nlines = 1;
+  in.S = &S;
+  in.g = &g;
+  in.n = n;
+  in.b = b;
+  in.velocity = velocity;
+  CMI_TRY(in.check(e, what));
+  CMI_TRY(absorption_check_rays(e, what, 1, 1, origin, direction, &length));
+  LineCubeAxis axis;
+  CMI_TRY(sky_cube_check(what, 1, 1, nchan, vmin, vmax, observer_velocity,
+                         axis, in.v_obs));
+  for (int32_t k = 0; k < nprobe; ++k)
+    if (channels[k] < 0 || channels[k] >= nchan)
+      return fail(CMI_GPU_EINVAL, "%s: no channel %d", what, (int)channels[k]);
+  HIP_TRY(hipSetDevice(e->device));
+  RenderArena arena;
+  CMI_TRY(in.begin(e, what, arena));
+  const size_t nvalue =
+      3 + (2 + (size_t)nprobe) * (size_t)max_cells + (size_t)nprobe;
+  const double ray[7] = {origin[0],    origin[1],    origin[2], direction[0],
+                         direction[1], direction[2], length};
+  double *dray = nullptr, *drow = nullptr;
+  int32_t *dchannels = nullptr;
+  CMI_TRY(arena.upload(dray, ray, 7));
+  CMI_TRY(arena.alloc(drow, nvalue));
+  CMI_TRY(arena.alloc(dchannels, CMI_ABSORPTION_PROBE_CHANNELS));
+  if (nprobe)
+    HIP_TRY(hipMemcpy(dchannels, channels, sizeof(int32_t) * nprobe,
+                      hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(drow, 0, sizeof(double) * nvalue, e->stream));
+  absorption_probe_kernel<<<1, 64, 0, e->stream>>>(
+      e->grid, dray, in.velocity_records, in.records, S, g, dchannels, nprobe,
+      axis.vmin, axis.dv, max_cells, drow);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  HIP_TRY(hipMemcpy(out, drow, sizeof(double) * nvalue,
+                    hipMemcpyDeviceToHost));
+  return CMI_GPU_OK;
+}
+
 #endif /* CMI_RENDER_DRIVER_H */

@@ -147,6 +147,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_get_lya_counters", "cmi_gpu_lyman_alpha_emissivity",
     "cmi_gpu_set_lya_field", "cmi_gpu_download_lya_field",
     "cmi_gpu_lya_spin_temperature",
+    "cmi_gpu_render_field_absorption_spectra",
+    "cmi_gpu_render_absorption_spectra", "cmi_gpu_absorption_probe",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -554,8 +556,102 @@ def load_library():
         L.cmi_gpu_absorbing_cube_probe.argtypes = [
             vp] + [_dp] * 7 + axis + [C.c_int32, _dp, _dp, C.c_int64, _dp,
                                       C.c_int32, _dp]
+    # (nor does a build from before the absorption spectra have them)
+    if hasattr(L, "cmi_gpu_render_field_absorption_spectra"):
+        ip = C.POINTER(C.c_int32)
+        axis = [C.c_int32, C.c_double, C.c_double]
+        sightlines = [C.c_int64, _dp, _dp, _dp, _dp]
+        L.cmi_gpu_render_field_absorption_spectra.argtypes = [
+            vp, C.c_int32, _dp, _dp, _dp, _dp, _dp] + sightlines + axis + [
+                _dp, _dp]
+        L.cmi_gpu_render_absorption_spectra.argtypes = [
+            vp, C.c_int32, ip, _dp, _dp, _dp, C.c_double] + sightlines + \
+            axis + [_dp, _dp]
+        L.cmi_gpu_absorption_probe.argtypes = [
+            vp, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _dp, C.c_double,
+            _dp] + axis + [C.c_int32, ip, C.c_int32, _dp]
     _lib = L
     return L
+
+
+# physical constants of the absorption lines (SI, CODATA 2018)
+_ELEMENTARY_CHARGE = 1.602176634e-19
+_VACUUM_PERMITTIVITY = 8.8541878128e-12
+_ELECTRON_MASS = 9.1093837015e-31
+_LIGHTSPEED = 299792458.
+
+# The ions the engine tracks, in the order of its ionic fractions.
+ION_NAMES = ("H0", "He0", "C+", "C2+", "N0", "N+", "N2+", "O0", "O+", "Ne0",
+             "Ne+", "S+", "S2+", "S3+")
+_ION_ELEMENTS = ("H", "He", "C", "C", "N", "N", "N", "O", "O", "Ne", "Ne",
+                 "S", "S", "S")
+
+# One resonance line per tracked ion: name -> (ion index, vacuum wavelength in
+# m, oscillator strength f, damping constant Gamma in s^-1). Wavelengths and f
+# values after Morton (2003, ApJS 149, 205) where that compilation has the
+# line and the NIST Atomic Spectra Database otherwise, rounded to the figures
+# given; Gamma is the sum of the upper level's transition probabilities as
+# NIST lists them, to two or three figures. H I carries the literals of the
+# Lyman-alpha transfer (CMI_LYA_LAMBDA0, CMI_LYA_A21), so that a = g / b is
+# that mode's. The other rows have not been checked against the two sources
+# entry by entry ("Not measured"): work that depends on a
+# line's f or Gamma should pass its own constants to
+# absorption_line_constants.
+ABSORPTION_LINES = {
+    "HI_1215": (0, LYA_LAMBDA0, 0.4164, 6.265e8),
+    "HeI_584": (1, 584.334e-10, 0.2763, 1.799e9),
+    "CII_1334": (2, 1334.532e-10, 0.1278, 2.88e8),
+    "CIII_977": (3, 977.020e-10, 0.7570, 1.767e9),
+    "NI_1199": (4, 1199.550e-10, 0.1320, 4.07e8),
+    "NII_1083": (5, 1083.994e-10, 0.1110, 3.74e8),
+    "NIII_989": (6, 989.799e-10, 0.1230, 5.00e8),
+    "OI_1302": (7, 1302.168e-10, 0.0480, 5.65e8),
+    "OII_834": (8, 834.466e-10, 0.1320, 8.60e8),
+    "NeI_735": (9, 735.896e-10, 0.1590, 6.11e8),
+    "NeII_460": (10, 460.728e-10, 0.0900, 7.00e9),
+    "SII_1259": (11, 1259.518e-10, 0.0166, 4.65e7),
+    "SIII_1190": (12, 1190.203e-10, 0.0237, 6.70e7),
+    "SIV_1062": (13, 1062.664e-10, 0.0494, 1.60e8),
+}
+
+
+def absorption_line_constants(wavelength, f, gamma):
+    """(S, g) of a line of rest wavelength `wavelength` (m), oscillator
+    strength f and damping constant gamma (s^-1): the cross section
+    integrated over velocity S = e^2 f lambda0 / (4 eps0 m_e c), m^2 m s^-1,
+    and the damping width g = gamma lambda0 / (4 pi), m s^-1
+    (include/cmi_gpu.h, "absorption spectra")."""
+    S = (_ELEMENTARY_CHARGE * _ELEMENTARY_CHARGE * f * wavelength /
+         (4. * _VACUUM_PERMITTIVITY * _ELECTRON_MASS * _LIGHTSPEED))
+    return S, gamma * wavelength / (4. * np.pi)
+
+
+def transmitted_flux(tau):
+    """exp(-tau): the flux of a background source of unit continuum."""
+    return np.exp(-np.asarray(tau, dtype=np.float64))
+
+
+def equivalent_width(tau, dv, wavelength):
+    """The equivalent width (m) of spectra tau[..., nchan] of channel width
+    dv (m s^-1): (lambda0 / c) sum_c (1 - exp(-tau_c)) dv."""
+    tau = np.asarray(tau, dtype=np.float64)
+    return (wavelength / _LIGHTSPEED) * (-np.expm1(-tau)).sum(axis=-1) * dv
+
+
+def apparent_column_density(tau, dv, S):
+    """The apparent column density (m^-2) of spectra tau[..., nchan]: sum_c
+    tau_c dv / S, the true one where the line is resolved."""
+    return np.asarray(tau, dtype=np.float64).sum(axis=-1) * dv / S
+
+
+def absorption_table_lines(names):
+    """(ions, weights, S, g, wavelengths) of entries of ABSORPTION_LINES."""
+    rows = [ABSORPTION_LINES[n] for n in names]
+    Sg = [absorption_line_constants(w, f, gamma) for _, w, f, gamma in rows]
+    return (np.array([r[0] for r in rows], dtype=np.int32),
+            np.array([_ELEMENT_WEIGHTS[_ION_ELEMENTS[r[0]]] for r in rows]),
+            np.array([s for s, _ in Sg]), np.array([g for _, g in Sg]),
+            np.array([r[1] for r in rows]))
 
 
 def projected_areas(directions):
@@ -1847,6 +1943,92 @@ class GpuEngine:
             self._h, *[_p_or_none(x) for x in f], _p_or_none(bg), nchan, vmin,
             vmax, int(point), _p(view), _p_or_none(vo), len(r), _p(r),
             int(max_cells), _p(out)))
+        return out
+
+    # absorption spectra -----------------------------------------------------
+    @staticmethod
+    def _sightlines(origins, directions, lengths):
+        d = _f64(directions).reshape(-1, 3)
+        o = _f64(np.broadcast_to(_f64(origins).reshape(-1, 3), d.shape))
+        if lengths is None:
+            lengths = np.inf
+        L = _f64(np.broadcast_to(_f64(lengths).reshape(-1), (len(d),)))
+        return o, d, L
+
+    def render_field_absorption_spectra(self, n, b, S, g, origins, directions,
+                                        nchan, vmin, vmax, lengths=None,
+                                        velocity=None, observer_velocity=None):
+        """Optical depths of K lines with Voigt profiles along sightlines
+        (include/cmi_gpu.h, "absorption spectra"): n[K][ncell] absorber
+        densities (m^-3), b[K][ncell] Doppler widths (m s^-1), S[K] and g[K]
+        as absorption_line_constants gives them. Sightline r runs from
+        origins[r] (one origin serves all) along the unit vector
+        directions[r] for lengths[r] metres (None or inf: to the edge of the
+        box). Returns tau (nrays, K, nchan) and the column densities N
+        (nrays, K), m^-2."""
+        S = _f64(S).reshape(-1)
+        g = _f64(g).reshape(len(S))
+        nn = _f64(n).reshape(len(S), self.n)
+        bb = _f64(b).reshape(len(S), self.n)
+        v = None if velocity is None else _f64(velocity).reshape(3, self.n)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o, d, L = self._sightlines(origins, directions, lengths)
+        tau = np.zeros((len(d), len(S), max(int(nchan), 0)))
+        N = np.zeros((len(d), len(S)))
+        self._check(self._lib.cmi_gpu_render_field_absorption_spectra(
+            self._h, len(S), _p(nn), _p(bb), _p(S), _p(g), _p_or_none(v),
+            len(d), _p(o), _p(d), _p(L), _p_or_none(vo), int(nchan), vmin,
+            vmax, _p(tau), _p(N)))
+        return tau, N
+
+    def render_absorption_spectra(self, lines, origins, directions, nchan,
+                                  vmin, vmax, lengths=None, sigma_turb=0.,
+                                  observer_velocity=None):
+        """The same for lines of the engine's own ions, from the cells as
+        they are: `lines` holds names of ABSORPTION_LINES or tuples (ion
+        index, atomic weight, S, g); n = n_H A_element x_ion and b = sqrt(2 k
+        T / (w m_u) + 2 sigma_turb^2) are built on the device."""
+        rows = []
+        for line in lines:
+            if isinstance(line, str):
+                ion, w, S, g, _ = absorption_table_lines([line])
+                rows.append((ion[0], w[0], S[0], g[0]))
+            else:
+                rows.append(tuple(line))
+        ions = np.array([r[0] for r in rows], dtype=np.int32)
+        w = _f64([r[1] for r in rows])
+        S = _f64([r[2] for r in rows])
+        g = _f64([r[3] for r in rows])
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        o, d, L = self._sightlines(origins, directions, lengths)
+        tau = np.zeros((len(d), len(rows), max(int(nchan), 0)))
+        N = np.zeros((len(d), len(rows)))
+        self._check(self._lib.cmi_gpu_render_absorption_spectra(
+            self._h, len(rows), ions.ctypes.data_as(C.POINTER(C.c_int32)),
+            _p(w), _p(S), _p(g), sigma_turb, len(d), _p(o), _p(d), _p(L),
+            _p_or_none(vo), int(nchan), vmin, vmax, _p(tau), _p(N)))
+        return tau, N
+
+    def absorption_probe(self, n, b, S, g, origin, direction, max_cells,
+                         nchan, vmin, vmax, channels=(), length=np.inf,
+                         velocity=None, observer_velocity=None):
+        """One sightline through one line, cell by cell: {t0, t1, steps,
+        cells[max_cells], ds[max_cells], tau[len(channels)][max_cells],
+        tau_end[len(channels)]} for up to 8 channels; no skips."""
+        nn = _f64(n).reshape(self.n)
+        bb = _f64(b).reshape(self.n)
+        v = None if velocity is None else _f64(velocity).reshape(3, self.n)
+        vo = (None if observer_velocity is None
+              else _f64(observer_velocity).reshape(3))
+        ch = np.ascontiguousarray(channels, dtype=np.int32).reshape(-1)
+        out = np.zeros(3 + (2 + len(ch)) * max_cells + len(ch))
+        self._check(self._lib.cmi_gpu_absorption_probe(
+            self._h, _p(nn), _p(bb), S, g, _p_or_none(v),
+            _p(_f64(origin).reshape(3)), _p(_f64(direction).reshape(3)),
+            length, _p_or_none(vo), int(nchan), vmin, vmax, len(ch),
+            ch.ctypes.data_as(C.POINTER(C.c_int32)), int(max_cells), _p(out)))
         return out
 
     # sky cubes --------------------------------------------------------------

@@ -172,6 +172,10 @@
  *                    "HI spin temperature type: Fixed" and with a background
  *                    temperature of 0. The H I cube of EmissionSkyMaps is not
  *                    coupled: it keeps its own spin temperature type.
+ * Absorption spectra: an "AbsorptionSpectra:" block gives
+ * the optical depths and column densities of resonance lines of the
+ * snapshot's ions along sightlines from an observer; its keys and files stand
+ * at AbsorptionSettings below. It needs no flagged emission line.
  * For the images and maps the cells go on the snapshot's real grid: the box
  * from /Parameters (SimulationBox:anchor, sides), each cell where its row of
  * /PartType0/Coordinates puts it (the box anchor is the origin in the file;
@@ -892,11 +896,187 @@ class EmissivityCalculationSimulation {
     }
   };
 
+  /* a resonance line of one of the engine's ions: the table of
+   * cmacionize_amd/engine.py (ABSORPTION_LINES has the sources), the same
+   * literals; tests/test_absorption_host.py holds the two together */
+  struct AbsorptionLine {
+    const char *name;
+    int32_t ion;
+    double weight, wavelength, f, gamma;
+    /* absorption_line_constants of engine.py, operation for operation */
+    double S() const {
+      return 1.602176634e-19 * 1.602176634e-19 * f * wavelength /
+             (4. * 8.8541878128e-12 * 9.1093837015e-31 * 299792458.);
+    }
+    double g() const { return gamma * wavelength / (4. * M_PI); }
+  };
+  static const AbsorptionLine *absorption_line(const std::string &name) {
+    static const AbsorptionLine table[] = {
+        {"HI_1215", 0, 1.00794, 1215.67e-10, 0.4164, 6.265e8},
+        {"HeI_584", 1, 4.002602, 584.334e-10, 0.2763, 1.799e9},
+        {"CII_1334", 2, 12.0107, 1334.532e-10, 0.1278, 2.88e8},
+        {"CIII_977", 3, 12.0107, 977.020e-10, 0.7570, 1.767e9},
+        {"NI_1199", 4, 14.0067, 1199.550e-10, 0.1320, 4.07e8},
+        {"NII_1083", 5, 14.0067, 1083.994e-10, 0.1110, 3.74e8},
+        {"NIII_989", 6, 14.0067, 989.799e-10, 0.1230, 5.00e8},
+        {"OI_1302", 7, 15.9994, 1302.168e-10, 0.0480, 5.65e8},
+        {"OII_834", 8, 15.9994, 834.466e-10, 0.1320, 8.60e8},
+        {"NeI_735", 9, 20.1797, 735.896e-10, 0.1590, 6.11e8},
+        {"NeII_460", 10, 20.1797, 460.728e-10, 0.0900, 7.00e9},
+        {"SII_1259", 11, 32.065, 1259.518e-10, 0.0166, 4.65e7},
+        {"SIII_1190", 12, 32.065, 1190.203e-10, 0.0237, 6.70e7},
+        {"SIV_1062", 13, 32.065, 1062.664e-10, 0.0494, 1.60e8}};
+    for (const AbsorptionLine &line : table)
+      if (name == line.name)
+        return &line;
+    return nullptr;
+  }
+
+  /* the AbsorptionSpectra: block (read only if the file has one; DESIGN.md
+   * 4.19): sightlines from an observer, each along a direction to the edge of
+   * the box or towards a target at a finite distance, and the optical depths
+   * of the named lines along them.
+   *   AbsorptionSpectra:observer position        required, a vector of lengths
+   *   AbsorptionSpectra:observer velocity        [0., 0., 0.] m s^-1
+   *   AbsorptionSpectra:number of sightlines     1
+   *   AbsorptionSpectra:sightline direction k    a vector, normalised here, or
+   *   AbsorptionSpectra:target position k        a vector of lengths: the
+   *                    direction towards it and L = its distance; exactly one
+   *                    of the two for every k = 0 .. K - 1
+   *   AbsorptionSpectra:lines                    required, [names] of the table
+   *   AbsorptionSpectra:velocity channels / velocity minimum / velocity
+   *                    maximum                   required
+   *   AbsorptionSpectra:turbulent velocity dispersion / velocity field type
+   *                    and its keys              as in EmissionImages
+   *   AbsorptionSpectra:filename prefix / output folder   absorption / .
+   * Written: <prefix>_absorption_tau.dat, raw doubles [ray][line][channel],
+   * and <prefix>_absorption_columns.txt, one row "ray line N W" per ray and
+   * line: the column density in m^-2 and the equivalent width in m. */
+  struct AbsorptionSettings : CubeSettings {
+    std::array<double, 3> position = {0., 0., 0.}, velocity = {0., 0., 0.};
+    std::vector<double> origins, directions, lengths;
+    std::vector<const AbsorptionLine *> lines;
+    std::string prefix, folder;
+
+    void read(ParameterFile &params) {
+      const std::string block = "AbsorptionSpectra";
+      if (!params.has_value(block + ":observer position"))
+        throw ParameterError(block + ":observer position is required");
+      position = params.get_physical_vector(
+          QUANTITY_LENGTH, block + ":observer position", "");
+      velocity = params.get_physical_vector(
+          QUANTITY_VELOCITY, block + ":observer velocity",
+          "[0. m s^-1, 0. m s^-1, 0. m s^-1]");
+      for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(position[a]) || !std::isfinite(velocity[a]))
+          throw ParameterError(block + ":observer position and velocity must "
+                               "be finite");
+      const long long nrays =
+          params.get_integer(block + ":number of sightlines", 1);
+      if (nrays < 1 || nrays > (1ll << 20))
+        throw ParameterError(block + ":number of sightlines must be between "
+                             "1 and 2^20");
+      for (long long k = 0; k < nrays; ++k) {
+        const std::string kd =
+            block + ":sightline direction " + std::to_string(k);
+        const std::string kt = block + ":target position " + std::to_string(k);
+        const bool has_d = params.has_value(kd), has_t = params.has_value(kt);
+        if (has_d && has_t)
+          throw ParameterError(kd + " and " + kt + " are both given: a "
+                               "sightline has a direction or a target");
+        if (!has_d && !has_t)
+          throw ParameterError("one of " + kd + " and " + kt +
+                               " is required");
+        std::array<double, 3> d;
+        if (has_d) {
+          d = params.get_double_vector(kd, {0., 0., 0.});
+        } else {
+          const std::array<double, 3> target =
+              params.get_physical_vector(QUANTITY_LENGTH, kt, "");
+          for (int a = 0; a < 3; ++a)
+            d[a] = target[a] - position[a];
+        }
+        const double norm = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        if (!(norm > 0.) || !std::isfinite(norm))
+          throw ParameterError((has_d ? kd : kt) + " must be a finite vector "
+                               "that is not zero" +
+                               (has_d ? "" : ", away from the observer"));
+        for (int a = 0; a < 3; ++a) {
+          origins.push_back(position[a]);
+          directions.push_back(d[a] / norm);
+        }
+        lengths.push_back(has_d ? HUGE_VAL : norm);
+      }
+      if (!params.has_value(block + ":lines"))
+        throw ParameterError(block + ":lines is required");
+      std::string names = params.get_string(block + ":lines", "");
+      for (char &c : names)
+        if (c == '[' || c == ']' || c == ',')
+          c = ' ';
+      std::istringstream words(names);
+      for (std::string name; words >> name;) {
+        const AbsorptionLine *line = absorption_line(name);
+        if (!line)
+          throw ParameterError("Unknown " + block + ":lines entry \"" + name +
+                               "\"");
+        lines.push_back(line);
+      }
+      if (lines.empty() || lines.size() > 16)
+        throw ParameterError(block + ":lines must name between 1 and 16 "
+                             "lines");
+      if (!params.has_value(block + ":velocity channels"))
+        throw ParameterError(block + ":velocity channels is required");
+      read_cubes(params, block, "BinaryArray");
+      if ((double)nrays * (double)lines.size() * (double)nchan >
+          (double)(1ll << 28))
+        throw ParameterError(block + ": more than 2^28 optical depths in one "
+                             "call");
+      prefix = params.get_string(block + ":filename prefix", "absorption");
+      folder = params.get_string(block + ":output folder", ".");
+    }
+
+    /* what --describe prints */
+    void describe(std::ostream &os) const {
+      char text[64];
+      auto number = [&text](double x) {
+        std::snprintf(text, sizeof text, "%.17g", x);
+        return std::string(std::isfinite(x) ? text : "null");
+      };
+      os << "{\"AbsorptionSpectra\": {\"observer position\": ["
+         << number(position[0]) << ", " << number(position[1]) << ", "
+         << number(position[2]) << "], \"observer velocity\": ["
+         << number(velocity[0]) << ", " << number(velocity[1]) << ", "
+         << number(velocity[2]) << "],\n  \"sightlines\": [";
+      for (size_t k = 0; k < lengths.size(); ++k)
+        os << (k ? ",\n    " : "\n    ") << "{\"direction\": ["
+           << number(directions[3 * k]) << ", "
+           << number(directions[3 * k + 1]) << ", "
+           << number(directions[3 * k + 2])
+           << "], \"length\": " << number(lengths[k]) << "}";
+      os << "],\n  \"lines\": [";
+      for (size_t l = 0; l < lines.size(); ++l)
+        os << (l ? ",\n    " : "\n    ") << "{\"name\": \"" << lines[l]->name
+           << "\", \"ion\": " << lines[l]->ion
+           << ", \"weight\": " << number(lines[l]->weight)
+           << ", \"wavelength\": " << number(lines[l]->wavelength)
+           << ", \"S\": " << number(lines[l]->S())
+           << ", \"g\": " << number(lines[l]->g()) << "}";
+      os << "],\n  \"velocity channels\": " << nchan
+         << ", \"velocity minimum\": " << number(vmin)
+         << ", \"velocity maximum\": " << number(vmax)
+         << ", \"turbulent velocity dispersion\": " << number(sigma_turb)
+         << ", \"velocity field type\": \"" << velocity_field
+         << "\",\n  \"filename prefix\": \"" << prefix
+         << "\", \"output folder\": \"" << folder << "\"}}" << std::endl;
+    }
+  };
+
 public:
   /* EmissivityCalculationSimulation::do_simulation, :58-299 */
   static int do_simulation(const std::string &parameterfile_name,
                            const std::string &input_file_name, int device,
-                           bool write_output, bool verbose) {
+                           bool write_output, bool verbose,
+                           bool describe = false) {
     auto status = [verbose](const std::string &text) {
       if (verbose)
         std::cout << text << std::endl;
@@ -917,6 +1097,16 @@ public:
     SkyMapSettings sky;
     if (do_sky)
       sky.read(params);
+    const bool do_absorption = params.has_block("AbsorptionSpectra");
+    AbsorptionSettings absorption;
+    if (do_absorption)
+      absorption.read(params);
+    if (describe && do_absorption) {
+      absorption.describe(std::cout);
+      /* a dry run that describes ends here: it needs no snapshot */
+      if (!write_output)
+        return 0;
+    }
     if (write_output) {
       std::ofstream pfile(parameterfile_name + ".used-values");
       params.print_contents(pfile);
@@ -1001,7 +1191,7 @@ public:
      * describes (its midpoint, with the box anchor as the origin) */
     std::array<double, 3> box_anchor = {0., 0., 0.}, box_sides = {1., 1., 1.};
     std::vector<size_t> cell_of_row;
-    if ((do_images || do_sky) && !lines.empty()) {
+    if (((do_images || do_sky) && !lines.empty()) || do_absorption) {
       box_anchor = simulation_parameters.get_physical_vector(
           QUANTITY_LENGTH, "SimulationBox:anchor", "");
       box_sides = simulation_parameters.get_physical_vector(
@@ -1088,10 +1278,13 @@ public:
     const std::vector<double> sky_velocities =
         do_sky ? cell_velocities(sky, "EmissionSkyMaps")
                : std::vector<double>();
+    const std::vector<double> absorption_velocities =
+        do_absorption ? cell_velocities(absorption, "AbsorptionSpectra")
+                      : std::vector<double>();
 
     status("Starting emissivity calculation...");
     std::vector<double> values(lines.size() * size);
-    if (!lines.empty()) {
+    if (!lines.empty() || do_absorption) {
       /* without images: the cells in the file's order on a device grid of
        * the same shape (every cell on its own: the shape only has to hold
        * them); with them, every cell in its place in the real box */
@@ -1123,7 +1316,7 @@ public:
       if (rc == CMI_GPU_OK)
         rc = cmi_gpu_upload_cells(engine, number_density.data(),
                                   temperature.data(), fractions.data());
-      if (rc == CMI_GPU_OK)
+      if (rc == CMI_GPU_OK && !lines.empty())
         rc = cmi_gpu_compute_emissivities(engine, (int32_t)lines.size(),
                                           lines.data(), 0, (int64_t)size,
                                           values.data());
@@ -1144,7 +1337,7 @@ public:
                                       "_scattered_U"};
       static const char *cube_stokes[3] = {
           "_scattered_cube_I", "_scattered_cube_Q", "_scattered_cube_U"};
-      if (rc == CMI_GPU_OK && placed && do_images) {
+      if (rc == CMI_GPU_OK && placed && do_images && !lines.empty()) {
         status("Rendering emission line images...");
         const size_t nviews = img.views.size();
         /* per view, default image: the rectangle around the box's projected
@@ -1480,7 +1673,7 @@ public:
         if (!img.lya_coupling)
           shoot_lyman_alpha();
       }
-      if (rc == CMI_GPU_OK && placed && do_sky) {
+      if (rc == CMI_GPU_OK && placed && do_sky && !lines.empty()) {
         status("Rendering emission line sky maps...");
         const size_t nviews = sky.observers.size();
         const size_t npixel = (size_t)sky.nlon * (size_t)sky.nlat;
@@ -1705,6 +1898,57 @@ public:
           if (rc == CMI_GPU_OK && sky.scattered_cubes)
             rc = cmi_gpu_set_scattered_cube(engine, 0, 0., 1., 0., nullptr,
                                             nullptr);
+        }
+      }
+      if (rc == CMI_GPU_OK && do_absorption) {
+        status("Rendering absorption spectra...");
+        const AbsorptionSettings &ab = absorption;
+        const size_t nrays = ab.lengths.size(), nl = ab.lines.size();
+        std::vector<int32_t> ions(nl);
+        std::vector<double> weights(nl), S(nl), g(nl);
+        for (size_t l = 0; l < nl; ++l) {
+          ions[l] = ab.lines[l]->ion;
+          weights[l] = ab.lines[l]->weight;
+          S[l] = ab.lines[l]->S();
+          g[l] = ab.lines[l]->g();
+        }
+        std::vector<double> tau(nrays * nl * (size_t)ab.nchan), N(nrays * nl);
+        /* the block's own velocity field, or none */
+        rc = cmi_gpu_set_cell_velocities(
+            engine, absorption_velocities.empty()
+                        ? nullptr
+                        : absorption_velocities.data());
+        if (rc == CMI_GPU_OK)
+          rc = cmi_gpu_render_absorption_spectra(
+              engine, (int32_t)nl, ions.data(), weights.data(), S.data(),
+              g.data(), ab.sigma_turb, (int64_t)nrays, ab.origins.data(),
+              ab.directions.data(), ab.lengths.data(), ab.velocity.data(),
+              (int32_t)ab.nchan, ab.vmin, ab.vmax, tau.data(), N.data());
+        if (rc == CMI_GPU_OK && write_output) {
+          const std::string base =
+              ab.folder + "/" + ab.prefix + "_absorption_";
+          written += " " + write_cube(base + "tau", tau.data(),
+                                      (long long)nrays, (long long)nl,
+                                      ab.nchan);
+          const std::string filename = base + "columns.txt";
+          std::FILE *out = std::fopen(filename.c_str(), "w");
+          if (!out)
+            throw std::runtime_error("Could not write " + filename);
+          const double dv = (ab.vmax - ab.vmin) / (double)ab.nchan;
+          for (size_t r = 0; r < nrays; ++r)
+            for (size_t l = 0; l < nl; ++l) {
+              /* W = (lambda0 / c) sum_c (1 - exp(-tau_c)) dv */
+              double sum = 0.;
+              const double *t = tau.data() + (r * nl + l) * (size_t)ab.nchan;
+              for (long long c = 0; c < ab.nchan; ++c)
+                sum += -std::expm1(-t[c]);
+              std::fprintf(out, "%zu %s %.17g %.17g\n", r, ab.lines[l]->name,
+                           N[r * nl + l],
+                           (ab.lines[l]->wavelength / constants::lightspeed) *
+                               sum * dv);
+            }
+          std::fclose(out);
+          written += " " + filename;
         }
       }
       const std::string message = rc ? cmi_gpu_last_error() : "";

@@ -227,7 +227,7 @@ int main(int argc, char **argv) {
     /* src/CMacIonize.cpp: the emission mode */
     try {
       return EmissivityCalculationSimulation::do_simulation(
-          params, input_file, device, !dry_run, true);
+          params, input_file, device, !dry_run, true, do_describe);
     } catch (std::exception &e) {
       std::cerr << "Error: " << e.what() << std::endl;
       return 1;

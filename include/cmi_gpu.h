@@ -2166,6 +2166,111 @@ int cmi_gpu_absorbing_cube_probe(
     const double *observer_velocity, int64_t n, const double *rays,
     int32_t max_cells, double *out);
 
+/* ---- absorption spectra ----
+ *
+ * The optical depth of K resonance lines (1 <= K <= 16) with Voigt profiles
+ * along sightlines of finite length, and the column density of each absorber:
+ * what UV and optical absorption against a star inside or behind the gas
+ * measures. DESIGN.md 4.19 has the reasoning and the figures.
+ *
+ * Sightlines: ray r is o_r + t d_r, 0 <= t <= L_r. origins[nrays][3] in m,
+ * every ray its own; directions[nrays][3] unit vectors, checked as the point
+ * camera's are (| |d|^2 - 1 | <= 1e-9, finite); lengths[nrays] in m, L_r > 0,
+ * +inf for "to the edge of the box". A ray is clipped to the box and walked
+ * as the rays of "sky maps" are (t_start, t_out and the cell-by-cell step of
+ * cmi_gpu_sky_probe). t is the running sum of the path lengths ds of the
+ * crossings, from t_start. With L_r >= t_out nothing is cut and the (cell,
+ * ds) list is cmi_gpu_sky_probe's, exactly; otherwise the crossing with t +
+ * ds >= L_r has ds = L_r - t and is the last one. With L_r <= t_start, or
+ * when the ray misses the box, the ray contributes nothing: tau = 0, N = 0.
+ *
+ * Lines: line l has an absorber density n_l[cell] (m^-3), a Doppler width
+ * b_l[cell] = sqrt(2) sigma (m s^-1), an integrated cross section in velocity
+ * S_l = e^2 f lambda0 / (4 eps0 m_e c) (m^2 m s^-1) and a damping width g_l =
+ * Gamma lambda0 / (4 pi) (m s^-1); a = g_l / b_l is the Voigt parameter of a
+ * cell. The velocity axis (nchan, vmin, vmax) is the cubes': e_c = vmin + c *
+ * dv, centre_c = 0.5 * (e_c + e_{c+1}); velocities are relative to each
+ * line's own rest wavelength, lines do not blend.
+ *
+ * Per crossing of length ds of a cell with n_l != 0 (a cell with n_l == 0
+ * contributes nothing, whatever its b), u = (w_x d_x + w_y d_y) + w_z d_z
+ * with w = v - v_obs, in this order and without contraction:
+ *   nds = n_l * ds;  N = N + nds;  A = nds * S_l
+ *   f_c = 0.5 * (E((e_{c+1} - u) / b) - E((e_c - u) / b)),  E of "spectral
+ *         line cubes", so that b == 0 is the inclusive step function
+ *   g_l == 0:  tau_c = tau_c + A * (f_c / dv)
+ *   g_l > 0:   x = (centre_c - u) / b;  wing = Q(g_l / b, x * x) / b
+ *              tau_c = tau_c + A * (f_c / dv + wing)
+ * Q is the wing term of the Voigt function of "Lyman alpha" (Tasitsiomi
+ * 2006: H(a, x) = sqrt(pi) Q + exp(-x^2)), at the channel centre; the
+ * Gaussian core is integrated over the channel, so that with g == 0 and an
+ * axis that covers the line sum_c tau_c dv = S N. A cell with n_l > 0, g_l >
+ * 0 and b_l == 0 has no a: such cells are counted on the device and the call
+ * fails with CMI_GPU_EINVAL.
+ *
+ * Output: tau[(r * K + l) * nchan + c] and N[r * K + l] (m^-2); K * nchan *
+ * nrays <= 2^28, nrays <= 2^24. The same call gives the same bits, and a
+ * channel's bits depend on (vmin, dv, c), the ray and the cells only: not on
+ * nchan, the ray's place in the list or the tuning below.
+ *
+ * Errors, each before any march and with the outputs untouched:
+ * CMI_GPU_EINVAL for K outside 1..16, nchan < 1, vmax <= vmin, directions
+ * that are not finite unit vectors, origins that are not finite, L_r <= 0 or
+ * NaN, an n, b, S or g that is negative or not finite (n and b are counted on
+ * the device), an ion outside 0..13, an atomic weight that is not positive,
+ * a null pointer, a periodic box; CMI_GPU_ESTATE on a block of a decomposed
+ * grid and for cmi_gpu_render_absorption_spectra without cell data. nrays ==
+ * 0 is an empty result (the other arguments are still checked), not an
+ * error.
+ *
+ * Tuning (cmi_gpu_set_tuning): absorption_slab_rows = 1, 2 or 4: a wave
+ * takes 64 times as many channels of one ray and line (0, the default: 4, and
+ * 1 or 2 for an axis of at most 64 or 128 channels); absorption_edge_sharing
+ * = 0: a lane evaluates E at both edges of its channels instead of taking the
+ * upper one from its neighbour; absorption_skips = 0: cells whose +-6 b
+ * window misses a wave's channels are not skipped. None changes a bit of the
+ * result. */
+
+/* The lines are the caller's: n[K][ncell], b[K][ncell], S[K], g[K] and
+ * velocity[3][ncell] or NULL (at rest). Needs only cmi_gpu_create. */
+int cmi_gpu_render_field_absorption_spectra(
+    cmi_gpu_engine *engine, int32_t nlines, const double *n, const double *b,
+    const double *S, const double *g, const double *velocity /* or NULL */,
+    int64_t nrays, const double *origins, const double *directions,
+    const double *lengths, const double *observer_velocity /* or NULL */,
+    int32_t nchan, double vmin, double vmax,
+    double *tau /* [nrays][K][nchan] */, double *N /* [nrays][K] */);
+
+/* The lines of the engine's own ions: line l absorbs in ion ions[l] (0..13,
+ * the order of the ionic fractions) of atomic weight weights[l], with n = n_H
+ * * A_element * x_ion (hydrogen's abundance is 1) and b = sqrt(2 * k_B * T /
+ * (w * m_u) + 2 * sigma_turb * sigma_turb), the thermal part dropped for T <=
+ * 0, built on the device from the cells as they are. Velocities are those of
+ * cmi_gpu_set_cell_velocities. */
+int cmi_gpu_render_absorption_spectra(
+    cmi_gpu_engine *engine, int32_t nlines, const int32_t *ions,
+    const double *weights, const double *S, const double *g,
+    double sigma_turb, int64_t nrays, const double *origins,
+    const double *directions, const double *lengths,
+    const double *observer_velocity, int32_t nchan, double vmin, double vmax,
+    double *tau, double *N);
+
+/* Test hook: one ray through one line n[ncell], b[ncell], S, g, cell by
+ * cell. `out` has 3 + (2 + nprobe) * max_cells + nprobe doubles: {t0, t1,
+ * steps, cells[max_cells], ds[max_cells], tau[nprobe][max_cells],
+ * tau_end[nprobe]}: t0 = t_start, t1 = t_out (NaN for a ray that misses),
+ * the crossings after the cut, tau[k][i] the optical depth of channel
+ * channels[k] (nprobe <= 8 of them) after crossing i and tau_end[k] what
+ * the render call returns. The probe has no skips. */
+int cmi_gpu_absorption_probe(cmi_gpu_engine *engine, const double *n,
+                             const double *b, double S, double g,
+                             const double *velocity, const double origin[3],
+                             const double direction[3], double length,
+                             const double *observer_velocity, int32_t nchan,
+                             double vmin, double vmax, int32_t nprobe,
+                             const int32_t *channels, int32_t max_cells,
+                             double *out);
+
 #ifdef __cplusplus
 }
 #endif
