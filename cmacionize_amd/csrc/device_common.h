@@ -507,25 +507,65 @@ struct TrackersDev {
  * LevelFrequencyBins.hpp:84-86 (Utilities::locate, src/Utilities.hpp:726-742:
  * bisection for the last edge below the frequency, the last bin for anything
  * above the upper edge) */
-__host__ __device__ inline int32_t cmi_frequency_bin(const TrackersDev &t,
-                                                     const int k,
-                                                     const double frequency) {
-  if (t.bins_type[k] == CMI_BINS_LEVEL) {
+__host__ __device__ inline int32_t
+cmi_frequency_bin_of(const int32_t bins_type, const int32_t nbins,
+                     const double bins_min, const double bins_max,
+                     const double inverse_frequency_width,
+                     const double *level_edges, const double frequency) {
+  if (bins_type == CMI_BINS_LEVEL) {
     uint32_t jl = 0, ju = CMI_NION + 1;
     while (ju - jl > 1) {
       const uint32_t jm = (ju + jl) >> 1;
-      if (frequency > t.level_edges[jm])
+      if (frequency > level_edges[jm])
         jl = jm;
       else
         ju = jm;
     }
     return jl == CMI_NION ? CMI_NION - 1 : (int32_t)jl;
   }
-  if (frequency < t.bins_min[k])
+  if (frequency < bins_min)
     return 0;
-  if (frequency >= t.bins_max[k])
-    return t.nbins[k] - 1;
-  return (int32_t)((frequency - t.bins_min[k]) * t.inverse_frequency_width[k]);
+  if (frequency >= bins_max)
+    return nbins - 1;
+  return (int32_t)((frequency - bins_min) * inverse_frequency_width);
+}
+__host__ __device__ inline int32_t cmi_frequency_bin(const TrackersDev &t,
+                                                     const int k,
+                                                     const double frequency) {
+  return cmi_frequency_bin_of(t.bins_type[k], t.nbins[k], t.bins_min[k],
+                              t.bins_max[k], t.inverse_frequency_width[k],
+                              t.level_edges, frequency);
+}
+
+/* The escape tally (include/cmi_gpu.h, "escape maps"): every packet that
+ * leaves the whole box adds its weight to
+ * sky[(type nfreq + bin) nlon nmu + pixel], the bin of its frequency by the
+ * weighted spectrum tracker's FrequencyBins, the pixel of its direction d on
+ * an equal-area grid in the frame e_1, e_2, e_3 (the rows of `frame`). */
+struct EscapeDev {
+  double *sky; /* NULL: no tally */
+  int32_t nlon, nmu, nfreq, bins_type;
+  double frame[9];
+  double bins_min, bins_max, inverse_frequency_width;
+  double level_edges[CMI_NION + 1];
+};
+
+/* pixel i nmu + j of a unit vector: mu = d . e_3 in nmu equal steps from -1,
+ * l = atan2(d . e_2, d . e_1) in nlon equal steps from -pi; an edge belongs to
+ * the pixel above it, the upper end of either range to the last pixel */
+__host__ __device__ inline int32_t cmi_escape_pixel(const double *frame,
+                                                    const int32_t nlon,
+                                                    const int32_t nmu,
+                                                    const double d[3]) {
+  const double x = d[0] * frame[0] + d[1] * frame[1] + d[2] * frame[2];
+  const double y = d[0] * frame[3] + d[1] * frame[4] + d[2] * frame[5];
+  const double mu = d[0] * frame[6] + d[1] * frame[7] + d[2] * frame[8];
+  const double l = atan2(y, x);
+  int32_t j = (int32_t)floor((mu + 1.) / 2. * nmu);
+  int32_t i = (int32_t)floor((l + M_PI) / (2. * M_PI) * nlon);
+  j = j < 0 ? 0 : (j > nmu - 1 ? nmu - 1 : j);
+  i = i < 0 ? 0 : (i > nlon - 1 ? nlon - 1 : i);
+  return i * nmu + j;
 }
 
 /* WeightedSpectrumTracker::get_projected_area,
@@ -586,6 +626,17 @@ struct CountersDev {
  * every launch waiting for ~0.4 ms - more than the work of a late tile round.) */
 #define CMI_COUNTER_SHARDS 1024
 static_assert(sizeof(CountersDev) == 64, "one counter shard per 64-B line");
+
+/* The escape tally's description sits in device memory behind the last
+ * counter shard, where every transport kernel finds it through the pointer it
+ * has anyway: the kernels' argument block keeps its size, and with it the
+ * builds that never count - table, pad, pre, the generic incremental ones -
+ * stay instruction for instruction what they were (a longer argument block
+ * moves the hidden arguments behind it, an offset in each of them). The host
+ * keeps sky == NULL there while nothing is to be counted. */
+__host__ __device__ inline EscapeDev *cmi_escape_of(CountersDev *counters) {
+  return reinterpret_cast<EscapeDev *>(counters + CMI_COUNTER_SHARDS);
+}
 
 #ifdef __HIPCC__
 __device__ __forceinline__ CountersDev *counter_shard(CountersDev *counters) {

@@ -157,6 +157,12 @@ struct cmi_gpu_engine {
   /* SpectrumTrackers: counted while enabled (the exact marcher then) */
   TrackersDev trackers = {};
   bool trackers_enabled = false;
+  /* the escape tally (cmi_gpu_set_escape_tally); counted like a tracker */
+  EscapeDev escape = {};
+  /* its copy behind the counters (cmi_escape_of) holds the array's address
+   * (publish_escape); what that copy was written from */
+  bool escape_counting = false;
+  EscapeDev escape_staged = {};
   /* PAD transport kernels: n x_H inside a layer of ghost cells; whether it
    * holds the records of the cells as they are (whatever writes
    * CellsDev::opacity clears this - pad_records_stale - except the update
@@ -1165,9 +1171,13 @@ int cmi_gpu_create(const cmi_gpu_config *config, cmi_gpu_engine **out) {
   }
   HIP_TRY(hipMemsetAsync(e->acc_block, 0, CMI_NACC * field_bytes, e->stream));
   HIP_TRY(hipMalloc(&e->opacity, (size_t)e->ncell * sizeof(double2)));
-  HIP_TRY(hipMalloc(&e->counters, sizeof(CountersDev) * CMI_COUNTER_SHARDS));
+  /* (... and the escape tally's description behind them, cmi_escape_of) */
+  HIP_TRY(hipMalloc(&e->counters, sizeof(CountersDev) * CMI_COUNTER_SHARDS +
+                                      sizeof(EscapeDev)));
   HIP_TRY(hipMemsetAsync(e->counters, 0,
-                         sizeof(CountersDev) * CMI_COUNTER_SHARDS, e->stream));
+                         sizeof(CountersDev) * CMI_COUNTER_SHARDS +
+                             sizeof(EscapeDev),
+                         e->stream));
   HIP_TRY(hipMalloc(&e->tables, sizeof(TablesDev)));
   {
     e->host_tables = new TablesDev;
@@ -1260,6 +1270,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->trackers.counts);
   (void)hipFree(e->trackers.absorption);
   (void)hipFree(e->trackers.flux);
+  (void)hipFree(e->escape.sky);
   (void)hipFree(e->temp_pipe_block);
   (void)hipFree(e->pad_H);
   (void)hipFree(e->metal_gate);
@@ -2330,6 +2341,21 @@ int cmi_gpu_compute_emissivities(cmi_gpu_engine *e, int32_t nlines,
   return CMI_GPU_OK;
 }
 
+/* LevelFrequencyBins::LevelFrequencyBins, src/LevelFrequencyBins.hpp:52-66:
+ * the ionization energies of src/ElementData.hpp:39-105 (Hz) in ascending
+ * order, closed by four times hydrogen's */
+static void level_frequency_edges(double edges[CMI_NION + 1]) {
+  const double energies[CMI_NION] = {
+      3.28810279e+15, 5.94523574e+15, 5.89588678e+15, 1.15792700e+16,
+      3.51435505e+15, 7.15759434e+15, 1.14732262e+16, 3.29284691e+15,
+      8.49136314e+15, 5.21432028e+15, 9.90492110e+15, 5.64310422e+15,
+      8.41222200e+15, 1.14182796e+16};
+  for (int i = 0; i < CMI_NION; ++i)
+    edges[i] = energies[i];
+  std::sort(edges, edges + CMI_NION);
+  edges[CMI_NION] = 4. * energies[ION_H_n];
+}
+
 int cmi_gpu_set_spectrum_trackers(cmi_gpu_engine *e, int32_t n,
                                   const double *positions, int32_t nbins,
                                   const double *opening_angles,
@@ -2394,20 +2420,7 @@ int cmi_gpu_set_trackers(cmi_gpu_engine *e, int32_t n, const double *positions,
       t.inverse_frequency_width[k] = nbins[k] / (t.bins_max[k] - t.bins_min[k]);
     }
   }
-  /* LevelFrequencyBins::LevelFrequencyBins, src/LevelFrequencyBins.hpp:52-66:
-   * the ionization energies of src/ElementData.hpp:39-105 (Hz) in ascending
-   * order, closed by four times hydrogen's */
-  {
-    const double energies[CMI_NION] = {
-        3.28810279e+15, 5.94523574e+15, 5.89588678e+15, 1.15792700e+16,
-        3.51435505e+15, 7.15759434e+15, 1.14732262e+16, 3.29284691e+15,
-        8.49136314e+15, 5.21432028e+15, 9.90492110e+15, 5.64310422e+15,
-        8.41222200e+15, 1.14182796e+16};
-    for (int i = 0; i < CMI_NION; ++i)
-      t.level_edges[i] = energies[i];
-    std::sort(t.level_edges, t.level_edges + CMI_NION);
-    t.level_edges[CMI_NION] = 4. * energies[ION_H_n];
-  }
+  level_frequency_edges(t.level_edges);
   const GridDev &g = e->grid;
   for (int32_t k = 0; k < n; ++k) {
     /* the cell that holds the position (CartesianDensityGrid::get_cell_indices,
@@ -2878,6 +2891,142 @@ static void dust_cube_mark_stale(cmi_gpu_engine *e, const char *why);
 /* the Monte Carlo scattered-light modes: dust images and cubes, the cell
  * source, the sky camera, several views, Lyman alpha */
 #include "scatter_driver.h"
+
+/* ------------------------------------------------------- escape maps -- */
+
+int cmi_gpu_set_escape_tally(cmi_gpu_engine *e, int32_t nlon, int32_t nmu,
+                             const double *frame, int32_t nfreq,
+                             int32_t bins_type, double minimum_frequency,
+                             double maximum_frequency) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (nlon < 0)
+    return fail(CMI_GPU_EINVAL, "set_escape_tally: %d longitude pixels",
+                (int)nlon);
+  EscapeDev s = EscapeDev();
+  if (nlon > 0) {
+    if (nmu < 1 || nfreq < 1 || !frame)
+      return fail(CMI_GPU_EINVAL, "set_escape_tally: %d x %d pixels, %d "
+                  "frequency bins%s", (int)nlon, (int)nmu, (int)nfreq,
+                  frame ? "" : ", no frame");
+    if (3 * (int64_t)nfreq * (int64_t)nlon * (int64_t)nmu > (1ll << 24))
+      return fail(CMI_GPU_EINVAL, "set_escape_tally: 3 x %d bins x %d x %d "
+                  "pixels are more than 2^24 sums", (int)nfreq, (int)nlon,
+                  (int)nmu);
+    if (!sky_frame_is_orthonormal(frame))
+      return fail(CMI_GPU_EINVAL, "set_escape_tally: the frame is not "
+                  "orthonormal to 1e-9");
+    if (bins_type == CMI_BINS_LEVEL) {
+      if (nfreq != CMI_NION)
+        return fail(CMI_GPU_EINVAL, "set_escape_tally: level bins are %d "
+                    "bins, %d asked for", CMI_NION, (int)nfreq);
+    } else if (bins_type == CMI_BINS_LINEAR) {
+      if (!std::isfinite(minimum_frequency) ||
+          !std::isfinite(maximum_frequency) ||
+          !(maximum_frequency > minimum_frequency))
+        return fail(CMI_GPU_EINVAL, "set_escape_tally: empty frequency range");
+      s.bins_min = minimum_frequency;
+      s.bins_max = maximum_frequency;
+      s.inverse_frequency_width =
+          nfreq / (maximum_frequency - minimum_frequency);
+    } else {
+      return fail(CMI_GPU_EINVAL, "Unknown FrequencyBins type: %d",
+                  (int)bins_type);
+    }
+    s.nlon = nlon;
+    s.nmu = nmu;
+    s.nfreq = nfreq;
+    s.bins_type = bins_type;
+    for (int i = 0; i < 9; ++i)
+      s.frame[i] = frame[i];
+    level_frequency_edges(s.level_edges);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  /* (kernels of an earlier call may still add to the old array) */
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  CMI_TRY(publish_escape(e, false));
+  (void)hipFree(e->escape.sky);
+  e->escape = EscapeDev();
+  if (nlon == 0)
+    return CMI_GPU_OK;
+  const size_t bytes = sizeof(double) * 3 * (size_t)nfreq * (size_t)nlon *
+                       (size_t)nmu;
+  if (hipMalloc(&s.sky, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CMI_GPU_ENOMEM, "set_escape_tally: no memory for %zu bytes",
+                bytes);
+  }
+  HIP_TRY(hipMemsetAsync(s.sky, 0, bytes, e->stream));
+  e->escape = s;
+  return CMI_GPU_OK;
+}
+
+static size_t escape_tally_doubles(const cmi_gpu_engine *e) {
+  return 3 * (size_t)e->escape.nfreq * (size_t)e->escape.nlon *
+         (size_t)e->escape.nmu;
+}
+
+int cmi_gpu_reset_escape_tally(cmi_gpu_engine *e) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (!e->escape.sky)
+    return fail(CMI_GPU_ESTATE, "reset_escape_tally: no escape tally set");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemsetAsync(e->escape.sky, 0,
+                         sizeof(double) * escape_tally_doubles(e), e->stream));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_download_escape_tally(cmi_gpu_engine *e, double *sky) {
+  if (!e || !sky)
+    return fail(CMI_GPU_EINVAL, "download_escape_tally: bad argument");
+  if (!e->escape.sky)
+    return fail(CMI_GPU_ESTATE, "download_escape_tally: no escape tally set");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpyAsync(sky, e->escape.sky,
+                         sizeof(double) * escape_tally_doubles(e),
+                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_escape_pixels(const double *frame, int32_t nlon, int32_t nmu,
+                          int64_t n, const double *directions, int32_t *pixels,
+                          double *centres) {
+  if (!frame || nlon < 1 || nmu < 1 || n < 0 ||
+      (n > 0 && (!directions || !pixels)))
+    return fail(CMI_GPU_EINVAL, "escape_pixels: bad argument");
+  if (!sky_frame_is_orthonormal(frame))
+    return fail(CMI_GPU_EINVAL, "escape_pixels: the frame is not orthonormal "
+                "to 1e-9");
+  for (int64_t k = 0; k < n; ++k)
+    pixels[k] = cmi_escape_pixel(frame, nlon, nmu, directions + 3 * k);
+  if (centres) {
+    for (int32_t i = 0; i < nlon; ++i)
+      for (int32_t j = 0; j < nmu; ++j) {
+        const double mu = -1. + (2. * j + 1.) / nmu;
+        const double l = -M_PI + 2. * M_PI * (i + 0.5) / nlon;
+        const double st = std::sqrt(1. - mu * mu);
+        const double c[3] = {st * std::cos(l), st * std::sin(l), mu};
+        double *out = centres + 3 * ((size_t)i * nmu + j);
+        for (int a = 0; a < 3; ++a)
+          out[a] = c[0] * frame[a] + c[1] * frame[3 + a] + c[2] * frame[6 + a];
+      }
+  }
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_cross_sections(cmi_gpu_engine *e, int64_t n,
+                           const double *frequencies, double *sigma) {
+  if (!e || n < 0 || (n > 0 && (!frequencies || !sigma)))
+    return fail(CMI_GPU_EINVAL, "cross_sections: bad argument");
+  if (!e->have_xsec)
+    return fail(CMI_GPU_ESTATE, "cross_sections: set cross sections first");
+  const ModelDev host_model = host_model_of(e);
+  for (int64_t k = 0; k < n; ++k)
+    cmi_cross_sections(host_model, frequencies[k], sigma + CMI_NION * k);
+  return CMI_GPU_OK;
+}
 
 } // extern "C"
 

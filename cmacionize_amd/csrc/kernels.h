@@ -2120,6 +2120,27 @@ __global__ void
               active = false; /* continues in another block */
             }
           }
+          /* the escape tally: the packet has left the WHOLE box (no hand-over,
+           * and a periodic face is never left). One fp64 atomic in a packet's
+           * life; in the builds with the trackers' hook only. (The tally's
+           * description lives behind the counters, not in the arguments: see
+           * cmi_escape_of.) */
+          if constexpr (EXACT || TRACK) {
+            const EscapeDev &s = *cmi_escape_of(a.counters);
+            if (done && s.sky != nullptr && p.type < TYPE_ABSORBED) {
+              const double direction[3] = {p.dir[0], p.dir[1], p.dir[2]};
+              const int32_t bin = cmi_frequency_bin_of(
+                  s.bins_type, s.nfreq, s.bins_min, s.bins_max,
+                  s.inverse_frequency_width, s.level_edges, p.nu);
+              atomic_add_f64(
+                  s.sky +
+                      ((size_t)p.type * (size_t)s.nfreq + (size_t)bin) *
+                          ((size_t)s.nlon * (size_t)s.nmu) +
+                      (size_t)cmi_escape_pixel(s.frame, s.nlon, s.nmu,
+                                               direction),
+                  p.weight);
+            }
+          }
         }
         if (absorbed && a.qout.id != nullptr) {
           /* park the packet for the interaction kernel (PhotonSource::reemit

@@ -349,7 +349,9 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
   const bool small_grid = e->ncell < CMI_FAST_MARCHER_MAX_CELLS;
   p.agg = small_grid ? tune.aggregate : CMI_AGG_NONE;
   p.agg_reemit = small_grid ? tune.aggregate_reemit : CMI_AGG_NONE;
-  p.tracking = e->trackers_enabled && e->trackers.n != 0;
+  /* (a set escape tally counts like a set tracker) */
+  p.tracking = e->trackers_enabled &&
+               (e->trackers.n != 0 || e->escape.sky != nullptr);
   /* (trackers count in the exact marcher on an undivided grid - the counts
    * equal the oracle's one by one - and in the incremental one on the blocks
    * of a decomposed grid, whose hand-overs carry its state) */
@@ -521,6 +523,26 @@ static QueueDev no_queue() {
   QueueDev q;
   memset(&q, 0, sizeof q);
   return q;
+}
+
+/* The escape tally's description on the device (cmi_escape_of) says "count"
+ * exactly while the call's plan tracks: written, in stream order, when that
+ * changes. */
+static int publish_escape(cmi_gpu_engine *e, bool count) {
+  count = count && e->escape.sky != nullptr;
+  if (count == e->escape_counting)
+    return CMI_GPU_OK;
+  e->escape_staged = e->escape;
+  if (!count)
+    e->escape_staged.sky = nullptr;
+  HIP_TRY(hipMemcpyAsync(cmi_escape_of(e->counters), &e->escape_staged,
+                         sizeof(EscapeDev), hipMemcpyHostToDevice,
+                         e->stream));
+  /* (the copy may read its source after the call returns, and the next
+   * change overwrites that source: wait - this happens twice per run) */
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->escape_counting = count;
+  return CMI_GPU_OK;
 }
 
 /* the arguments of the first-generation launch over the ids [done, done +
@@ -1170,6 +1192,7 @@ static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
 
   LaunchPlan plan;
   CMI_TRY(plan_launches(e, n_packets, flights, plan));
+  CMI_TRY(publish_escape(e, plan.tracking));
   const uint64_t max_launch = e->tune.max_packets_per_launch;
   if (!plan.select_mode)
     CMI_TRY(reserve_for(e, plan, n_packets < max_launch ? n_packets

@@ -149,6 +149,9 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_lya_spin_temperature",
     "cmi_gpu_render_field_absorption_spectra",
     "cmi_gpu_render_absorption_spectra", "cmi_gpu_absorption_probe",
+    "cmi_gpu_set_escape_tally", "cmi_gpu_reset_escape_tally",
+    "cmi_gpu_download_escape_tally", "cmi_gpu_escape_pixels",
+    "cmi_gpu_cross_sections",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -403,6 +406,14 @@ def load_library():
     L.cmi_gpu_get_tracker_flux.argtypes = [vp, _dp]
     L.cmi_gpu_projected_areas.argtypes = [_dp, C.c_int64, _dp]
     L.cmi_gpu_get_tracker_counts.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.cmi_gpu_set_escape_tally.argtypes = [
+        vp, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_double,
+        C.c_double]
+    L.cmi_gpu_reset_escape_tally.argtypes = [vp]
+    L.cmi_gpu_download_escape_tally.argtypes = [vp, _dp]
+    L.cmi_gpu_escape_pixels.argtypes = [_dp, C.c_int32, C.c_int32, C.c_int64,
+                                        _dp, C.POINTER(C.c_int32), _dp]
+    L.cmi_gpu_cross_sections.argtypes = [vp, C.c_int64, _dp, _dp]
     L.cmi_gpu_update_cells_range.argtypes = [vp, C.c_uint32, C.c_double,
                                              C.c_int64, C.c_int64]
     L.cmi_gpu_refresh_transport_records.argtypes = [vp]
@@ -709,6 +720,51 @@ def sky_frame(pole=(0., 0., 1.), zero_longitude=(1., 0., 0.)):
     return np.array([e1, np.cross(e3, e1), e3])
 
 
+def escape_pixels(directions, nlon, nmu, frame=IDENTITY_FRAME):
+    """The escape tally's pixel i * nmu + j of unit vectors ([n][3]), by the
+    function the transport kernels call, run on the host (include/cmi_gpu.h,
+    "escape maps")."""
+    d = _f64(directions).reshape(-1, 3)
+    out = np.zeros(len(d), dtype=np.int32)
+    L = load_library()
+    rc = L.cmi_gpu_escape_pixels(
+        _p(_f64(frame).reshape(9)), int(nlon), int(nmu), len(d), _p(d),
+        out.ctypes.data_as(C.POINTER(C.c_int32)), None)
+    if rc != 0:
+        raise EngineError("cmi_gpu error %d: %s" % (
+            rc, L.cmi_gpu_last_error().decode()))
+    return out
+
+
+def escape_pixel_centres(nlon, nmu, frame=IDENTITY_FRAME):
+    """The unit vectors (nlon, nmu, 3) of the escape tally's pixel centres."""
+    out = np.zeros((int(nlon), int(nmu), 3))
+    L = load_library()
+    rc = L.cmi_gpu_escape_pixels(
+        _p(_f64(frame).reshape(9)), int(nlon), int(nmu), 0, None, None,
+        _p(out))
+    if rc != 0:
+        raise EngineError("cmi_gpu error %d: %s" % (
+            rc, L.cmi_gpu_last_error().decode()))
+    return out
+
+
+def escape_fraction_map(tally, totweight):
+    """The escaping luminosity per steradian in units of L / 4 pi, (nlon,
+    nmu): an escape tally (3, nfreq, nlon, nmu) summed over types and bins,
+    times the number of pixels over the total weight of the packets. Its mean
+    is the escape fraction."""
+    t = np.asarray(tally, dtype=np.float64)
+    return t.sum(axis=(0, 1)) * (t.shape[2] * t.shape[3]) / totweight
+
+
+def escape_spectrum(tally, totweight, luminosity):
+    """Escaping photons s^-1 per type and frequency bin, (3, nfreq), of a
+    source of `luminosity` photons s^-1."""
+    t = np.asarray(tally, dtype=np.float64)
+    return t.sum(axis=(2, 3)) * (luminosity / totweight)
+
+
 def check_sky_camera(box_anchor, box_sides, origin, nlon, nlat,
                      exclusion_radius, lon_range=FULL_SKY_LONGITUDE,
                      lat_range=FULL_SKY_LATITUDE, frame=IDENTITY_FRAME):
@@ -827,6 +883,8 @@ class GpuEngine:
         self.cube_channels = 0  # set_scattered_cube's nchan; 0: off
         self.lya_channels = 0  # set_lyman_alpha's nchan; 0: off
         self.lya_x_crit = 0.
+        self._abundances = np.zeros(6)  # He, C, N, O, Ne, S per hydrogen
+        self._escape = None  # set_escape_tally's (nfreq, nlon, nmu)
         self.cell_volume = float(np.prod([float(sides[a]) / int(ncell[a])
                                           for a in range(3)]))  # m^3
         # tests, bench and tools read device timings; the engine records them
@@ -939,6 +997,7 @@ class GpuEngine:
         a = _f64(abundances)
         assert a.shape == (6,)
         self._check(self._lib.cmi_gpu_set_abundances(self._h, _p(a)))
+        self._abundances = a.copy()
 
     def set_reemission(self, kind, probability=0., frequency=0.):
         self._check(self._lib.cmi_gpu_set_reemission(self._h, kind,
@@ -1195,6 +1254,67 @@ class GpuEngine:
         if len(set(bins)) <= 1:
             return np.array(out).reshape(n, 3, bins[0] if bins else 0)
         return out
+
+    # escape maps ------------------------------------------------------------
+    def set_escape_tally(self, nlon, nmu, frame=IDENTITY_FRAME, nfreq=1,
+                         bins="Linear", minimum_frequency=3.289e15,
+                         maximum_frequency=4. * 3.289e15):
+        """A tally of the packets that leave the whole box, by photon type,
+        frequency bin ("Linear": nfreq bins between the two frequencies;
+        "Level": the 14 level bins) and the equal-area pixel of their
+        direction in `frame` (include/cmi_gpu.h, "escape maps"). Counts while
+        trackers are enabled. nlon = 0 removes it."""
+        kind = {"Linear": 0, "Level": 1}[bins]
+        if kind == 1:
+            nfreq = NION
+        self._check(self._lib.cmi_gpu_set_escape_tally(
+            self._h, int(nlon), int(nmu), _p(_f64(frame).reshape(9)),
+            int(nfreq), kind, minimum_frequency, maximum_frequency))
+        self._escape = (int(nfreq), int(nlon), int(nmu)) if nlon else None
+
+    def reset_escape_tally(self):
+        self._check(self._lib.cmi_gpu_reset_escape_tally(self._h))
+
+    def escape_tally(self):
+        """The sums (3, nfreq, nlon, nmu) in packet weight since the tally
+        was set or reset."""
+        shape = self._escape if self._escape is not None else (1, 1, 1)
+        out = np.zeros((3,) + shape)
+        self._check(self._lib.cmi_gpu_download_escape_tally(self._h, _p(out)))
+        return out
+
+    def cross_sections(self, frequencies):
+        """The engine's cross sections (n, 14) in m^2 at frequencies in Hz."""
+        nu = _f64(frequencies).reshape(-1)
+        out = np.zeros((len(nu), NION))
+        self._check(self._lib.cmi_gpu_cross_sections(self._h, len(nu), _p(nu),
+                                                     _p(out)))
+        return out
+
+    def ionizing_columns(self, origin, directions):
+        """Column densities N[ray][ion] (m^-2) of the 14 ions from `origin`
+        (m) along the unit vectors directions[nrays][3] to the edge of the
+        box, from the state on the device: the hydrogen density times the
+        element's abundance times the ionic fraction, through
+        render_field_sky (whose surface brightness is the line integral over
+        4 pi; like it, not for periodic boxes or blocks of a decomposed
+        grid)."""
+        n_H = self.download_field(FIELD_NUMBER_DENSITY)
+        abundance = {"H": 1.}
+        abundance.update(zip(("He", "C", "N", "O", "Ne", "S"),
+                             self._abundances))
+        fields = np.empty((NION, self.n))
+        for ion in range(NION):
+            fields[ion] = (n_H * abundance[_ION_ELEMENTS[ion]] *
+                           self.download_field(FIELD_IONIC_FRACTION + ion))
+        return np.ascontiguousarray(
+            4. * np.pi * self.render_field_sky(fields, origin, directions).T)
+
+    def ionizing_optical_depths(self, origin, directions, frequencies):
+        """tau[ray][frequency] of the ionizing continuum from `origin` to the
+        edge of the box: ionizing_columns @ cross_sections."""
+        return (self.ionizing_columns(origin, directions) @
+                self.cross_sections(frequencies).T)
 
     def set_tuning(self, **kw):
         for k, v in kw.items():

@@ -872,6 +872,190 @@ public:
   }
 };
 
+/* The optional "EscapeTally:" block: the ionizing packets that leave the box
+ * in the last iteration, by photon type, frequency bin and direction
+ * (include/cmi_gpu.h, "escape maps"; no counterpart in the reference).
+ *   EscapeTally:number of longitude pixels       12
+ *   EscapeTally:number of mu pixels              6
+ *   EscapeTally:frame pole                       [0, 0, 1]
+ *   EscapeTally:frame zero longitude             [1, 0, 0]
+ *       (the EmissionSkyMaps: keys and their orthogonalisation)
+ *   EscapeTally:FrequencyBins:type               Linear (or Level)
+ *   EscapeTally:FrequencyBins:number of bins     1
+ *   EscapeTally:FrequencyBins:minimum frequency  13.6 eV
+ *   EscapeTally:FrequencyBins:maximum frequency  54.4 eV
+ *       (a weighted spectrum tracker's FrequencyBins)
+ *   EscapeTally:output name                      escape_tally
+ * The tally counts with the trackers' switch, in the last iteration. The run
+ * writes <output name>.dat - raw doubles [type][bin][i][j], photons s^-1 per
+ * pixel - and <output name>.txt - the total escape fraction, those per type
+ * and per bin, and the bin edges in Hz. */
+class EscapeTally {
+public:
+  int32_t nlon, nmu, nfreq, bins_type;
+  double frame[9];
+  double minimum_frequency, maximum_frequency;
+  std::string output_name;
+
+  explicit EscapeTally(ParameterFile &params) {
+    const long long lon =
+        params.get_integer("EscapeTally:number of longitude pixels", 12);
+    const long long mu = params.get_integer("EscapeTally:number of mu pixels", 6);
+    const std::array<double, 3> pole =
+        params.get_double_vector("EscapeTally:frame pole", {0., 0., 1.});
+    const std::array<double, 3> zero = params.get_double_vector(
+        "EscapeTally:frame zero longitude", {1., 0., 0.});
+    const std::string bt =
+        params.get_string("EscapeTally:FrequencyBins:type", "Linear");
+    long long bins = NUMBER_OF_IONNAMES;
+    minimum_frequency = maximum_frequency = 0.;
+    if (bt == "Level") {
+      bins_type = CMI_GPU_FREQUENCY_BINS_LEVEL;
+    } else if (bt == "Linear") {
+      bins_type = CMI_GPU_FREQUENCY_BINS_LINEAR;
+      bins = params.get_integer("EscapeTally:FrequencyBins:number of bins", 1);
+      minimum_frequency = params.get_physical_value(
+          QUANTITY_FREQUENCY, "EscapeTally:FrequencyBins:minimum frequency",
+          "13.6 eV");
+      maximum_frequency = params.get_physical_value(
+          QUANTITY_FREQUENCY, "EscapeTally:FrequencyBins:maximum frequency",
+          "54.4 eV");
+      if (!(maximum_frequency > minimum_frequency))
+        throw ParameterError("EscapeTally:FrequencyBins: empty frequency "
+                             "range");
+    } else {
+      throw ParameterError("Unknown FrequencyBins type: \"" + bt + "\".");
+    }
+    output_name = params.get_string("EscapeTally:output name", "escape_tally");
+    if (lon < 1 || mu < 1 || bins < 1 ||
+        3 * bins * lon * mu > (1ll << 24) || lon > (1ll << 24) ||
+        mu > (1ll << 24) || bins > (1ll << 24))
+      throw ParameterError(
+          "EscapeTally: the numbers of longitude pixels, mu pixels and bins "
+          "must be positive and 3 x bins x pixels at most 2^24");
+    nlon = (int32_t)lon;
+    nmu = (int32_t)mu;
+    nfreq = (int32_t)bins;
+    /* Gram-Schmidt as for the sky maps: e_3 = the pole, e_1 = the zero of
+     * longitude made perpendicular to it, e_2 = e_3 x e_1 */
+    double e3[3], e1[3];
+    double norm = std::sqrt(pole[0] * pole[0] + pole[1] * pole[1] +
+                            pole[2] * pole[2]);
+    const double zero_norm = std::sqrt(zero[0] * zero[0] + zero[1] * zero[1] +
+                                       zero[2] * zero[2]);
+    if (!(norm > 0.) || !std::isfinite(norm) || !(zero_norm > 0.) ||
+        !std::isfinite(zero_norm))
+      throw ParameterError("EscapeTally:frame pole and frame zero longitude "
+                           "must be finite vectors, not zero");
+    for (int a = 0; a < 3; ++a)
+      e3[a] = pole[a] / norm;
+    const double along = zero[0] * e3[0] + zero[1] * e3[1] + zero[2] * e3[2];
+    for (int a = 0; a < 3; ++a)
+      e1[a] = zero[a] - along * e3[a];
+    norm = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+    if (!(norm > 1.e-8 * zero_norm))
+      throw ParameterError("EscapeTally:frame pole and frame zero longitude "
+                           "are parallel");
+    for (int a = 0; a < 3; ++a)
+      e1[a] /= norm;
+    const double e2[3] = {e3[1] * e1[2] - e3[2] * e1[1],
+                          e3[2] * e1[0] - e3[0] * e1[2],
+                          e3[0] * e1[1] - e3[1] * e1[0]};
+    for (int a = 0; a < 3; ++a) {
+      frame[a] = e1[a];
+      frame[3 + a] = e2[a];
+      frame[6 + a] = e3[a];
+    }
+  }
+
+  size_t size() const { return 3 * (size_t)nfreq * (size_t)nlon * (size_t)nmu; }
+
+  int lower(cmi_gpu_engine *engine) const {
+    int rc = cmi_gpu_set_escape_tally(engine, nlon, nmu, frame, nfreq,
+                                      bins_type, minimum_frequency,
+                                      maximum_frequency);
+    if (rc == CMI_GPU_OK)
+      rc = cmi_gpu_enable_trackers(engine, 1);
+    return rc;
+  }
+
+  /* adds the engine's sums to `sky` (blocks and replicas add up) */
+  int collect(cmi_gpu_engine *engine, std::vector<double> &sky) const {
+    std::vector<double> part(size());
+    const int rc = cmi_gpu_download_escape_tally(engine, part.data());
+    if (rc != CMI_GPU_OK)
+      return rc;
+    sky.resize(size(), 0.);
+    for (size_t k = 0; k < part.size(); ++k)
+      sky[k] += part[k];
+    return cmi_gpu_set_escape_tally(engine, 0, 0, nullptr, 0, 0, 0., 0.);
+  }
+
+  /* the edges of the bins in Hz: nfreq + 1 values */
+  std::vector<double> bin_edges() const {
+    std::vector<double> edges;
+    if (bins_type == CMI_GPU_FREQUENCY_BINS_LEVEL) {
+      /* src/LevelFrequencyBins.hpp:52-66 */
+      for (int ion = 0; ion < NUMBER_OF_IONNAMES; ++ion)
+        edges.push_back(ionization_energy_Hz[ion]);
+      std::sort(edges.begin(), edges.end());
+      edges.push_back(4. * ionization_energy_Hz[0]);
+    } else {
+      for (int32_t k = 0; k <= nfreq; ++k)
+        edges.push_back(minimum_frequency +
+                        (maximum_frequency - minimum_frequency) * k / nfreq);
+    }
+    return edges;
+  }
+
+  /* sky in packet weight -> the two files */
+  void output(const std::vector<double> &sky, double totweight,
+              double luminosity) const {
+    const size_t npix = (size_t)nlon * (size_t)nmu;
+    std::vector<double> scaled(sky.size());
+    std::vector<double> by_type(3, 0.), by_bin((size_t)nfreq, 0.);
+    double total = 0.;
+    for (size_t t = 0; t < 3; ++t)
+      for (size_t b = 0; b < (size_t)nfreq; ++b)
+        for (size_t k = 0; k < npix; ++k) {
+          const double w = sky[(t * (size_t)nfreq + b) * npix + k];
+          scaled[(t * (size_t)nfreq + b) * npix + k] =
+              w * (luminosity / totweight);
+          by_type[t] += w;
+          by_bin[b] += w;
+          total += w;
+        }
+    std::ofstream dat(output_name + ".dat", std::ios::binary);
+    dat.write(reinterpret_cast<const char *>(scaled.data()),
+              (std::streamsize)(sizeof(double) * scaled.size()));
+    std::ofstream txt(output_name + ".txt");
+    txt.precision(17);
+    txt << "# escape tally: [type (3)][bin (" << nfreq << ")][longitude ("
+        << nlon << ")][mu (" << nmu << ")], photons s^-1 per pixel of "
+        << "4 pi / " << npix << " sr\n";
+    txt << "total escape fraction:\t" << total / totweight << "\n";
+    txt << "type escape fractions:";
+    for (double v : by_type)
+      txt << "\t" << v / totweight;
+    txt << "\nbin escape fractions:";
+    for (double v : by_bin)
+      txt << "\t" << v / totweight;
+    txt << "\nbin edges (Hz):";
+    for (double v : bin_edges())
+      txt << "\t" << v;
+    txt << "\n";
+  }
+
+private:
+  /* src/ElementData.hpp:39-105 */
+  static constexpr double ionization_energy_Hz[NUMBER_OF_IONNAMES] = {
+      3.28810279e+15, 5.94523574e+15, 5.89588678e+15, 1.15792700e+16,
+      3.51435505e+15, 7.15759434e+15, 1.14732262e+16, 3.29284691e+15,
+      8.49136314e+15, 5.21432028e+15, 9.90492110e+15, 5.64310422e+15,
+      8.41222200e+15, 1.14182796e+16};
+};
+
+
 class GpuIonizationSimulation {
   const bool _every_iteration_output;
   const bool _output_statistics;
@@ -1161,6 +1345,7 @@ class GpuIonizationSimulation {
    * snapshot as the same datasets. */
   std::vector<int32_t> _emission_lines;
   std::unique_ptr<TrackerManager> _trackers;
+  std::unique_ptr<EscapeTally> _escape_tally;
 
   template <typename F> void for_each_engine(F f) {
     if (decomposed()) {
@@ -1345,6 +1530,8 @@ public:
     /* src/IonizationSimulation.cpp:208-213 */
     if (_parameter_file.get_bool("IonizationSimulation:enable trackers", false))
       _trackers.reset(new TrackerManager(_parameter_file));
+    if (_parameter_file.has_block("EscapeTally"))
+      _escape_tally.reset(new EscapeTally(_parameter_file));
 
     /* all parameters read: dump them (src/IonizationSimulation.cpp:218-226) */
     if (write_output) {
@@ -1631,6 +1818,7 @@ public:
   CrossSections *cross_sections() { return _cross_sections.get(); }
   RecombinationRates *recombination_rates() { return _recombination_rates.get(); }
   int32_t random_seed() const { return _random_seed; }
+  const EscapeTally *escape_tally() const { return _escape_tally.get(); }
 
   /* IonizationSimulation::initialize, src/IonizationSimulation.cpp:239-325:
    * evaluate the DensityFunction on every cell (host), upload SoA arrays */
@@ -1708,6 +1896,10 @@ public:
         });
         lnumphoton = std::max(lnumphoton, _trackers->get_number_of_photons());
       }
+      if (_escape_tally && loop == _number_of_iterations - 1)
+        for_each_engine([&](cmi_gpu_engine *e) {
+          check(_escape_tally->lower(e), "set_escape_tally");
+        });
 
       status("Start shooting " + std::to_string(lnumphoton) + " photons...");
       auto t0 = std::chrono::steady_clock::now();
@@ -1790,6 +1982,16 @@ public:
       /* src/IonizationSimulation.cpp:621-624 */
       _trackers->normalize(total_luminosity() / _last_totweight);
       _trackers->output_trackers();
+    }
+    if (_escape_tally && _number_of_iterations > 0) {
+      std::vector<double> sky;
+      for_each_engine([&](cmi_gpu_engine *e) {
+        check(_escape_tally->collect(e, sky), "download_escape_tally");
+        check(cmi_gpu_enable_trackers(e, 0), "enable_trackers");
+      });
+      _escape_tally->output(sky, _last_totweight, total_luminosity());
+      status("Wrote the escape tally to " + _escape_tally->output_name +
+             ".dat and .txt.");
     }
     download_state();
     compute_emissivities();

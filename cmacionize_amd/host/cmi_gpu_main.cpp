@@ -123,7 +123,21 @@ static void describe(GpuIonizationSimulation &sim) {
             << ", \"cr_limit\": " << t.cosmic_ray_heating_limit
             << ", \"cr_scale\": " << t.cosmic_ray_heating_scale_length
             << ", \"T_min_ionized\": " << t.minimum_ionized_temperature
-            << "}\n}\n";
+            << "}";
+  if (const EscapeTally *esc = sim.escape_tally()) {
+    std::cout << ",\n  \"escape_tally\": {\"nlon\": " << esc->nlon
+              << ", \"nmu\": " << esc->nmu << ", \"frame\": [";
+    for (int i = 0; i < 9; ++i)
+      std::cout << (i ? ", " : "") << esc->frame[i];
+    std::cout << "], \"bins\": \""
+              << (esc->bins_type == CMI_GPU_FREQUENCY_BINS_LEVEL ? "Level"
+                                                                 : "Linear")
+              << "\", \"nfreq\": " << esc->nfreq
+              << ", \"minimum_frequency\": " << esc->minimum_frequency
+              << ", \"maximum_frequency\": " << esc->maximum_frequency
+              << ", \"output_name\": \"" << esc->output_name << "\"}";
+  }
+  std::cout << "\n}\n";
 }
 
 int main(int argc, char **argv) {

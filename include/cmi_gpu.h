@@ -534,6 +534,66 @@ int cmi_gpu_get_tracker_absorption(cmi_gpu_engine *engine,
  * Synchronous. */
 int cmi_gpu_get_tracker_counts(cmi_gpu_engine *engine, uint64_t *counts);
 
+/* ---- escape maps: the ionizing packets that leave the box, by direction ----
+ * (no counterpart in the reference, whose trackers sit in cells.) A tally
+ * sky[3][nfreq][nlon * nmu] of doubles on the device. While trackers are
+ * enabled (cmi_gpu_enable_trackers: the one switch of the last iteration),
+ * every packet whose flight ends because it has left the WHOLE box - the
+ * packets cmi_gpu_get_counters counts in typecount[0..2] - adds its weight,
+ * once, to
+ *     sky[(type * nfreq + bin) * nlon * nmu + i * nmu + j]
+ * type: 0 primary, 1 diffuse H I, 2 diffuse He I (src/PhotonType.hpp:36-50).
+ * bin: that of the packet's frequency by the weighted spectrum tracker's
+ *   FrequencyBins: CMI_GPU_FREQUENCY_BINS_LINEAR nfreq bins between
+ *   minimum_frequency and maximum_frequency (Hz), frequencies outside in the
+ *   first / last; CMI_GPU_FREQUENCY_BINS_LEVEL the 14 level bins (nfreq must
+ *   be 14, the two frequencies are ignored).
+ * (i, j): the pixel of the packet's direction of travel d on an equal-area
+ *   grid in the frame e_1, e_2, e_3 - frame[9] holds them as rows, the sky
+ *   maps' convention, orthonormal to 1e-9 -:
+ *     mu = d . e_3,                    j = min(nmu - 1, floor((mu + 1) / 2 * nmu))
+ *     l = atan2(d . e_2, d . e_1),     i = min(nlon - 1, floor((l + pi) / (2 pi) * nlon))
+ *   Every pixel covers 4 pi / (nlon nmu) sr; a direction on an edge belongs to
+ *   the pixel above it. The pixel says where a distant observer who receives
+ *   the packet sits (in direction +d from the box), not a line of sight from
+ *   inside. With an even nmu and e_3 a disc's normal the hemispheres separate
+ *   exactly.
+ * The unit is packet weight, not normalised: sky * luminosity / totweight is
+ * photons s^-1 per pixel, bin and type. On a block of a decomposed grid a
+ * hand-over to another block is no escape, and a periodic face is never
+ * left; the blocks' arrays add up to the undivided grid's (the caller adds
+ * them, over ranks too). While the tally counts, transport is routed as with
+ * a tracker set: the exact marcher on an undivided grid, the incremental
+ * marcher's tracker builds on a block; without it, or with trackers disabled,
+ * nothing changes.
+ * nlon == 0 removes the tally. CMI_GPU_EINVAL for a negative size, nmu or
+ * nfreq < 1 with nlon > 0, 3 * nfreq * nlon * nmu > 2^24, level bins with
+ * nfreq != 14, an empty linear range, a frame that is not orthonormal.
+ * Setting zeroes the sums. */
+int cmi_gpu_set_escape_tally(cmi_gpu_engine *engine, int32_t nlon, int32_t nmu,
+                             const double frame[9], int32_t nfreq,
+                             int32_t bins_type, double minimum_frequency,
+                             double maximum_frequency);
+/* zeroes the sums; CMI_GPU_ESTATE without a tally */
+int cmi_gpu_reset_escape_tally(cmi_gpu_engine *engine);
+/* sky[3 * nfreq * nlon * nmu] to the host. Synchronous. CMI_GPU_ESTATE without
+ * a tally. */
+int cmi_gpu_download_escape_tally(cmi_gpu_engine *engine, double *sky);
+/* Host only: the kernel's binning function for n directions (unit vectors
+ * directions[n][3] -> pixels[n] = i * nmu + j; either may be NULL with n = 0),
+ * and / or the unit vectors centres[nlon * nmu][3] of the pixel centres
+ * (mu = -1 + (2 j + 1) / nmu, l = -pi + 2 pi (i + 0.5) / nlon; NULL: not
+ * wanted). CMI_GPU_EINVAL for nlon or nmu < 1 or a frame that is not
+ * orthonormal. */
+int cmi_gpu_escape_pixels(const double frame[9], int32_t nlon, int32_t nmu,
+                          int64_t n, const double *directions, int32_t *pixels,
+                          double *centres);
+/* sigma[n][14] (m^2): the engine's configured cross sections (fixed, Verner or
+ * table) at n frequencies (Hz), by the function the emission code uses, run on
+ * the host. CMI_GPU_ESTATE before cross sections are set. */
+int cmi_gpu_cross_sections(cmi_gpu_engine *engine, int64_t n,
+                           const double *frequencies, double *sigma);
+
 /* Performance knobs (no effect on what is computed, only on how):
  *   "sort_packets" (1)      process the packets of a launch in emission-
  *                           direction order, so that the lanes of a wave cross
