@@ -14,11 +14,10 @@
 #define CMI_NEMISSIONLINE 42
 #define CMI_NLINESTRENGTH (10 * CMI_LC_NFIVE_DEV + CMI_LC_NTWO_DEV)
 
-/* ions of the line-cooling data (src/LineCoolingData.hpp) and transitions of
- * a five-level ion (:87-114) */
+/* ions of the line-cooling data (cmi_lc_ion, device_thermal.h) and
+ * transitions of a five-level ion (src/LineCoolingData.hpp:87-114) */
 namespace cmi_em {
-enum { NI = 0, NII, OI, OII, OIII, NeIII, SII, SIII, CII, CIII, NIII, NeII,
-       SIV };
+using namespace cmi_lc_ion;
 enum { T01 = 0, T02, T03, T04, T12, T13, T14, T23, T24, T34 };
 /* src/EmissivityValues.hpp:36-81 */
 enum {
@@ -218,22 +217,8 @@ __device__ inline void cell_emissivities(const ModelDev &m, double ntot,
   const double nhp = ntot * (1. - x[ION_H_n]);
   const double nhep = ntot * (1. - x[ION_He_n]) * AHe;
   const double ne = nhp + nhep;
-  const double AC = m.abundance[1], AN = m.abundance[2], AO = m.abundance[3],
-               ANe = m.abundance[4], AS = m.abundance[5];
   double abund[13];
-  abund[CII] = AC * (1. - x[ION_C_p1] - x[ION_C_p2]);
-  abund[CIII] = AC * x[ION_C_p1];
-  abund[NI] = AN * (1. - x[ION_N_n] - x[ION_N_p1] - x[ION_N_p2]);
-  abund[NII] = AN * x[ION_N_n];
-  abund[NIII] = AN * x[ION_N_p1];
-  abund[OI] = AO * (1. - x[ION_O_n] - x[ION_O_p1]);
-  abund[OII] = AO * x[ION_O_n];
-  abund[OIII] = AO * x[ION_O_p1];
-  abund[NeII] = ANe * x[ION_Ne_n];
-  abund[NeIII] = ANe * x[ION_Ne_p1];
-  abund[SII] = AS * (1. - x[ION_S_p1] - x[ION_S_p2] - x[ION_S_p3]);
-  abund[SIII] = AS * x[ION_S_p1];
-  abund[SIV] = AS * x[ION_S_p2];
+  balance_abundances(m, x, abund, 1);
 
   double strength[CMI_NLINESTRENGTH];
   line_strengths(m.tables->lc, T, ne, abund, strength);

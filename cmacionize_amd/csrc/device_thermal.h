@@ -1,10 +1,26 @@
 /*
  * device_thermal.h - line cooling and the thermal balance of one cell.
+ *
+ * The balance and the secant step are stated once, in pieces (balance_head,
+ * balance_abundances, balance_continuum_losses, balance_close, lc_ion_term,
+ * temperature_step_finish), because the solve exists in several device forms
+ * that must agree bit for bit: temperature_kernel and thermal_probe_kernel
+ * evaluate a balance whole on one lane (cooling_and_heating_balance), the
+ * kernels of temperature_pipeline.h split it over launches and over lanes.
+ * All of them call the same pieces; only the order of the additions into
+ * gain, loss and cooling counts, and the pieces fix it.
  */
 #ifndef CMI_DEVICE_THERMAL_H
 #define CMI_DEVICE_THERMAL_H
 
 #include "device_physics.h"
+
+/* ions of the line-cooling data (src/LineCoolingData.hpp): ten five-level
+ * ions, then three two-level ions */
+namespace cmi_lc_ion {
+enum { NI = 0, NII, OI, OII, OIII, NeIII, SII, SIII, CII, CIII, NIII, NeII,
+       SIV };
+}
 
 /* transition (lower i, upper j) -> index of the 10-entry transition tables */
 __device__ __forceinline__ constexpr int lc_tr(int i, int j) {
@@ -228,6 +244,39 @@ lc_two_level_cooling(const LineCoolingDev &lc, int i, double prefactor,
   return pop;
 }
 
+/* what the line cooling of one evaluation depends on besides the ion */
+struct LineCoolingPoint {
+  double prefactor, temperature, Tinv, logT;
+};
+__device__ __forceinline__ LineCoolingPoint
+lc_point(const LineCoolingDev &lc, double temperature,
+         double electron_density) {
+  LineCoolingPoint p;
+  p.prefactor = lc.prefactor * electron_density / sqrt(temperature);
+  p.temperature = temperature;
+  p.Tinv = 1. / temperature;
+  p.logT = log(temperature);
+  return p;
+}
+
+/* the line cooling of a gas without electrons (the reference's value) */
+#define CMI_LC_NO_ELECTRONS 1.e-99
+
+/* the cooling term of ion e < 13 (cmi_lc_ion) with number fraction abund */
+__device__ __forceinline__ double lc_ion_term(const LineCoolingDev &lc, int e,
+                                              double abund,
+                                              const LineCoolingPoint &p) {
+  const double kb = CMI_BOLTZMANN;
+  if (e < CMI_LC_NFIVE_DEV)
+    return abund * kb *
+           lc_five_level_cooling(lc, e, p.prefactor, p.temperature, p.Tinv,
+                                 p.logT);
+  const int i = e - CMI_LC_NFIVE_DEV;
+  return abund * kb * lc.two_energy[i] * lc.two_A[i] *
+         lc_two_level_cooling(lc, i, p.prefactor, p.temperature, p.Tinv,
+                              p.logT);
+}
+
 /* (the body, for a kernel that wants it in its own register budget:
  * temp_linecool_kernel; everybody else calls line_cooling below) */
 __device__ __forceinline__ double
@@ -235,11 +284,8 @@ line_cooling_inlined(const LineCoolingDev &lc, double temperature,
                      double electron_density, const double *abund,
                      int abund_stride) {
   if (electron_density == 0.)
-    return 1.e-99;
-  const double kb = CMI_BOLTZMANN;
-  const double prefactor = lc.prefactor * electron_density / sqrt(temperature);
-  const double Tinv = 1. / temperature;
-  const double logT = log(temperature);
+    return CMI_LC_NO_ELECTRONS;
+  const LineCoolingPoint p = lc_point(lc, temperature, electron_density);
 
   double cooling = 0.;
   /* (one loop body for the ten ions: unrolled, the ~300 exp() expansions of a
@@ -248,13 +294,11 @@ line_cooling_inlined(const LineCoolingDev &lc, double temperature,
    * cache) */
 #pragma unroll 1
   for (int e = 0; e < CMI_LC_NFIVE_DEV; ++e)
-    cooling += abund[e * abund_stride] * kb *
-               lc_five_level_cooling(lc, e, prefactor, temperature, Tinv, logT);
+    cooling += lc_ion_term(lc, e, abund[e * abund_stride], p);
 #pragma unroll 1
   for (int i = 0; i < CMI_LC_NTWO_DEV; ++i)
-    cooling += abund[(CMI_LC_NFIVE_DEV + i) * abund_stride] * kb *
-               lc.two_energy[i] * lc.two_A[i] *
-               lc_two_level_cooling(lc, i, prefactor, temperature, Tinv, logT);
+    cooling += lc_ion_term(lc, CMI_LC_NFIVE_DEV + i,
+                           abund[(CMI_LC_NFIVE_DEV + i) * abund_stride], p);
   return cooling;
 }
 
@@ -285,50 +329,61 @@ struct CellIntegrals {
 };
 
 /* TemperatureCalculator::compute_cooling_and_heating_balance,
- * src/TemperatureCalculator.cpp:207-501. j: normalised mean intensities,
- * h[2]: normalised heating terms; x[2..13] receive the metal fractions at
- * temperature T; abund / abund_stride: 13 doubles of work space
- * (line_cooling). */
-__device__ inline void cooling_and_heating_balance(
-    const ModelDev &m, double &h0, double &he0, double &gain, double &loss,
-    double T, double n, double midpoint_z, const CellIntegrals &j,
-    const double h[2], double x[CMI_NION], double *abund, int abund_stride) {
-  enum { NI = 0, NII, OI, OII, OIII, NeIII, SII, SIII, CII, CIII, NIII, NeII,
-         SIV };
+ * src/TemperatureCalculator.cpp:207-501, in pieces. Its head: the hydrogen
+ * and helium balance at temperature T, the densities that follow from it and
+ * the four gain terms (j: normalised mean intensities, h[2]: normalised
+ * heating terms) ... */
+struct BalanceHead {
+  double T4, sqrtT, logT;
+  double h0, he0, gain;
+  double ne, nhp, nhep, nenhp, nenhep, nh0, nhe0;
+};
+__device__ __forceinline__ BalanceHead
+balance_head(const ModelDev &m, double T, double n, double midpoint_z,
+             const CellIntegrals &j, const double h[2]) {
+  BalanceHead b;
   const double alphaH = cmi_recombination_rate(m, ION_H_n, T);
   const double alphaHe = cmi_recombination_rate(m, ION_He_n, T);
-  const double T4 = T * 1.e-4;
-  const double sqrtT = sqrt(T);
-  const double logT = log(T);
+  b.T4 = T * 1.e-4;
+  b.sqrtT = sqrt(T);
+  b.logT = log(T);
   const double AHe = m.abundance[0];
 
   cmi_ionization_states_hydrogen_helium(alphaH, alphaHe, j(ION_H_n),
-                                        j(ION_He_n), n, AHe, T, h0, he0);
-  const double ne = n * (1. - h0 + AHe * (1. - he0));
-  const double nhp = n * (1. - h0);
-  const double nhep = (1. - he0) * n * AHe;
-  const double nenhp = ne * nhp;
-  const double nenhep = ne * nhep;
+                                        j(ION_He_n), n, AHe, T, b.h0, b.he0);
+  b.ne = n * (1. - b.h0 + AHe * (1. - b.he0));
+  b.nhp = n * (1. - b.h0);
+  b.nhep = (1. - b.he0) * n * AHe;
+  b.nenhp = b.ne * b.nhp;
+  b.nenhep = b.ne * b.nhep;
 
-  gain = n * (h[0] * h0 + h[1] * AHe * he0);
+  b.gain = n * (h[0] * b.h0 + h[1] * AHe * b.he0);
   /* T4^-0.861 and T^0.3647 from the logarithm at hand (ln 1e4 = 9.2103...) */
   const double alpha_e_2sP =
-      4.17e-20 * exp(-0.861 * (logT - 9.210340371976184));
-  const double pHots = 1. / (1. + 77. * he0 / (sqrtT * h0));
-  gain += pHots * 1.21765423e-18 * alpha_e_2sP * nenhep;
-  gain += 1.5e-37 * n * ne * m.pahfac;
+      4.17e-20 * exp(-0.861 * (b.logT - 9.210340371976184));
+  const double pHots = 1. / (1. + 77. * b.he0 / (b.sqrtT * b.h0));
+  b.gain += pHots * 1.21765423e-18 * alpha_e_2sP * b.nenhep;
+  b.gain += 1.5e-37 * n * b.ne * m.pahfac;
   double heatcr = 0.;
   if (m.crfac > 0.) {
-    heatcr = m.crfac * 1.2e-25 / sqrt(ne);
+    heatcr = m.crfac * 1.2e-25 / sqrt(b.ne);
     if (m.crscale > 0.)
       heatcr *= exp(-fabs(midpoint_z) / m.crscale);
   }
-  gain += heatcr;
+  b.gain += heatcr;
 
-  const double nh0 = n * h0;
-  const double nhe0 = n * he0 * AHe;
-  cmi_ionization_states_metals(m, j, ne, T, T4, nh0, nhe0, nhp, x);
+  b.nh0 = n * b.h0;
+  b.nhe0 = n * b.he0 * AHe;
+  return b;
+}
 
+/* ... the number fractions relative to H of the 13 line-cooling ions from the
+ * metal fractions x: abund[k * abund_stride], k in cmi_lc_ion ... */
+__device__ __forceinline__ void balance_abundances(const ModelDev &m,
+                                                   const double x[CMI_NION],
+                                                   double *abund,
+                                                   size_t abund_stride) {
+  using namespace cmi_lc_ion;
   const double AC = m.abundance[1], AN = m.abundance[2], AO = m.abundance[3],
                ANe = m.abundance[4], AS = m.abundance[5];
 #define AB(k) abund[(k)*abund_stride]
@@ -346,17 +401,52 @@ __device__ inline void cooling_and_heating_balance(
   AB(SIII) = AS * x[ION_S_p1];
   AB(SIV) = AS * x[ION_S_p2];
 #undef AB
+}
 
-  loss = line_cooling(m.tables->lc, T, ne, abund, abund_stride) * n;
-  const double c = 5.5 - logT;
+/* ... the losses of the continuum: free-free, and the recombination of H+
+ * and He+ ... */
+__device__ __forceinline__ void
+balance_continuum_losses(const BalanceHead &b, double T, double &loss_ff,
+                         double &loss_rec) {
+  const double c = 5.5 - b.logT;
   const double gff = 1.1 + 0.34 * exp(-c * c / 3.);
-  loss += 1.42e-40 * gff * sqrtT * (nenhp + nenhep);
-  const double Lhp =
-      2.85e-40 * nenhp * sqrtT * (5.914 - 0.5 * logT + 0.01184 * cbrt(T));
-  const double Lhep = 1.55e-39 * nenhep * exp(0.3647 * logT);
-  loss += Lhp + Lhep;
+  loss_ff = 1.42e-40 * gff * b.sqrtT * (b.nenhp + b.nenhep);
+  const double Lhp = 2.85e-40 * b.nenhp * b.sqrtT *
+                     (5.914 - 0.5 * b.logT + 0.01184 * cbrt(T));
+  const double Lhep = 1.55e-39 * b.nenhep * exp(0.3647 * b.logT);
+  loss_rec = Lhp + Lhep;
+}
+
+/* ... and how the loss is put together from the line cooling (per hydrogen
+ * atom) and the two above, with the clamps of gain and loss. */
+__device__ __forceinline__ void balance_close(double lines, double n,
+                                              double loss_ff, double loss_rec,
+                                              double &gain, double &loss) {
+  loss = lines * n;
+  loss += loss_ff;
+  loss += loss_rec;
   loss = fmax(loss, 0.);
   gain = fmax(gain, 0.);
+}
+
+/* The balance whole on one lane. x[2..13] receive the metal fractions at
+ * temperature T; abund / abund_stride: 13 doubles of work space
+ * (line_cooling). */
+__device__ inline void cooling_and_heating_balance(
+    const ModelDev &m, double &h0, double &he0, double &gain, double &loss,
+    double T, double n, double midpoint_z, const CellIntegrals &j,
+    const double h[2], double x[CMI_NION], double *abund, int abund_stride) {
+  const BalanceHead b = balance_head(m, T, n, midpoint_z, j, h);
+  h0 = b.h0;
+  he0 = b.he0;
+  gain = b.gain;
+  cmi_ionization_states_metals(m, j, b.ne, T, b.T4, b.nh0, b.nhe0, b.nhp, x);
+  balance_abundances(m, x, abund, abund_stride);
+  const double lines =
+      line_cooling(m.tables->lc, T, b.ne, abund, abund_stride);
+  double loss_ff, loss_rec;
+  balance_continuum_losses(b, T, loss_ff, loss_rec);
+  balance_close(lines, n, loss_ff, loss_rec, gain, loss);
 }
 
 /* TemperatureCalculator::calculate_temperature(vars, jfac, hfac, midpoint),
@@ -421,40 +511,15 @@ __device__ __forceinline__ bool temperature_goes_on(const ModelDev &m,
          s.niter < m.t_max_iterations;
 }
 
-/* ... one secant step (:654-745): the three balance evaluations - at 1.1 T0,
- * 0.9 T0 and T0, in the reference's order - as three trips of one loop body
- * ... */
-__device__ inline void temperature_step(const ModelDev &m, double ntot,
-                                        double midpoint_z,
-                                        const CellIntegrals &j,
-                                        TemperatureSolve &s, double *abund,
-                                        int abund_stride) {
+/* ... the rest of a secant step after its three balance evaluations
+ * (:716-745): gain1, loss1 at 1.1 T0, gain2, loss2 at 0.9 T0, and in s those
+ * at T0 ... */
+__device__ __forceinline__ void
+temperature_step_finish(const ModelDev &m, TemperatureSolve &s, double T0,
+                        double gain1, double loss1, double gain2,
+                        double loss2) {
   const double logtt = log(1.1 / 0.9);
-  ++s.niter;
-  const double T0 = s.T0;
   const double T1 = 1.1 * T0;
-  s.Tlast = T0;
-  double gain1 = 0., loss1 = 0., gain2 = 0., loss2 = 0.;
-#pragma unroll 1
-  for (int k = 0; k < 3; ++k) {
-    const double Tk = (k == 0) ? T1 : ((k == 1) ? 0.9 * T0 : T0);
-    double h0k, he0k, gaink, lossk;
-    double x[CMI_NION]; /* the metal fractions at Tk: only feed the cooling */
-    cooling_and_heating_balance(m, h0k, he0k, gaink, lossk, Tk, ntot,
-                                midpoint_z, j, s.h, x, abund, abund_stride);
-    if (k == 0) {
-      gain1 = gaink;
-      loss1 = lossk;
-    } else if (k == 1) {
-      gain2 = gaink;
-      loss2 = lossk;
-    } else {
-      s.h0 = h0k;
-      s.he0 = he0k;
-      s.gain0 = gaink;
-      s.loss0 = lossk;
-    }
-  }
   double expgain;
   if (gain2 > 0.)
     expgain = (gain1 > 0.) ? log(gain1 / gain2) : -99.;
@@ -484,6 +549,42 @@ __device__ inline void temperature_step(const ModelDev &m, double ntot,
     s.gain0 = 1.;
     s.loss0 = 1.;
   }
+}
+
+/* ... one secant step (:654-745): the three balance evaluations - at 1.1 T0,
+ * 0.9 T0 and T0, in the reference's order - as three trips of one loop body
+ * ... */
+__device__ inline void temperature_step(const ModelDev &m, double ntot,
+                                        double midpoint_z,
+                                        const CellIntegrals &j,
+                                        TemperatureSolve &s, double *abund,
+                                        int abund_stride) {
+  ++s.niter;
+  const double T0 = s.T0;
+  const double T1 = 1.1 * T0;
+  s.Tlast = T0;
+  double gain1 = 0., loss1 = 0., gain2 = 0., loss2 = 0.;
+#pragma unroll 1
+  for (int k = 0; k < 3; ++k) {
+    const double Tk = (k == 0) ? T1 : ((k == 1) ? 0.9 * T0 : T0);
+    double h0k, he0k, gaink, lossk;
+    double x[CMI_NION]; /* the metal fractions at Tk: only feed the cooling */
+    cooling_and_heating_balance(m, h0k, he0k, gaink, lossk, Tk, ntot,
+                                midpoint_z, j, s.h, x, abund, abund_stride);
+    if (k == 0) {
+      gain1 = gaink;
+      loss1 = lossk;
+    } else if (k == 1) {
+      gain2 = gaink;
+      loss2 = lossk;
+    } else {
+      s.h0 = h0k;
+      s.he0 = he0k;
+      s.gain0 = gaink;
+      s.loss0 = lossk;
+    }
+  }
+  temperature_step_finish(m, s, T0, gain1, loss1, gain2, loss2);
 }
 
 /* ... and its end (:747-931). The reference leaves in the cell the metal

@@ -1,9 +1,10 @@
 /*
  * temperature_pipeline.h - TemperatureCalculator::calculate_temperature
  * (src/TemperatureCalculator.cpp:567-931) over the grid as a pipeline of
- * small kernels instead of one: the same functions of device_thermal.h, the
- * same arithmetic in the same order - results equal those of
- * temperature_kernel bit for bit (tests/test_gpu_physics.py) - but
+ * small kernels instead of one: every kernel calls the functions of
+ * device_thermal.h that temperature_kernel calls, which fix the arithmetic
+ * and its order - results equal those of temperature_kernel bit for bit
+ * (tests/test_gpu_physics.py, tests/test_gpu_temperature_branches.py) - but
  *
  *   temp_begin_kernel     every cell: cells that need no solve are stored,
  *                         the others get a slot (solve state in global memory)
@@ -112,12 +113,14 @@ __device__ __forceinline__ CellIntegrals temp_integrals(const UpdateArgs &a,
   return J;
 }
 
-/* the coefficient tables in LDS (read hundreds of times per evaluation) */
-__device__ __forceinline__ void temp_stage_tables(const TablesDev *global,
-                                                  TablesDev *lds) {
+/* the coefficient tables - all of them (TablesDev) or those of the line
+ * cooling (LineCoolingDev) - in LDS (read hundreds of times per evaluation) */
+template <typename Tables>
+__device__ __forceinline__ void temp_stage_tables(const Tables *global,
+                                                  Tables *lds) {
   const uint64_t *src = reinterpret_cast<const uint64_t *>(global);
   uint64_t *dst = reinterpret_cast<uint64_t *>(lds);
-  for (unsigned k = threadIdx.x; k < sizeof(TablesDev) / 8; k += blockDim.x)
+  for (unsigned k = threadIdx.x; k < sizeof(Tables) / 8; k += blockDim.x)
     dst[k] = src[k];
   __syncthreads();
 }
@@ -174,78 +177,24 @@ __global__ void __launch_bounds__(CMI_BLOCK)
   }
 }
 
-/* cooling_and_heating_balance (device_thermal.h) without its line cooling:
- * the same statements in the same order; what the line cooling is added to
- * comes back in pieces (loss = lines * n; loss += free-free; loss +=
- * recombination; then the clamps - temp_secant_kernel) */
+/* cooling_and_heating_balance (device_thermal.h) without its line cooling
+ * and without the closing: the same pieces; what the line cooling is added to
+ * comes back in pieces (balance_close - temp_secant_kernel) */
 __device__ inline void
 balance_without_lines(const ModelDev &m, double &h0, double &he0, double &gain,
                       double &ne_out, double &loss_ff, double &loss_rec,
                       double T, double n, double midpoint_z,
                       const CellIntegrals &j, const double h[2], double *abund,
                       size_t abund_stride) {
-  enum { NI = 0, NII, OI, OII, OIII, NeIII, SII, SIII, CII, CIII, NIII, NeII,
-         SIV };
   double x[CMI_NION];
-  const double alphaH = cmi_recombination_rate(m, ION_H_n, T);
-  const double alphaHe = cmi_recombination_rate(m, ION_He_n, T);
-  const double T4 = T * 1.e-4;
-  const double sqrtT = sqrt(T);
-  const double logT = log(T);
-  const double AHe = m.abundance[0];
-
-  cmi_ionization_states_hydrogen_helium(alphaH, alphaHe, j(ION_H_n),
-                                        j(ION_He_n), n, AHe, T, h0, he0);
-  const double ne = n * (1. - h0 + AHe * (1. - he0));
-  const double nhp = n * (1. - h0);
-  const double nhep = (1. - he0) * n * AHe;
-  const double nenhp = ne * nhp;
-  const double nenhep = ne * nhep;
-
-  gain = n * (h[0] * h0 + h[1] * AHe * he0);
-  const double alpha_e_2sP =
-      4.17e-20 * exp(-0.861 * (logT - 9.210340371976184));
-  const double pHots = 1. / (1. + 77. * he0 / (sqrtT * h0));
-  gain += pHots * 1.21765423e-18 * alpha_e_2sP * nenhep;
-  gain += 1.5e-37 * n * ne * m.pahfac;
-  double heatcr = 0.;
-  if (m.crfac > 0.) {
-    heatcr = m.crfac * 1.2e-25 / sqrt(ne);
-    if (m.crscale > 0.)
-      heatcr *= exp(-fabs(midpoint_z) / m.crscale);
-  }
-  gain += heatcr;
-
-  const double nh0 = n * h0;
-  const double nhe0 = n * he0 * AHe;
-  cmi_ionization_states_metals(m, j, ne, T, T4, nh0, nhe0, nhp, x);
-
-  const double AC = m.abundance[1], AN = m.abundance[2], AO = m.abundance[3],
-               ANe = m.abundance[4], AS = m.abundance[5];
-#define AB(k) abund[(size_t)(k)*abund_stride]
-  AB(CII) = AC * (1. - x[ION_C_p1] - x[ION_C_p2]);
-  AB(CIII) = AC * x[ION_C_p1];
-  AB(NI) = AN * (1. - x[ION_N_n] - x[ION_N_p1] - x[ION_N_p2]);
-  AB(NII) = AN * x[ION_N_n];
-  AB(NIII) = AN * x[ION_N_p1];
-  AB(OI) = AO * (1. - x[ION_O_n] - x[ION_O_p1]);
-  AB(OII) = AO * x[ION_O_n];
-  AB(OIII) = AO * x[ION_O_p1];
-  AB(NeII) = ANe * x[ION_Ne_n];
-  AB(NeIII) = ANe * x[ION_Ne_p1];
-  AB(SII) = AS * (1. - x[ION_S_p1] - x[ION_S_p2] - x[ION_S_p3]);
-  AB(SIII) = AS * x[ION_S_p1];
-  AB(SIV) = AS * x[ION_S_p2];
-#undef AB
-
-  ne_out = ne;
-  const double c = 5.5 - logT;
-  const double gff = 1.1 + 0.34 * exp(-c * c / 3.);
-  loss_ff = 1.42e-40 * gff * sqrtT * (nenhp + nenhep);
-  const double Lhp =
-      2.85e-40 * nenhp * sqrtT * (5.914 - 0.5 * logT + 0.01184 * cbrt(T));
-  const double Lhep = 1.55e-39 * nenhep * exp(0.3647 * logT);
-  loss_rec = Lhp + Lhep;
+  const BalanceHead b = balance_head(m, T, n, midpoint_z, j, h);
+  h0 = b.h0;
+  he0 = b.he0;
+  gain = b.gain;
+  ne_out = b.ne;
+  cmi_ionization_states_metals(m, j, b.ne, T, b.T4, b.nh0, b.nhe0, b.nhp, x);
+  balance_abundances(m, x, abund, abund_stride);
+  balance_continuum_losses(b, T, loss_ff, loss_rec);
 }
 
 /* lane t: evaluation k = t / nactive of the a = t % nactive -th active slot */
@@ -301,15 +250,7 @@ __global__ void __launch_bounds__(CMI_BLOCK)
 __global__ void __launch_bounds__(CMI_BLOCK, CMI_LINECOOL_WAVES)
     temp_linecool_kernel(const TempPipeArgs a) {
   __shared__ LineCoolingDev lds_lc;
-  {
-    const uint64_t *src =
-        reinterpret_cast<const uint64_t *>(&a.u.model.tables->lc);
-    uint64_t *dst = reinterpret_cast<uint64_t *>(&lds_lc);
-    for (unsigned k = threadIdx.x; k < sizeof(LineCoolingDev) / 8;
-         k += blockDim.x)
-      dst[k] = src[k];
-    __syncthreads();
-  }
+  temp_stage_tables(&a.u.model.tables->lc, &lds_lc);
   const uint64_t total = 3ull * a.nactive;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   const size_t estride = 3 * (size_t)a.capacity;
@@ -322,44 +263,6 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_LINECOOL_WAVES)
         line_cooling_inlined(lds_lc, e[(size_t)TE_T * estride],
                      e[(size_t)TE_NE * estride],
                      e + (size_t)TE_ABUND * estride, (int)estride);
-  }
-}
-
-/* the rest of temperature_step after its three evaluations (:716-745) */
-__device__ __forceinline__ void
-temperature_step_finish(const ModelDev &m, TemperatureSolve &s, double T0,
-                        double gain1, double loss1, double gain2,
-                        double loss2) {
-  const double logtt = log(1.1 / 0.9);
-  const double T1 = 1.1 * T0;
-  double expgain;
-  if (gain2 > 0.)
-    expgain = (gain1 > 0.) ? log(gain1 / gain2) : -99.;
-  else
-    expgain = (gain1 > 0.) ? 99. : 0.;
-  double exploss;
-  if (loss2 > 0.)
-    exploss = (loss1 > 0.) ? log(loss1 / loss2) : -99.;
-  else
-    exploss = (loss1 > 0.) ? 99. : 0.;
-  const double expdiff = expgain - exploss;
-  if (s.gain0 > 0. && expdiff != 0.)
-    s.T0 = T0 * pow(s.loss0 / s.gain0, logtt / expdiff);
-  else
-    s.T0 = T1;
-  if (s.T0 < m.t_min_ionized) {
-    s.T0 = 500.;
-    s.h0 = 1.;
-    s.he0 = 1.;
-    s.gain0 = 1.;
-    s.loss0 = 1.;
-  }
-  if (s.T0 > 1.e10) {
-    s.T0 = 1.e10;
-    s.h0 = 1.e-10;
-    s.he0 = 1.e-10;
-    s.gain0 = 1.;
-    s.loss0 = 1.;
   }
 }
 
@@ -394,12 +297,11 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_SECANT_WAVES)
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
         const double *e = a.eval + (size_t)k * a.capacity + i;
-        /* loss = line_cooling * n; += free-free; += recombination; clamps */
-        double l = e[(size_t)TE_LINES * estride] * e[(size_t)TE_N * estride];
-        l += e[(size_t)TE_LOSS_FF * estride];
-        l += e[(size_t)TE_LOSS_REC * estride];
-        loss[k] = fmax(l, 0.);
-        gain[k] = fmax(e[(size_t)TE_GAIN * estride], 0.);
+        gain[k] = e[(size_t)TE_GAIN * estride];
+        balance_close(e[(size_t)TE_LINES * estride],
+                      e[(size_t)TE_N * estride],
+                      e[(size_t)TE_LOSS_FF * estride],
+                      e[(size_t)TE_LOSS_REC * estride], gain[k], loss[k]);
       }
       {
         const double *e = a.eval + (size_t)2 * a.capacity + i;
@@ -444,9 +346,12 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_SECANT_WAVES)
  *   - lane r < 10 solves the level populations of five-level ion r, lanes 10
  *     .. 12 the two-level ions; the thirteen cooling terms are summed by
  *     every lane in line_cooling()'s order.
- * Every number is computed by the statements of cooling_and_heating_balance
- * (device_thermal.h) in their order - the results equal temperature_kernel's
- * bit for bit - but a step is as long as one ion's fits, not thirteen ions':
+ * Every number comes from the functions cooling_and_heating_balance calls
+ * (device_thermal.h: balance_head, cmi_metal_ratio, balance_abundances,
+ * lc_ion_term, balance_continuum_losses, balance_close,
+ * temperature_step_finish) - the results equal temperature_kernel's bit for
+ * bit; the kernel's own are the lanes' roles and the shuffles between them -
+ * but a step is as long as one ion's fits, not thirteen ions':
  * round 4's form (four lanes per slot, an evaluation whole on one lane) spent
  * 7.2 ms per 256^3 update on a few dozen cells while the GPU idled. */
 __global__ void __launch_bounds__(CMI_BLOCK)
@@ -470,49 +375,16 @@ __global__ void __launch_bounds__(CMI_BLOCK)
   const double midpoint_z = a.state[(size_t)TS_ZMID * a.capacity + slot];
   const int64_t cell = a.chunk_first + a.slot_cell[slot];
   const CellIntegrals j = temp_integrals(a.u, cell);
-  enum { NI = 0, NII, OI, OII, OIII, NeIII, SII, SIII, CII, CIII, NIII, NeII,
-         SIV };
-  const double AHe = m.abundance[0];
-  const double AC = m.abundance[1], AN = m.abundance[2], AO = m.abundance[3],
-               ANe = m.abundance[4], AS = m.abundance[5];
   /* (listed: its last step left it unconverged) */
   do {
     const double T0 = s.T0;
     const double T = (k == 0) ? 1.1 * T0 : ((k == 1) ? 0.9 * T0 : T0);
-    /* ---- cooling_and_heating_balance(m, h0, he0, gain, loss, T, n, ...) */
-    double h0, he0, gain, loss;
-    const double alphaH = cmi_recombination_rate(m, ION_H_n, T);
-    const double alphaHe = cmi_recombination_rate(m, ION_He_n, T);
-    const double T4 = T * 1.e-4;
-    const double sqrtT = sqrt(T);
-    const double logT = log(T);
-    cmi_ionization_states_hydrogen_helium(alphaH, alphaHe, j(ION_H_n),
-                                          j(ION_He_n), n, AHe, T, h0, he0);
-    const double ne = n * (1. - h0 + AHe * (1. - he0));
-    const double nhp = n * (1. - h0);
-    const double nhep = (1. - he0) * n * AHe;
-    const double nenhp = ne * nhp;
-    const double nenhep = ne * nhep;
-    gain = n * (s.h[0] * h0 + s.h[1] * AHe * he0);
-    const double alpha_e_2sP =
-        4.17e-20 * exp(-0.861 * (logT - 9.210340371976184));
-    const double pHots = 1. / (1. + 77. * he0 / (sqrtT * h0));
-    gain += pHots * 1.21765423e-18 * alpha_e_2sP * nenhep;
-    gain += 1.5e-37 * n * ne * m.pahfac;
-    double heatcr = 0.;
-    if (m.crfac > 0.) {
-      heatcr = m.crfac * 1.2e-25 / sqrt(ne);
-      if (m.crscale > 0.)
-        heatcr *= exp(-fabs(midpoint_z) / m.crscale);
-    }
-    gain += heatcr;
-    const double nh0 = n * h0;
-    const double nhe0 = n * he0 * AHe;
+    const BalanceHead b = balance_head(m, T, n, midpoint_z, j, s.h);
     /* cmi_ionization_states_metals: one ion per lane */
     double my_ratio = 0.;
     if (role < 12)
-      my_ratio = cmi_metal_ratio(m, j, ION_C_p1 + role, ne, T, T4, nh0, nhe0,
-                                 nhp);
+      my_ratio = cmi_metal_ratio(m, j, ION_C_p1 + role, b.ne, T, b.T4, b.nh0,
+                                 b.nhe0, b.nhp);
     double ratio[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i)
@@ -520,19 +392,7 @@ __global__ void __launch_bounds__(CMI_BLOCK)
     double x[CMI_NION];
     cmi_metal_fractions(ratio, x);
     double ab[13];
-    ab[CII] = AC * (1. - x[ION_C_p1] - x[ION_C_p2]);
-    ab[CIII] = AC * x[ION_C_p1];
-    ab[NI] = AN * (1. - x[ION_N_n] - x[ION_N_p1] - x[ION_N_p2]);
-    ab[NII] = AN * x[ION_N_n];
-    ab[NIII] = AN * x[ION_N_p1];
-    ab[OI] = AO * (1. - x[ION_O_n] - x[ION_O_p1]);
-    ab[OII] = AO * x[ION_O_n];
-    ab[OIII] = AO * x[ION_O_p1];
-    ab[NeII] = ANe * x[ION_Ne_n];
-    ab[NeIII] = ANe * x[ION_Ne_p1];
-    ab[SII] = AS * (1. - x[ION_S_p1] - x[ION_S_p2] - x[ION_S_p3]);
-    ab[SIII] = AS * x[ION_S_p1];
-    ab[SIV] = AS * x[ION_S_p2];
+    balance_abundances(m, x, ab, 1);
     double my_ab = 0.;
 #pragma unroll
     for (int i = 0; i < 13; ++i)
@@ -540,35 +400,17 @@ __global__ void __launch_bounds__(CMI_BLOCK)
         my_ab = ab[i];
     /* line_cooling(lc, T, ne, abund): one ion per lane */
     const LineCoolingDev &lc = m.tables->lc;
-    const double kb = CMI_BOLTZMANN;
     double term = 0.;
-    if (ne != 0.) {
-      const double prefactor = lc.prefactor * ne / sqrt(T);
-      const double Tinv = 1. / T;
-      const double logT_lc = log(T);
-      if (role < CMI_LC_NFIVE_DEV)
-        term = my_ab * kb *
-               lc_five_level_cooling(lc, role, prefactor, T, Tinv, logT_lc);
-      else if (role < CMI_LC_NFIVE_DEV + CMI_LC_NTWO_DEV) {
-        const int i = role - CMI_LC_NFIVE_DEV;
-        term = my_ab * kb * lc.two_energy[i] * lc.two_A[i] *
-               lc_two_level_cooling(lc, i, prefactor, T, Tinv, logT_lc);
-      }
-    }
+    if (b.ne != 0. && role < CMI_LC_NFIVE_DEV + CMI_LC_NTWO_DEV)
+      term = lc_ion_term(lc, role, my_ab, lc_point(lc, T, b.ne));
     double cooling = 0.;
 #pragma unroll
     for (int e = 0; e < CMI_LC_NFIVE_DEV + CMI_LC_NTWO_DEV; ++e)
       cooling += __shfl(term, quarter + e, 64);
-    loss = ((ne == 0.) ? 1.e-99 : cooling) * n;
-    const double c = 5.5 - logT;
-    const double gff = 1.1 + 0.34 * exp(-c * c / 3.);
-    loss += 1.42e-40 * gff * sqrtT * (nenhp + nenhep);
-    const double Lhp =
-        2.85e-40 * nenhp * sqrtT * (5.914 - 0.5 * logT + 0.01184 * cbrt(T));
-    const double Lhep = 1.55e-39 * nenhep * exp(0.3647 * logT);
-    loss += Lhp + Lhep;
-    loss = fmax(loss, 0.);
-    gain = fmax(gain, 0.);
+    double loss_ff, loss_rec, gain = b.gain, loss;
+    balance_continuum_losses(b, T, loss_ff, loss_rec);
+    balance_close((b.ne == 0.) ? CMI_LC_NO_ELECTRONS : cooling, n, loss_ff,
+                  loss_rec, gain, loss);
     /* ---- temperature_step's bookkeeping, on every lane alike */
     const double gain1 = __shfl(gain, 0, 64);
     const double loss1 = __shfl(loss, 0, 64);
@@ -576,8 +418,8 @@ __global__ void __launch_bounds__(CMI_BLOCK)
     const double loss2 = __shfl(loss, 16, 64);
     ++s.niter;
     s.Tlast = T0;
-    s.h0 = __shfl(h0, 32, 64);
-    s.he0 = __shfl(he0, 32, 64);
+    s.h0 = __shfl(b.h0, 32, 64);
+    s.he0 = __shfl(b.he0, 32, 64);
     s.gain0 = __shfl(gain, 32, 64);
     s.loss0 = __shfl(loss, 32, 64);
     temperature_step_finish(m, s, T0, gain1, loss1, gain2, loss2);
