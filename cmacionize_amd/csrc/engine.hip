@@ -163,12 +163,18 @@ struct cmi_gpu_engine {
    * (publish_escape); what that copy was written from */
   bool escape_counting = false;
   EscapeDev escape_staged = {};
-  /* PAD transport kernels: n x_H inside a layer of ghost cells; whether it
-   * holds the records of the cells as they are (whatever writes
-   * CellsDev::opacity clears this - pad_records_stale - except the update
-   * that writes the padded records itself, hydrogen_update_kernel) */
+  /* PAD transport kernels: sigma_H n x_H inside a layer of ghost cells;
+   * whether it holds the records of the cells and the cross section as they
+   * are (whatever writes CellsDev::opacity clears this - pad_records_stale -
+   * except the update that writes the padded records itself,
+   * hydrogen_update_kernel; so does every setter of the cross sections,
+   * update_full_flag) */
   double *pad_H = nullptr;
   bool pad_valid = false;
+  /* the first-generation build of the last transport call's plan (FirstBuild)
+   * and whether it was the UNIFORM one: cmi_gpu_get_transport_plan */
+  int32_t last_first_build = 0;
+  bool last_pad_uniform = false;
   /* the hydrogen-only update's deferred half: the gates of the last whole-grid
    * update, a bit per cell, and whether x[2..13] have still to be made from
    * them (settle_metal_fractions). Once a pointer to a state field has been
@@ -251,6 +257,10 @@ struct cmi_gpu_engine {
     /* hydrogen-only first generation on a whole non-periodic grid: march
      * through the padded records (shoot_kernel<..., PAD>) */
     bool pad_march = true;
+    /* ... and, where every packet of a call carries one weight and no heating
+     * term is tracked, sum path lengths and weigh the sums at the flush
+     * (shoot_kernel<..., PAD, UNIFORM>) */
+    bool pad_uniform = true;
     /* sorted first generation: the blocks of an XCD take neighbouring
      * positions of the packet order */
     bool xcd_remap = false;
@@ -1001,6 +1011,9 @@ int update_full_flag(cmi_gpu_engine *e) {
   /* the light transport kernel is exact iff no ion other than H0 can ever
    * have a non-zero cross section */
   bool full = e->model.xsec_verner != 0;
+  /* (every setter of the cross sections ends here: the padded records hold
+   * sigma_H n x_H - cmi_pad_record - and are those of another model now) */
+  e->pad_valid = false;
   if (!full)
     for (int i = 1; i < CMI_NION; ++i)
       if (e->model.xsec_fixed[i] != 0.)
@@ -1794,6 +1807,17 @@ int cmi_gpu_get_update_state(cmi_gpu_engine *e, int32_t *metals_pending,
   return CMI_GPU_OK;
 }
 
+int cmi_gpu_get_transport_plan(cmi_gpu_engine *e, int32_t *first_build,
+                               int32_t *uniform_weight) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (first_build)
+    *first_build = e->last_first_build;
+  if (uniform_weight)
+    *uniform_weight = e->last_pad_uniform ? 1 : 0;
+  return CMI_GPU_OK;
+}
+
 int cmi_gpu_reset_grid(cmi_gpu_engine *e) {
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
@@ -1880,6 +1904,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.temperature_pipeline = value != 0;
   else if (k == "pad_march")
     e->tune.pad_march = value != 0;
+  else if (k == "pad_uniform")
+    e->tune.pad_uniform = value != 0;
   else if (k == "xcd_remap")
     e->tune.xcd_remap = value != 0;
   else if (k == "pre_emission")
@@ -2260,6 +2286,7 @@ int cmi_gpu_update_cells_range(cmi_gpu_engine *e, uint32_t loop,
     h.gate = e->metal_gate;
     /* (the ghost layer is in place from the last pad_records) */
     h.pad_H = (e->pad_valid && e->tune.update_writes_pad) ? e->pad_H : nullptr;
+    h.pad_sigma = e->model.xsec_fixed[ION_H_n];
     h.ny = (uint32_t)e->grid.ncell[1];
     h.nz = (uint32_t)e->grid.ncell[2];
     if (!h.pad_H)

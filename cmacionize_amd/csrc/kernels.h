@@ -225,12 +225,18 @@ struct ShootArgs {
   const uint32_t *xin_slots = nullptr;
 #endif
   ExchangeDev xout;
-  /* PAD kernels: n x_H of every cell of the grid with CMI_PAD_LAYERS layers
-   * of ghost cells around it (pad_record_kernel): -0. marks a vacuum cell
-   * (no opacity, and a sign bit that says "no gas"), -2 a ghost cell - the
-   * march learns from the record it loads anyway that the packet has left
-   * the box */
+  /* PAD kernels: sigma_H n x_H of every cell of the grid with CMI_PAD_LAYERS
+   * layers of ghost cells around it (cmi_pad_record; sigma_H is
+   * ModelDev::xsec_fixed[ION_H_n], the one cross section every packet of a
+   * hydrogen-only launch carries - the march reads a step's opacity, it does
+   * not multiply for it): -0. marks a vacuum cell (no opacity, and a sign bit
+   * that says "no gas"), -2 a ghost cell - the march learns from the record
+   * it loads anyway that the packet has left the box */
   const double *pad_H;
+  /* PAD kernels of a launch whose packets all carry one weight (UNIFORM): the
+   * table sums path lengths, and a sum is multiplied by this - weight x
+   * sigma_H - on its way to the cell's accumulator */
+  double uniform_scale;
   int32_t xcd_remap;
   /* padded extents ny + 2 L, nz + 2 L (L = CMI_PAD_LAYERS) and the
    * reciprocals of (ny + 2 L)(nz + 2 L) and nz + 2 L */
@@ -294,6 +300,15 @@ enum {
 #define CMI_PAD_LAYERS 1
 #define CMI_PAD_VACUUM (-0.)
 #define CMI_PAD_GHOST (-2.)
+/* The padded record of a cell inside the grid from its transport record's
+ * n x_H (negative: no gas) and the launch's cross section: the product the
+ * march formed at every crossing, fl(sigma x fl(n x_H)), formed once - the
+ * same operation on the same operands (-ffp-contract=off), so optical depths
+ * and path-length corrections are bit for bit what they were. sigma >= 0
+ * (plan_launches): vacuum stays -0. and no record reaches the ghost's -2. */
+__device__ __forceinline__ double cmi_pad_record(double sigma, double nx) {
+  return sigma * ((nx >= 0.) ? nx : CMI_PAD_VACUUM);
+}
 /* The PAD march keeps a packet's cell - Packet::cell and cstep[], the run key,
  * the table's tags, last_cell until the flight's end - as the BYTE OFFSET of
  * the cell's record, 8 x the padded long index (< 2^32: an unsigned 32-bit
@@ -1141,8 +1156,11 @@ block_owns_start(const GridDev &g, Packet<FULL> &p, uint32_t packet_id,
 #ifndef CMI_FULL_PASS_WAVES
 #define CMI_FULL_PASS_WAVES 3
 #endif
+/* (SWITCH8 is two switches that never meet and share a place in the list, so
+ * that the kernels' names keep nine flags for the tools that read the
+ * listing: TRACK outside the PAD kernels, UNIFORM in them) */
 template <bool FULL, bool HEAT, bool REEMIT, bool EXACT, bool TABLE = false,
-          bool PRE = false, bool PAD = false, bool TRACK = false,
+          bool PRE = false, bool PAD = false, bool SWITCH8 = false,
           bool BIG = false>
 __global__ void
     __launch_bounds__((shoot_block_threads<FULL, TABLE, BIG>()),
@@ -1165,8 +1183,16 @@ __global__ void
    * marching through the padded records (ShootArgs::pad_H) */
   static_assert(!PAD || (TABLE && !FULL && !REEMIT && !EXACT && !PRE),
                 "PAD is a specialisation of the hydrogen-only TABLE kernel");
-  static_assert(!TRACK || (!TABLE && !EXACT && !PRE && !PAD),
+  constexpr bool TRACK = SWITCH8 && !PAD;
+  static_assert(!TRACK || (!TABLE && !EXACT && !PRE),
                 "TRACK is the tracker hook in the plain incremental marcher");
+  /* UNIFORM: every packet of the launch carries one weight (plan_launches),
+   * and one cross section as in every PAD kernel: the run sums and the table
+   * add path lengths, and a slot's sum is multiplied by weight x sigma_H
+   * (ShootArgs::uniform_scale) once, where it leaves the table */
+  constexpr bool UNIFORM = SWITCH8 && PAD;
+  static_assert(!UNIFORM || !HEAT,
+                "the heating term's weight differs from packet to packet");
   const int lane = threadIdx.x & 63;
   const uint64_t lane_lt = (1ull << lane) - 1ull;
   /* Blocks are dealt round-robin over the 8 XCDs (blocks b and b + 8 share
@@ -1405,7 +1431,8 @@ __global__ void
         if (PAD ? t != -1 : t >= 0) {
           const int32_t c =
               PAD ? cmi_unpad_cell(a, a.grid, cmi_pad_index(t)) : t;
-          atomic_add_f64(acc_at(a.cells, ION_H_n, c), lds_val[k]);
+          atomic_add_f64(acc_at(a.cells, ION_H_n, c),
+                         UNIFORM ? lds_val[k] * a.uniform_scale : lds_val[k]);
           lds_val[k] = 0.;
           if (HEAT) {
             atomic_add_f64(acc_at(a.cells, CMI_NION, c),
@@ -1524,7 +1551,8 @@ __global__ void
     if (lanes_of(looking)) {
       const int32_t c =
           PAD ? cmi_unpad_cell(a, a.grid, cmi_pad_index(cell)) : cell;
-      atomic_add_f64(acc_at(a.cells, ION_H_n, c), v0);
+      atomic_add_f64(acc_at(a.cells, ION_H_n, c),
+                     UNIFORM ? v0 * a.uniform_scale : v0);
       if (HEAT)
         atomic_add_f64(acc_at(a.cells, CMI_NION, c), v1);
       natomics += HEAT ? 2 : 1;
@@ -1736,11 +1764,13 @@ __global__ void
        * axis (the ghost record says "outside"), every tied axis advances by
        * selects, run sums over groups of 8 lanes, a 24-bit multiply for the
        * hash. */
-      const double sigma = p.sigma_H;
-      double wsig = p.weight * p.sigma_H;
+      /* (the cross section itself is not in the loop: the records carry it,
+       * cmi_pad_record) */
+      double wsig = UNIFORM ? 0. : p.weight * p.sigma_H;
       double hw = HEAT ? wsig * (p.nu - a.model.nu_H) : 0.;
       /* (kept in registers: recomputing them costs a multiplication a step) */
-      asm volatile("" : "+v"(wsig), "+v"(hw));
+      if (!UNIFORM)
+        asm volatile("" : "+v"(wsig), "+v"(hw));
       /* Round 4: every condition of the loop is a wave mask in scalar
        * registers (mask_gt, mask_eq, lanes_of): which lanes step, which axes
        * advance, where runs end, who still looks for a slot. The loop's exit
@@ -1792,20 +1822,25 @@ __global__ void
         /* the run key - the cell about to be crossed, or something no other
          * lane has - before the march moves on (this IS the copy of the old
          * cell index the accumulation needs) */
+        /* (the smaller of two walls for every lane, stepping or not, next to
+         * the key's compare and select: inside the branch of the stepping
+         * lanes nothing is there to fill the wait state between the two
+         * dependent minima, and it cost a no-op on the scalar side) */
+        double t12 = min_f64(p.tmax[1], p.tmax[2]);
         int32_t key = lanes_of(accumulating) ? p.cell : not_lane;
         /* (here, not after the march: that would take a copy of the cell) */
-        asm volatile("" : "+v"(key));
+        asm volatile("" : "+v"(key), "+v"(t12));
         /* (lanes that do not step take part in the run sums with a key of
          * their own and are never a tail that adds: their path length may be
          * anything, run_sums_masked selects, it does not multiply) */
         double ds;
         asm volatile("" : "=v"(ds));
         if (stepping) {
-          const double tmin =
-              min_f64(p.tmax[0], min_f64(p.tmax[1], p.tmax[2]));
+          const double tmin = min_f64(p.tmax[0], t12);
           const double t_old = p.t;
           ds = tmin - t_old;
-          const double sk = sigma * pad_next;
+          /* sigma n x_H of the cell: the record as it stands */
+          const double sk = pad_next;
           p.tau -= ds * sk;
           /* every tied axis advances, under the execution mask: one add each
            * for the wall parameter and the cell (vector instructions are what
@@ -1869,7 +1904,8 @@ __global__ void
           asm volatile("" ::"v"(ds), "s"(accumulating));
           continue;
         }
-        double v[2] = {ds * wsig, HEAT ? ds * hw : 0.};
+        /* (UNIFORM: the path length; its weight comes at the flush) */
+        double v[2] = {UNIFORM ? ds : ds * wsig, HEAT ? ds * hw : 0.};
         /* run sums over groups of 2^rounds lanes (measured at 8 waves/SIMD
          * in round 3, ms per iteration of 1e8 packets: groups of 4 44.2,
          * groups of 8 43.0, groups of 16 44.6) */
@@ -3473,6 +3509,10 @@ struct HydrogenUpdateArgs {
    * update - the cells' records are then written here as pad_record_kernel
    * would, the ghost layer stays -, or null */
   double *pad_H;
+  /* ... and the cross section they carry, model.xsec_fixed[ION_H_n] (an
+   * argument of its own: the kernel keeps the model in scratch, and reading
+   * it from there for every cell cost 0.05 ms of the 0.39 at 256^3) */
+  double pad_sigma;
   uint32_t ny, nz;
 };
 
@@ -3522,7 +3562,7 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_HYDROGEN_UPDATE_WAVES)
         const uint32_t px = xy / h.ny, py = xy - px * h.ny;
         const uint32_t padded =
             ((px + L) * (h.ny + 2 * L) + (py + L)) * (h.nz + 2 * L) + pz + L;
-        h.pad_H[padded] = (k.x >= 0.) ? k.x : CMI_PAD_VACUUM;
+        h.pad_H[padded] = cmi_pad_record(h.pad_sigma, k.x);
       }
     }
     const unsigned long long word = wave_ballot(gate);
@@ -3872,11 +3912,11 @@ __global__ void __launch_bounds__(CMI_BLOCK)
   }
 }
 
-/* PAD kernels: n x_H of every cell inside one layer of ghost cells
+/* PAD kernels: sigma_H n x_H of every cell inside one layer of ghost cells
  * (ShootArgs::pad_H), from the transport records */
 __global__ void __launch_bounds__(CMI_BLOCK)
     pad_record_kernel(const double2 *__restrict__ opacity, double *pad,
-                      int32_t nx, int32_t ny, int32_t nz) {
+                      double sigma, int32_t nx, int32_t ny, int32_t nz) {
   const int64_t total = (int64_t)(nx + 2 * CMI_PAD_LAYERS) *
                         (ny + 2 * CMI_PAD_LAYERS) * (nz + 2 * CMI_PAD_LAYERS);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -3887,10 +3927,9 @@ __global__ void __launch_bounds__(CMI_BLOCK)
     const int32_t py = (int32_t)((c / (nz + 2 * L)) % (ny + 2 * L)) - L;
     const int32_t px = (int32_t)(c / ((int64_t)(nz + 2 * L) * (ny + 2 * L))) - L;
     double v = CMI_PAD_GHOST;
-    if (px >= 0 && px < nx && py >= 0 && py < ny && pz >= 0 && pz < nz) {
-      const double k = opacity[((int64_t)px * ny + py) * nz + pz].x;
-      v = (k >= 0.) ? k : CMI_PAD_VACUUM;
-    }
+    if (px >= 0 && px < nx && py >= 0 && py < ny && pz >= 0 && pz < nz)
+      v = cmi_pad_record(sigma,
+                         opacity[((int64_t)px * ny + py) * nz + pz].x);
     pad[c] = v;
   }
 }

@@ -238,6 +238,10 @@ struct LaunchPlan {
   int agg, agg_reemit;
   FirstBuild first;
   bool pad, pad_big;     /* first is FIRST_PAD or FIRST_PAD_BIG / the latter */
+  /* pad, no heating term, and every packet of the call carries one weight:
+   * the UNIFORM build, whose table sums path lengths; weight x sigma_H */
+  bool pad_uniform;
+  double uniform_scale;
   int64_t padded_cells;
   /* the kernel of a pass, the one that follows re-emissions in place, and the
    * first generation's, with their workgroups per CU */
@@ -258,7 +262,8 @@ struct LaunchPlan {
  * These tables are all the builds there are, listed in the order the code
  * object holds them. */
 static ShootKernel shoot_build(bool full, bool heat, bool reemit, bool exact,
-                               bool track, FirstBuild first) {
+                               bool track, FirstBuild first,
+                               bool uniform = false) {
   /* [exact][2 full + heat][reemit] */
   static const ShootKernel generic[2][4][2] = {
       {{shoot_kernel<false, false, false, false>,
@@ -293,13 +298,15 @@ static ShootKernel shoot_build(bool full, bool heat, bool reemit, bool exact,
        shoot_kernel<true, false, false, false, true>},
       {shoot_kernel<false, true, false, false, true>,
        shoot_kernel<false, false, false, false, true>}};
-  /* [!heat] */
-  static const ShootKernel pad_big[2] = {
+  /* [!heat + uniform] (UNIFORM: the eighth flag of a PAD kernel) */
+  static const ShootKernel pad_big[3] = {
       shoot_kernel<false, true, false, false, true, false, true, false, true>,
-      shoot_kernel<false, false, false, false, true, false, true, false, true>};
-  static const ShootKernel pad[2] = {
+      shoot_kernel<false, false, false, false, true, false, true, false, true>,
+      shoot_kernel<false, false, false, false, true, false, true, true, true>};
+  static const ShootKernel pad[3] = {
       shoot_kernel<false, true, false, false, true, false, true>,
-      shoot_kernel<false, false, false, false, true, false, true>};
+      shoot_kernel<false, false, false, false, true, false, true>,
+      shoot_kernel<false, false, false, false, true, false, true, true>};
   static const ShootKernel pre[2] = {
       shoot_kernel<true, true, false, false, true, true>,
       shoot_kernel<true, false, false, false, true, true>};
@@ -307,9 +314,9 @@ static ShootKernel shoot_build(bool full, bool heat, bool reemit, bool exact,
   case FIRST_TABLE:
     return table[!full][!heat];
   case FIRST_PAD:
-    return pad[!heat];
+    return pad[!heat + (!heat && uniform)];
   case FIRST_PAD_BIG:
-    return pad_big[!heat];
+    return pad_big[!heat + (!heat && uniform)];
   case FIRST_PRE:
     return pre[!heat];
   case FIRST_GENERIC:
@@ -391,9 +398,28 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
                    ((int64_t)e->grid.ncell[2] + 2 * CMI_PAD_LAYERS);
   /* (a block of a decomposed grid: its ghost layer says "left the block", the
    * end of the flight then decides between "left the box" and a hand-over) */
+  /* The padded records hold sigma_H n x_H (cmi_pad_record): the cross section
+   * must be one number for the call, not negative (a record's sign bit says
+   * "no gas") and finite. !full_ions is that guarantee (update_full_flag): the
+   * cross sections are the fixed ones and only hydrogen's is non-zero, so
+   * set_cross_sections gives every packet xsec_fixed[ION_H_n], whatever its
+   * frequency or source; handed-over flights and re-emitted packets never
+   * come here (table: !flights, passes or no re-emission). */
+  const double sigma_H = e->model.xsec_fixed[ION_H_n];
   p.pad = table && !e->full_ions && tune.pad_march &&
-          p.padded_cells < ((int64_t)1 << 29);
+          p.padded_cells < ((int64_t)1 << 29) && sigma_H >= 0. &&
+          std::isfinite(sigma_H);
   p.pad_big = p.pad && e->ncell > CMI_TABLE_BIG_CELLS;
+  /* one weight for every packet of the call: all from the discrete sources
+   * (photon_weight[0]), all from the continuous one ([1]: emit_geometry
+   * draws the origin against continuous_probability), or both weights equal.
+   * The kernels with the heating term keep the product per lane. */
+  const double pc = e->model.continuous_probability;
+  const double *pw = e->model.photon_weight;
+  p.pad_uniform = p.pad && !p.heat && tune.pad_uniform &&
+                  (pc <= 0. || pc >= 1. || pw[0] == pw[1]);
+  /* (the product the per-lane build forms: weight x sigma_H) */
+  p.uniform_scale = (pc >= 1. ? pw[1] : pw[0]) * sigma_H;
   p.first = FIRST_GENERIC;
   if (p.pad)
     p.first = p.pad_big ? FIRST_PAD_BIG : FIRST_PAD;
@@ -417,7 +443,7 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
                  : shoot_build(e->full_ions, p.heat, false, p.exact, track,
                                FIRST_GENERIC);
   p.kernel_first = table ? shoot_build(e->full_ions, p.heat, false, false,
-                                       false, p.first)
+                                       false, p.first, p.pad_uniform)
                          : p.kernel;
   CMI_TRY(blocks_per_cu_of(p.kernel, CMI_BLOCK, tune.max_blocks_per_cu,
                            p.blocks_per_cu));
@@ -567,6 +593,7 @@ static ShootArgs shoot_args(const cmi_gpu_engine *e, const LaunchPlan &p,
   a.xout.count = e->export_count;
   a.xout.capacity = (unsigned int)e->export_capacity;
   a.pad_H = p.pad ? e->pad_H : nullptr;
+  a.uniform_scale = p.uniform_scale;
   a.xcd_remap = (p.sorted && e->tune.xcd_remap) ? 1 : 0;
   a.pad_ny = e->grid.ncell[1] + 2 * CMI_PAD_LAYERS;
   a.pad_nz = e->grid.ncell[2] + 2 * CMI_PAD_LAYERS;
@@ -609,7 +636,8 @@ static int pad_records(cmi_gpu_engine *e, const LaunchPlan &p) {
     HIP_TRY(hipMalloc(&e->pad_H, sizeof(double) * (size_t)p.padded_cells));
   pad_record_kernel<<<grid_blocks(e, p.padded_cells, 8), CMI_BLOCK, 0,
                       e->stream>>>(cells_of_iteration(e).opacity, e->pad_H,
-                                   g.ncell[0], g.ncell[1], g.ncell[2]);
+                                   e->model.xsec_fixed[ION_H_n], g.ncell[0],
+                                   g.ncell[1], g.ncell[2]);
   HIP_TRY(hipGetLastError());
   e->pad_valid = true;
   return CMI_GPU_OK;
@@ -1192,6 +1220,10 @@ static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
 
   LaunchPlan plan;
   CMI_TRY(plan_launches(e, n_packets, flights, plan));
+  if (!flights) { /* (for cmi_gpu_get_transport_plan) */
+    e->last_first_build = (int32_t)plan.first;
+    e->last_pad_uniform = plan.pad_uniform;
+  }
   CMI_TRY(publish_escape(e, plan.tracking));
   const uint64_t max_launch = e->tune.max_packets_per_launch;
   if (!plan.select_mode)

@@ -151,7 +151,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_render_absorption_spectra", "cmi_gpu_absorption_probe",
     "cmi_gpu_set_escape_tally", "cmi_gpu_reset_escape_tally",
     "cmi_gpu_download_escape_tally", "cmi_gpu_escape_pixels",
-    "cmi_gpu_cross_sections",
+    "cmi_gpu_cross_sections", "cmi_gpu_get_transport_plan",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -349,6 +349,9 @@ def load_library():
     L.cmi_gpu_field_device_pointer.argtypes = [vp, C.c_int32]
     if hasattr(L, "cmi_gpu_get_update_state"):  # (as for the stamps below)
         L.cmi_gpu_get_update_state.argtypes = [vp] + 3 * [C.POINTER(C.c_int32)]
+    if hasattr(L, "cmi_gpu_get_transport_plan"):
+        L.cmi_gpu_get_transport_plan.argtypes = [vp] + 2 * [
+            C.POINTER(C.c_int32)]
     L.cmi_gpu_reset_grid.argtypes = [vp]
     L.cmi_gpu_shoot.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64,
                                 C.c_uint64]
@@ -1048,6 +1051,16 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_get_update_state(
             self._h, *[C.byref(x) for x in v]))
         return tuple(bool(x.value) for x in v)
+
+    def transport_plan(self):
+        """(first-generation build, built for packets of one weight) of the
+        last shoot: 0 the general kernel, 1 the block table, 2 / 3 the padded
+        march in its smaller / larger blocks, 4 the multi-ion kernel with the
+        emission physics done ahead."""
+        first, uniform = C.c_int32(), C.c_int32()
+        self._check(self._lib.cmi_gpu_get_transport_plan(
+            self._h, C.byref(first), C.byref(uniform)))
+        return first.value, bool(uniform.value)
 
     # iteration body -----------------------------------------------------------
     def field_tensor(self, field):

@@ -306,6 +306,13 @@ void *cmi_gpu_field_device_pointer(cmi_gpu_engine *engine, int32_t field);
 int cmi_gpu_get_update_state(cmi_gpu_engine *engine, int32_t *metals_pending,
                              int32_t *pad_records_valid,
                              int32_t *deferral_allowed);
+/* What the last call that transported new packets flew its first generation
+ * with (any pointer may be NULL): the build - 0 the general kernel, 1 the
+ * block table, 2 and 3 the padded march in its smaller and larger blocks, 4
+ * the multi-ion kernel with the emission physics done ahead - and whether it
+ * was the padded march's build for packets of one weight ("pad_uniform"). */
+int cmi_gpu_get_transport_plan(cmi_gpu_engine *engine, int32_t *first_build,
+                               int32_t *uniform_weight);
 int cmi_gpu_accumulator_layout(cmi_gpu_engine *engine, int64_t *field_stride,
                                int64_t *cell_stride);
 
@@ -673,9 +680,16 @@ int cmi_gpu_cross_sections(cmi_gpu_engine *engine, int64_t n,
  *                           (a wave per cell)
  *   "pad_march" (1)         hydrogen-only runs on a whole, non-periodic grid:
  *                           the first generation marches through a copy of
- *                           n x_H with one layer of ghost cells, whose record
- *                           says that the packet has left the box (no cell
- *                           counters per axis in the march)
+ *                           sigma_H n x_H with one layer of ghost cells, whose
+ *                           record says that the packet has left the box (no
+ *                           cell counters per axis in the march)
+ *   "pad_uniform" (1)       ... and where every packet of the call carries one
+ *                           weight (no continuous source beside the discrete
+ *                           ones, or equal weights) and no heating term is
+ *                           tracked, it sums path lengths and multiplies a
+ *                           cell's sum by weight x sigma_H once (J_H equal up
+ *                           to rounding, counters identical) - 0: a product
+ *                           per step
  *   "xcd_remap" (0)         sorted first generation: the blocks that share an
  *                           XCD (block index mod 8) take neighbouring
  *                           positions of the packet order, so that bundles
