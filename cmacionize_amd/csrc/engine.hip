@@ -121,6 +121,15 @@ struct cmi_gpu_engine {
   void *sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
   uint64_t sort_capacity = 0;
+  /* 32-bit words of the block the keys and ids live in: 4 per packet, or
+   * what the bucket order lays into it (BucketPlan::total_words) */
+  uint64_t sort_block_words = 0;
+  /* the bucket order's cursors, leaf offsets and counts (bucket_meta_words) */
+  uint32_t *bucket_meta = nullptr;
+  /* how the last launch of new packets was ordered (OrderPath), the bits of
+   * its two scatter levels: cmi_gpu_get_order_plan */
+  int32_t last_order_path = 0;
+  int32_t last_bucket_bits[2] = {0, 0};
   /* the span cursors of a first-generation launch (ShootArgs::span_cursor) */
   uint32_t *span_cursor = nullptr;
 #ifdef CMI_EXPERIMENTS
@@ -211,7 +220,16 @@ struct cmi_gpu_engine {
      * (KeyArgs::class_order); -1 = the default of the run's kind, hydrogen-only
      * or multi-ion (DESIGN_LOG.md 14) */
     int class_order = -1;
-    int aggregate = CMI_AGG_BLOCK;      /* first generation (sorted bundles) */
+    /* hydrogen-only launches of bucket_min_packets packets and more: ordered
+     * by two scatter levels and a sort of the leaves in LDS (packet_order.h)
+     * instead of the radix sort; the levels' bits and the room of a region
+     * and a leaf beyond its mean, in thousandths (-1: packet_order_plan.h
+     * chooses) */
+    bool bucket_order = true;
+    int bucket_bits1 = -1, bucket_bits2 = -1;
+    int bucket_slack_permille = -1;
+    uint64_t bucket_min_packets = 1000000;
+    int aggregate = CMI_AGG_BLOCK;     /* first generation (sorted bundles) */
     int aggregate_reemit = CMI_AGG_NONE; /* later generations (random flights) */
     int refill_threshold = CMI_REFILL_THRESHOLD;
     uint32_t chunk = 64;
@@ -1304,6 +1322,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->select_ids);
   (void)hipFree(e->select_rows);
   (void)hipFree(e->sort_temp);
+  (void)hipFree(e->bucket_meta);
   (void)hipFree(e->queue_block);
   (void)hipFree(e->queue_counts);
   if (e->mailbox)
@@ -1818,6 +1837,48 @@ int cmi_gpu_get_transport_plan(cmi_gpu_engine *e, int32_t *first_build,
   return CMI_GPU_OK;
 }
 
+/* the words of cmi_gpu_engine::bucket_meta: the regions' and the leaves'
+ * cursors, the overflow list's, the count of ordered ids - cleared before
+ * every launch - and the leaves' offsets */
+#define CMI_BUCKET_META_LEAF_CURSOR                                            \
+  ((size_t)CMI_BUCKET_MAX * CMI_BUCKET_REGION_CURSOR_STRIDE)
+#define CMI_BUCKET_META_OVERFLOW                                               \
+  (CMI_BUCKET_META_LEAF_CURSOR + (size_t)CMI_BUCKET_MAX * CMI_BUCKET_MAX)
+#define CMI_BUCKET_META_ORDERED (CMI_BUCKET_META_OVERFLOW + 1)
+#define CMI_BUCKET_META_CLEARED (CMI_BUCKET_META_OVERFLOW + 8)
+#define CMI_BUCKET_META_LEAF_OFFSET CMI_BUCKET_META_CLEARED
+#define CMI_BUCKET_META_WORDS                                                  \
+  (CMI_BUCKET_META_LEAF_OFFSET + (size_t)CMI_BUCKET_MAX * CMI_BUCKET_MAX)
+static uint32_t *bucket_overflow_cursor(const cmi_gpu_engine *e) {
+  return e->bucket_meta + CMI_BUCKET_META_OVERFLOW;
+}
+
+int cmi_gpu_get_order_plan(cmi_gpu_engine *e, int32_t *path, int32_t *bits1,
+                           int32_t *bits2, uint64_t *overflow) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  const bool bucket = e->last_order_path == CMI_GPU_ORDER_BUCKET;
+  if (path)
+    *path = e->last_order_path;
+  if (bits1)
+    *bits1 = bucket ? e->last_bucket_bits[0] : 0;
+  if (bits2)
+    *bits2 = bucket ? e->last_bucket_bits[1] : 0;
+  if (overflow) {
+    *overflow = 0;
+    if (bucket) {
+      /* (the launch's cursors stay as they are until the next launch) */
+      uint32_t sent = 0;
+      HIP_TRY(hipSetDevice(e->device));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      HIP_TRY(hipMemcpy(&sent, bucket_overflow_cursor(e), sizeof sent,
+                        hipMemcpyDeviceToHost));
+      *overflow = sent;
+    }
+  }
+  return CMI_GPU_OK;
+}
+
 int cmi_gpu_reset_grid(cmi_gpu_engine *e) {
   if (!e)
     return fail(CMI_GPU_EINVAL, "null engine");
@@ -1855,8 +1916,19 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.sort_tau_bits = (int)(value < 0 ? -1 : (value > 3 ? 3 : value));
   else if (k == "class_order")
     e->tune.class_order = (int)(value < 0 ? -1 : (value != 0 ? 1 : 0));
+  else if (k == "bucket_order")
+    e->tune.bucket_order = value != 0;
+  else if (k == "bucket_bits1")
+    e->tune.bucket_bits1 = (int)(value < 0 ? -1 : (value > 8 ? 8 : value));
+  else if (k == "bucket_bits2")
+    e->tune.bucket_bits2 = (int)(value < 0 ? -1 : (value > 8 ? 8 : value));
+  else if (k == "bucket_slack_permille")
+    e->tune.bucket_slack_permille =
+        (int)(value < 0 ? -1 : (value > 1000000 ? 1000000 : value));
+  else if (k == "bucket_min_packets")
+    e->tune.bucket_min_packets = (uint64_t)(value < 0 ? 0 : value);
   else if (k == "aggregate")
-    e->tune.aggregate = (int)(value < 0 ? 0 : (value > 2 ? 2 : value));
+    e->tune.aggregate =(int)(value < 0 ? 0 : (value > 2 ? 2 : value));
   else if (k == "aggregate_reemit")
     e->tune.aggregate_reemit = (int)(value < 0 ? 0 : (value > 2 ? 2 : value));
   else if (k == "refill_threshold")
@@ -1984,6 +2056,55 @@ static int read_counters(cmi_gpu_engine *e, const unsigned int *src, int n,
 int cmi_gpu_shoot(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
                   uint64_t first_packet, uint64_t n_packets) {
   return shoot_impl(e, seed, iteration, first_packet, n_packets, nullptr);
+}
+
+int cmi_gpu_order_packets(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
+                          uint64_t first_packet, uint64_t n, uint32_t *out_ids,
+                          uint32_t *out_keys) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  if (!e->have_sources || (e->model.nsource > 0 && !e->have_spectrum) ||
+      (e->model.continuous_type != 0 && !e->have_continuous_spectrum) ||
+      !e->have_xsec || !e->have_cells)
+    return fail(CMI_GPU_ESTATE,
+                "order_packets: sources, their spectra, cross sections and "
+                "cell data must be set first");
+  if (n == 0)
+    return CMI_GPU_OK;
+  if (n > e->tune.max_packets_per_launch)
+    return fail(CMI_GPU_EINVAL, "order_packets: %llu packets are more than "
+                "one launch (max_packets_per_launch)", (unsigned long long)n);
+  HIP_TRY(hipSetDevice(e->device));
+  CMI_TRY(ensure_spectra(e));
+  LaunchPlan plan;
+  CMI_TRY(plan_launches(e, n, nullptr, plan));
+  if (!plan.sorted || plan.select_mode)
+    return fail(CMI_GPU_ESTATE, "order_packets: a transport call of this "
+                "engine %s", plan.sorted ? "orders a block's selection"
+                                         : "does not order its packets");
+  CMI_TRY(reserve_for(e, plan, n));
+  ShootArgs a = shoot_args(e, plan, seed, iteration, first_packet, 0, n,
+                           nullptr);
+  CMI_TRY(order_packets(e, plan, a, n, nullptr));
+  uint32_t *dkeys = nullptr;
+  if (out_keys) {
+    HIP_TRY(hipMalloc(&dkeys, sizeof(uint32_t) * n));
+    const KeyArgs k = key_args(e, plan, a, n, nullptr);
+    order_probe_kernel<<<grid_blocks(e, (int64_t)n, 8), CMI_BLOCK, 0,
+                         e->stream>>>(k, a.order, dkeys);
+  }
+  hipError_t err = hipGetLastError();
+  if (err == hipSuccess)
+    err = hipStreamSynchronize(e->stream);
+  if (err == hipSuccess && out_ids)
+    err = hipMemcpy(out_ids, a.order, sizeof(uint32_t) * n,
+                    hipMemcpyDeviceToHost);
+  if (err == hipSuccess && out_keys)
+    err = hipMemcpy(out_keys, dkeys, sizeof(uint32_t) * n,
+                    hipMemcpyDeviceToHost);
+  (void)hipFree(dkeys);
+  HIP_TRY(err);
+  return CMI_GPU_OK;
 }
 
 int cmi_gpu_shoot_flights(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,

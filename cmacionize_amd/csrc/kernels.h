@@ -3272,6 +3272,58 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_KEY_WAVES)
   direction_key_batches(a);
 }
 
+/* The key of entry i of a launch without emission rows (pre_rows == nullptr),
+ * and in `id` the packet's id in the launch: what direction_key_kernel writes,
+ * and what the bucket order (packet_order.h) scatters by. */
+__device__ __forceinline__ uint32_t direction_key_of(const KeyArgs &a,
+                                                     const PacketOrigin &from,
+                                                     uint64_t i,
+                                                     uint32_t &id_out) {
+  const uint32_t lo_bits = a.dir_bits - a.dir_hi_bits;
+  PacketRng rng;
+  const uint64_t id = a.select ? (uint64_t)a.select[i] : i;
+  rng.init(a.seed, a.iteration, a.first_packet + id);
+  uint32_t src;
+  const uint32_t origin = from.draw(a.model, rng, src);
+  if (origin != 0) {
+    /* the continuous source: one more "source" (src = nsource), its packets
+     * ordered by direction like the others (they enter all over the box) */
+    (void)rng.next(); /* the focus point, or the point in the plane */
+    (void)rng.next();
+    if (a.model.continuous_type == 1)
+      (void)rng.next();
+  }
+  const double u_cost = rng.next(); /* cos(theta) = 2 u - 1 */
+  const double u_phi = rng.next();  /* phi = 2 pi u */
+  const uint32_t ic = (uint32_t)(u_cost * 2048.);
+  const uint32_t ip = (uint32_t)(u_phi * 2048.);
+  const uint32_t morton =
+      (spread_bits_11(ic) | (spread_bits_11(ip) << 1)) >> (22u - a.dir_bits);
+  uint32_t tau_class = 0;
+  if (a.tau_bits != 0) {
+    if (!a.full_ions) {
+      (void)sample_source_spectrum(a.model, rng, origin); /* its draws */
+      const double u_tau = rng.next();            /* tau = -ln u */
+      tau_class = (uint32_t)(u_tau * (double)(1u << a.tau_bits));
+    } else {
+      const double nu = sample_source_spectrum(a.model, rng, origin);
+      const double tau = -log(rng.next());
+      /* (single precision: the class only orders the packets) */
+      const float sigma = approximate_opacity_cross_section(a.model, nu);
+      const float range = (float)(tau * a.sigma_ref) / sigma;
+      const int octave = (int)floorf(log2f(range)) + (1 << (a.tau_bits - 1));
+      const int top = (1 << a.tau_bits) - 1;
+      tau_class = (uint32_t)(octave < 0 ? 0 : (octave > top ? top : octave));
+    }
+  }
+  const uint32_t hi = morton >> lo_bits;
+  const uint32_t lo = morton & ((1u << lo_bits) - 1u);
+  id_out = (uint32_t)id;
+  return ((src & a.source_mask) << (a.dir_bits + a.tau_bits)) |
+         (hi << (a.tau_bits + lo_bits)) |
+         (key_class_field(a, hi, tau_class) << lo_bits) | lo;
+}
+
 /* ... and without (pre_rows == nullptr): a kernel of its own, so that its few
  * registers are not the other's 168 */
 /* (5 waves per SIMD, as before the table modes and the selection list joined
@@ -3279,54 +3331,16 @@ __global__ void __launch_bounds__(CMI_BLOCK, CMI_KEY_WAVES)
 __global__ void __launch_bounds__(CMI_BLOCK, 5)
     direction_key_kernel(const KeyArgs a) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const uint32_t lo_bits = a.dir_bits - a.dir_hi_bits;
   const PacketOrigin from(a.model);
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
        i < a.n_packets; i += stride) {
-    PacketRng rng;
-    const uint64_t id = a.select ? (uint64_t)a.select[i] : i;
-    rng.init(a.seed, a.iteration, a.first_packet + id);
-    uint32_t src;
-    const uint32_t origin = from.draw(a.model, rng, src);
-    if (origin != 0) {
-      /* the continuous source: one more "source" (src = nsource), its packets
-       * ordered by direction like the others (they enter all over the box) */
-      (void)rng.next(); /* the focus point, or the point in the plane */
-      (void)rng.next();
-      if (a.model.continuous_type == 1)
-        (void)rng.next();
-    }
-    const double u_cost = rng.next(); /* cos(theta) = 2 u - 1 */
-    const double u_phi = rng.next();  /* phi = 2 pi u */
-    const uint32_t ic = (uint32_t)(u_cost * 2048.);
-    const uint32_t ip = (uint32_t)(u_phi * 2048.);
-    const uint32_t morton =
-        (spread_bits_11(ic) | (spread_bits_11(ip) << 1)) >> (22u - a.dir_bits);
-    uint32_t tau_class = 0;
-    if (a.tau_bits != 0) {
-      if (!a.full_ions) {
-        (void)sample_source_spectrum(a.model, rng, origin); /* its draws */
-        const double u_tau = rng.next();            /* tau = -ln u */
-        tau_class = (uint32_t)(u_tau * (double)(1u << a.tau_bits));
-      } else {
-        const double nu = sample_source_spectrum(a.model, rng, origin);
-        const double tau = -log(rng.next());
-        /* (single precision: the class only orders the packets) */
-        const float sigma = approximate_opacity_cross_section(a.model, nu);
-        const float range = (float)(tau * a.sigma_ref) / sigma;
-        const int octave = (int)floorf(log2f(range)) + (1 << (a.tau_bits - 1));
-        const int top = (1 << a.tau_bits) - 1;
-        tau_class = (uint32_t)(octave < 0 ? 0 : (octave > top ? top : octave));
-      }
-    }
-    const uint32_t hi = morton >> lo_bits;
-    const uint32_t lo = morton & ((1u << lo_bits) - 1u);
-    a.keys[i] = ((src & a.source_mask) << (a.dir_bits + a.tau_bits)) |
-                (hi << (a.tau_bits + lo_bits)) |
-                (key_class_field(a, hi, tau_class) << lo_bits) | lo;
-    a.ids[i] = (uint32_t)id;
+    uint32_t id;
+    a.keys[i] = direction_key_of(a, from, i, id);
+    a.ids[i] = id;
   }
 }
+
+#include "packet_order.h"
 
 /* ------------------------------------------------------- cell update -- */
 

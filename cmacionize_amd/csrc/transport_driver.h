@@ -8,18 +8,27 @@
 #ifndef CMI_TRANSPORT_DRIVER_H
 #define CMI_TRANSPORT_DRIVER_H
 
-/* make sure the sort buffers hold n packets */
-static int reserve_sort_buffers(cmi_gpu_engine *e, uint64_t n) {
-  if (e->sort_capacity >= n)
+/* make sure the sort buffers hold n packets, in a block of at least `words`
+ * 32-bit words (what the bucket order of such a launch lays into it; the
+ * radix sort needs 4 n) */
+static int reserve_sort_buffers(cmi_gpu_engine *e, uint64_t n,
+                                uint64_t words = 0) {
+  if (e->sort_capacity >= n && e->sort_block_words >= words)
     return CMI_GPU_OK;
+  if (n < e->sort_capacity)
+    n = e->sort_capacity;
+  if (words < 4 * n)
+    words = 4 * n;
   HIP_TRY(hipStreamSynchronize(e->stream));
   (void)hipFree(e->sort_keys[0]);
   (void)hipFree(e->sort_temp);
   e->sort_keys[0] = nullptr;
   e->sort_temp = nullptr;
   e->sort_capacity = 0;
+  e->sort_block_words = 0;
   uint32_t *block = nullptr;
-  HIP_TRY(hipMalloc(&block, sizeof(uint32_t) * 4 * n));
+  HIP_TRY(hipMalloc(&block, sizeof(uint32_t) * words));
+  e->sort_block_words = words;
   e->sort_keys[0] = block;
   e->sort_keys[1] = block + n;
   e->sort_ids[0] = block + 2 * n;
@@ -252,6 +261,10 @@ struct LaunchPlan {
   uint32_t tau_bits, source_bits, dir_bits;
   int key_bits;
   double sigma_ref;
+  /* the launches that are large enough get their order from the bucket
+   * order (packet_order.h; bucket_plan_of decides per launch), the others
+   * and every launch of the other plans from key kernel and radix sort */
+  bool bucket_order;
   TileKernel tile_kernel;
   int tile_threads, tile_blocks_per_cu;
 };
@@ -513,7 +526,25 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
       p.dir_bits = 22u - over;
   }
   p.key_bits = (int)(p.dir_bits + p.tau_bits + p.source_bits);
+  /* the bucket order counts on uniform keys: the hydrogen-only ones are (the
+   * Morton code of two uniform draws, the class from a third), the octaves of
+   * a multi-ion packet's range are not; a block's selection and the key
+   * kernel that writes the emission rows keep their own path */
+  p.bucket_order = p.sorted && !p.select_mode && p.first != FIRST_PRE &&
+                   !e->full_ions && tune.bucket_order;
   return CMI_GPU_OK;
+}
+
+/* the bucket order of a launch of n packets (take == 0: the radix sort) */
+static BucketPlan bucket_plan_of(const cmi_gpu_engine *e, const LaunchPlan &p,
+                                 uint64_t n) {
+  if (!p.bucket_order) {
+    BucketPlan none = {};
+    return none;
+  }
+  return cmi_bucket_plan(n, p.key_bits, e->tune.bucket_bits1,
+                         e->tune.bucket_bits2, e->tune.bucket_slack_permille,
+                         e->tune.bucket_min_packets);
 }
 
 /* the buffers of a launch of at most `cap` flights */
@@ -521,7 +552,10 @@ static int reserve_for(cmi_gpu_engine *e, const LaunchPlan &p, uint64_t cap) {
   if (!e->span_cursor)
     HIP_TRY(hipMalloc(&e->span_cursor, sizeof(uint32_t) * CMI_SPAN_CURSORS));
   if (p.sorted || p.tiles)
-    CMI_TRY(reserve_sort_buffers(e, cap));
+    CMI_TRY(reserve_sort_buffers(e, cap, bucket_plan_of(e, p, cap).total_words));
+  if (p.bucket_order && !e->bucket_meta)
+    HIP_TRY(hipMalloc(&e->bucket_meta,
+                      sizeof(uint32_t) * CMI_BUCKET_META_WORDS));
   if (p.passes)
     CMI_TRY(reserve_queues(e, cap));
   if (p.tiles)
@@ -692,8 +726,17 @@ static int open_ended_queue(cmi_gpu_engine *e, ShootArgs &a) {
  * tau class (and a.pre_rows holds their emission rows, FIRST_PRE); nids ids
  * in the launch, of which `select` (if not NULL) lists the a.n_packets that
  * fly */
-static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
-                         uint64_t nids, const uint32_t *select) {
+enum OrderPath {
+  ORDER_NONE = CMI_GPU_ORDER_NONE,
+  ORDER_RADIX = CMI_GPU_ORDER_RADIX,
+  ORDER_BUCKET = CMI_GPU_ORDER_BUCKET
+};
+
+/* the sort keys of a launch: nids ids, of which `select` (if not NULL) lists
+ * the a.n_packets that fly; keys, ids and rows are the caller's to set */
+static KeyArgs key_args(const cmi_gpu_engine *e, const LaunchPlan &p,
+                        const ShootArgs &a, uint64_t nids,
+                        const uint32_t *select) {
   const uint64_t n = a.n_packets;
   KeyArgs k;
   k.model = e->model;
@@ -724,6 +767,78 @@ static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
            (per_source >> (k.dir_hi_bits + 1u)) >= per_bin)
       ++k.dir_hi_bits;
   }
+  k.keys = nullptr;
+  k.ids = nullptr;
+  k.pre_rows = nullptr;
+  k.select = select;
+  return k;
+}
+
+/* The bucket order of a launch (packet_order.h): a.order lists its packets as
+ * the radix sort would, with those that overflowed behind them. The regions,
+ * the leaves and the order lie in the block of the sort buffers. */
+static int order_packets_bucket(cmi_gpu_engine *e, const BucketPlan &bp,
+                                const KeyArgs &k, ShootArgs &a) {
+  uint32_t *block = e->sort_keys[0];
+  uint32_t *meta = e->bucket_meta;
+  BucketArgs b;
+  b.n = (uint32_t)a.n_packets;
+  b.key_bits = (uint32_t)(bp.bits1 + bp.bits2 + bp.rem_bits);
+  b.bits1 = (uint32_t)bp.bits1;
+  b.bits2 = (uint32_t)bp.bits2;
+  b.rem_bits = (uint32_t)bp.rem_bits;
+  b.region_cap = bp.region_cap;
+  b.leaf_cap = bp.leaf_cap;
+  b.order = block;
+  b.regions = reinterpret_cast<uint2 *>(block + bp.region_begin);
+  b.leaves = reinterpret_cast<uint2 *>(block + bp.leaf_begin);
+  b.region_cursor = meta;
+  b.leaf_cursor = meta + CMI_BUCKET_META_LEAF_CURSOR;
+  b.overflow_cursor = meta + CMI_BUCKET_META_OVERFLOW;
+  b.ordered = meta + CMI_BUCKET_META_ORDERED;
+  b.leaf_offset = meta + CMI_BUCKET_META_LEAF_OFFSET;
+  HIP_TRY(hipMemsetAsync(meta, 0, sizeof(uint32_t) * CMI_BUCKET_META_CLEARED,
+                         e->stream));
+  const uint32_t ntiles =
+      (b.n + CMI_BUCKET_TILE - 1u) / CMI_BUCKET_TILE;
+  int per_cu = 0;
+  CMI_TRY(blocks_per_cu_of(bucket_key_kernel, CMI_BUCKET_THREADS, 8, per_cu));
+  const uint32_t most = (uint32_t)(e->num_cu * per_cu);
+  bucket_key_kernel<<<ntiles < most ? ntiles : most, CMI_BUCKET_THREADS, 0,
+                      e->stream>>>(k, b);
+  const uint32_t region_tiles =
+      (b.region_cap + CMI_BUCKET_TILE - 1u) / CMI_BUCKET_TILE;
+  bucket_split_kernel<<<dim3(region_tiles, 1u << b.bits1), CMI_BUCKET_THREADS,
+                        0, e->stream>>>(b);
+  const uint32_t nleaves = 1u << (b.bits1 + b.bits2);
+  bucket_offsets_kernel<<<(nleaves + CMI_BUCKET_SCAN_THREADS - 1u) /
+                              CMI_BUCKET_SCAN_THREADS,
+                          CMI_BUCKET_SCAN_THREADS, 0, e->stream>>>(b);
+  bucket_leaf_kernel<<<nleaves, CMI_BUCKET_LEAF_THREADS, 0, e->stream>>>(b);
+  HIP_TRY(hipGetLastError());
+  a.order = b.order;
+  return CMI_GPU_OK;
+}
+
+/* keys and sort: a.order lists the launch's packets by source, direction and
+ * tau class (and a.pre_rows holds their emission rows, FIRST_PRE); nids ids
+ * in the launch, of which `select` (if not NULL) lists the a.n_packets that
+ * fly */
+static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
+                         uint64_t nids, const uint32_t *select) {
+  const uint64_t n = a.n_packets;
+  KeyArgs k = key_args(e, p, a, nids, select);
+  const BucketPlan bp = bucket_plan_of(e, p, n);
+  /* (a launch whose plan needs more room than the block has - the buffers
+   * were reserved for another plan - keeps the radix sort) */
+  if (bp.take && !select && e->bucket_meta &&
+      bp.total_words <= e->sort_block_words) {
+    e->last_order_path = ORDER_BUCKET;
+    e->last_bucket_bits[0] = bp.bits1;
+    e->last_bucket_bits[1] = bp.bits2;
+    return order_packets_bucket(e, bp, k, a);
+  }
+  e->last_order_path = ORDER_RADIX;
   k.keys = e->sort_keys[0];
   k.ids = e->sort_ids[0];
   k.pre_rows = p.first == FIRST_PRE ? e->tile_rows[1].weights : nullptr;
@@ -736,7 +851,6 @@ static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
                  sizeof(double) * CMI_NACC * (size_t)nids));
     k.pre_rows = e->select_rows;
   }
-  k.select = select;
   a.pre_rows = k.pre_rows;
   if (k.pre_rows)
     emission_key_kernel<<<grid_blocks(e, (int64_t)n, 8), CMI_BLOCK, 0,
@@ -1223,6 +1337,8 @@ static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
   if (!flights) { /* (for cmi_gpu_get_transport_plan) */
     e->last_first_build = (int32_t)plan.first;
     e->last_pad_uniform = plan.pad_uniform;
+    if (!plan.sorted) /* (order_packets says which way otherwise) */
+      e->last_order_path = ORDER_NONE;
   }
   CMI_TRY(publish_escape(e, plan.tracking));
   const uint64_t max_launch = e->tune.max_packets_per_launch;

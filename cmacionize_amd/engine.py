@@ -26,6 +26,8 @@ FIELD_MEAN_INTENSITY = 16
 FIELD_HEATING = 30
 
 REEMIT_NONE, REEMIT_PHYSICAL, REEMIT_FIXED = 0, 1, 2
+# how a launch's packets were ordered (GpuEngine.order_plan)
+ORDER_NONE, ORDER_RADIX, ORDER_BUCKET = 0, 1, 2
 CONTINUOUS_NONE, CONTINUOUS_ISOTROPIC, CONTINUOUS_PLANAR = 0, 1, 2
 # cmi_gpu_set_*_table (the generic lowering of a plugin into a table)
 ROLE_SOURCE, ROLE_CONTINUOUS = 0, 1
@@ -152,6 +154,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_set_escape_tally", "cmi_gpu_reset_escape_tally",
     "cmi_gpu_download_escape_tally", "cmi_gpu_escape_pixels",
     "cmi_gpu_cross_sections", "cmi_gpu_get_transport_plan",
+    "cmi_gpu_get_order_plan", "cmi_gpu_order_packets",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -352,6 +355,14 @@ def load_library():
     if hasattr(L, "cmi_gpu_get_transport_plan"):
         L.cmi_gpu_get_transport_plan.argtypes = [vp] + 2 * [
             C.POINTER(C.c_int32)]
+    # (a build from before the bucket order, loaded through CMI_GPU_LIBRARY
+    # for a comparison, does not have them)
+    if hasattr(L, "cmi_gpu_get_order_plan"):
+        L.cmi_gpu_get_order_plan.argtypes = [vp] + 3 * [
+            C.POINTER(C.c_int32)] + [C.POINTER(C.c_uint64)]
+        L.cmi_gpu_order_packets.argtypes = [
+            vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+            C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.cmi_gpu_reset_grid.argtypes = [vp]
     L.cmi_gpu_shoot.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64,
                                 C.c_uint64]
@@ -1062,6 +1073,18 @@ class GpuEngine:
             self._h, C.byref(first), C.byref(uniform)))
         return first.value, bool(uniform.value)
 
+    def order_plan(self):
+        """(path, bits of the first scatter level, of the second, packets
+        that overflowed) of the last launch of new packets: path ORDER_NONE,
+        ORDER_RADIX (key kernel and radix sort) or ORDER_BUCKET (the bucket
+        order, tuning "bucket_order")."""
+        path, b1, b2 = C.c_int32(), C.c_int32(), C.c_int32()
+        overflow = C.c_uint64()
+        self._check(self._lib.cmi_gpu_get_order_plan(
+            self._h, C.byref(path), C.byref(b1), C.byref(b2),
+            C.byref(overflow)))
+        return path.value, b1.value, b2.value, overflow.value
+
     # iteration body -----------------------------------------------------------
     def field_tensor(self, field):
         """Zero-copy torch view of a state field ([ncell] doubles on the
@@ -1348,6 +1371,18 @@ class GpuEngine:
             self._h, seed, iteration, first_packet, n, _p(pos), _p(dirn),
             _p(nu), _p(sig), _p(tau)))
         return pos, dirn, nu, sig, tau
+
+    def order_packets(self, seed, iteration, first_packet, n):
+        """(ids, keys) of the order a shoot of these n packets - one launch -
+        would fly them in: position j is packet first_packet + ids[j], its
+        sort key keys[j]."""
+        ids = np.empty(n, dtype=np.uint32)
+        keys = np.empty(n, dtype=np.uint32)
+        u32 = C.POINTER(C.c_uint32)
+        self._check(self._lib.cmi_gpu_order_packets(
+            self._h, seed, iteration, first_packet, n,
+            ids.ctypes.data_as(u32), keys.ctypes.data_as(u32)))
+        return ids, keys
 
     def trace_packets(self, position, direction, tau, sigma_H, sigma_He_corr,
                       max_steps):

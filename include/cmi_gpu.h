@@ -313,6 +313,19 @@ int cmi_gpu_get_update_state(cmi_gpu_engine *engine, int32_t *metals_pending,
  * was the padded march's build for packets of one weight ("pad_uniform"). */
 int cmi_gpu_get_transport_plan(cmi_gpu_engine *engine, int32_t *first_build,
                                int32_t *uniform_weight);
+/* How the last launch of new packets got its order (any pointer may be
+ * NULL): path - CMI_GPU_ORDER_NONE: the packets flew in the order of their
+ * ids, _RADIX: key kernel and radix sort, _BUCKET: the bucket order (tuning
+ * "bucket_order") -, the bits of the bucket order's two scatter levels, and
+ * the packets that found their region or leaf full and fly, unordered, behind
+ * the ordered ones (0 on the other paths). Asking for the overflow waits for
+ * the engine's stream. */
+#define CMI_GPU_ORDER_NONE 0
+#define CMI_GPU_ORDER_RADIX 1
+#define CMI_GPU_ORDER_BUCKET 2
+int cmi_gpu_get_order_plan(cmi_gpu_engine *engine, int32_t *path,
+                           int32_t *bits1, int32_t *bits2,
+                           uint64_t *overflow);
 int cmi_gpu_accumulator_layout(cmi_gpu_engine *engine, int64_t *field_stride,
                                int64_t *cell_stride);
 
@@ -623,6 +636,23 @@ int cmi_gpu_cross_sections(cmi_gpu_engine *engine, int64_t n,
  *                           2048 x 2048 lattice, Morton order); -1 = auto: 22,
  *                           or one or two fewer where that saves the radix
  *                           sort a pass
+ *   "bucket_order" (1)      hydrogen-only launches on an undivided grid: the
+ *                           order by two scatter levels - the first inside
+ *                           the key kernel - and a sort of the leaves in LDS
+ *                           instead of key kernel and radix sort; the same
+ *                           order, word for word, unless a region or a leaf
+ *                           overflows (cmi_gpu_get_order_plan). Taken where
+ *                           the two levels leave at most 8 key bits to the
+ *                           leaves; 0 = always the radix sort
+ *   "bucket_min_packets" (1000000) launches of fewer packets keep the radix
+ *                           sort
+ *   "bucket_bits1", "bucket_bits2" (-1) bits of the two levels, 0 .. 8; -1 =
+ *                           from the launch's packets, a mean leaf of 1024 to
+ *                           2047 pairs (8 + 8 at 1e8 packets)
+ *   "bucket_slack_permille" (-1) room of a region and a leaf beyond its mean
+ *                           share of the launch, in thousandths; -1 = 12 and
+ *                           9 standard deviations of a Poisson count (2 % and
+ *                           23 % at 1e8 packets): uniform keys never overflow
  *   "aggregate" (2)         what happens to a step's contributions before
  *                           HBM sees an atomic: 0 = one atomic per lane and
  *                           step; 1 = lanes of a wave in the same cell are
@@ -837,6 +867,18 @@ int cmi_gpu_emit_packets(cmi_gpu_engine *engine, uint32_t seed,
                          double *position, double *direction,
                          double *frequency, double *cross_sections,
                          double *tau);
+
+/* Probe of the packet order: what a cmi_gpu_shoot of packets [first_packet,
+ * first_packet + n) - one launch: n <= "max_packets_per_launch" - would fly
+ * its first generation in, by the same plan and the same kernels. Host
+ * outputs: out_ids [n] - position j of the launch is packet first_packet +
+ * out_ids[j] -, out_keys [n] - the sort keys of those packets, in that order
+ * (either may be NULL). cmi_gpu_get_order_plan then speaks of this launch.
+ * CMI_GPU_ESTATE where such a call would not order its packets, or - a block
+ * of a decomposed grid - orders a selection of them. Synchronous. */
+int cmi_gpu_order_packets(cmi_gpu_engine *engine, uint32_t seed,
+                          uint32_t iteration, uint64_t first_packet,
+                          uint64_t n, uint32_t *out_ids, uint32_t *out_keys);
 
 /* Parity probe of CartesianDensityGrid::interact
  * (src/CartesianDensityGrid.cpp:375-452) for n caller-specified packets:
