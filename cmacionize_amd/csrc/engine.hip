@@ -184,6 +184,8 @@ struct cmi_gpu_engine {
    * and whether it was the UNIFORM one: cmi_gpu_get_transport_plan */
   int32_t last_first_build = 0;
   bool last_pad_uniform = false;
+  /* ... and whether it was the bundle build: cmi_gpu_get_bundle_march */
+  bool last_bundle_march = false;
   /* the hydrogen-only update's deferred half: the gates of the last whole-grid
    * update, a bit per cell, and whether x[2..13] have still to be made from
    * them (settle_metal_fractions). Once a pointer to a state field has been
@@ -220,6 +222,11 @@ struct cmi_gpu_engine {
      * (KeyArgs::class_order); -1 = the default of the run's kind, hydrogen-only
      * or multi-ion (DESIGN_LOG.md 14) */
     int class_order = -1;
+    /* the coarse direction bins of that key hold this many chunks of 64 per
+     * tau class (key_args): with 8 a (bin, class) group is wider than a span,
+     * so the chunks a block's waves fly in one round come from one class or
+     * two neighbouring ones */
+    int class_group_chunks = 1;
     /* hydrogen-only launches of bucket_min_packets packets and more: ordered
      * by two scatter levels and a sort of the leaves in LDS (packet_order.h)
      * instead of the radix sort; the levels' bits and the room of a region
@@ -302,6 +309,11 @@ struct cmi_gpu_engine {
      * are what DESIGN_LOG.md 13 measured) */
     bool span_claim = CMI_SPAN_CLAIM_DEFAULT;
     bool emit_before_flush = CMI_EMIT_BEFORE_FLUSH_DEFAULT;
+    /* the padded first generation whose every refill fills a whole idle wave
+     * (chunk 64, refill_threshold 64, claimed spans, new packets, no heating,
+     * no re-emission, an undivided grid): the bundle build,
+     * shoot_bundle_kernel (false: the general kernel) */
+    bool bundle_march = true;
     bool phase_stamps = false; /* experiments build: ShootArgs::phase_clock */
     /* continuum images: channels per march launch (4, 8 or 16) and the rays
      * per launch (0: the images' and the sky maps' own bounds) */
@@ -1837,6 +1849,13 @@ int cmi_gpu_get_transport_plan(cmi_gpu_engine *e, int32_t *first_build,
   return CMI_GPU_OK;
 }
 
+int cmi_gpu_get_bundle_march(cmi_gpu_engine *e, int32_t *flown) {
+  if (!e || !flown)
+    return fail(CMI_GPU_EINVAL, "get_bundle_march: bad argument");
+  *flown = e->last_bundle_march ? 1 : 0;
+  return CMI_GPU_OK;
+}
+
 /* the words of cmi_gpu_engine::bucket_meta: the regions' and the leaves'
  * cursors, the overflow list's, the count of ordered ids - cleared before
  * every launch - and the leaves' offsets */
@@ -1916,6 +1935,9 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.sort_tau_bits = (int)(value < 0 ? -1 : (value > 3 ? 3 : value));
   else if (k == "class_order")
     e->tune.class_order = (int)(value < 0 ? -1 : (value != 0 ? 1 : 0));
+  else if (k == "class_group_chunks")
+    e->tune.class_group_chunks =
+        (int)(value < 1 ? 1 : (value > 64 ? 64 : value));
   else if (k == "bucket_order")
     e->tune.bucket_order = value != 0;
   else if (k == "bucket_bits1")
@@ -1996,6 +2018,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.span_claim = value != 0;
   else if (k == "emit_before_flush")
     e->tune.emit_before_flush = value != 0;
+  else if (k == "bundle_march")
+    e->tune.bundle_march = value != 0;
   else if (k == "phase_stamps")
     e->tune.phase_stamps = value != 0;
   else if (k == "continuum_channel_block") {

@@ -252,6 +252,10 @@ struct LaunchPlan {
   bool pad_uniform;
   double uniform_scale;
   int64_t padded_cells;
+  /* pad, and every refill of the launch fills a whole idle wave from one
+   * claimed chunk of 64 new packets that fly to their end where they are: the
+   * bundle build (shoot_bundle_kernel) */
+  bool bundle;
   /* the kernel of a pass, the one that follows re-emissions in place, and the
    * first generation's, with their workgroups per CU */
   ShootKernel kernel, kernel_inline, kernel_first;
@@ -458,6 +462,18 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
   p.kernel_first = table ? shoot_build(e->full_ions, p.heat, false, false,
                                        false, p.first, p.pad_uniform)
                          : p.kernel;
+  /* The bundle build of the padded march (tuning "bundle_march"): new packets
+   * from ids (table: !flights), claimed spans of chunks of 64 that a wave
+   * takes only when all its lanes are idle, an undivided grid in the smaller
+   * blocks, no heating term, and no re-emission - in passes it would park the
+   * absorbed packets, in place the table is not taken at all. Everything else
+   * keeps the general kernels. */
+  p.bundle = p.pad && !p.pad_big && !p.heat && !p.reemit &&
+             !e->grid.decomposed && tune.span_claim && tune.chunk == 64 &&
+             tune.refill_threshold == 64 && tune.bundle_march;
+  if (p.bundle)
+    p.kernel_first = p.pad_uniform ? shoot_bundle_kernel<true>
+                                   : shoot_bundle_kernel<false>;
   CMI_TRY(blocks_per_cu_of(p.kernel, CMI_BLOCK, tune.max_blocks_per_cu,
                            p.blocks_per_cu));
   CMI_TRY(blocks_per_cu_of(p.kernel_inline, CMI_BLOCK, tune.max_blocks_per_cu,
@@ -754,11 +770,13 @@ static KeyArgs key_args(const cmi_gpu_engine *e, const LaunchPlan &p,
   k.full_ions = e->full_ions ? 1 : 0;
   k.sigma_ref = p.sigma_ref;
   k.source_mask = (1u << p.source_bits) - 1u;
-  /* coarse direction bins of ~64 x 2^tau_bits packets per source */
+  /* coarse direction bins of ~64 x 2^tau_bits packets per source - or, tuning
+   * "class_group_chunks", that many chunks of 64 per class */
   k.dir_hi_bits = 0;
   k.dir_bits = p.dir_bits;
   if (p.tau_bits != 0) {
-    const uint64_t per_bin = 64ull << p.tau_bits;
+    const uint64_t per_bin =
+        (64ull * (uint64_t)e->tune.class_group_chunks) << p.tau_bits;
     /* (a block's own packets fill its part of the sphere as densely as
      * the launch's ids fill the whole) */
     const uint64_t per_source =
@@ -1337,6 +1355,7 @@ static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
   if (!flights) { /* (for cmi_gpu_get_transport_plan) */
     e->last_first_build = (int32_t)plan.first;
     e->last_pad_uniform = plan.pad_uniform;
+    e->last_bundle_march = plan.bundle;
     if (!plan.sorted) /* (order_packets says which way otherwise) */
       e->last_order_path = ORDER_NONE;
   }

@@ -155,6 +155,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_download_escape_tally", "cmi_gpu_escape_pixels",
     "cmi_gpu_cross_sections", "cmi_gpu_get_transport_plan",
     "cmi_gpu_get_order_plan", "cmi_gpu_order_packets",
+    "cmi_gpu_get_bundle_march",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -355,6 +356,8 @@ def load_library():
     if hasattr(L, "cmi_gpu_get_transport_plan"):
         L.cmi_gpu_get_transport_plan.argtypes = [vp] + 2 * [
             C.POINTER(C.c_int32)]
+    if hasattr(L, "cmi_gpu_get_bundle_march"):
+        L.cmi_gpu_get_bundle_march.argtypes = [vp, C.POINTER(C.c_int32)]
     # (a build from before the bucket order, loaded through CMI_GPU_LIBRARY
     # for a comparison, does not have them)
     if hasattr(L, "cmi_gpu_get_order_plan"):
@@ -1072,6 +1075,14 @@ class GpuEngine:
         self._check(self._lib.cmi_gpu_get_transport_plan(
             self._h, C.byref(first), C.byref(uniform)))
         return first.value, bool(uniform.value)
+
+    def bundle_march_flown(self):
+        """Whether the first generation of the last shoot flew the bundle
+        build of the padded march (tuning "bundle_march")."""
+        flown = C.c_int32()
+        self._check(self._lib.cmi_gpu_get_bundle_march(self._h,
+                                                       C.byref(flown)))
+        return bool(flown.value)
 
     def order_plan(self):
         """(path, bits of the first scatter level, of the second, packets

@@ -313,6 +313,10 @@ int cmi_gpu_get_update_state(cmi_gpu_engine *engine, int32_t *metals_pending,
  * was the padded march's build for packets of one weight ("pad_uniform"). */
 int cmi_gpu_get_transport_plan(cmi_gpu_engine *engine, int32_t *first_build,
                                int32_t *uniform_weight);
+/* Whether that first generation flew the bundle build of the padded march
+ * (tuning "bundle_march"): 1 or 0. cmi_gpu_get_transport_plan answers 2 for
+ * either build of it. */
+int cmi_gpu_get_bundle_march(cmi_gpu_engine *engine, int32_t *flown);
 /* How the last launch of new packets got its order (any pointer may be
  * NULL): path - CMI_GPU_ORDER_NONE: the packets flew in the order of their
  * ids, _RADIX: key kernel and radix sort, _BUCKET: the bucket order (tuning
@@ -766,6 +770,19 @@ int cmi_gpu_cross_sections(cmi_gpu_engine *engine, int64_t n,
  *   "emit_before_flush" (1) the same kernels: the refill ahead of the flush
  *                           point's barrier - a wave that arrives early emits
  *                           its next bundle while it would wait
+ *   "class_group_chunks" (1) sorted launches with tau classes: the key's
+ *                           coarse direction bins hold this many chunks of 64
+ *                           packets per class (1 to 64) - with 8 the chunks of
+ *                           one round of a block come from one class, or two
+ *                           neighbouring ones, of a patch eight times as wide
+ *   "bundle_march" (1)      the padded first generation of launches whose
+ *                           every refill fills a whole idle wave - "chunk" 64,
+ *                           "refill_threshold" 64, "span_claim", new packets
+ *                           on an undivided grid of at most 2^25 cells, no
+ *                           heating term, no re-emission -: the build of the
+ *                           kernel made for exactly that (shoot_bundle_kernel;
+ *                           the same packets in the same rounds) - 0: the
+ *                           general kernel
  *   "phase_stamps" (0)      EXPERIMENT ONLY: cmi_gpu_get_phase_clocks
  *   "exp_no_atomics" (0)    EXPERIMENT ONLY, builds with -DCMI_EXPERIMENTS
  *                           (results are wrong): 1 = skip the
