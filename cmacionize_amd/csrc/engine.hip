@@ -18,6 +18,7 @@
 #include "absorbing_cube_kernels.h"
 #include "lyman_alpha_kernels.h"
 #include "absorption_kernels.h"
+#include "sph_map_kernels.h"
 #include "sort.h"
 
 #include <algorithm>
@@ -172,6 +173,8 @@ struct cmi_gpu_engine {
    * (publish_escape); what that copy was written from */
   bool escape_counting = false;
   EscapeDev escape_staged = {};
+  /* what the last SPH mapping did (cmi_gpu_get_sph_map_stats) */
+  int64_t sph_map_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   /* PAD transport kernels: sigma_H n x_H inside a layer of ghost cells;
    * whether it holds the records of the cells and the cross section as they
    * are (whatever writes CellsDev::opacity clears this - pad_records_stale -
@@ -3197,6 +3200,351 @@ int cmi_gpu_cross_sections(cmi_gpu_engine *e, int64_t n,
   const ModelDev host_model = host_model_of(e);
   for (int64_t k = 0; k < n; ++k)
     cmi_cross_sections(host_model, frequencies[k], sigma + CMI_NION * k);
+  return CMI_GPU_OK;
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------ SPH mappings -- */
+
+namespace {
+
+/* device memory of one call */
+struct SphScratch {
+  std::vector<void *> blocks;
+  ~SphScratch() {
+    for (void *b : blocks)
+      (void)hipFree(b);
+  }
+  template <typename T> int get(T **ptr, size_t count, const char *what) {
+    void *b = nullptr;
+    if (hipMalloc(&b, sizeof(T) * (count ? count : 1)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(CMI_GPU_ENOMEM, "sph_map: no memory for %zu bytes of %s",
+                  sizeof(T) * count, what);
+    }
+    blocks.push_back(b);
+    *ptr = static_cast<T *>(b);
+    return CMI_GPU_OK;
+  }
+};
+
+/* device time between pairs of events, summed into the stats */
+struct SphTimer {
+  hipEvent_t events[4] = {nullptr, nullptr, nullptr, nullptr};
+  int used = 0;
+  ~SphTimer() {
+    for (hipEvent_t ev : events)
+      if (ev)
+        (void)hipEventDestroy(ev);
+  }
+  void mark(hipStream_t stream) {
+    if (used < 4 && hipEventCreate(&events[used]) == hipSuccess) {
+      (void)hipEventRecord(events[used], stream);
+      ++used;
+    }
+  }
+  /* after the stream was synchronized */
+  int64_t nanoseconds() const {
+    double ms = 0.;
+    for (int k = 0; k + 1 < used; k += 2) {
+      float part = 0.f;
+      if (hipEventElapsedTime(&part, events[k], events[k + 1]) == hipSuccess)
+        ms += part;
+    }
+    return (int64_t)(ms * 1.e6);
+  }
+};
+
+const char *const sph_decline_names[4] = {
+    "taken", "no particles",
+    "twice the largest reach is not below the smallest side of the periodic "
+    "box",
+    "the tile lists exceed the cap"};
+
+int sph_declined(cmi_gpu_engine *e, const char *call, int reason) {
+  e->sph_map_stats[6] = reason;
+  return fail(CMI_GPU_EDECLINED, "%s declined: %s", call,
+              sph_decline_names[reason]);
+}
+
+/* the arguments both mappings share; fills the geometry, uploads the
+ * particles and returns the largest reach */
+int sph_map_begin(cmi_gpu_engine *e, const char *call, int32_t form, int64_t n,
+                  const double *positions, const double *h,
+                  const double *periodic_box, const double *grid_anchor,
+                  const double *grid_sides, const int32_t *ncell,
+                  SphMapGeometry *g, SphScratch &mem, double **d_positions,
+                  double **d_h) {
+  if (!e)
+    return fail(CMI_GPU_EINVAL, "null engine");
+  for (int k = 0; k < 8; ++k)
+    e->sph_map_stats[k] = 0;
+  e->sph_map_stats[3] = CMI_SPH_STAGE_CHUNK;
+  if (form != CMI_SPH_FORM_SPLINE_H && form != CMI_SPH_FORM_SPLINE_2H)
+    return fail(CMI_GPU_EINVAL, "%s: unknown kernel form %d", call, (int)form);
+  if (n < 0 || !grid_anchor || !grid_sides || !ncell ||
+      (n > 0 && (!positions || !h)))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", call);
+  for (int a = 0; a < 3; ++a) {
+    if (ncell[a] < 1 || !(grid_sides[a] > 0.) || !std::isfinite(grid_sides[a]) ||
+        !std::isfinite(grid_anchor[a]))
+      return fail(CMI_GPU_EINVAL, "%s: bad grid", call);
+    if (periodic_box &&
+        (!(periodic_box[3 + a] > 0.) || !std::isfinite(periodic_box[3 + a])))
+      return fail(CMI_GPU_EINVAL, "%s: bad periodic box", call);
+  }
+  if ((int64_t)ncell[0] * ncell[1] * ncell[2] >= ((int64_t)1 << 31) ||
+      n >= ((int64_t)1 << 31))
+    return fail(CMI_GPU_EINVAL, "%s: 2^31 cells or particles or more", call);
+  double largest = 0.;
+  for (int64_t i = 0; i < n; ++i) {
+    if (!(h[i] > 0.) || !std::isfinite(h[i]) ||
+        !std::isfinite(positions[3 * i]) ||
+        !std::isfinite(positions[3 * i + 1]) ||
+        !std::isfinite(positions[3 * i + 2]))
+      return fail(CMI_GPU_EINVAL, "%s: particle %lld is not finite or has no "
+                  "smoothing length", call, (long long)i);
+    largest = std::max(largest, cmi_sph_reach(form, h[i]));
+  }
+  const int early =
+      cmi_sph_decline_early(n, largest, periodic_box ? periodic_box + 3 : nullptr);
+  if (early)
+    return sph_declined(e, call, early);
+  *g = cmi_sph_geometry(grid_anchor, grid_sides, ncell,
+                        periodic_box ? periodic_box + 3 : nullptr);
+  HIP_TRY(hipSetDevice(e->device));
+  CMI_TRY(mem.get(d_positions, 3 * (size_t)n, "positions"));
+  CMI_TRY(mem.get(d_h, (size_t)n, "smoothing lengths"));
+  HIP_TRY(hipMemcpyAsync(*d_positions, positions, sizeof(double) * 3 * n,
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(*d_h, h, sizeof(double) * n, hipMemcpyHostToDevice,
+                         e->stream));
+  return CMI_GPU_OK;
+}
+
+template <int FORM, bool PERIODIC>
+void sph_launch_cells(int K, int ntiles, hipStream_t stream,
+                      const SphMapGeometry &g, int64_t n, const double *pos,
+                      const double *h, const double *amp,
+                      const unsigned int *offsets, const uint32_t *list,
+                      double *out) {
+  const dim3 grid(ntiles), block(CMI_SPH_TILE_CELLS);
+  switch (K) {
+  case 1:
+    hipLaunchKernelGGL((sph_cells_kernel<FORM, 1, PERIODIC>), grid, block, 0,
+                       stream, g, n, pos, h, amp, offsets, list, out);
+    break;
+  case 2:
+    hipLaunchKernelGGL((sph_cells_kernel<FORM, 2, PERIODIC>), grid, block, 0,
+                       stream, g, n, pos, h, amp, offsets, list, out);
+    break;
+  case 3:
+    hipLaunchKernelGGL((sph_cells_kernel<FORM, 3, PERIODIC>), grid, block, 0,
+                       stream, g, n, pos, h, amp, offsets, list, out);
+    break;
+  default:
+    hipLaunchKernelGGL((sph_cells_kernel<FORM, 4, PERIODIC>), grid, block, 0,
+                       stream, g, n, pos, h, amp, offsets, list, out);
+    break;
+  }
+}
+
+template <int FORM, bool PERIODIC>
+void sph_launch_particles(hipStream_t stream, const SphMapGeometry &g,
+                          int64_t nlane, const uint32_t *lane_ids,
+                          int64_t nwave, const uint32_t *wave_ids,
+                          const double *pos, const double *h,
+                          const double *values, double *out) {
+  if (nlane > 0)
+    hipLaunchKernelGGL((sph_particles_lane_kernel<FORM, PERIODIC>),
+                       dim3((unsigned)((nlane + 255) / 256)), dim3(256), 0,
+                       stream, g, nlane, lane_ids, pos, h, values, out);
+  if (nwave > 0)
+    hipLaunchKernelGGL((sph_particles_wave_kernel<FORM, PERIODIC>),
+                       dim3((unsigned)((nwave + 3) / 4)), dim3(256), 0, stream,
+                       g, nwave, wave_ids, pos, h, values, out);
+}
+
+} // namespace
+
+extern "C" {
+
+int cmi_gpu_sph_map_to_cells(cmi_gpu_engine *e, int32_t form, int64_t n,
+                             const double *positions, const double *h,
+                             int32_t K, const double *amplitudes,
+                             const double *periodic_box,
+                             const double *grid_anchor,
+                             const double *grid_sides, const int32_t *ncell,
+                             double *out) {
+  static const char call[] = "sph_map_to_cells";
+  if (K < 1 || K > CMI_SPH_MAX_AMPLITUDES || !out || (n > 0 && !amplitudes))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument (%d amplitude arrays)", call,
+                (int)K);
+  SphMapGeometry g;
+  SphScratch mem;
+  double *d_pos = nullptr, *d_h = nullptr;
+  CMI_TRY(sph_map_begin(e, call, form, n, positions, h, periodic_box,
+                        grid_anchor, grid_sides, ncell, &g, mem, &d_pos, &d_h));
+  const size_t ncells = (size_t)ncell[0] * ncell[1] * ncell[2];
+  const size_t ntiles = (size_t)g.ntile[0] * g.ntile[1] * g.ntile[2];
+  e->sph_map_stats[0] = (int64_t)ntiles;
+
+  /* count, scan (host), fill */
+  unsigned int *d_counts = nullptr, *d_offsets = nullptr;
+  CMI_TRY(mem.get(&d_counts, ntiles, "tile counts"));
+  CMI_TRY(mem.get(&d_offsets, ntiles + 1, "tile offsets"));
+  HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(unsigned int) * ntiles, e->stream));
+  const dim3 pgrid((unsigned)((n + 255) / 256)), pblock(256);
+  SphTimer timer;
+  timer.mark(e->stream);
+  if (form == CMI_SPH_FORM_SPLINE_H)
+    hipLaunchKernelGGL((sph_tile_count_kernel<0>), pgrid, pblock, 0, e->stream,
+                       g, n, d_pos, d_h, d_counts);
+  else
+    hipLaunchKernelGGL((sph_tile_count_kernel<1>), pgrid, pblock, 0, e->stream,
+                       g, n, d_pos, d_h, d_counts);
+  HIP_TRY(hipGetLastError());
+  timer.mark(e->stream);
+  std::vector<unsigned int> counts(ntiles), offsets(ntiles + 1);
+  HIP_TRY(hipMemcpyAsync(counts.data(), d_counts, sizeof(unsigned int) * ntiles,
+                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int64_t entries = 0, longest = 0;
+  for (size_t t = 0; t < ntiles; ++t) {
+    entries += counts[t];
+    longest = std::max<int64_t>(longest, counts[t]);
+  }
+  e->sph_map_stats[1] = entries;
+  e->sph_map_stats[2] = longest;
+  if (cmi_sph_decline_lists(entries, CMI_SPH_LIST_CAP))
+    return sph_declined(e, call, CMI_SPH_DECLINE_LIST_SIZE);
+  offsets[0] = 0;
+  for (size_t t = 0; t < ntiles; ++t)
+    offsets[t + 1] = offsets[t] + counts[t];
+
+  uint32_t *d_list = nullptr;
+  double *d_amp = nullptr, *d_out = nullptr;
+  CMI_TRY(mem.get(&d_list, (size_t)entries, "tile lists"));
+  CMI_TRY(mem.get(&d_amp, (size_t)K * n, "amplitudes"));
+  CMI_TRY(mem.get(&d_out, (size_t)K * ncells, "cell sums"));
+  HIP_TRY(hipMemsetAsync(d_list, 0, sizeof(uint32_t) * (entries ? entries : 1),
+                         e->stream));
+  HIP_TRY(hipMemcpyAsync(d_offsets, offsets.data(),
+                         sizeof(unsigned int) * (ntiles + 1),
+                         hipMemcpyHostToDevice, e->stream));
+  /* the cursors: the counts' array, set to the offsets */
+  HIP_TRY(hipMemcpyAsync(d_counts, offsets.data(), sizeof(unsigned int) * ntiles,
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(d_amp, amplitudes, sizeof(double) * (size_t)K * n,
+                         hipMemcpyHostToDevice, e->stream));
+  timer.mark(e->stream);
+  if (form == CMI_SPH_FORM_SPLINE_H)
+    hipLaunchKernelGGL((sph_tile_fill_kernel<0>), pgrid, pblock, 0, e->stream,
+                       g, n, d_pos, d_h, d_counts, d_offsets + 1, d_list);
+  else
+    hipLaunchKernelGGL((sph_tile_fill_kernel<1>), pgrid, pblock, 0, e->stream,
+                       g, n, d_pos, d_h, d_counts, d_offsets + 1, d_list);
+  HIP_TRY(hipGetLastError());
+  if (form == CMI_SPH_FORM_SPLINE_H) {
+    if (g.periodic)
+      sph_launch_cells<0, true>(K, (int)ntiles, e->stream, g, n, d_pos, d_h,
+                                d_amp, d_offsets, d_list, d_out);
+    else
+      sph_launch_cells<0, false>(K, (int)ntiles, e->stream, g, n, d_pos, d_h,
+                                 d_amp, d_offsets, d_list, d_out);
+  } else {
+    if (g.periodic)
+      sph_launch_cells<1, true>(K, (int)ntiles, e->stream, g, n, d_pos, d_h,
+                                d_amp, d_offsets, d_list, d_out);
+    else
+      sph_launch_cells<1, false>(K, (int)ntiles, e->stream, g, n, d_pos, d_h,
+                                 d_amp, d_offsets, d_list, d_out);
+  }
+  HIP_TRY(hipGetLastError());
+  timer.mark(e->stream);
+  HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)K * ncells,
+                         hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->sph_map_stats[7] = timer.nanoseconds();
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_sph_map_to_particles(cmi_gpu_engine *e, int32_t form, int64_t n,
+                                 const double *positions, const double *h,
+                                 const double *periodic_box,
+                                 const double *grid_anchor,
+                                 const double *grid_sides,
+                                 const int32_t *ncell,
+                                 const double *cell_values, double *out) {
+  static const char call[] = "sph_map_to_particles";
+  if (!cell_values || (n > 0 && !out))
+    return fail(CMI_GPU_EINVAL, "%s: bad argument", call);
+  SphMapGeometry g;
+  SphScratch mem;
+  double *d_pos = nullptr, *d_h = nullptr;
+  CMI_TRY(sph_map_begin(e, call, form, n, positions, h, periodic_box,
+                        grid_anchor, grid_sides, ncell, &g, mem, &d_pos, &d_h));
+  const size_t ncells = (size_t)ncell[0] * ncell[1] * ncell[2];
+
+  /* the class split */
+  std::vector<uint32_t> ids((size_t)n);
+  int64_t nlane = 0, nwave = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t candidates = cmi_sph_particle_candidates(
+        g, positions + 3 * i, cmi_sph_reach(form, h[i]));
+    const int cls = cmi_sph_particle_class(candidates);
+    if (cls == 1)
+      ids[nlane++] = (uint32_t)i; /* from the front */
+    else if (cls == 2)
+      ids[n - 1 - nwave++] = (uint32_t)i; /* from the back */
+  }
+  e->sph_map_stats[4] = nwave;
+  e->sph_map_stats[5] = nlane;
+
+  uint32_t *d_ids = nullptr;
+  double *d_values = nullptr, *d_out = nullptr;
+  CMI_TRY(mem.get(&d_ids, (size_t)n, "class lists"));
+  CMI_TRY(mem.get(&d_values, ncells, "cell values"));
+  CMI_TRY(mem.get(&d_out, (size_t)n, "particle sums"));
+  HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), sizeof(uint32_t) * n,
+                         hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(d_values, cell_values, sizeof(double) * ncells,
+                         hipMemcpyHostToDevice, e->stream));
+  /* (a particle without a candidate midpoint is in neither class) */
+  HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(double) * n, e->stream));
+  const uint32_t *lane_ids = d_ids, *wave_ids = d_ids + (n - nwave);
+  SphTimer timer;
+  timer.mark(e->stream);
+  if (form == CMI_SPH_FORM_SPLINE_H) {
+    if (g.periodic)
+      sph_launch_particles<0, true>(e->stream, g, nlane, lane_ids, nwave,
+                                    wave_ids, d_pos, d_h, d_values, d_out);
+    else
+      sph_launch_particles<0, false>(e->stream, g, nlane, lane_ids, nwave,
+                                     wave_ids, d_pos, d_h, d_values, d_out);
+  } else {
+    if (g.periodic)
+      sph_launch_particles<1, true>(e->stream, g, nlane, lane_ids, nwave,
+                                    wave_ids, d_pos, d_h, d_values, d_out);
+    else
+      sph_launch_particles<1, false>(e->stream, g, nlane, lane_ids, nwave,
+                                     wave_ids, d_pos, d_h, d_values, d_out);
+  }
+  HIP_TRY(hipGetLastError());
+  timer.mark(e->stream);
+  HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * n, hipMemcpyDeviceToHost,
+                         e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->sph_map_stats[7] = timer.nanoseconds();
+  return CMI_GPU_OK;
+}
+
+int cmi_gpu_get_sph_map_stats(cmi_gpu_engine *e, int64_t *stats) {
+  if (!e || !stats)
+    return fail(CMI_GPU_EINVAL, "get_sph_map_stats: bad argument");
+  for (int k = 0; k < 8; ++k)
+    stats[k] = e->sph_map_stats[k];
   return CMI_GPU_OK;
 }
 

@@ -76,6 +76,21 @@ class EngineError(RuntimeError):
     pass
 
 
+class SphMapDeclined(EngineError):
+    """An SPH mapping declined (include/cmi_gpu.h, "SPH mappings"): nothing was
+    computed and the caller runs the host path. `reason` is one of
+    SPH_DECLINE_REASONS."""
+
+    def __init__(self, message, reason):
+        EngineError.__init__(self, message)
+        self.reason = reason
+
+
+EDECLINED = 5
+SPH_KERNELS = {"spline_h": 0, "spline_2h": 1}
+SPH_DECLINE_REASONS = {1: "no_particles", 2: "wide_kernel", 3: "list_size"}
+
+
 # every symbol include/cmi_gpu.h declares
 EXPORTED_SYMBOLS = [
     "cmi_gpu_create", "cmi_gpu_destroy", "cmi_gpu_last_error",
@@ -156,6 +171,8 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_cross_sections", "cmi_gpu_get_transport_plan",
     "cmi_gpu_get_order_plan", "cmi_gpu_order_packets",
     "cmi_gpu_get_bundle_march",
+    "cmi_gpu_sph_map_to_cells", "cmi_gpu_sph_map_to_particles",
+    "cmi_gpu_get_sph_map_stats",
 ]
 
 # the emission lines of EmissivityValues (src/EmissivityValues.hpp:36-81), in
@@ -431,6 +448,13 @@ def load_library():
     L.cmi_gpu_escape_pixels.argtypes = [_dp, C.c_int32, C.c_int32, C.c_int64,
                                         _dp, C.POINTER(C.c_int32), _dp]
     L.cmi_gpu_cross_sections.argtypes = [vp, C.c_int64, _dp, _dp]
+    L.cmi_gpu_sph_map_to_cells.argtypes = [
+        vp, C.c_int32, C.c_int64, _dp, _dp, C.c_int32, _dp, _dp, _dp, _dp,
+        C.POINTER(C.c_int32), _dp]
+    L.cmi_gpu_sph_map_to_particles.argtypes = [
+        vp, C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _dp,
+        C.POINTER(C.c_int32), _dp, _dp]
+    L.cmi_gpu_get_sph_map_stats.argtypes = [vp, C.POINTER(C.c_int64)]
     L.cmi_gpu_update_cells_range.argtypes = [vp, C.c_uint32, C.c_double,
                                              C.c_int64, C.c_int64]
     L.cmi_gpu_refresh_transport_records.argtypes = [vp]
@@ -902,6 +926,10 @@ class GpuEngine:
         self.lya_x_crit = 0.
         self._abundances = np.zeros(6)  # He, C, N, O, Ne, S per hydrogen
         self._escape = None  # set_escape_tally's (nfreq, nlon, nmu)
+        # the whole grid, the default grid of the SPH mappings
+        self._grid = (tuple(float(a) for a in anchor),
+                      tuple(float(s) for s in sides),
+                      tuple(int(n) for n in ncell))
         self.cell_volume = float(np.prod([float(sides[a]) / int(ncell[a])
                                           for a in range(3)]))  # m^3
         # tests, bench and tools read device timings; the engine records them
@@ -1329,6 +1357,74 @@ class GpuEngine:
         out = np.zeros((3,) + shape)
         self._check(self._lib.cmi_gpu_download_escape_tally(self._h, _p(out)))
         return out
+
+    # SPH mappings -----------------------------------------------------------
+    def _sph_arguments(self, positions, h, kernel, periodic_box, grid):
+        pos = _f64(positions).reshape(-1, 3)
+        hh = _f64(h).reshape(-1)
+        if len(hh) != len(pos):
+            raise ValueError("%d positions, %d smoothing lengths" %
+                             (len(pos), len(hh)))
+        anchor, sides, ncell = grid if grid is not None else self._grid
+        box = None
+        if periodic_box is not None:
+            box = _f64(periodic_box).reshape(6)
+        nc = (C.c_int32 * 3)(*[int(n) for n in ncell])
+        return (pos, hh, SPH_KERNELS[kernel], box, _f64(anchor).reshape(3),
+                _f64(sides).reshape(3), nc, tuple(int(n) for n in ncell))
+
+    def _sph_check(self, rc):
+        if rc == EDECLINED:
+            raise SphMapDeclined(
+                self._lib.cmi_gpu_last_error().decode(),
+                SPH_DECLINE_REASONS[self.sph_map_stats()["declined"]])
+        self._check(rc)
+
+    def sph_map_to_cells(self, positions, h, amplitudes, kernel="spline_h",
+                         periodic_box=None, grid=None):
+        """out[k][c] = sum_i amplitudes[k][i] W(|c - p_i|, h_i) at the cell
+        midpoints c of `grid` = (anchor, sides, ncell), by default the
+        engine's whole grid: (K, nx, ny, nz) for K <= 4 amplitude arrays
+        (K, n) or one (n,). kernel: "spline_h" (CubicSplineKernel, support h)
+        or "spline_2h" (Price 2007, support 2 h). periodic_box: None or
+        (anchor[3], sides[3]), minimum image per axis. Raises SphMapDeclined
+        when the call declines (include/cmi_gpu.h, "SPH mappings")."""
+        pos, hh, form, box, anchor, sides, nc, ncell = self._sph_arguments(
+            positions, h, kernel, periodic_box, grid)
+        amp = _f64(amplitudes)
+        if amp.ndim == 1:
+            amp = amp.reshape(1, -1)
+        if amp.ndim != 2 or amp.shape[1] != len(hh):
+            raise ValueError("amplitudes of shape %r for %d particles" %
+                             (amp.shape, len(hh)))
+        out = np.zeros((amp.shape[0],) + ncell)
+        self._sph_check(self._lib.cmi_gpu_sph_map_to_cells(
+            self._h, form, len(hh), _p(pos), _p(hh), amp.shape[0], _p(amp),
+            _p_or_none(box), _p(anchor), _p(sides), nc, _p(out)))
+        return out
+
+    def sph_map_to_particles(self, positions, h, cell_values,
+                             kernel="spline_h", periodic_box=None, grid=None):
+        """out[i] = sum_c W(|c - p_i|, h_i) cell_values[c] over the cell
+        midpoints of `grid`: (n,). Arguments as sph_map_to_cells."""
+        pos, hh, form, box, anchor, sides, nc, ncell = self._sph_arguments(
+            positions, h, kernel, periodic_box, grid)
+        g = _f64(cell_values).reshape(-1)
+        if len(g) != int(np.prod(ncell)):
+            raise ValueError("%d cell values for %r cells" % (len(g), ncell))
+        out = np.zeros(len(hh))
+        self._sph_check(self._lib.cmi_gpu_sph_map_to_particles(
+            self._h, form, len(hh), _p(pos), _p(hh), _p_or_none(box),
+            _p(anchor), _p(sides), nc, _p(g), _p(out)))
+        return out
+
+    def sph_map_stats(self):
+        """What the last SPH mapping of this engine did."""
+        raw = (C.c_int64 * 8)()
+        self._check(self._lib.cmi_gpu_get_sph_map_stats(self._h, raw))
+        names = ("tiles", "list_entries", "longest_list", "stage_chunk",
+                 "wave_class", "lane_class", "declined", "kernel_ns")
+        return {name: int(raw[k]) for k, name in enumerate(names)}
 
     def cross_sections(self, frequencies):
         """The engine's cross sections (n, 14) in m^2 at frequencies in Hz."""

@@ -29,6 +29,7 @@
 #include "SPHArrayInterface.hpp"
 
 #include "../../include/cmi_library.h"
+#include "../../include/cmi_library_mapping.h"
 
 #include <cstdlib>
 #include <iostream>
@@ -254,6 +255,91 @@ int cmi_gpu_library_map_to_particles(
     return 0;
   } catch (const std::exception &e) {
     std::cerr << "cmi_gpu_library_map_to_particles: " << e.what() << std::endl;
+    return 1;
+  }
+}
+
+void cmi_gpu_library_set_device_mapping(int on) {
+  sph_device_mapping_switch() = on ? 1 : 0;
+}
+
+long cmi_gpu_library_device_mapping_count() {
+  return sph_device_mapping_count();
+}
+
+int cmi_gpu_library_device_map_to_cells(
+    const char *mapping_type, int precision, const void *x, const void *y,
+    const void *z, const void *h, const void *m, size_t N,
+    double unit_length_in_SI, double unit_mass_in_SI,
+    const double *periodic_box, const double *grid_anchor,
+    const double *grid_sides, const int *ncell, double *number_density) {
+  try {
+    std::unique_ptr<SPHArrayInterface> interface(make_interface(
+        mapping_type, unit_length_in_SI, unit_mass_in_SI, periodic_box));
+    reset_interface(*interface, precision, x, y, z, h, m, N);
+    std::unique_ptr<DensityGrid> grid(
+        make_grid(grid_anchor, grid_sides, ncell));
+    const int64_t n = grid->get_number_of_cells();
+    SphParticleDescription d;
+    if (!interface->describe_particles(d))
+      d.declined = interface->device_mapping_objection();
+    std::string why = d.declined;
+    std::vector<double> sums((size_t)n);
+    if (why.empty()) {
+      SphMappingEngine engine(nullptr, device_from_environment());
+      const int32_t nc[3] = {ncell[0], ncell[1], ncell[2]};
+      sph_mapping_taken(
+          cmi_gpu_sph_map_to_cells(engine.get(), d.form, (int64_t)d.n,
+                                   d.positions, d.smoothing_lengths, 1,
+                                   d.amplitudes[0],
+                                   d.periodic ? d.box : nullptr, grid_anchor,
+                                   grid_sides, nc, sums.data()),
+          why);
+    }
+    if (!why.empty()) {
+      std::cerr << "cmi_gpu_library_device_map_to_cells declined: " << why
+                << std::endl;
+      return 2;
+    }
+    for (int64_t i = 0; i < n; ++i)
+      number_density[i] =
+          d.values(&sums[i], grid->get_cell_volume()).get_number_density();
+    return 0;
+  } catch (const std::exception &e) {
+    std::cerr << "cmi_gpu_library_device_map_to_cells: " << e.what()
+              << std::endl;
+    return 1;
+  }
+}
+
+int cmi_gpu_library_device_map_to_particles(
+    const char *mapping_type, int precision, const void *x, const void *y,
+    const void *z, const void *h, const void *m, size_t N,
+    double unit_length_in_SI, double unit_mass_in_SI,
+    const double *periodic_box, const double *grid_anchor,
+    const double *grid_sides, const int *ncell,
+    const double *neutral_fraction_of_cells, double *nH) {
+  try {
+    std::unique_ptr<SPHArrayInterface> interface(make_interface(
+        mapping_type, unit_length_in_SI, unit_mass_in_SI, periodic_box));
+    reset_interface(*interface, precision, x, y, z, h, m, N);
+    std::unique_ptr<DensityGrid> grid(
+        make_grid(grid_anchor, grid_sides, ncell));
+    const int64_t n = grid->get_number_of_cells();
+    grid->_ionic_fraction[ION_H_n].assign(neutral_fraction_of_cells,
+                                          neutral_fraction_of_cells + n);
+    interface->set_device_mapping(nullptr, device_from_environment(), false);
+    std::string why;
+    if (!interface->write_on_device(*grid, why)) {
+      std::cerr << "cmi_gpu_library_device_map_to_particles declined: " << why
+                << std::endl;
+      return 2;
+    }
+    interface->fill_array(nH);
+    return 0;
+  } catch (const std::exception &e) {
+    std::cerr << "cmi_gpu_library_device_map_to_particles: " << e.what()
+              << std::endl;
     return 1;
   }
 }

@@ -163,6 +163,10 @@ public:
   virtual ~DensityGridWriter() {}
   virtual void write(DensityGrid &grid, uint_fast32_t iteration,
                      ParameterFile &params, double time = 0.) = 0;
+  /* for a writer that maps cells onto SPH particles (SPHArrayInterface): the
+   * engine its device mapping may use (null: it makes one), that engine's
+   * device, whether to say which path ran */
+  virtual void set_device_mapping(cmi_gpu_engine *, int, bool) {}
 };
 
 /* Utilities::compose_filename, src/Utilities.hpp:756-775 */
@@ -1060,6 +1064,7 @@ class GpuIonizationSimulation {
   const bool _every_iteration_output;
   const bool _output_statistics;
   const bool _verbose;
+  const int _device; /* of the first engine, and of a mapping's own */
   ParameterFile _parameter_file;
   uint_fast32_t _number_of_iterations;
   uint_fast64_t _number_of_photons;
@@ -1442,7 +1447,7 @@ public:
                           const bool task_based = false)
       : _every_iteration_output(every_iteration_output),
         _output_statistics(output_statistics), _verbose(verbose),
-        _parameter_file(parameterfile),
+        _device(device), _parameter_file(parameterfile),
         _number_of_iterations((uint_fast32_t)_parameter_file.get_integer(
             task_based ? "TaskBasedIonizationSimulation:number of iterations"
                        : "IonizationSimulation:number of iterations",
@@ -1820,8 +1825,74 @@ public:
   int32_t random_seed() const { return _random_seed; }
   const EscapeTally *escape_tally() const { return _escape_tally.get(); }
 
+  /* the engine a mapping of SPH particles runs on: the first there is (a
+   * decomposed run maps the whole grid on it), none in a dry run */
+  cmi_gpu_engine *mapping_engine() const {
+    if (_engine)
+      return _engine;
+    if (!_replicas.empty())
+      return _replicas[0];
+    return _blocks.empty() ? nullptr : _blocks[0].engine;
+  }
+
+  /* The cells' values of a DensityFunction that is a sum over SPH particles,
+   * by one call of the device operator - when device mapping is switched on,
+   * the function describes its particles and the call does not decline.
+   * false: nothing stored, the host loop runs. */
+  template <typename Store>
+  bool initialize_on_device(DensityFunction *density_function, Store store) {
+    if (!sph_device_mapping_on())
+      return false;
+    SphParticleDescription d;
+    if (!density_function->describe_particles(d)) {
+      status("Device mapping is on, but this DensityFunction is not a sum "
+             "over SPH particles: evaluating it on the host.");
+      return false;
+    }
+    std::string why = d.declined;
+    std::vector<double> sums;
+    DensityGrid &g = *_density_grid;
+    const int64_t n = g.get_number_of_cells();
+    const size_t K = d.amplitudes.size();
+    if (why.empty()) {
+      std::vector<double> amplitudes(K * d.n);
+      for (size_t k = 0; k < K; ++k)
+        std::copy(d.amplitudes[k], d.amplitudes[k] + d.n,
+                  amplitudes.begin() + k * d.n);
+      const int32_t nc[3] = {(int32_t)_ncell[0], (int32_t)_ncell[1],
+                             (int32_t)_ncell[2]};
+      SphMappingEngine engine(mapping_engine(), _device);
+      sums.resize(K * (size_t)n);
+      if (!sph_mapping_taken(
+              cmi_gpu_sph_map_to_cells(
+                  engine.get(), d.form, (int64_t)d.n, d.positions,
+                  d.smoothing_lengths, (int32_t)K, amplitudes.data(),
+                  d.periodic ? d.box : nullptr, _simulation_box.anchor.data(),
+                  _simulation_box.sides.data(), nc, sums.data()),
+              why))
+        sums.clear();
+    }
+    if (sums.empty()) {
+      status("Device mapping declined (" + why +
+             "): mapping the particles onto the cells on the host.");
+      return false;
+    }
+    const double volume = g.get_cell_volume();
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; ++i) {
+      double cell_sums[CMI_GPU_SPH_MAX_AMPLITUDES];
+      for (size_t k = 0; k < K; ++k)
+        cell_sums[k] = sums[k * (size_t)n + i];
+      store(i, d.values(cell_sums, volume));
+    }
+    status("Mapped " + std::to_string(d.n) +
+           " particles onto the cells on the device.");
+    return true;
+  }
+
   /* IonizationSimulation::initialize, src/IonizationSimulation.cpp:239-325:
-   * evaluate the DensityFunction on every cell (host), upload SoA arrays */
+   * evaluate the DensityFunction on every cell (host, or the device for SPH
+   * particles: initialize_on_device), upload SoA arrays */
   void initialize(DensityFunction *density_function = nullptr) {
     if (density_function == nullptr)
       density_function = _density_function.get();
@@ -1831,16 +1902,20 @@ public:
     DensityGrid &g = *_density_grid;
     const int64_t n = g.get_number_of_cells();
     std::vector<double> x((size_t)NUMBER_OF_IONNAMES * n);
-    /* DensityGridInitializationFunction, src/DensityGrid.hpp:775-790 */
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < n; ++i) {
-      DensityGrid::iterator cell(&g, i);
-      const DensityValues vals = (*density_function)(cell);
+    auto store = [&](int64_t i, const DensityValues &vals) {
       g._number_density[i] = vals.get_number_density();
       g._temperature[i] = vals.get_temperature();
       for (int ion = 0; ion < NUMBER_OF_IONNAMES; ++ion) {
         g._ionic_fraction[ion][i] = vals.get_ionic_fraction(ion);
         x[(size_t)ion * n + i] = vals.get_ionic_fraction(ion);
+      }
+    };
+    if (!initialize_on_device(density_function, store)) {
+      /* DensityGridInitializationFunction, src/DensityGrid.hpp:775-790 */
+#pragma omp parallel for schedule(static)
+      for (int64_t i = 0; i < n; ++i) {
+        DensityGrid::iterator cell(&g, i);
+        store(i, (*density_function)(cell));
       }
     }
     density_function->free();
@@ -1998,9 +2073,13 @@ public:
     if (_density_grid_writer)
       _density_grid_writer->write(*_density_grid, _number_of_iterations,
                                   _parameter_file);
-    if (density_grid_writer)
+    if (density_grid_writer) {
+      density_grid_writer->set_device_mapping(mapping_engine(), _device,
+                                              _verbose);
       density_grid_writer->write(*_density_grid, _number_of_iterations,
                                  _parameter_file);
+      density_grid_writer->set_device_mapping(nullptr, _device, false);
+    }
     /* the reference's own packets/s instrument,
      * src/IonizationSimulation.cpp:667-674 */
     std::ostringstream s;

@@ -40,9 +40,11 @@
 #include <array>
 #include <cfloat>
 #include <cmath>
+#include <cstdlib>
 #include <functional>
 #include <map>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -106,13 +108,100 @@ public:
 
 /* ------------------------------------------------------- DensityFunction */
 
+/* What a DensityFunction over SPH particles says of itself, so that the
+ * driver can map all cells in one call of the device operator
+ * (cmi_gpu_sph_map_to_cells, include/cmi_gpu.h "SPH mappings") instead of
+ * asking cell by cell: every cell's values are `values` of the K sums
+ * sum_i amplitudes[k][i] W(|midpoint - p_i|, h_i) and the cell's volume. The
+ * arrays stay the function's (valid from its initialize() to its free()). */
+struct SphParticleDescription {
+  int form = CMI_GPU_SPH_SPLINE_H;
+  size_t n = 0;
+  const double *positions = nullptr;         /* [n][3], m */
+  const double *smoothing_lengths = nullptr; /* [n], m */
+  std::vector<const double *> amplitudes;    /* K arrays of n */
+  std::vector<std::vector<double>> owned;    /* (amplitudes made for this) */
+  bool periodic = false;
+  double box[6] = {0., 0., 0., 0., 0., 0.}; /* anchor, sides of that box */
+  /* not empty: the function's own host path does something the operator
+   * does not for these particles - why; the host path runs */
+  std::string declined;
+  std::function<DensityValues(const double *sums, double volume)> values;
+};
+
 class DensityFunction {
 public:
   virtual ~DensityFunction() {}
   virtual void initialize() {}
   virtual void free() {}
   virtual DensityValues operator()(const Cell &cell) = 0;
+  /* after initialize(); false: not a sum over particles (the default) */
+  virtual bool describe_particles(SphParticleDescription &) { return false; }
 };
+
+/* Device mapping of SPH particles, off unless switched on: by
+ * cmi_gpu_library_set_device_mapping, `cmi-gpu --device-mapping`, or
+ * CMI_GPU_DEVICE_MAPPING=1 in the environment. */
+inline int &sph_device_mapping_switch() {
+  static int value = -1; /* -1: not set, the environment decides */
+  return value;
+}
+inline bool sph_device_mapping_on() {
+  const int value = sph_device_mapping_switch();
+  if (value >= 0)
+    return value != 0;
+  const char *env = std::getenv("CMI_GPU_DEVICE_MAPPING");
+  return env && std::atoi(env) != 0;
+}
+
+/* An engine for a mapping: the caller's, or - there is none in a dry run or
+ * in the library's probes - one of a single cell made for the call. */
+class SphMappingEngine {
+  cmi_gpu_engine *_engine = nullptr;
+  bool _own = false;
+
+public:
+  SphMappingEngine(cmi_gpu_engine *engine, int device) : _engine(engine) {
+    if (_engine)
+      return;
+    cmi_gpu_config config = {};
+    for (int a = 0; a < 3; ++a) {
+      config.sides[a] = 1.;
+      config.ncell[a] = 1;
+    }
+    config.device = device;
+    if (cmi_gpu_create(&config, &_engine) != CMI_GPU_OK)
+      throw std::runtime_error(std::string("device mapping: cmi_gpu_create: ") +
+                               cmi_gpu_last_error());
+    _own = true;
+  }
+  ~SphMappingEngine() {
+    if (_own)
+      cmi_gpu_destroy(_engine);
+  }
+  SphMappingEngine(const SphMappingEngine &) = delete;
+  SphMappingEngine &operator=(const SphMappingEngine &) = delete;
+  cmi_gpu_engine *get() const { return _engine; }
+};
+
+/* rc of one of the two operators: true = done, false = it declined (why),
+ * anything else throws */
+inline long &sph_device_mapping_count() {
+  static long count = 0; /* operator calls that ran, since the start */
+  return count;
+}
+inline bool sph_mapping_taken(int rc, std::string &why) {
+  if (rc == CMI_GPU_OK) {
+    ++sph_device_mapping_count();
+    return true;
+  }
+  if (rc == CMI_GPU_EDECLINED) {
+    why = cmi_gpu_last_error();
+    return false;
+  }
+  throw std::runtime_error(std::string("device mapping: ") +
+                           cmi_gpu_last_error());
+}
 
 /* src/SpiralGalaxyDensityFunction.hpp:73-130: the dusty disc of the
  * DustSimulation mode (which constructs it directly, whatever
@@ -913,6 +1002,11 @@ public:
               neutral_fraction += splineval * _neutral_fractions[index];
           }
         }
+    return cell_values(density, temperature, neutral_fraction);
+  }
+  /* a cell's values from its three kernel sums (neutral_fraction < 0: none) */
+  static DensityValues cell_values(double density, double temperature,
+                                   double neutral_fraction) {
     DensityValues values;
     values.set_number_density(density / 1.6737236e-27);
     values.set_temperature(temperature);
@@ -921,6 +1015,33 @@ public:
                                            : 1.e-6);
     values.set_ionic_fraction(ION_He_n, 1.e-6);
     return values;
+  }
+
+  /* the same sums for all cells at once: m, m T / rho and - with neutral
+   * fractions - m x through the kernel; the quotients stay here */
+  bool describe_particles(SphParticleDescription &d) override {
+    const size_t n = _masses.size();
+    d.form = CMI_GPU_SPH_SPLINE_H;
+    d.n = n;
+    d.positions = _positions.data();
+    d.smoothing_lengths = _smoothing_lengths.data();
+    const bool fractions = !_neutral_fractions.empty();
+    d.owned.assign(fractions ? 2 : 1, std::vector<double>(n));
+    for (size_t i = 0; i < n; ++i) {
+      d.owned[0][i] = _masses[i] * _temperatures[i] / _densities[i];
+      if (fractions)
+        d.owned[1][i] = _masses[i] * _neutral_fractions[i];
+    }
+    d.amplitudes = {_masses.data(), d.owned[0].data()};
+    if (fractions)
+      d.amplitudes.push_back(d.owned[1].data());
+    d.periodic = _periodic;
+    for (int a = 0; a < 3; ++a)
+      d.box[3 + a] = _box_sides[a];
+    d.values = [fractions](const double *sums, double) {
+      return cell_values(sums[0], sums[1], fractions ? sums[2] : -1.);
+    };
+    return true;
   }
 
   /* :366-372 */

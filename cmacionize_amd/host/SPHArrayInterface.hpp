@@ -4,8 +4,10 @@
  * that maps a cloud of SPH particles (positions, smoothing lengths, masses -
  * arrays owned by the calling code) onto the cells of the grid, and a
  * DensityGridWriter that maps the converged neutral fractions back onto the
- * particles. Host side only: the mapping runs once before and once after the
- * simulation; everything in between is the GPU engine.
+ * particles. The mapping runs once before and once after the simulation, on
+ * the host; with device mapping switched on (sph_device_mapping_on) the
+ * "centroid" mapping runs both ways through the device operators of
+ * include/cmi_gpu.h, "SPH mappings" - the other mapping types stay here.
  *
  * Mapping types of the reference (get_mapping_type, src/SPHArrayInterface.hpp:
  * 105-118):
@@ -43,6 +45,7 @@
 
 #include <cfloat>
 #include <cmath>
+#include <iostream>
 #include <memory>
 #include <vector>
 
@@ -87,6 +90,12 @@ class SPHArrayInterface : public DensityFunction, public DensityGridWriter {
   /* the pre-computed vertex integrals, built by the constructors like the
    * reference's gridding() (182 MB, a few seconds) */
   std::unique_ptr<PetkovaMapping> _petkova;
+
+  /* device mapping of write(): the engine to use (may be none: one is made
+   * for the call), its device, whether to say which path ran */
+  cmi_gpu_engine *_mapping_engine = nullptr;
+  int _mapping_device = 0;
+  bool _mapping_talk = false;
 
   static SPHArrayMappingType get_mapping_type(const std::string &name) {
     if (name == "M_over_V")
@@ -386,14 +395,122 @@ public:
       for_cell_masses(cell, [&](size_t, double mass) { density += mass; });
       density = density / cell.get_volume();
     }
+    return cell_values(density, cell.get_volume(), _masses[0]);
+  }
+  /* a cell's values from its mass density */
+  static DensityValues cell_values(double density, double volume,
+                                   double first_mass) {
+    DensityValues values;
     /* "Ensure that the density > 0" */
     if (density <= 0.)
-      density = _masses[0] / cell.get_volume() * 1.e-6;
+      density = first_mass / volume * 1.e-6;
     values.set_number_density(density / 1.6737236e-27);
     values.set_temperature(8000.);
     values.set_ionic_fraction(ION_H_n, 1.e-6);
     values.set_ionic_fraction(ION_He_n, 1.e-6);
     return values;
+  }
+
+  /* Why the device operators would not give the host's "centroid" sums for
+   * these particles (empty: they do). Without a periodic box the host's
+   * kernel sums still wrap in the box of the particles (reset_impl) while
+   * its search does not; the two agree while twice the largest smoothing
+   * length is below the smallest side - the operator's own rule for a
+   * periodic box, applied here to that box. */
+  std::string device_mapping_objection() const {
+    if (_mapping_type != SPHARRAY_MAPPING_CENTROID)
+      return "only the \"centroid\" mapping has a device operator";
+    if (_masses.empty())
+      return "no particles";
+    if (!_is_periodic) {
+      double hmax = 0.;
+      for (double h : _smoothing_lengths)
+        hmax = std::max(hmax, h);
+      const double smallest =
+          std::min(_box_sides[0], std::min(_box_sides[1], _box_sides[2]));
+      if (!(2. * hmax < smallest))
+        return "twice the largest smoothing length is not below the smallest "
+               "side of the box of the particles";
+    }
+    return "";
+  }
+  const double *periodic_box_or_null(double box[6]) const {
+    if (!_is_periodic)
+      return nullptr;
+    for (int a = 0; a < 3; ++a) {
+      box[a] = _box_anchor[a];
+      box[3 + a] = _box_sides[a];
+    }
+    return box;
+  }
+
+  bool describe_particles(SphParticleDescription &d) override {
+    if (_mapping_type != SPHARRAY_MAPPING_CENTROID)
+      return false;
+    d.form = CMI_GPU_SPH_SPLINE_H;
+    d.n = _masses.size();
+    d.positions = _positions.data();
+    d.smoothing_lengths = _smoothing_lengths.data();
+    d.amplitudes = {_masses.data()};
+    d.periodic = periodic_box_or_null(d.box) != nullptr;
+    d.declined = device_mapping_objection();
+    const double first_mass = _masses.empty() ? 0. : _masses[0];
+    d.values = [first_mass](const double *sums, double volume) {
+      return cell_values(sums[0], volume, first_mass);
+    };
+    return true;
+  }
+
+  /* write() of the "centroid" mapping goes through the device operators
+   * when device mapping is switched on; the engine may be null */
+  void set_device_mapping(cmi_gpu_engine *engine, int device,
+                          bool talk) override {
+    _mapping_engine = engine;
+    _mapping_device = device;
+    _mapping_talk = talk;
+  }
+
+  /* The inverse "centroid" mapping on the device: the cells' masses by the
+   * forward operator (the unfloored sums), g = (1 - x_H) / cellmass per cell,
+   * nH_i = 1 - m_i sum_c W g_c by the inverse operator. false: a call
+   * declined (why) and nothing was written. */
+  bool write_on_device(DensityGrid &grid, std::string &why) {
+    why = device_mapping_objection();
+    if (!why.empty())
+      return false;
+    const int64_t ncell = grid.get_number_of_cells();
+    const SimulationBox &sbox = grid.box();
+    const int32_t nc[3] = {(int32_t)grid.ncell()[0], (int32_t)grid.ncell()[1],
+                           (int32_t)grid.ncell()[2]};
+    double box[6];
+    const double *periodic = periodic_box_or_null(box);
+    SphMappingEngine engine(_mapping_engine, _mapping_device);
+    std::vector<double> g((size_t)ncell);
+    if (!sph_mapping_taken(
+            cmi_gpu_sph_map_to_cells(
+                engine.get(), CMI_GPU_SPH_SPLINE_H, (int64_t)_masses.size(),
+                _positions.data(), _smoothing_lengths.data(), 1,
+                _masses.data(), periodic, sbox.anchor.data(),
+                sbox.sides.data(), nc, g.data()),
+            why))
+      return false;
+    for (int64_t c = 0; c < ncell; ++c) {
+      const double xH = grid._ionic_fraction[ION_H_n][c];
+      /* (a cell no kernel covers hands nothing out) */
+      g[c] = g[c] > 0. ? (1. - xH) / g[c] : 0.;
+    }
+    std::vector<double> lost(_masses.size());
+    if (!sph_mapping_taken(
+            cmi_gpu_sph_map_to_particles(
+                engine.get(), CMI_GPU_SPH_SPLINE_H, (int64_t)_masses.size(),
+                _positions.data(), _smoothing_lengths.data(), periodic,
+                sbox.anchor.data(), sbox.sides.data(), nc, g.data(),
+                lost.data()),
+            why))
+      return false;
+    for (size_t i = 0; i < _masses.size(); ++i)
+      _neutral_fractions[i] = 1. - _masses[i] * lost[i];
+    return true;
   }
 
   /* SPHArrayInterface::write, :1049-1075 with InverseMappingFunction,
@@ -403,6 +520,19 @@ public:
     for (double &nf : _neutral_fractions)
       nf = 1.;
     const int64_t ncell = grid.get_number_of_cells();
+    if (_mapping_type == SPHARRAY_MAPPING_CENTROID && sph_device_mapping_on()) {
+      std::string why;
+      const bool done = write_on_device(grid, why);
+      if (_mapping_talk)
+        std::cout << (done ? "Mapped the cells onto the particles on the "
+                             "device."
+                           : "Device mapping declined (" + why +
+                                 "): mapping the cells onto the particles on "
+                                 "the host.")
+                  << std::endl;
+      if (done)
+        return;
+    }
     if (_mapping_type == SPHARRAY_MAPPING_M_OVER_V) {
       /* the last cell that names a particle wins: in cell order */
       for (int64_t c = 0; c < ncell; ++c) {

@@ -310,12 +310,32 @@ public:
                    kernel(r / _smoothing_lengths[i], _smoothing_lengths[i]);
       });
     }
+    return cell_values(density, _initial_temperature);
+  }
+  static DensityValues cell_values(double density, double temperature) {
     DensityValues values;
     values.set_number_density(density / 1.6737236e-27);
-    values.set_temperature(_initial_temperature);
+    values.set_temperature(temperature);
     values.set_ionic_fraction(ION_H_n, 1.e-6);
     values.set_ionic_fraction(ION_He_n, 1.e-6);
     return values;
+  }
+  /* the kernel at the midpoints for all cells at once (not the integral of
+   * `use new algorithm`) */
+  bool describe_particles(SphParticleDescription &d) override {
+    if (_use_new_algorithm)
+      return false;
+    d.form = CMI_GPU_SPH_SPLINE_2H;
+    d.n = _masses.size();
+    d.positions = _positions.data();
+    d.smoothing_lengths = _smoothing_lengths.data();
+    d.amplitudes = {_masses.data()};
+    d.periodic = false;
+    const double temperature = _initial_temperature;
+    d.values = [temperature](const double *sums, double) {
+      return cell_values(sums[0], temperature);
+    };
+    return true;
   }
 };
 

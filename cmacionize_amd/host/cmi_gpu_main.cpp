@@ -20,7 +20,10 @@
  * --devices D0,D1,... (the blocks' devices, round-robin; default --device),
  * --copies K (K engines for every block that contains a source - the
  * reference's TaskBasedIonizationSimulation:source copy level; default: one
- * per device, 2^level at most).
+ * per device, 2^level at most), --device-mapping (a DensityFunction of SPH
+ * particles is mapped onto the cells by the device operator of
+ * include/cmi_gpu.h, "SPH mappings", instead of cell by cell on the host; also
+ * CMI_GPU_DEVICE_MAPPING=1 in the environment; needs a GPU in a dry run too).
  */
 #include "EmissivityCalculationSimulation.hpp"
 #include "GpuDustSimulation.hpp"
@@ -205,6 +208,9 @@ int main(int argc, char **argv) {
       verbose = true;
     else if (a == "--describe")
       do_describe = true;
+    else if (a == "--device-mapping")
+      /* SPH particles onto the cells by the device operator (Plugins.hpp) */
+      cmi::sph_device_mapping_switch() = 1;
     else if (a == "--task-based")
       task_based = true; /* src/CMacIonize.cpp: TaskBasedIonizationSimulation */
     else if (a == "--dirty" || a == "-d" || a == "--no-initial-output")
@@ -214,7 +220,8 @@ int main(int argc, char **argv) {
                 << "usage: cmi-gpu --params FILE [--threads N] [--device N] "
                    "[--blocks BX,BY,BZ] [--devices D0,D1,...] [--copies K] "
                    "[--task-based] [--every-iteration-output] [--output-statistics] "
-                   "[--dry-run] [--dry-run-snapshot] [--describe] [--verbose]\n"
+                   "[--dry-run] [--dry-run-snapshot] [--describe] [--verbose] "
+                   "[--device-mapping]\n"
                    "       cmi-gpu --emission --params FILE --file "
                    "SNAPSHOT.hdf5 [--device N]\n"
                    "       cmi-gpu --dusty-radiative-transfer --params FILE "

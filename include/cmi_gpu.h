@@ -48,7 +48,9 @@ enum {
   CMI_GPU_EINVAL = 1,   /* bad argument */
   CMI_GPU_EDEVICE = 2,  /* HIP runtime error / no device */
   CMI_GPU_ESTATE = 3,   /* call sequence error (e.g. shoot before sources) */
-  CMI_GPU_ENOMEM = 4
+  CMI_GPU_ENOMEM = 4,
+  /* the call did nothing and the caller runs its own path (SPH mappings) */
+  CMI_GPU_EDECLINED = 5
 };
 
 /* field ids for upload / download / device pointers */
@@ -2403,6 +2405,95 @@ int cmi_gpu_absorption_probe(cmi_gpu_engine *engine, const double *n,
                              double vmin, double vmax, int32_t nprobe,
                              const int32_t *channels, int32_t max_cells,
                              double *out);
+
+/* ------------------------------------------------------------------------
+ * SPH mappings
+ *
+ * The two linear operators between a cloud of SPH particles and the
+ * midpoints of a Cartesian grid that the reference evaluates cell by cell on
+ * the host: SPHArrayInterface::operator() / ::write with mapping "centroid"
+ * (src/SPHArrayInterface.cpp:931-1075), GadgetSnapshotDensityFunction::
+ * operator() (src/GadgetSnapshotDensityFunction.cpp:313-359) and the Phantom
+ * / SPHNG density functions without `use new algorithm`
+ * (src/PhantomSnapshotDensityFunction.cpp:669-832).
+ *
+ * Particles: positions p_i [n][3] (m) and smoothing lengths h_i [n] (m,
+ * positive). The grid is given in the call - grid_anchor[3], grid_sides[3],
+ * ncell[3] - and is NOT the engine's: a decomposed run maps the whole grid
+ * on one engine. The midpoint of cell i along an axis is
+ * (anchor + side * i) + side / 2 with side = sides / ncell; the cell index is
+ * z-fastest as everywhere. Kernel forms W(r, h):
+ *   CMI_GPU_SPH_SPLINE_H   the cubic spline of src/CubicSplineKernel.hpp:
+ *                          36-59, support h;
+ *   CMI_GPU_SPH_SPLINE_2H  the M4 spline of Price 2007
+ *                          (PhantomSnapshotDensityFunction::kernel), support
+ *                          2 h.
+ * The reach of a particle is that support. periodic_box: NULL, or
+ * {anchor[3], sides[3]} of a periodic box (m): every separation then takes
+ * the minimum image per axis as Box::periodic_distance does, once: if
+ * 2 d < -L then d += L; if 2 d >= L then d -= L.
+ *
+ *   cells <- particles   out[k][c] = sum_i a_k[i] W(|c - p_i|, h_i)
+ *       for K <= CMI_GPU_SPH_MAX_AMPLITUDES amplitude arrays
+ *       amplitudes[K][n]; out[K][ncells].
+ *   particles <- cells   out[i] = sum_c W(|c - p_i|, h_i) g[c]
+ *       for one array cell_values g[ncells]; out[n]. With
+ *       g_c = (1 - x_c) / cellmass_c this is the reference's inverse
+ *       "centroid" mapping: nH_i = 1 - m_i out[i].
+ *
+ * All pointers are host pointers; the calls are synchronous. Sums are fp64
+ * and every output is written by one owner (no floating-point atomics); the
+ * order of a cell's terms follows the order the tile lists were filled in,
+ * so two calls may differ in the last bits. A pair exactly at the edge of
+ * the support has weight 0.
+ *
+ * A call DECLINES - returns CMI_GPU_EDECLINED, writes nothing, the caller
+ * runs its host path - when
+ *   CMI_GPU_SPH_DECLINE_NO_PARTICLES  n is 0;
+ *   CMI_GPU_SPH_DECLINE_WIDE_KERNEL   a periodic box is given and twice the
+ *       largest reach is not below its smallest side (a cell could see two
+ *       images of one particle; below that limit the wrapped and the plain
+ *       neighbour sets of the host coincide). Without a periodic box the
+ *       operator never wraps and never declines for width: a caller whose
+ *       host path wraps in a box of its own - the library mode's box of the
+ *       particles - applies the rule to that box itself;
+ *   CMI_GPU_SPH_DECLINE_LIST_SIZE     the (tile, particle) lists of
+ *       cells <- particles would hold more than 2^28 entries (1 GiB).
+ *
+ * cmi_gpu_get_sph_map_stats, for the last of the two calls on this engine:
+ *   [0] tiles of 4 x 8 x 8 cells   [1] (tile, particle) list entries
+ *   [2] the longest tile list      [3] records staged through LDS at a time
+ *   [4] particles in the wave class [5] in the lane class (particles <- cells:
+ *       more than 64 candidate midpoints in the reach box, or up to 64)
+ *   [6] 0, or the reason the call declined
+ *   [7] device time of the call's kernels in ns, between events: counting,
+ *       filling and summing for cells <- particles, the two class kernels
+ *       for particles <- cells
+ * ([0]-[2] are of cells <- particles, [4]-[5] of particles <- cells.)
+ */
+enum { CMI_GPU_SPH_SPLINE_H = 0, CMI_GPU_SPH_SPLINE_2H = 1 };
+#define CMI_GPU_SPH_MAX_AMPLITUDES 4
+enum {
+  CMI_GPU_SPH_TAKEN = 0,
+  CMI_GPU_SPH_DECLINE_NO_PARTICLES = 1,
+  CMI_GPU_SPH_DECLINE_WIDE_KERNEL = 2,
+  CMI_GPU_SPH_DECLINE_LIST_SIZE = 3
+};
+int cmi_gpu_sph_map_to_cells(cmi_gpu_engine *engine, int32_t form, int64_t n,
+                             const double *positions, const double *h,
+                             int32_t K, const double *amplitudes,
+                             const double *periodic_box,
+                             const double *grid_anchor,
+                             const double *grid_sides, const int32_t *ncell,
+                             double *out);
+int cmi_gpu_sph_map_to_particles(cmi_gpu_engine *engine, int32_t form,
+                                 int64_t n, const double *positions,
+                                 const double *h, const double *periodic_box,
+                                 const double *grid_anchor,
+                                 const double *grid_sides,
+                                 const int32_t *ncell,
+                                 const double *cell_values, double *out);
+int cmi_gpu_get_sph_map_stats(cmi_gpu_engine *engine, int64_t *stats);
 
 #ifdef __cplusplus
 }
