@@ -204,7 +204,69 @@ def test_emission_driver_reads_the_exclusion_radii_with_scattering_only(
     assert "exclusion radius 2: value not used" in used
 
 
+# what the two blocks read with the same code: the least of each block, the
+# keys of the scattered light and a velocity axis
+BLOCKS = {
+    "EmissionImages": "EmissionImages:\n  view theta: 60. degrees\n",
+    "EmissionSkyMaps": ("EmissionSkyMaps:\n"
+                        "  observer position: [1.e16 m, 2.e16 m, -3.e16 m]\n"
+                        "  exclusion radius: 1.e16 m\n"),
+}
+SCATTERING = ("  dust cross section per hydrogen: 2.e-27 m^2\n"
+              "  scattering: true\n  number of packets: 20000\n"
+              "  random seed: 7\n  dust albedo: 0.54\n  dust asymmetry: 0.44\n"
+              "  dust peak linear polarisation: 0.43\n")
+SCATTERING_KEYS = ("scattering", "number of packets", "random seed",
+                   "dust albedo", "dust asymmetry",
+                   "dust peak linear polarisation")
+CHANNELS = ("  velocity channels: 4\n  velocity minimum: -10. km s^-1\n"
+            "  velocity maximum: 10. km s^-1\n")
+
+
+def _without(key):
+    return "".join(l + "\n" for l in SCATTERING.split("\n")
+                   if l and not l.startswith("  %s:" % key))
+
+
+# (what follows the block's first lines, the message after "<block>:")
+SHARED_ERRORS = [
+    (SCATTERING.replace("20000", "0"), "number of packets must be positive"),
+    (SCATTERING.replace("20000", "-3"), "number of packets must be positive"),
+    (SCATTERING.replace("seed: 7", "seed: 4294967296"),
+     "random seed must fit 32 bits"),
+    (SCATTERING.replace("seed: 7", "seed: -1"),
+     "random seed must fit 32 bits"),
+    (SCATTERING.replace("0.54", "1.5"), "dust albedo must be in [0, 1]"),
+    (SCATTERING.replace("0.54", "-0.1"), "dust albedo must be in [0, 1]"),
+    (SCATTERING.replace("0.44", "0."),
+     "dust asymmetry must be non-zero and inside (-1, 1)"),
+    (SCATTERING.replace("0.44", "1."),
+     "dust asymmetry must be non-zero and inside (-1, 1)"),
+    (SCATTERING.replace("0.44", "-1.5"),
+     "dust asymmetry must be non-zero and inside (-1, 1)"),
+] + [
+    (_without(key), key + " is required for scattering off dust with a "
+     "cross section above 0")
+    for key in ("dust albedo", "dust asymmetry",
+                "dust peak linear polarisation")
+] + [
+    (CHANNELS + "  scattered cubes: true\n",
+     "scattered cubes needs scattering: true"),
+    (SCATTERING + "  scattered cubes: true\n",
+     "scattered cubes needs velocity channels"),
+    ("  dust cross section per hydrogen: -1. m^2\n",
+     "dust cross section per hydrogen must not be negative"),
+]
+
+
 @pytest.mark.parametrize("text, message", [
+    (BLOCKS[block] + more, block + ":" + message)
+    for block in sorted(BLOCKS) for more, message in SHARED_ERRORS
+] + [
+    (BLOCKS[block] + "  type: JPEG\n",
+     "Unknown %s:type \"JPEG\" (BinaryArray or PGM)" % block)
+    for block in sorted(BLOCKS)
+] + [
     (IMAGES + "  number of views: 2\n  view phi 1: 0. degrees\n",
      "EmissionImages:view theta 1 is required"),
     (IMAGES + "  number of views: 2\n  view theta 1: 0. degrees\n",
@@ -238,6 +300,27 @@ def test_emission_driver_parameter_errors(tmp_path, text, message):
     assert r.returncode != 0 and message in r.stderr, r.stderr
     assert "Could not open" not in r.stderr
     assert not os.path.exists(used)
+
+
+@pytest.mark.parametrize("block", sorted(BLOCKS))
+def test_emission_driver_reads_the_scattering_keys_with_the_switch_only(
+        tmp_path, block):
+    """with `scattering: false` none of the keys of the scattered light is
+    read, the switches included"""
+    text = ("EmissivityValues:\n  Halpha: true\n" + BLOCKS[block] +
+            SCATTERING.replace("scattering: true", "scattering: false") +
+            "  scattered cubes: false\n")
+    r, used = _emission(tmp_path, text, dry_run=False)
+    assert "Could not open" in r.stderr, r.stderr
+    used = open(used).read()
+    assert used.startswith(block + ":\n")
+    keys = SCATTERING_KEYS + ("scattered cubes",)
+    if block == "EmissionSkyMaps":
+        keys += ("exclusion radius",)
+    for key in keys:
+        assert "  %s: value not used #" % key in used, (key, used)
+    assert used.count("value not used") == len(keys)
+    assert "  dust cross section per hydrogen: 2e-27 m^2 " in used
 
 
 # ------------------------------------------------------- the library --
