@@ -189,6 +189,11 @@ struct cmi_gpu_engine {
   bool last_pad_uniform = false;
   /* ... and whether it was the bundle build: cmi_gpu_get_bundle_march */
   bool last_bundle_march = false;
+  /* ... and the point build of it: cmi_gpu_get_bundle_point */
+  bool last_bundle_point = false;
+  /* the block that build's refill reads, written ahead of every launch of it
+   * (write_point_block) */
+  PointEmitDev *point_emit = nullptr;
   /* the hydrogen-only update's deferred half: the gates of the last whole-grid
    * update, a bit per cell, and whether x[2..13] have still to be made from
    * them (settle_metal_fractions). Once a pointer to a state field has been
@@ -317,6 +322,10 @@ struct cmi_gpu_engine {
      * no re-emission, an undivided grid): the bundle build,
      * shoot_bundle_kernel (false: the general kernel) */
     bool bundle_march = true;
+    /* ... and, where all its packets come from one discrete source and no
+     * continuous one, the point build of that kernel
+     * (shoot_bundle_kernel<true, true>; false: the bundle build) */
+    bool bundle_point = true;
     bool phase_stamps = false; /* experiments build: ShootArgs::phase_clock */
     /* continuum images: channels per march launch (4, 8 or 16) and the rays
      * per launch (0: the images' and the sky maps' own bounds) */
@@ -1331,6 +1340,7 @@ int cmi_gpu_destroy(cmi_gpu_engine *e) {
   (void)hipFree(e->sort_keys[0]);
   (void)hipFree(e->select_count);
   (void)hipFree(e->span_cursor);
+  (void)hipFree(e->point_emit);
 #ifdef CMI_EXPERIMENTS
   (void)hipFree(e->phase_clock);
 #endif
@@ -1859,6 +1869,13 @@ int cmi_gpu_get_bundle_march(cmi_gpu_engine *e, int32_t *flown) {
   return CMI_GPU_OK;
 }
 
+int cmi_gpu_get_bundle_point(cmi_gpu_engine *e, int32_t *flown) {
+  if (!e || !flown)
+    return fail(CMI_GPU_EINVAL, "get_bundle_point: bad argument");
+  *flown = e->last_bundle_point ? 1 : 0;
+  return CMI_GPU_OK;
+}
+
 /* the words of cmi_gpu_engine::bucket_meta: the regions' and the leaves'
  * cursors, the overflow list's, the count of ordered ids - cleared before
  * every launch - and the leaves' offsets */
@@ -2023,6 +2040,8 @@ int cmi_gpu_set_tuning(cmi_gpu_engine *e, const char *key, int64_t value) {
     e->tune.emit_before_flush = value != 0;
   else if (k == "bundle_march")
     e->tune.bundle_march = value != 0;
+  else if (k == "bundle_point")
+    e->tune.bundle_point = value != 0;
   else if (k == "phase_stamps")
     e->tune.phase_stamps = value != 0;
   else if (k == "continuum_channel_block") {

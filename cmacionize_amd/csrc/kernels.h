@@ -171,6 +171,42 @@ __device__ __forceinline__ double wave_sum(double v) {
  * (ShootArgs::park_in_place; packet ids of a call are < 2^32 - 1) */
 #define CMI_QUEUE_HOLE 0xffffffffu
 
+/* What the refill of the point build of the bundle kernel
+ * (shoot_bundle_kernel<true, true>: every packet of the launch from ONE
+ * discrete source, no continuous one) reads, in device memory: the refill
+ * fetches it with scalar loads where it needs it, round by round, instead of
+ * holding the kernel's arguments - grid, model, pointers - in registers across
+ * the march. point_emit_kernel writes it ahead of every such launch. */
+struct PointEmitDev {
+  /* the launch: ShootArgs' members of these names */
+  uint64_t first_packet;
+  uint64_t batch_offset;
+  const uint32_t *order;
+  uint32_t seed;
+  uint32_t iteration;
+  /* the source's spectrum: ModelDev's members of these names
+   * (sample_source_spectrum) and the weight of a packet, photon_weight[0] */
+  int32_t spectrum_type;
+  int32_t pad0;
+  double mono_frequency;
+  const SpectraDev *spectra;
+  TableDev spectrum_table;
+  double weight;
+  /* where every flight starts - the same for every packet of one source -:
+   * the walls of the source's cell relative to the source, lo - pos and
+   * hi - pos of start_flight per axis, the cells' sides, the byte strides of
+   * the padded records along x and y, the byte offset of the start cell's
+   * record (0 for a source outside the box) and that record as the launch
+   * finds it (CMI_PAD_GHOST outside the box) */
+  double wall_lo[3];
+  double wall_hi[3];
+  double cellside[3];
+  int32_t stride_x, stride_y;
+  int32_t start_offset;
+  int32_t pad1;
+  double start_record;
+};
+
 struct ShootArgs {
   GridDev grid;
   ModelDev model;
@@ -1184,7 +1220,8 @@ __global__ void
                                        : BIG          ? 4
                                                       : 6)))
         shoot_kernel(const ShootArgs a) {
-  constexpr bool BUNDLE = false;
+  constexpr bool BUNDLE = false, POINT = false;
+  const PointEmitDev *const point = nullptr; /* (the point build's) */
 #include "shoot_body.h"
 }
 
@@ -1196,8 +1233,89 @@ __global__ void __launch_bounds__((shoot_block_threads<false, true, false>()),
     shoot_bundle_kernel(const ShootArgs a) {
   constexpr bool FULL = false, HEAT = false, REEMIT = false, EXACT = false,
                  TABLE = true, PRE = false, PAD = true,
-                 SWITCH8 = UNIFORM_WEIGHT, BIG = false, BUNDLE = true;
+                 SWITCH8 = UNIFORM_WEIGHT, BIG = false, BUNDLE = true,
+                 POINT = false;
+  const PointEmitDev *const point = nullptr; /* (the point build's) */
 #include "shoot_body.h"
+}
+
+/* ... and the point build of it: the launch's packets all come from one
+ * discrete source and there is no continuous one (PacketOrigin::fixed; such a
+ * launch carries one weight). The refill reads what it needs from the
+ * block `point`, nothing of it is held across the march; only the discrete
+ * source's emission is compiled; and where a flight starts - cell, walls,
+ * record - is the block's, computed once per launch by point_emit_kernel.
+ * (A second template of the name, not a second parameter of the first, and
+ * the block's pointer an argument of its own, not a member of ShootArgs: the
+ * other builds keep their symbols and their code, to the offsets of the
+ * hidden arguments behind ShootArgs.) */
+template <bool UNIFORM_WEIGHT, bool POINT_SOURCE>
+__global__ void __launch_bounds__((shoot_block_threads<false, true, false>()),
+                                  CMI_PAD_WAVES)
+    shoot_bundle_kernel(const ShootArgs a, const PointEmitDev *const point) {
+  static_assert(UNIFORM_WEIGHT && POINT_SOURCE,
+                "the point build: one source, one weight");
+  constexpr bool FULL = false, HEAT = false, REEMIT = false, EXACT = false,
+                 TABLE = true, PRE = false, PAD = true,
+                 SWITCH8 = UNIFORM_WEIGHT, BIG = false, BUNDLE = true,
+                 POINT = POINT_SOURCE;
+#include "shoot_body.h"
+}
+
+/* The block of the point build for one launch. One thread: the start of a
+ * flight from the source with start_flight itself, flown once along (1, 1, 1)
+ * and once along (-1, -1, -1) - tmax is then (hi - pos) x 1 and (lo - pos) x
+ * -1, the differences themselves (a product with 1 or -1 is exact, and so is
+ * the change of sign back) - so the refill's (hi - pos) x inv_dir is the same
+ * operation on the same operands as the general kernels' and tmax bit for bit
+ * what start_flight gives every packet. The cell, the start outside the box
+ * and the padded index are the lines of the general refill. */
+struct PointEmitArgs {
+  GridDev grid;
+  PointEmitDev launch; /* the members that are the host's to say */
+  const double *source_position;
+  const double *pad_H;
+  int32_t pad_ny, pad_nz;
+  PointEmitDev *out;
+};
+__global__ void point_emit_kernel(const PointEmitArgs s) {
+  if (blockIdx.x != 0 || threadIdx.x != 0)
+    return;
+  PointEmitDev b = s.launch;
+  Packet<false> p;
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    p.pos[ax] = s.source_position[ax];
+    p.dir[ax] = 1.;
+    p.inv_dir[ax] = 1.;
+  }
+  start_flight<false, false>(s.grid, p);
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    b.wall_hi[ax] = p.tmax[ax];
+    p.dir[ax] = -1.;
+    p.inv_dir[ax] = -1.;
+  }
+  start_flight<false, false>(s.grid, p);
+#pragma unroll
+  for (int ax = 0; ax < 3; ++ax) {
+    b.wall_lo[ax] = -p.tmax[ax];
+    b.cellside[ax] = s.grid.cellside[ax];
+  }
+  /* (the general refill's lines) */
+  const int32_t sy = s.pad_nz, sx = s.pad_ny * s.pad_nz;
+  b.stride_x = 8 * sx;
+  b.stride_y = 8 * sy;
+  const bool outside = fast_outside(p);
+  const int32_t padded =
+      outside ? 0
+              : ((p.index[0] + CMI_PAD_LAYERS) * s.pad_ny +
+                 (p.index[1] + CMI_PAD_LAYERS)) *
+                        s.pad_nz +
+                    (p.index[2] + CMI_PAD_LAYERS);
+  b.start_offset = (int32_t)((uint32_t)padded << 3);
+  b.start_record = outside ? CMI_PAD_GHOST : s.pad_H[padded];
+  *s.out = b;
 }
 
 #include "tile_kernels.h"

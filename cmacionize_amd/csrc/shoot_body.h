@@ -1,7 +1,9 @@
 /* The text of the transport kernels (kernels.h: shoot_kernel and
  * shoot_bundle_kernel include it as their body, with the flags FULL ... BIG
- * and BUNDLE as constants in scope and the arguments as `a`). No include
+ * BUNDLE and POINT as constants in scope and the arguments as `a`). No include
  * guard: it is included once per kernel template. */
+  static_assert(!POINT || (BUNDLE && SWITCH8),
+                "POINT is a specialisation of the bundle build of one weight");
   static_assert(!BIG || PAD, "BIG: the padded march on large grids");
   static_assert(!BUNDLE || (PAD && !HEAT && !BIG),
                 "BUNDLE is a specialisation of the padded march without the "
@@ -414,6 +416,15 @@
      * of the last round's packets is read again */
     if (BUNDLE)
       active = false;
+    /* POINT: the block the refill reads (PointEmitDev), through a pointer the
+     * compiler learns anew every round - its loads stay in the refill, they
+     * cannot be lifted above the march and their values kept across it */
+    const __attribute__((address_space(4))) PointEmitDev *point_block = nullptr;
+    if constexpr (POINT) {
+      point_block =
+          (const __attribute__((address_space(4))) PointEmitDev *)point;
+      asm volatile("" : "+s"(point_block));
+    }
     const unsigned long long active_mask = BUNDLE ? 0ull : __ballot(active);
     const unsigned long long idle_mask = ~active_mask;
     if (!claim && pos == pos_end &&
@@ -515,6 +526,53 @@
           p.tau = a.qin.tau[i];
           set_cross_sections(a.model, p, weights);
           start_flight<FULL, EXACT>(a.grid, p);
+        } else if constexpr (POINT) {
+          /* a new packet of the one discrete source: emit_geometry's discrete
+           * branch (PacketOrigin::fixed: draws 0 and 1 are passed over) and
+           * emit_physics, on the block's values. Where the flight starts is
+           * the block's: per lane the direction, its reciprocals, and for
+           * every axis the wall ahead - a select by the direction's sign and
+           * start_flight's product - and the wall distance. */
+          const auto *pe = point_block;
+          const auto *order =
+              (const __attribute__((address_space(1))) uint32_t *)pe->order;
+          packet_id =
+              (uint32_t)pe->batch_offset + (order ? order[i] : (uint32_t)i);
+          rng.init(pe->seed, pe->iteration, pe->first_packet + packet_id);
+          rng.skip_block();
+          random_direction(p, rng);
+          p.type = TYPE_PRIMARY;
+          p.t = 0.;
+#pragma unroll
+          for (int ax = 0; ax < 3; ++ax) {
+            p.tmax[ax] = (p.dir[ax] > 0.)
+                             ? pe->wall_hi[ax] * p.inv_dir[ax]
+                             : ((p.dir[ax] < 0.)
+                                    ? pe->wall_lo[ax] * p.inv_dir[ax]
+                                    : DBL_MAX);
+            p.tdelta[ax] = (p.dir[ax] != 0.)
+                               ? pe->cellside[ax] * fabs(p.inv_dir[ax])
+                               : 0.;
+          }
+          const int32_t sx = pe->stride_x, sy = pe->stride_y;
+          p.cstep[0] = (p.dir[0] > 0.) ? sx : -sx;
+          p.cstep[1] = (p.dir[1] > 0.) ? sy : -sy;
+          p.cstep[2] = (p.dir[2] > 0.) ? 8 : -8;
+          p.cell = pe->start_offset;
+          pad_next = pe->start_record;
+          /* (the frequency: the draws it takes are what the march needs of
+           * it - the records carry the one cross section) */
+          ModelDev source;
+          source.spectrum_type = pe->spectrum_type;
+          source.mono_frequency = pe->mono_frequency;
+          source.spectra = pe->spectra;
+          source.spectrum_table[0].x = pe->spectrum_table.x;
+          source.spectrum_table[0].y = pe->spectrum_table.y;
+          source.spectrum_table[0].n = pe->spectrum_table.n;
+          source.spectrum_table[0].interpolation =
+              pe->spectrum_table.interpolation;
+          p.nu = sample_source_spectrum(source, rng, 0u);
+          p.tau = -log(rng.next());
         } else {
           packet_id =
               (uint32_t)a.batch_offset + (a.order ? a.order[i] : (uint32_t)i);
@@ -586,7 +644,8 @@
       const uint64_t taken = __popcll(idle_mask);
       pos += taken < avail ? taken : avail;
     }
-    if (BUNDLE) {
+    /* (POINT: there is no continuous source) */
+    if (BUNDLE && !POINT) {
       const unsigned long long continuous_lanes =
           wave_ballot(active && cmi_meta_origin(lane_meta) != 0);
       if (lane == 0)
@@ -1114,7 +1173,13 @@
       const unsigned long long absorbed_lanes =
           wave_ballot(ended_type == TYPE_ABSORBED);
       /* (LDS operations of a wave execute in order: no barrier) */
-      if (lane == 0) {
+      if constexpr (POINT) {
+        if (lane == 0) {
+          unsigned int *all = s_ended[threadIdx.x >> 6];
+          all[0] += (unsigned int)__popcll(ended & ~absorbed_lanes);
+          all[1] += (unsigned int)__popcll(absorbed_lanes);
+        }
+      } else if (lane == 0) {
         const unsigned long long continuous_lanes =
             s_continuous_lanes[threadIdx.x >> 6];
         unsigned int *all = s_ended[threadIdx.x >> 6];
@@ -1149,7 +1214,15 @@
   double s2 = BUNDLE ? 0. : wave_sum((double)tc2);
   double s3 = BUNDLE ? (double)s_ended[threadIdx.x >> 6][1]
                      : wave_sum((double)tc3);
-  {
+  if constexpr (POINT) {
+    /* every packet carries the one source's weight */
+    const __attribute__((address_space(4))) PointEmitDev *pe =
+        (const __attribute__((address_space(4))) PointEmitDev *)point;
+    asm volatile("" : "+s"(pe));
+    const double w = pe->weight;
+    s0 = s0 * w;
+    s3 = s3 * w;
+  } else {
     /* n packets of a type, c of them from the continuous source:
      * (n - c) w_discrete + c w_continuous */
     const unsigned int *c =

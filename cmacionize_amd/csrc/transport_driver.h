@@ -216,6 +216,7 @@ static uint64_t reemit_inline_below(const cmi_gpu_engine *e) {
 
 typedef void (*ShootKernel)(const ShootArgs);
 typedef void (*TileKernel)(const TileArgs);
+typedef void (*PointKernel)(const ShootArgs, const PointEmitDev *);
 
 /* the build of shoot_kernel that flies the first generation of new packets:
  * the one of the later generations, or one of the specialised builds */
@@ -256,6 +257,10 @@ struct LaunchPlan {
    * claimed chunk of 64 new packets that fly to their end where they are: the
    * bundle build (shoot_bundle_kernel) */
   bool bundle;
+  /* bundle and pad_uniform, and every packet comes from one discrete source
+   * (PacketOrigin::fixed): the point build of the bundle kernel */
+  bool bundle_point;
+  PointKernel kernel_point; /* (in place of kernel_first) */
   /* the kernel of a pass, the one that follows re-emissions in place, and the
    * first generation's, with their workgroups per CU */
   ShootKernel kernel, kernel_inline, kernel_first;
@@ -474,13 +479,23 @@ static int plan_launches(cmi_gpu_engine *e, uint64_t n_packets,
   if (p.bundle)
     p.kernel_first = p.pad_uniform ? shoot_bundle_kernel<true>
                                    : shoot_bundle_kernel<false>;
+  /* ... and its point build (tuning "bundle_point"): PacketOrigin::fixed, as
+   * the host knows it - no continuous source, one discrete one (whose
+   * cumulative weight cmi_gpu_set_sources sets to 1) */
+  p.bundle_point = p.bundle && p.pad_uniform && tune.bundle_point &&
+                   e->model.continuous_probability == 0. &&
+                   e->model.nsource == 1;
+  p.kernel_point = p.bundle_point ? shoot_bundle_kernel<true, true> : nullptr;
   CMI_TRY(blocks_per_cu_of(p.kernel, CMI_BLOCK, tune.max_blocks_per_cu,
                            p.blocks_per_cu));
   CMI_TRY(blocks_per_cu_of(p.kernel_inline, CMI_BLOCK, tune.max_blocks_per_cu,
                            p.blocks_per_cu_inline));
   /* (the specialised first-generation kernels may fit more blocks per CU) */
   p.blocks_per_cu_first = p.blocks_per_cu;
-  if (table)
+  if (p.bundle_point)
+    CMI_TRY(blocks_per_cu_of(p.kernel_point, p.first_threads,
+                             tune.max_blocks_per_cu, p.blocks_per_cu_first));
+  else if (table)
     CMI_TRY(blocks_per_cu_of(p.kernel_first, p.first_threads,
                              tune.max_blocks_per_cu, p.blocks_per_cu_first));
   p.tile_kernel = nullptr;
@@ -884,10 +899,46 @@ static int order_packets(cmi_gpu_engine *e, const LaunchPlan &p, ShootArgs &a,
   return CMI_GPU_OK;
 }
 
+/* The block the point build's refill reads (PointEmitDev), for this launch:
+ * written on the device, in stream order, ahead of EVERY launch of that
+ * build - it holds the launch's seed, iteration, ids and order next to the
+ * start of the source's flights, and the start cell's record as the cell
+ * update before this launch left it. So there is no state of it to keep
+ * valid: whatever a setter of sources, grid or records changed, the next
+ * launch's block is made from what the engine then holds. (One thread, a few
+ * microseconds a launch.) */
+static int write_point_block(cmi_gpu_engine *e, const ShootArgs &a) {
+  if (!e->point_emit)
+    HIP_TRY(hipMalloc(&e->point_emit, sizeof(PointEmitDev)));
+  PointEmitArgs s;
+  memset(&s, 0, sizeof s);
+  s.grid = a.grid;
+  s.launch.first_packet = a.first_packet;
+  s.launch.batch_offset = a.batch_offset;
+  s.launch.order = a.order;
+  s.launch.seed = a.seed;
+  s.launch.iteration = a.iteration;
+  s.launch.spectrum_type = a.model.spectrum_type;
+  s.launch.mono_frequency = a.model.mono_frequency;
+  s.launch.spectra = a.model.spectra;
+  s.launch.spectrum_table = a.model.spectrum_table[0];
+  s.launch.weight = a.model.photon_weight[0];
+  s.source_position = a.model.source_position;
+  s.pad_H = a.pad_H;
+  s.pad_ny = a.pad_ny;
+  s.pad_nz = a.pad_nz;
+  s.out = e->point_emit;
+  point_emit_kernel<<<1, 64, 0, e->stream>>>(s);
+  HIP_TRY(hipGetLastError());
+  return CMI_GPU_OK;
+}
+
 /* the first generation: one timed launch over the launch's flights */
 static int launch_first_generation(cmi_gpu_engine *e, const LaunchPlan &p,
                                    const ShootArgs &args) {
   ShootArgs a = args;
+  if (p.bundle_point)
+    CMI_TRY(write_point_block(e, a));
   const unsigned blocks = transport_blocks(
       e, a.n_packets, a.chunk, p.blocks_per_cu_first, p.first_threads);
   if (e->tune.span_claim) {
@@ -920,7 +971,11 @@ static int launch_first_generation(cmi_gpu_engine *e, const LaunchPlan &p,
 #endif
   EventPair kev;
   CMI_TRY(timer_begin(e, kev));
-  p.kernel_first<<<blocks, p.first_threads, 0, e->stream>>>(a);
+  if (p.bundle_point)
+    p.kernel_point<<<blocks, p.first_threads, 0, e->stream>>>(a,
+                                                              e->point_emit);
+  else
+    p.kernel_first<<<blocks, p.first_threads, 0, e->stream>>>(a);
   HIP_TRY(hipGetLastError());
   return timer_end(e, e->kernel_events, kev, a.n_packets);
 }
@@ -1356,6 +1411,7 @@ static int shoot_impl(cmi_gpu_engine *e, uint32_t seed, uint32_t iteration,
     e->last_first_build = (int32_t)plan.first;
     e->last_pad_uniform = plan.pad_uniform;
     e->last_bundle_march = plan.bundle;
+    e->last_bundle_point = plan.bundle_point;
     if (!plan.sorted) /* (order_packets says which way otherwise) */
       e->last_order_path = ORDER_NONE;
   }

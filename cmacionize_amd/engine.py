@@ -170,7 +170,7 @@ EXPORTED_SYMBOLS = [
     "cmi_gpu_download_escape_tally", "cmi_gpu_escape_pixels",
     "cmi_gpu_cross_sections", "cmi_gpu_get_transport_plan",
     "cmi_gpu_get_order_plan", "cmi_gpu_order_packets",
-    "cmi_gpu_get_bundle_march",
+    "cmi_gpu_get_bundle_march", "cmi_gpu_get_bundle_point",
     "cmi_gpu_sph_map_to_cells", "cmi_gpu_sph_map_to_particles",
     "cmi_gpu_get_sph_map_stats",
 ]
@@ -375,6 +375,8 @@ def load_library():
             C.POINTER(C.c_int32)]
     if hasattr(L, "cmi_gpu_get_bundle_march"):
         L.cmi_gpu_get_bundle_march.argtypes = [vp, C.POINTER(C.c_int32)]
+    if hasattr(L, "cmi_gpu_get_bundle_point"):
+        L.cmi_gpu_get_bundle_point.argtypes = [vp, C.POINTER(C.c_int32)]
     # (a build from before the bucket order, loaded through CMI_GPU_LIBRARY
     # for a comparison, does not have them)
     if hasattr(L, "cmi_gpu_get_order_plan"):
@@ -1109,6 +1111,14 @@ class GpuEngine:
         build of the padded march (tuning "bundle_march")."""
         flown = C.c_int32()
         self._check(self._lib.cmi_gpu_get_bundle_march(self._h,
+                                                       C.byref(flown)))
+        return bool(flown.value)
+
+    def bundle_point_flown(self):
+        """... and whether it was the point build of the bundle build: one
+        discrete source, no continuous one (tuning "bundle_point")."""
+        flown = C.c_int32()
+        self._check(self._lib.cmi_gpu_get_bundle_point(self._h,
                                                        C.byref(flown)))
         return bool(flown.value)
 

@@ -319,6 +319,9 @@ int cmi_gpu_get_transport_plan(cmi_gpu_engine *engine, int32_t *first_build,
  * (tuning "bundle_march"): 1 or 0. cmi_gpu_get_transport_plan answers 2 for
  * either build of it. */
 int cmi_gpu_get_bundle_march(cmi_gpu_engine *engine, int32_t *flown);
+/* ... and whether it was the point build of the bundle build (tuning
+ * "bundle_point"): 1 or 0; cmi_gpu_get_bundle_march answers 1 for it too. */
+int cmi_gpu_get_bundle_point(cmi_gpu_engine *engine, int32_t *flown);
 /* How the last launch of new packets got its order (any pointer may be
  * NULL): path - CMI_GPU_ORDER_NONE: the packets flew in the order of their
  * ids, _RADIX: key kernel and radix sort, _BUCKET: the bucket order (tuning
@@ -785,7 +788,16 @@ int cmi_gpu_cross_sections(cmi_gpu_engine *engine, int64_t n,
  *                           kernel made for exactly that (shoot_bundle_kernel;
  *                           the same packets in the same rounds) - 0: the
  *                           general kernel
- *   "phase_stamps" (0)      EXPERIMENT ONLY: cmi_gpu_get_phase_clocks
+ *   "bundle_point" (1)      such a launch whose packets all carry one weight
+ *                           and come from ONE discrete source, with no
+ *                           continuous source: the point build of that kernel
+ *                           (shoot_bundle_kernel<true, true>: the refill reads
+ *                           its arguments from a block on the device, only the
+ *                           discrete source's emission is compiled, the start
+ *                           cell and its walls are computed once per launch;
+ *                           the same packets in the same rounds) - 0: the
+ *                           bundle build
+ *   "phase_stamps" (0)     EXPERIMENT ONLY: cmi_gpu_get_phase_clocks
  *   "exp_no_atomics" (0)    EXPERIMENT ONLY, builds with -DCMI_EXPERIMENTS
  *                           (results are wrong): 1 = skip the
  *                           accumulation; multi-ion kernels: 2 = post

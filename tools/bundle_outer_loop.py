@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """After `make -C cmacionize_amd/csrc asm`: what the padded first-generation
 kernels hold OUTSIDE their march loop, the general builds next to the bundle
-builds (shoot_bundle_kernel, DESIGN_LOG.md 21).
+builds (shoot_bundle_kernel, DESIGN_LOG.md 21) and the point build of those
+(DESIGN_LOG.md 22).
 
 The march loop is found as tools/march_common_path.py finds it; the outer loop
 is the largest loop around it (refill, flush point, end of flights). Per
@@ -23,7 +24,10 @@ import march_common_path as mcp  # noqa: E402
 
 GENERAL = re.compile(
     r"^(_Z12shoot_kernelILb0ELb0ELb0ELb0ELb1ELb0ELb1ELb[01]ELb0EEv9ShootArgs):")
-BUNDLE = re.compile(r"^(_Z19shoot_bundle_kernelILb[01]EEv9ShootArgs):")
+# (<UNIFORM>, and <true, true>: the point build, DESIGN_LOG.md 22)
+BUNDLE = re.compile(
+    r"^(_Z19shoot_bundle_kernelILb[01](?:ELb[01])?EEv9ShootArgs"
+    r"(?:PK12PointEmitDev)?):")
 
 
 def kernel_bodies(text):
